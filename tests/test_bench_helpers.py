@@ -88,10 +88,11 @@ def test_launcher_refuses_cleanly_without_gpus_and_never_imports_torch_first():
     """`python bench.py --gpus N` as a plain process: the parent counts GPUs from the KFD topology (no HIP call) and, on a box with fewer
     GPUs than ranks, returns 3 without starting anything"""
     import subprocess, sys
-    if bench.visible_gpu_count() not in (0, None):
+    have = bench.visible_gpu_count()
+    if have is None:                     # a KFD device without a readable topology: the launcher starts the ranks and they check for themselves
         import pytest
-        pytest.skip("GPUs present")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], capture_output=True, text=True, timeout=120)
+        pytest.skip("GPU count not readable from the KFD topology")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(max(2, have + 1))], capture_output=True, text=True, timeout=120)
     assert r.returncode == 3 and r.stdout == "" and "nothing was launched" in r.stderr
 
 
