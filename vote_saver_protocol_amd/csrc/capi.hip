@@ -321,8 +321,7 @@ static bool fp28_known_answer_check(vsp_ctx *ctx, int group) {
     const size_t esz = group == 1 ? sizeof(G1Affine) : sizeof(G2Affine), row = group == 1 ? sizeof(Affine28) : sizeof(Affine28x2);
     void *d_pts = nullptr, *t28 = nullptr;
     bool same = false, ran = false;
-    const long saved_split = ctx->opts.count("msm_split") ? ctx->opts["msm_split"] : 0, saved_db = ctx->opts.count("msm_dimbits") ? ctx->opts["msm_dimbits"] : -1;
-    const long saved_wb = ctx->opts.count("msm_window_bits") ? ctx->opts["msm_window_bits"] : 0;
+    OptScope saved(ctx, {"msm_split", "msm_dimbits", "msm_window_bits"});      // (the legs below set them; they come back at the return)
     if (ensure(ctx, ctx->msm_scalars, 2 * n * 32) == VSP_OK && ensure(ctx, ctx->val_flag, 16) == VSP_OK &&
         hipMemcpyAsync(ctx->msm_scalars.p, sc.data(), 2 * n * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
         hipStreamSynchronize(ctx->stream) == hipSuccess && hipMalloc(&d_pts, n * esz) == hipSuccess && hipMalloc(&t28, 2 * n * row) == hipSuccess) {
@@ -337,13 +336,14 @@ static bool fp28_known_answer_check(vsp_ctx *ctx, int group) {
                 if (wbits) ctx->opts["msm_window_bits"] = wbits; else ctx->opts.erase("msm_window_bits");
                 if (split) ctx->opts["msm_split"] = split; else ctx->opts.erase("msm_split");
                 if (dimbits >= 0) ctx->opts["msm_dimbits"] = dimbits; else ctx->opts.erase("msm_dimbits");
+                MsmRequest rq(ds, n); rq.bases = d_pts; rq.dense = true; rq.table28 = table; rq.glv = glv;
                 if (group == 1) {
                     XYZZ<HFp> r;
-                    if (msm_g1_launch(ctx, 0, (const G1Affine *)d_pts, ds, n, VSP_MSM_DENSE, nullptr, table, glv) != VSP_OK || msm_g1_finish(ctx, 0, &r) != VSP_OK) return false;
+                    if (msm_g1_launch(ctx, 0, rq) != VSP_OK || msm_g1_finish(ctx, 0, &r) != VSP_OK) return false;
                     Affine<HFp> a = xyzz_to_affine(r); host_store_g1(aff, a); *inf = is_inf(r);
                 } else {
                     XYZZ<HFp2> r;
-                    if (msm_g2_launch(ctx, 0, (const G2Affine *)d_pts, ds, n, VSP_MSM_DENSE, nullptr, table, glv) != VSP_OK || msm_g2_finish(ctx, 0, &r) != VSP_OK) return false;
+                    if (msm_g2_launch(ctx, 0, rq) != VSP_OK || msm_g2_finish(ctx, 0, &r) != VSP_OK) return false;
                     Affine<HFp2> a = xyzz_to_affine(r); host_store_g2(aff, a); *inf = is_inf(r);
                 }
                 return true;
@@ -361,14 +361,11 @@ static bool fp28_known_answer_check(vsp_ctx *ctx, int group) {
                          ((id != ic || memcmp(rd, rc3, sizeof rd)) ? 16 : 0) | ((ie != ic || memcmp(re, rc3, sizeof re)) ? 32 : 0));
         }
     }
-    if (saved_split) ctx->opts["msm_split"] = saved_split; else ctx->opts.erase("msm_split");
-    if (saved_db >= 0) ctx->opts["msm_dimbits"] = saved_db; else ctx->opts.erase("msm_dimbits");
-    if (saved_wb) ctx->opts["msm_window_bits"] = saved_wb; else ctx->opts.erase("msm_window_bits");
     if (d_pts) hipFree(d_pts);
     if (t28) hipFree(t28);
     hipGetLastError();
     if (!ran) { ctx->stats[group == 1 ? "msm_fp28_selfcheck_g1" : "msm_fp28_selfcheck_g2"] = 0.0; return false; }      // could not run (out of memory): no verdict, no 28-bit table this time
-    { auto it = ctx->opts.find("msm_fp28_selfcheck_fault"); if (it != ctx->opts.end() && it->second) same = false; }   // test hook: exercise the fallback
+    if (opt(ctx, "msm_fp28_selfcheck_fault", 0)) same = false;   // test hook: exercise the fallback
     ctx->fp28_checked[gi] = same ? 1 : -1;
     ctx->stats[group == 1 ? "msm_fp28_selfcheck_g1" : "msm_fp28_selfcheck_g2"] = same ? 1.0 : -1.0;
     if (!same) { ctx->opts["msm_fp28"] = 0; ctx->err = "msm: the 28-bit-limb kernels failed their known-answer check; generic kernels in use"; }
@@ -378,8 +375,7 @@ static bool fp28_known_answer_check(vsp_ctx *ctx, int group) {
 // Plain bases (no window multiples) whose points are known to satisfy phi(P) = lambda P (vsp_bases.in_subgroup) get the endomorphism
 // layout: 2 count rows, (P_i, phi(P_i)) interleaved (option "msm_glv" = 0: off; 2: on for any size and WITHOUT the check -- the caller vouches)
 static bool glv_wanted(vsp_ctx *ctx, int group, size_t count, unsigned pre_c) {
-    long want = 1; { auto it = ctx->opts.find("msm_fp28"); if (it != ctx->opts.end()) want = it->second; }
-    long want_glv = 1; { auto it = ctx->opts.find("msm_glv"); if (it != ctx->opts.end()) want_glv = it->second; }
+    const long want = opt(ctx, "msm_fp28", 1), want_glv = opt(ctx, "msm_glv", 1);
     const size_t row = group == 1 ? sizeof(Affine28) : sizeof(Affine28x2);
     // The split halves the bucket sets (and the host Horner chain) but doubles the table and the sort's input.  Measured
     // (tools/msm_sizes.py, bench.py; one in flight / three in flight, ms): G1 2^16 1.49 / 1.42 -> 1.35 / 0.80, G1 2^18 2.31 / 1.29 ->
@@ -393,8 +389,7 @@ static bool glv_wanted(vsp_ctx *ctx, int group, size_t count, unsigned pre_c) {
 static void build_table28(vsp_ctx *ctx, vsp_bases *b, size_t count) {
     if (b->d28) { hipFree(b->d28); b->d28 = nullptr; }
     b->glv = false;
-    long want = 1; { auto it = ctx->opts.find("msm_fp28"); if (it != ctx->opts.end()) want = it->second; }
-    long want_glv = 1; { auto it = ctx->opts.find("msm_glv"); if (it != ctx->opts.end()) want_glv = it->second; }
+    const long want = opt(ctx, "msm_fp28", 1), want_glv = opt(ctx, "msm_glv", 1);
     // "msm_fp28" = 2 (diagnostics: bisecting a failed check with tools/fuzz_msm.py): the 28-bit kernels WITHOUT the context-time check
     if (!want || (want < 2 && !fp28_known_answer_check(ctx, b->group))) return;   // the check may have just switched "msm_fp28" off
     const size_t row = b->group == 1 ? sizeof(Affine28) : sizeof(Affine28x2);
@@ -426,11 +421,11 @@ vsp_bases *bases_create(vsp_ctx *ctx, int group, const void *src, bool src_on_de
             src = b->d;                      // convert in place
         }
         // boundary validation (include/vsp.h): coordinates below p always; the curve equation unless option "bases_check_curve" = 0
-        long check_curve = 1; { auto it = ctx->opts.find("bases_check_curve"); if (it != ctx->opts.end()) check_curve = it->second; }
+        const long check_curve = opt(ctx, "bases_check_curve", 1);
         // the subgroup (option "bases_check_subgroup"): 1 (default) = checked where the endomorphism split would be used -- bases that fail
         // keep the plain layout, whose result is exact for ANY curve point (like the reference's generic multiexp); 2 = always checked, a
         // failing upload is refused; 0 = never checked, and then never split unless "msm_glv" = 2 (the caller vouches for the points)
-        long check_sub = 1; { auto it = ctx->opts.find("bases_check_subgroup"); if (it != ctx->opts.end()) check_sub = it->second; }
+        const long check_sub = opt(ctx, "bases_check_subgroup", 1);
         uint32_t h_flag = 0;
         rc = ensure(ctx, ctx->val_flag, 16);
         if (rc == VSP_OK && hipMemsetAsync(ctx->val_flag.p, 0, 16, ctx->stream) != hipSuccess) rc = set_error(ctx, VSP_ERR_HIP, "bases: memset failed");
@@ -488,35 +483,18 @@ void vsp_bases_free(vsp_ctx *ctx, vsp_bases *b) {
 // ---- MSM ----------------------------------------------------------------------------------------
 }  // extern "C"
 namespace vsp {
-// queue the multi-exponentiation over points [first, first+n) of resident bases on a work slot (plain or precomputed bases)
-int launch_on_bases(vsp_ctx *ctx, unsigned slot, const vsp_bases *bases, size_t first, size_t n, const Fr *d_scalars, int plan_from_slot) {
+// queue the multi-exponentiation rq over points [first, first + rq.n) of resident bases on a work slot: plain bases or a table of window
+// multiples, one scalar vector or a batch
+int launch_on_bases(vsp_ctx *ctx, unsigned slot, const vsp_bases *bases, size_t first, MsmRequest rq) {
     if (slot < VSP_MSM_SLOTS) ctx->slot_group[slot] = bases->group;
-    if (bases->pre_c) {
-        MsmPre pre{bases->n, first, bases->pre_c, bases->d28, bases->glv};
-        if (bases->group == 1) return msm_g1_launch(ctx, slot, (const G1Affine *)bases->d, d_scalars, n, plan_from_slot, &pre, nullptr, bases->glv);
-        return msm_g2_launch(ctx, slot, (const G2Affine *)bases->d, d_scalars, n, plan_from_slot, &pre, nullptr, bases->glv);
-    }
-    if (bases->group == 1)
-        return msm_g1_launch(ctx, slot, (const G1Affine *)bases->d + first, d_scalars, n, plan_from_slot, nullptr,
-                             bases->d28 ? (const char *)bases->d28 + first * sizeof(Affine28) * (bases->glv ? 2 : 1) : nullptr, bases->glv);
-    return msm_g2_launch(ctx, slot, (const G2Affine *)bases->d + first, d_scalars, n, plan_from_slot, nullptr,
-                         bases->d28 ? (const char *)bases->d28 + first * sizeof(Affine28x2) * (bases->glv ? 2 : 1) : nullptr, bases->glv);
-}
-// the same for a batch of scalar vectors (vector k at d_scalars + k * stride) over PLAIN resident bases: one launch, one result per vector
-int launch_on_bases_batch(vsp_ctx *ctx, unsigned slot, const vsp_bases *bases, size_t first, size_t n, const Fr *d_scalars, unsigned batch, size_t stride, bool dense, int plan_from_slot) {
-    if (slot < VSP_MSM_SLOTS) ctx->slot_group[slot] = bases->group;
-    if (bases->pre_c) {                                       // the table of window multiples: ONE bucket set per vector (round 4, last hours)
-        long allow = 1; { auto it = ctx->opts.find("msm_batch_tables"); if (it != ctx->opts.end()) allow = it->second; }
-        if (!allow || bases->pre_c > 16) return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: a batch over this table of window multiples is not supported (plain bases, or windows of at most 16 bits)");
-        MsmPre pre{bases->n, first, bases->pre_c, bases->d28, bases->glv};
-        if (bases->group == 1) return msm_g1_launch_batch(ctx, slot, (const G1Affine *)bases->d, d_scalars, n, batch, stride, dense, nullptr, bases->glv, plan_from_slot, &pre);
-        return msm_g2_launch_batch(ctx, slot, (const G2Affine *)bases->d, d_scalars, n, batch, stride, dense, nullptr, bases->glv, plan_from_slot, &pre);
-    }
-    if (bases->group == 1)
-        return msm_g1_launch_batch(ctx, slot, (const G1Affine *)bases->d + first, d_scalars, n, batch, stride, dense,
-                                   bases->d28 ? (const char *)bases->d28 + first * sizeof(Affine28) * (bases->glv ? 2 : 1) : nullptr, bases->glv, plan_from_slot);
-    return msm_g2_launch_batch(ctx, slot, (const G2Affine *)bases->d + first, d_scalars, n, batch, stride, dense,
-                               bases->d28 ? (const char *)bases->d28 + first * sizeof(Affine28x2) * (bases->glv ? 2 : 1) : nullptr, bases->glv, plan_from_slot);
+    if (bases->pre_c && rq.batch && (!opt(ctx, "msm_batch_tables", 1) || bases->pre_c > 16))      // (a batch over the table: ONE bucket set per vector)
+        return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: a batch over this table of window multiples is not supported (plain bases, or windows of at most 16 bits)");
+    const size_t row = bases->group == 1 ? sizeof(Affine28) : sizeof(Affine28x2), esz = bases->group == 1 ? sizeof(G1Affine) : sizeof(G2Affine);
+    MsmPre pre{bases->n, first, bases->pre_c, bases->d28, bases->glv};
+    rq.glv = bases->glv;
+    if (bases->pre_c) { rq.bases = bases->d; rq.pre = &pre; }
+    else { rq.bases = (const char *)bases->d + first * esz; rq.table28 = bases->d28 ? (const char *)bases->d28 + first * row * (bases->glv ? 2 : 1) : nullptr; }
+    return bases->group == 1 ? msm_g1_launch(ctx, slot, rq) : msm_g2_launch(ctx, slot, rq);
 }
 }  // namespace vsp
 extern "C" {
@@ -529,7 +507,7 @@ static int bases_precompute(vsp_ctx *ctx, vsp_bases *b, unsigned window_bits, bo
     if (!b) return set_error(ctx, VSP_ERR_ARG, "precompute: null bases");
     if (split && b->pre_c == 0) {
         // the endomorphism rows need the order-r subgroup (include/vsp.h "bases_check_subgroup"): bases that were not checked at upload are checked now
-        long want_glv = 1; { auto it = ctx->opts.find("msm_glv"); if (it != ctx->opts.end()) want_glv = it->second; }
+        const long want_glv = opt(ctx, "msm_glv", 1);
         if (b->in_subgroup == 0 && want_glv == 1 && b->n) {
             VSP_HIP(hipSetDevice(ctx->device));
             VSP_TRY(ensure(ctx, ctx->val_flag, 16));
@@ -571,11 +549,7 @@ static int bases_precompute(vsp_ctx *ctx, vsp_bases *b, unsigned window_bits, bo
 
 static int msm_resident_xyzz(vsp_ctx *ctx, const vsp_bases *bases, size_t first, size_t n, const void *d_scalars,
                              XYZZ<HFp> *o1, XYZZ<HFp2> *o2) {
-    if (!ctx) return VSP_ERR_ARG;
-    if (!bases || (!d_scalars && n)) return set_error(ctx, VSP_ERR_ARG, "msm: null argument");
-    if (first > bases->n || n > bases->n - first) return set_error(ctx, VSP_ERR_ARG, "msm: range outside the resident bases");
-    VSP_HIP(hipSetDevice(ctx->device));
-    VSP_TRY(launch_on_bases(ctx, 0, bases, first, n, (const Fr *)d_scalars, -1));
+    VSP_TRY(vsp_msm_launch(ctx, 0, bases, first, n, d_scalars));      // (its argument checks, on slot 0)
     if (bases->group == 1) return msm_g1_finish(ctx, 0, o1);
     return msm_g2_finish(ctx, 0, o2);
 }
@@ -593,7 +567,8 @@ int vsp_msm_resident_batch(vsp_ctx *ctx, const vsp_bases *bases, size_t first, s
     if (first > bases->n || n > bases->n - first) return set_error(ctx, VSP_ERR_ARG, "msm: range outside the resident bases");
     VSP_HIP(hipSetDevice(ctx->device));
     const size_t words = bases->group == 1 ? 12 : 24;
-    VSP_TRY(launch_on_bases_batch(ctx, 0, bases, first, n, (const Fr *)d_scalars, (unsigned)batch, stride, false));
+    MsmRequest rq((const Fr *)d_scalars, n); rq.batch = (unsigned)batch; rq.stride = stride;
+    VSP_TRY(launch_on_bases(ctx, 0, bases, first, rq));
     if (bases->group == 1) {
         std::vector<XYZZ<HFp>> r(batch);
         VSP_TRY(msm_g1_finish_batch(ctx, 0, r.data(), (unsigned)batch));
@@ -628,7 +603,7 @@ int vsp_msm_launch(vsp_ctx *ctx, unsigned slot, const vsp_bases *bases, size_t f
     if (!bases || (!d_scalars && n)) return set_error(ctx, VSP_ERR_ARG, "msm: null argument");
     if (first > bases->n || n > bases->n - first) return set_error(ctx, VSP_ERR_ARG, "msm: range outside the resident bases");
     VSP_HIP(hipSetDevice(ctx->device));
-    return launch_on_bases(ctx, slot, bases, first, n, (const Fr *)d_scalars, -1);
+    return launch_on_bases(ctx, slot, bases, first, MsmRequest((const Fr *)d_scalars, n));
 }
 // the Jacobian record of a finished slot (18 / 36 canonical words); returns the words written
 static int finish_record(vsp_ctx *ctx, unsigned slot, uint64_t *out_jacobian, size_t *words) {

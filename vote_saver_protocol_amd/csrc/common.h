@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
@@ -13,7 +14,6 @@
 #include <atomic>
 #include <mutex>
 #include <thread>
-#include <vector>
 #include "curve.h"
 
 namespace vsp {
@@ -94,9 +94,23 @@ struct MsmWork {
     size_t n = 0, n_eff = 0;
 };
 static constexpr unsigned VSP_MSM_SLOTS = 6;
-static constexpr int VSP_MSM_DENSE = -2;      // plan_from_slot value: the scalars are known to be dense, skip the 0/1 census
-static constexpr int VSP_MSM_PLAN_ONLY = -3;  // plan_from_slot value: queue only the digit sort and the bucket plan (up to plan_ready); a later launch on the
-                                              // SAME slot with plan_from_slot = that slot queues the accumulation and the reduction over it
+// one multi-exponentiation queued on a work slot (msm_g1_launch / msm_g2_launch)
+struct MsmRequest {
+    const void *bases = nullptr;        // Affine<Fp> / Affine<Fp2>, Montgomery form: the points, or with `pre` the table of window multiples
+    const Fr *scalars = nullptr;
+    size_t n = 0;
+    int plan_from = -1;                 // a slot whose digit sort and bucket plan over the SAME scalars this launch reuses (the prover's
+                                        // A_query, B_query(G1) and B_query(G2) all multiply by the same witness vector), or -1
+    bool dense = false;                 // the scalars are known to be dense: skip the 0/1 census
+    bool plan_only = false;             // queue the digit sort and the bucket plan only; a later launch on the SAME slot with plan_from = that
+                                        // slot queues the accumulation and the reduction over it
+    const MsmPre *pre = nullptr;
+    const void *table28 = nullptr;      // plain bases: the same points on 28-bit limbs, or null
+    bool glv = false;                   // table28 (or pre->table28) holds (P_i, phi(P_i)) interleaved: split the scalars k = k1 + k2 lambda
+    unsigned batch = 0;                 // 0: one scalar vector; K >= 1: a batch (MsmGeom.K), vector k at scalars + k * stride, one result each
+    size_t stride = 0;
+    MsmRequest(const Fr *scalars_ = nullptr, size_t n_ = 0) : scalars(scalars_), n(n_) {}
+};
 
 }  // namespace vsp
 
@@ -194,6 +208,21 @@ struct vsp_pk {
 
 namespace vsp {
 
+// option `name` of the context (vsp_set_option), or dflt when it was never set
+inline long opt(const vsp_ctx *ctx, const char *name, long dflt) { auto it = ctx->opts.find(name); return it != ctx->opts.end() ? it->second : dflt; }
+// the named options as they are at construction, present with a value or absent, put back when the scope ends (the known-answer
+// checks run their legs under settings of their own)
+class OptScope {
+  public:
+    OptScope(vsp_ctx *ctx, std::initializer_list<const char *> names) : ctx_(ctx) {
+        for (const char *name : names) { auto it = ctx->opts.find(name); saved_.push_back({name, it != ctx->opts.end(), it != ctx->opts.end() ? it->second : 0}); }
+    }
+    ~OptScope() { for (const Saved &s : saved_) { if (s.had) ctx_->opts[s.name] = s.value; else ctx_->opts.erase(s.name); } }
+    OptScope(const OptScope &) = delete; OptScope &operator=(const OptScope &) = delete;
+  private:
+    struct Saved { std::string name; bool had; long value; };
+    vsp_ctx *ctx_; std::vector<Saved> saved_;
+};
 int set_hip_error(vsp_ctx *ctx, hipError_t e, const char *what, const char *file, int line);
 // f(0) .. f(n - 1) on up to `max_threads` host threads (the host steps of a BATCH: the Horner chains over the window results of K
 // multi-exponentiations and the assembly of K proofs are independent pieces of a few hundred group operations each)
@@ -247,30 +276,24 @@ HFr domain_element(const vsp_domain *d, size_t idx);
 int witness_map_device(vsp_ctx *ctx, Fr *dA, Fr *dB, Fr *dC, const vsp_domain *d, Fr *dH);
 
 // MSM on device-resident Montgomery bases; result as host XYZZ (Montgomery, 64-bit limbs)
-int msm_g1_device(vsp_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, size_t n, XYZZ<HFp> *out);
-int msm_g2_device(vsp_ctx *ctx, const G2Affine *d_bases, const Fr *d_scalars, size_t n, XYZZ<HFp2> *out);
-int msm_g1_launch(vsp_ctx *ctx, unsigned slot, const G1Affine *d_bases, const Fr *d_scalars, size_t n, int plan_from_slot, const MsmPre *pre,
-                  const void *plain_table28 = nullptr, bool glv = false);   // plain bases (pre == null): the same points as Affine28 (glv: 2n rows, P and phi(P) interleaved), or null
+int msm_g1_launch(vsp_ctx *ctx, unsigned slot, const MsmRequest &rq);
+int msm_g2_launch(vsp_ctx *ctx, unsigned slot, const MsmRequest &rq);
 int msm_g1_precompute(vsp_ctx *ctx, G1Affine *table, size_t n, unsigned c);
 int msm_g2_precompute(vsp_ctx *ctx, G2Affine *table, size_t n, unsigned c);
 int msm_g1_table28(vsp_ctx *ctx, const G1Affine *table, size_t count, void *d_out /* count (glv: 2 count) rows of 128 bytes */, bool glv);
 int msm_g2_table28(vsp_ctx *ctx, const G2Affine *table, size_t count, void *d_out /* count (glv: 2 count) rows of 256 bytes */, bool glv);
 int msm_g1_finish(vsp_ctx *ctx, unsigned slot, XYZZ<HFp> *out);
-int msm_g2_launch(vsp_ctx *ctx, unsigned slot, const G2Affine *d_bases, const Fr *d_scalars, size_t n, int plan_from_slot, const MsmPre *pre,
-                  const void *plain_table28 = nullptr, bool glv = false);
 int msm_g2_finish(vsp_ctx *ctx, unsigned slot, XYZZ<HFp2> *out);
-// a batch of scalar vectors over one set of PLAIN bases (MsmGeom.K): vector k at d_scalars + k * stride; one result per vector
-int msm_g1_launch_batch(vsp_ctx *ctx, unsigned slot, const G1Affine *d_bases, const Fr *d_scalars, size_t n, unsigned batch, size_t stride, bool dense, const void *plain_table28, bool glv, int plan_from_slot = -1, const MsmPre *pre = nullptr);
+// the results of a batch launch: one per vector
 int msm_g1_finish_batch(vsp_ctx *ctx, unsigned slot, XYZZ<HFp> *out, unsigned batch);
-int msm_g2_launch_batch(vsp_ctx *ctx, unsigned slot, const G2Affine *d_bases, const Fr *d_scalars, size_t n, unsigned batch, size_t stride, bool dense, const void *plain_table28, bool glv, int plan_from_slot = -1, const MsmPre *pre = nullptr);
 int msm_g2_finish_batch(vsp_ctx *ctx, unsigned slot, XYZZ<HFp2> *out, unsigned batch);
 // a finish in two halves: the wait (context state: caller's thread) and the fold of the window results (pure host arithmetic over the slot: any thread)
 int msm_g1_finish_wait(vsp_ctx *ctx, unsigned slot, bool *empty);
 void msm_g1_fold(vsp_ctx *ctx, unsigned slot, XYZZ<HFp> *out);
 int msm_g2_finish_wait(vsp_ctx *ctx, unsigned slot, bool *empty);
 void msm_g2_fold(vsp_ctx *ctx, unsigned slot, XYZZ<HFp2> *out);
-int launch_on_bases(vsp_ctx *ctx, unsigned slot, const vsp_bases *bases, size_t first, size_t n, const Fr *d_scalars, int plan_from_slot);
-int launch_on_bases_batch(vsp_ctx *ctx, unsigned slot, const vsp_bases *bases, size_t first, size_t n, const Fr *d_scalars, unsigned batch, size_t stride, bool dense, int plan_from_slot = -1);
+// rq over points [first, first + rq.n) of resident bases: fills in rq's bases, pre, table28 and glv
+int launch_on_bases(vsp_ctx *ctx, unsigned slot, const vsp_bases *bases, size_t first, MsmRequest rq);
 int msm_slot_stream(vsp_ctx *ctx, unsigned slot, hipStream_t *out);
 int msm_slot_census(vsp_ctx *ctx, unsigned slot, const Fr *d_scalars, size_t n);
 void msm_free_slots(vsp_ctx *ctx);

@@ -323,7 +323,7 @@ int domain_lagrange_device(vsp_ctx *ctx, const vsp_domain *d, const HFr &t, Fr *
 int witness_map_device(vsp_ctx *ctx, Fr *dA, Fr *dB, Fr *dC, const vsp_domain *d, Fr *dH) {
     const size_t m = d->m;
     Fr *v[3] = {dA, dB, dC};
-    { long batched = 1; auto it = ctx->opts.find("witness_map_batched"); if (it != ctx->opts.end()) batched = it->second;
+    { const long batched = opt(ctx, "witness_map_batched", 1);
       if (batched && !d->step && m >= 2 && ntt29_in_use(ctx)) {
         // basic radix-2 domain, 29-bit butterflies: the three inverse transforms as ONE launch per pass, the three coset transforms likewise, and
         // the pointwise step A B - C inside the first pass of the last transform: 3 x passes launches instead of 7 x passes + 1, and the

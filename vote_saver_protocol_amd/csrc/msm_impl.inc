@@ -1684,12 +1684,10 @@ __global__ __launch_bounds__(MSM_THREADS, AccumWaves<F>::W) void k_subgroup_chec
 // the bit-decomposed last step (k_dimbits) or the weighted one (k_dimweight): option "msm_dimbits" 1 / 0 forces either, default by group
 template <class FT> static bool use_dimbits(vsp_ctx *ctx, const MsmGeom &g) {
     // room for 25 records per window in the slot's pinned buffer: the initial buffer for one vector (52 windows of 5 bits: no), the grown one
-    // for a batch (msm_launch grows it up to 64 MiB: K x Wk windows; k_dimweight's 16-addition chains took a fifth of a batch prover's kernel time)
+    // for a batch (msm_buffers grows it up to 64 MiB: K x Wk windows; k_dimweight's 16-addition chains took a fifth of a batch prover's kernel time)
     const size_t cap = g.K > 1 ? ((size_t)64 << 20) : MsmWork::PINNED_BYTES;
-    auto it = ctx->opts.find("msm_dimbits");
-    if (it != ctx->opts.end() && it->second >= 0)
-        return it->second != 0 && (size_t)g.Wr * DIMBITS_STRIDE * sizeof(XYZZ<typename WinOut<FT>::type>) <= cap;
-    const bool want = LaneView<FT>::LANES == 1 || g.Wr <= 2 || g.c > 16;      // wide windows: digits of 2^10 values and more only k_dimbits takes
+    const long forced = opt(ctx, "msm_dimbits", -1);
+    const bool want = forced >= 0 ? forced != 0 : (LaneView<FT>::LANES == 1 || g.Wr <= 2 || g.c > 16);      // wide windows: digits of 2^10 values and more only k_dimbits takes
     return want && (size_t)g.Wr * DIMBITS_STRIDE * sizeof(XYZZ<typename WinOut<FT>::type>) <= cap;
 }
 // merges + bucket reduction over the bucket sums of field FT (F, or Fp28 on the G1 28-bit path); winres in the host's form
@@ -1732,14 +1730,14 @@ static int launch_tail(vsp_ctx *ctx, hipStream_t st, const MsmWork *pl, const Ms
             if (cost < best) { best = cost; lps = cand; }
         }
         long forced_lanes = 0;
-        { long t = 0; auto it = ctx->opts.find("msm_dimsum_lanes"); if (it != ctx->opts.end()) t = it->second; if (t == 8 || t == 16 || t == 32 || (t == 64 && LL == 64)) { lps = (unsigned)t; forced_lanes = t; } }
+        { const long t = opt(ctx, "msm_dimsum_lanes", 0); if (t == 8 || t == 16 || t == 32 || (t == 64 && LL == 64)) { lps = (unsigned)t; forced_lanes = t; } }
         const unsigned spw = LL / lps;
         const dim3 grid((sums + spw - 1) / spw);
         DimSumPlan pl; pl.wave0[3] = 0;
-        unsigned maxw = 1024; { auto it = ctx->opts.find("msm_dimsum_maxw"); if (it != ctx->opts.end() && it->second >= 256 && it->second <= 4096) maxw = (unsigned)it->second; }
+        const long mw = opt(ctx, "msm_dimsum_maxw", 1024); const unsigned maxw = mw >= 256 && mw <= 4096 ? (unsigned)mw : 1024u;
         if (!forced_lanes) pl = dimsum_plan<F>(g, maxw);      // a lane count per digit (k_dimsum_mixed); "msm_dimsum_lanes" keeps one count for all
         ctx->stats["msm_dimsum_waves"] = pl.wave0[3];
-        long pf = 0; { auto it = ctx->opts.find("msm_dimsum_prefetch"); if (it != ctx->opts.end()) pf = it->second; }
+        const long pf = opt(ctx, "msm_dimsum_prefetch", 0);
         if (pl.wave0[3] && pf && LaneView<F>::LANES == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dimsum_mixed<F, true>), dim3(pl.wave0[3]), dim3(64), 0, st, (const XYZZ<F> *)buckets, g, dims, pl);
         else if (pl.wave0[3]) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dimsum_mixed<F, false>), dim3(pl.wave0[3]), dim3(64), 0, st, (const XYZZ<F> *)buckets, g, dims, pl);
         else
@@ -1764,9 +1762,7 @@ static int launch_tail(vsp_ctx *ctx, hipStream_t st, const MsmWork *pl, const Ms
 // ------------------------------------------------------------------------------------------------
 // n: scalars that are neither 0 nor 1 (twice that with the endomorphism split: half-length scalars); windows: how many windows c bits need
 static unsigned pick_window_bits(vsp_ctx *ctx, size_t n, bool glv) {
-    long forced = 0;
-    auto it = ctx->opts.find("msm_window_bits");
-    if (it != ctx->opts.end()) forced = it->second;
+    const long forced = opt(ctx, "msm_window_bits", 0);
     if (forced >= 2 && forced <= 23) return (unsigned)forced;
     unsigned L = ceil_log2(n ? n : 1);
     // mean bucket load n / 2^(c-1) of about 32 points balances the accumulation against the
@@ -1786,7 +1782,7 @@ static unsigned pick_window_bits(vsp_ctx *ctx, size_t n, bool glv) {
     // 2^18 1.30 / 1.86 -> 1.13 / 1.50 (2^16: a tie); G2 2^18 3.05 / 4.21 -> 3.04 / 3.67 (2^17 and below: 16 bits lose when pipelined).
     // n is the doubled count here.
     if (glv && c < 16 && n >= ((size_t)1 << (VSP_MSM_GROUP == 1 ? 18 : 19))) c = 16;
-    long wide = 1; { auto iw = ctx->opts.find("msm_wide_windows"); if (iw != ctx->opts.end()) wide = iw->second; }
+    const long wide = opt(ctx, "msm_wide_windows", 1);
     // 255-bit scalars (no endomorphism split), 2^20 points and more: 17 bits.  255 = 15 x 17, and with the scalars folded to below 2^254
     // (load_scalar) 15 windows carry everything, against 16 windows of 16 bits: G1 2^21 5.84 against 6.01 ms, 2^22 10.57 against 10.91;
     // G2 2^20 9.15 against 9.44, 2^21 16.8 against 17.3, 2^22 31.4 against 32.8 (profiles/r3_window_sweep.txt)
@@ -1854,7 +1850,7 @@ static int exclusive_scan_w(vsp_ctx *ctx, MsmWork &wk, const uint32_t *in, size_
     return VSP_OK;
 }
 
-static int work_init(vsp_ctx *ctx, MsmWork &wk, hipStream_t stream_or_null, bool favoured = false) {
+static int work_init(vsp_ctx *ctx, MsmWork &wk, hipStream_t stream_or_null) {
     if (!wk.inited) {
         VSP_HIP(hipEventCreate(&wk.ev0)); VSP_HIP(hipEventCreate(&wk.ev1));
         VSP_HIP(hipEventCreateWithFlags(&wk.done, hipEventDisableTiming));
@@ -1887,51 +1883,46 @@ static int msm_census(vsp_ctx *ctx, MsmWork &wk, const Fr *d_scalars, size_t n, 
     return VSP_OK;
 }
 
-// plan_from: another in-flight work over the SAME scalars whose digit sort / bucket plan is reused (the prover's
-// A_query, B_query(G1) and B_query(G2) all multiply by the same witness vector)
-// pre != nullptr: d_bases is the start of a precomputed table [W][stride] (slice w holds 2^(c*w) * P) and the MSM runs over
-// points [first, first + n) of every slice with ONE shared bucket set
-// glv: plain bases whose 28-bit table holds (P_i, phi(P_i)) interleaved: the scalars are split k = k1 + k2 lambda and the pipeline runs
-// over 2n points with 128-bit scalars (k_glv_split above)
-template <class F>
-static int msm_launch(vsp_ctx *ctx, MsmWork &wk, const Affine<F> *d_bases, const Fr *d_scalars, size_t n, const MsmWork *plan_from, bool dense,
-                      const MsmPre *pre, const void *plain_table28 = nullptr, bool glv = false, bool plan_only = false,
-                      unsigned batch = 1, size_t batch_stride = 0) {
-    wk.active = false; wk.n = n;
-    if (n == 0) { wk.active = true; wk.empty = true; wk.g.K = batch ? batch : 1; return VSP_OK; }
-    wk.empty = false;
-    if (batch < 1) batch = 1;
-    // a batch (MsmGeom.K): plain bases, its own digit sort through the LDS counting sort, 16-bit windows at most
-    // (a shared plan must be a batch of the same vectors: the prover's A, B1 and B2 multiply by the same K witness vectors)
-    if (batch > 1 && plan_only) return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: a batch plans and accumulates in one launch");
-    if (batch > 1 && plan_from && (plan_from->g.K != batch || plan_from->g.kstride != batch_stride || !plan_from->active || plan_from->empty))
-        return set_error(ctx, VSP_ERR_ARG, "msm: shared plan of another batch");
-    if (pre ? !(pre->glv && pre->table28) : !plain_table28) glv = false;      // the split needs the interleaved table
-    const uint32_t imul = glv ? 2u : 1u;                    // rows per point in that table
-    if (n >= ((size_t)1 << (glv ? 30 : 31))) return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: n >= 2^31");
-    hipStream_t st = wk.stream;
-    MsmGeom g;
-    size_t n_eff = n;
-    if (plan_from && plan_from->glv != glv) plan_from = nullptr;      // a plan over split scalars serves only launches that split alike
-    wk.glv = glv;
-    if (plan_from) {
-        g = plan_from->g; n_eff = plan_from->n_eff;
-        if (plan_from->n != n) return set_error(ctx, VSP_ERR_ARG, "msm: shared plan of a different size");
+#if VSP_MSM_GROUP == 1
+using F28 = Fp28; using Row28 = Affine28;                   // this group's field and base rows on 28-bit limbs
+#else
+using F28 = Fp2x28; using Row28 = Affine28x2;
+#endif
+// what the stages of one msm_launch share: the request as the kernels see it and the sizes its geometry gives
+struct MsmLaunch {
+    MsmRequest rq;                      // the caller's, with batch >= 1 and glv only where the interleaved table is there
+    hipStream_t st;
+    const MsmWork *plan_from;           // the work whose digit sort / bucket plan this launch reuses, or null
+    const void *table28;                // the bases (or table) on 28-bit limbs, or null
+    const Fr *scalars; size_t n;        // what the sort reads: with the endomorphism split 2 rq.n half-length scalars (k_glv_split)
+    long sort_mode;                     // option "msm_sort": 1 never staged, 2 staged whenever c >= 17
+    bool fused_split, fused_scans, dimbits;      // dimbits: the bucket reduction's last step is k_dimbits (which decides how wide a digit may be)
+    size_t M, Smax;                     // upper bounds on sorted entries and on bucket parts
+    unsigned per_w, nblk, gblk, ablk;
+};
+
+// geometry: the window size and the part length from the effective problem size (or from the shared plan), then the digit split
+template <class F> static int msm_geometry(vsp_ctx *ctx, MsmWork &wk, MsmLaunch &L, MsmGeom &g, size_t &n_eff) {
+    const MsmPre *pre = L.rq.pre; const bool glv = L.rq.glv; const size_t n = L.rq.n; const unsigned batch = L.rq.batch;
+    const uint32_t imul = glv ? 2u : 1u;                    // rows per point in the interleaved table
+    n_eff = n;
+    if (L.plan_from) {
+        g = L.plan_from->g; n_eff = L.plan_from->n_eff;
+        if (L.plan_from->n != n) return set_error(ctx, VSP_ERR_ARG, "msm: shared plan of a different size");
         if ((g.single != 0) != (pre != nullptr) || (pre && (g.idx_stride != pre->stride * imul || g.idx_first != pre->first * imul || g.c != pre->c)))
             return set_error(ctx, VSP_ERR_ARG, "msm: shared plan needs bases precomputed alike");
     } else {
-        VSP_TRY(ensure_w(ctx, st, wk.counters, 64));
+        VSP_TRY(ensure_w(ctx, L.st, wk.counters, 64));
         // effective problem size: scalars other than 0 and 1 (one small kernel + a read-back); the census may have been queued
         // earlier by msm_census (the prover queues all of them before any heavy kernel).  The same kernel flags scalars >= r.
         // The count only steers the window size / part length, never the result, so a slot that has seen a vector of this
         // length before plans from that earlier count and reads the fresh one at finish: no host wait on the launch path.
         wk.check_pending = false;
-        if (!dense) {
-            if (!(wk.census_pending && wk.census_n == n && wk.census_scalars == (const void *)d_scalars)) VSP_TRY(msm_census(ctx, wk, d_scalars, n, nullptr, batch, batch_stride));
+        if (!L.rq.dense) {
+            if (!(wk.census_pending && wk.census_n == n && wk.census_scalars == (const void *)L.rq.scalars)) VSP_TRY(msm_census(ctx, wk, L.rq.scalars, n, nullptr, batch, L.rq.stride));
             wk.check_pending = true;
             if (n >= 4096) {
-                long nocache = 0; { auto it = ctx->opts.find("msm_census_sync"); if (it != ctx->opts.end()) nocache = it->second; }
-                if (wk.neff_cache_n == n && !nocache) n_eff = wk.neff_cache;
+                if (wk.neff_cache_n == n && !opt(ctx, "msm_census_sync", 0)) n_eff = wk.neff_cache;
                 else {
                     VSP_HIP(hipEventSynchronize(wk.census_done));
                     uint32_t h_cnt = *(volatile uint32_t *)wk.h_census / batch;      // (a batch is counted together: the mean per vector)
@@ -1945,12 +1936,11 @@ static int msm_launch(vsp_ctx *ctx, MsmWork &wk, const Affine<F> *d_bases, const
         g.sbits = glv ? 128u : 255u;
         // 255-bit scalars: 255 / c + 1 windows cover the bits plus the carry of the signed recoding; split halves are magnitudes below
         // 2^127: ceil(128 / c) windows, and the top window's spare bit absorbs the carry
-        { long fo = 1; auto itf = ctx->opts.find("msm_fold"); if (itf != ctx->opts.end()) fo = itf->second;
-          g.fold = (!glv && fo && 255u % g.c == 0u) ? 1u : 0u; }
+        g.fold = (!glv && opt(ctx, "msm_fold", 1) && 255u % g.c == 0u) ? 1u : 0u;
         if (batch > 1 && g.c > 16) g.c = 16;
         if (batch > 1 && g.c < 7) g.c = 7;                      // (a batch of tiny vectors: not hundreds of 4-bit windows per vector)
         g.Wk = glv ? (128u + g.c - 1) / g.c : (g.fold ? 254u / g.c + 1 : g.sbits / g.c + 1);
-        g.K = batch; g.kstride = batch > 1 ? batch_stride : 0;
+        g.K = batch; g.kstride = batch > 1 ? L.rq.stride : 0;
         g.W = g.Wk * g.K;                                      // what the sort, the accumulation and the reduction see: one bucket set per (vector, window)
         g.B = 1u << (g.c - 1);
         g.lb = g.c > 16 ? g.c - 16 : 0u;
@@ -1958,7 +1948,7 @@ static int msm_launch(vsp_ctx *ctx, MsmWork &wk, const Affine<F> *d_bases, const
         g.single = pre ? 1u : 0u; g.idx_stride = pre ? (uint32_t)(pre->stride * imul) : 0u; g.idx_first = pre ? (uint32_t)(pre->first * imul) : 0u;
         g.Wr = pre ? g.K : g.W;                                // bucket sets: one per vector over a table of window multiples, else one per window
         g.G = (size_t)g.Wr * g.B;
-        long t = 0; auto it = ctx->opts.find("msm_split"); if (it != ctx->opts.end()) t = it->second;
+        const long t = opt(ctx, "msm_split", 0);
         if (pre) {
             // one bucket set: ~n_eff*W/B points per bucket; parts of T points, about 2^18 of them to fill the GPU evenly
             size_t est = n_eff * g.W / ((size_t)1 << 18);
@@ -1984,39 +1974,37 @@ static int msm_launch(vsp_ctx *ctx, MsmWork &wk, const Affine<F> *d_bases, const
         }
     }
     g.bd = 8;
-    bool last_step_dimbits = false;
-    {   // per group: a shared plan carries the window size, not the digit split.  Which last step the bucket reduction takes decides how wide a digit may be
-        MsmGeom probe = g; probe.q0 = probe.q1 = probe.q2 = 0;
-        const bool table28 = pre ? pre->table28 != nullptr : plain_table28 != nullptr;
-#if VSP_MSM_GROUP == 1
-        const bool db = table28 ? use_dimbits<Fp28>(ctx, probe) : use_dimbits<F>(ctx, probe);
-#else
-        const bool db = table28 ? use_dimbits<Fp2x28>(ctx, probe) : use_dimbits<F>(ctx, probe);
-#endif
-        split_digits<F>(g, db);
-        last_step_dimbits = db;
+    // per group: a shared plan carries the window size, not the digit split.  Which last step the bucket reduction takes decides how wide a digit may be
+    MsmGeom probe = g; probe.q0 = probe.q1 = probe.q2 = 0;
+    L.dimbits = L.table28 ? use_dimbits<F28>(ctx, probe) : use_dimbits<F>(ctx, probe);
+    split_digits<F>(g, L.dimbits);
+    return VSP_OK;
+}
+
+// the endomorphism split k = k1 + k2 lambda: a kernel of its own, or inside the digit kernel where the LDS counting sort follows (k_glv_digits)
+static int msm_split_scalars(vsp_ctx *ctx, MsmWork &wk, MsmLaunch &L, const MsmGeom &g) {
+    const size_t n = L.rq.n;
+    L.fused_split = L.rq.glv && !L.plan_from && g.c <= 16 && ((opt(ctx, "msm_fused_split", 1) && 2 * n >= ((size_t)1 << 15) && L.sort_mode != 2) || g.K > 1);
+    if (!L.rq.glv) return VSP_OK;
+    if (!L.plan_from && !L.fused_split) {
+        VSP_TRY(ensure_w(ctx, L.st, wk.glv_scalars, 2 * n * sizeof(Fr)));
+        hipLaunchKernelGGL(k_glv_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, L.st, L.rq.scalars, n, (Fr *)wk.glv_scalars.p);
+        VSP_LAUNCH_CHECK();
+        L.scalars = (const Fr *)wk.glv_scalars.p;
     }
-    wk.g = g; wk.n_eff = n_eff;
-    // the split and the digits in one kernel where the LDS counting sort follows (k_glv_digits)
-    long sort_mode_early = 0; { auto is = ctx->opts.find("msm_sort"); if (is != ctx->opts.end()) sort_mode_early = is->second; }
-    long fuse_opt = 1; { auto is = ctx->opts.find("msm_fused_split"); if (is != ctx->opts.end()) fuse_opt = is->second; }
-    const bool fused_split = glv && !plan_from && g.c <= 16 && ((fuse_opt && 2 * n >= ((size_t)1 << 15) && sort_mode_early != 2) || g.K > 1);
-    const Fr *d_scalars_orig = d_scalars; const size_t n_orig = n;
-    if (glv) {
-        if (!plan_from && !fused_split) {
-            VSP_TRY(ensure_w(ctx, st, wk.glv_scalars, 2 * n * sizeof(Fr)));
-            hipLaunchKernelGGL(k_glv_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_scalars, n, (Fr *)wk.glv_scalars.p);
-            VSP_LAUNCH_CHECK();
-            d_scalars = (const Fr *)wk.glv_scalars.p;
-        }
-        n *= 2;                                             // from here on: 2n points (P_i, phi(P_i)), 2n scalars (k1_i, k2_i)
-    }
-    if (!last_step_dimbits && ((1u << g.q0) > MsmBlock<F>::NTL || (1u << g.q2) > MsmBlock<F>::NTL)) return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: window too wide");
+    L.n = 2 * n;                                            // from here on: 2n points (P_i, phi(P_i)), 2n scalars (k1_i, k2_i)
+    return VSP_OK;
+}
+
+// buffer sizing: the pinned landing buffer of the window results, the bucket arrays, and the plan's arrays when this launch makes a plan
+template <class F> static int msm_buffers(vsp_ctx *ctx, MsmWork &wk, MsmLaunch &L, const MsmGeom &g) {
+    const hipStream_t st = L.st;
+    if (!L.dimbits && ((1u << g.q0) > MsmBlock<F>::NTL || (1u << g.q2) > MsmBlock<F>::NTL)) return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: window too wide");
     if (g.c > 23) return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: windows wider than 23 bits are not built");
-    const size_t M = n * g.W;                               // upper bound on sorted entries
-    if (M >= ((size_t)1 << 32)) return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: n * windows >= 2^32 (sorted positions are 32-bit); use wider windows or shard the points");
-    const size_t Smax = g.G + M / g.T + 1;                   // upper bound on bucket parts
-    const unsigned per_w = dims_per_w(g);
+    L.M = L.n * g.W;
+    if (L.M >= ((size_t)1 << 32)) return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: n * windows >= 2^32 (sorted positions are 32-bit); use wider windows or shard the points");
+    L.Smax = g.G + L.M / g.T + 1;
+    L.per_w = dims_per_w(g);
     { const size_t need = (size_t)g.Wr * DIMBITS_STRIDE * sizeof(XYZZ<F>);      // room for either layout of the window results
       if (need > wk.pinned_cap) {                                                // (a batch: K times the windows; the slot is idle here, nothing writes the old buffer)
           if (need > ((size_t)64 << 20)) return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: too many windows (a batch: fewer vectors per call)");
@@ -2025,182 +2013,202 @@ static int msm_launch(vsp_ctx *ctx, MsmWork &wk, const Affine<F> *d_bases, const
           if (hipHostMalloc(&nb, need, hipHostMallocDefault) != hipSuccess) return set_error(ctx, VSP_ERR_NOMEM, "msm: pinned buffer for the window results");
           hipHostFree(wk.h_pinned); wk.h_pinned = nb; wk.pinned_cap = need;
       } }
-
     VSP_TRY(ensure_w(ctx, st, wk.buckets, g.G * sizeof(XYZZ<F>)));
-    VSP_TRY(ensure_w(ctx, st, wk.partials, Smax * sizeof(XYZZ<F>)));
-    VSP_TRY(ensure_w(ctx, st, wk.dims, (size_t)g.Wr * per_w * sizeof(XYZZ<F>)));
+    VSP_TRY(ensure_w(ctx, st, wk.partials, L.Smax * sizeof(XYZZ<F>)));
+    VSP_TRY(ensure_w(ctx, st, wk.dims, (size_t)g.Wr * L.per_w * sizeof(XYZZ<F>)));
     VSP_TRY(ensure_w(ctx, st, wk.winres, (size_t)g.Wr * DIMBITS_STRIDE * sizeof(XYZZ<F>)));      // room for either layout (4 or 25 records per window)
-    XYZZ<F> *buckets = (XYZZ<F> *)wk.buckets.p, *partials = (XYZZ<F> *)wk.partials.p;
-    XYZZ<F> *dims = (XYZZ<F> *)wk.dims.p, *winres = (XYZZ<F> *)wk.winres.p;
-    const unsigned nblk = (unsigned)((n + MSM_THREADS - 1) / MSM_THREADS);
-    const unsigned gblk = (unsigned)((g.G + MSM_THREADS - 1) / MSM_THREADS);
-    const unsigned ablk = (unsigned)((Smax + MSM_THREADS - 1) / MSM_THREADS);
+    L.nblk = (unsigned)((L.n + MSM_THREADS - 1) / MSM_THREADS);
+    L.gblk = (unsigned)((g.G + MSM_THREADS - 1) / MSM_THREADS);
+    L.ablk = (unsigned)((L.Smax + MSM_THREADS - 1) / MSM_THREADS);
+    if (L.plan_from) return VSP_OK;
+    for (DevBuf *b : {&wk.cnt, &wk.off, &wk.cursor, &wk.nsub, &wk.suboff, &wk.heavy, &wk.medium}) VSP_TRY(ensure_w(ctx, st, *b, (g.G + 1) * 4));
+    VSP_TRY(ensure_w(ctx, st, wk.sorted, L.M * 4));
+    VSP_TRY(ensure_w(ctx, st, wk.partbucket, L.Smax * 4));
+    VSP_TRY(ensure_w(ctx, st, wk.perm, L.Smax * 4));
+    VSP_TRY(ensure_w(ctx, st, wk.sizehist, 2 * SZ_BINS * 4));
+    return VSP_OK;
+}
 
-    const MsmWork *pl = plan_from ? plan_from : &wk;
-    if (!plan_from) {
-        VSP_TRY(ensure_w(ctx, st, wk.cnt, (g.G + 1) * 4));
-        VSP_TRY(ensure_w(ctx, st, wk.off, (g.G + 1) * 4));
-        VSP_TRY(ensure_w(ctx, st, wk.cursor, (g.G + 1) * 4));
-        VSP_TRY(ensure_w(ctx, st, wk.nsub, (g.G + 1) * 4));
-        VSP_TRY(ensure_w(ctx, st, wk.suboff, (g.G + 1) * 4));
-        VSP_TRY(ensure_w(ctx, st, wk.heavy, (g.G + 1) * 4));
-        VSP_TRY(ensure_w(ctx, st, wk.medium, (g.G + 1) * 4));
-        VSP_TRY(ensure_w(ctx, st, wk.sorted, M * 4));
-        VSP_TRY(ensure_w(ctx, st, wk.partbucket, Smax * 4));
-        VSP_TRY(ensure_w(ctx, st, wk.perm, Smax * 4));
-        VSP_TRY(ensure_w(ctx, st, wk.sizehist, 2 * SZ_BINS * 4));
-        uint32_t *cnt = (uint32_t *)wk.cnt.p, *off = (uint32_t *)wk.off.p, *cursor = (uint32_t *)wk.cursor.p;
-        uint32_t *nsub = (uint32_t *)wk.nsub.p, *suboff = (uint32_t *)wk.suboff.p, *heavy = (uint32_t *)wk.heavy.p;
-        uint32_t *counters = (uint32_t *)wk.counters.p, *sorted = (uint32_t *)wk.sorted.p;
-        VSP_HIP(hipMemsetAsync(counters, 0, 64, st));
-        // the two scans over the buckets in one kernel each (k_scan_tiles256) while a workgroup can add up the tile sums before its own
-        // cheaply: up to 4096 tiles of 256 buckets (2^20 buckets); beyond that the three-kernel scan.  Option "msm_fused_scans" = 0: never.
-        long fs_opt = 1; { auto ifs = ctx->opts.find("msm_fused_scans"); if (ifs != ctx->opts.end()) fs_opt = ifs->second; }
-        const bool fused_scans = fs_opt && gblk <= 4096;
-        const bool lds_sort = g.c <= 16 && (n >= ((size_t)1 << 15) || g.K > 1);
-        const bool wide_sort = g.c > 16 && n >= ((size_t)1 << 15);
-        long sort_mode = 0; { auto is = ctx->opts.find("msm_sort"); if (is != ctx->opts.end()) sort_mode = is->second; }      // 1: never staged, 2: staged whenever c >= 17
-        const bool staged_sort = g.K == 1 && g.c >= 12 && g.c <= 23 && n >= 4096 && sort_mode != 1 && (sort_mode == 2 || (g.c >= 17 && n >= ((size_t)1 << 20)));
-        if (staged_sort) {
-            // 8 + 8 bits through LDS tiles, the rest inside LDS (k_ms_*): every global write is a run of whole lines
-            // the bits of the bucket index (c - 1): 8 for the first pass, rb <= 6 for the last step, the rest (1 .. 8) for the second pass;
-            // rb as large as keeps the last step's segments at ~1024 entries (2^23 points, c = 19: 2^13 segments per window, not 2^16
-            // of 128 entries each -- the last step paid per segment: 1.4 ms)
-            const unsigned parents = g.single ? 1u : g.W;
-            const size_t npp = g.single ? (size_t)g.W * n : n;
-            unsigned rb = g.c > 17 ? g.c - 17 : 0;          // (the staged sort forced below 17 bits, "msm_sort" = 2: no minimum)
-            { const unsigned hi = g.c - 10 < 6 ? g.c - 10 : 6; const unsigned lg = ceil_log2(npp / 1024 + 1);
-              const unsigned want = g.c - 1 > lg ? g.c - 1 - lg : 0; if (want > rb) rb = want; if (rb > hi) rb = hi; }
-            const unsigned bits2 = g.c - 9 - rb, nb2 = 1u << bits2;
-            if (bits2 < 1 || bits2 > 8) return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: staged sort: window size outside its range");
-            const unsigned chunks = (unsigned)((npp + MS_CHUNK - 1) / MS_CHUNK);
-            const size_t H1 = (size_t)parents * 257 * chunks, S1 = (size_t)parents * 256, H2 = S1 * nb2;
-            const size_t P2 = (M + MS_CHUNK - 1) / MS_CHUNK + S1;      // pieces of the second pass: at most one partial piece per segment
-            VSP_TRY(ensure_w(ctx, st, wk.pairs_a, M * sizeof(uint2)));
-            VSP_TRY(ensure_w(ctx, st, wk.pairs_b, M * sizeof(uint2)));
-            VSP_TRY(ensure_w(ctx, st, wk.ms_h1, (H1 + 1) * 4)); VSP_TRY(ensure_w(ctx, st, wk.ms_h1s, (H1 + 1) * 4));
-            const size_t P3 = (M + MS_CHUNK - 1) / MS_CHUNK + M / MS_SEG_LONG + 1;      // pieces of the third: only segments longer than MS_SEG_LONG have any
-            // ms_h2: the second pass's piece histograms | the third's | piece counts | pbase2 | pbase3
-            VSP_TRY(ensure_w(ctx, st, wk.ms_h2, (P2 * 256 + P3 * 64 + (H2 + 1) + (S1 + 1) + (H2 + 1)) * 4)); VSP_TRY(ensure_w(ctx, st, wk.ms_h2s, (H2 + 1) * 4));
-            uint2 *pa = (uint2 *)wk.pairs_a.p, *pb = (uint2 *)wk.pairs_b.p;
-            uint32_t *h1 = (uint32_t *)wk.ms_h1.p, *h1s = (uint32_t *)wk.ms_h1s.p, *h2 = (uint32_t *)wk.ms_h2.p, *h2s = (uint32_t *)wk.ms_h2s.p;
-            uint32_t *h3 = h2 + P2 * 256, *pcount = h3 + P3 * 64, *pbase2 = pcount + (H2 + 1), *pbase3 = pbase2 + (S1 + 1);
-            hipLaunchKernelGGL(k_ms_pairs, dim3(nblk), dim3(MSM_THREADS), 0, st, d_scalars, g, pa);
-            MsPass p1; p1.npp = npp; p1.parents = parents; p1.chunks = chunks; p1.seg = nullptr; p1.seg_stride = 0; p1.pbase = nullptr; p1.S = 0;
-            p1.shift = g.c - 9; p1.mask = 0xFFu; p1.bins = 256; p1.slots = 256;
-            MsPass p2 = p1; p2.seg = h1s; p2.seg_stride = chunks; p2.pbase = pbase2; p2.S = (unsigned)S1; p2.shift = rb; p2.mask = nb2 - 1u; p2.bins = nb2;
-            MsPass p3 = p1; p3.seg = h2s; p3.seg_stride = 1; p3.pbase = pbase3; p3.S = (unsigned)H2; p3.shift = 0; p3.mask = (1u << rb) - 1u; p3.bins = 1u << rb; p3.slots = 64;
-            hipLaunchKernelGGL(k_ms_hist, dim3(parents * chunks), dim3(MS_THREADS), 0, st, (const uint2 *)pa, p1, h1);
-            VSP_LAUNCH_CHECK();
-            VSP_TRY(exclusive_scan_w(ctx, wk, h1, H1, h1s, nullptr));
-            hipLaunchKernelGGL(k_ms_scatter, dim3(parents * chunks), dim3(MS_THREADS), 0, st, (const uint2 *)pa, pb, (uint32_t *)nullptr, p1, (const uint32_t *)h1s, (const uint32_t *)nullptr);
-            // second pass over the segments of the first ((parent, top 8 bits): h1s[segment * chunks] is where one starts; the parked entries
-            // follow the last one at h1s[S1 * chunks]), in pieces of MS_CHUNK elements
-            hipLaunchKernelGGL(k_ms_piece_counts, dim3((unsigned)((S1 + MSM_THREADS) / MSM_THREADS)), dim3(MSM_THREADS), 0, st, (const uint32_t *)h1s, chunks, S1, 0u, pcount);
-            VSP_TRY(exclusive_scan_w(ctx, wk, pcount, S1 + 1, pbase2, nullptr));
-            hipLaunchKernelGGL(k_ms_hist, dim3((unsigned)P2), dim3(MS_THREADS), 0, st, (const uint2 *)pb, p2, h2);
-            hipLaunchKernelGGL(k_ms_cursors, dim3((unsigned)S1), dim3(256), 0, st, h2, (const uint32_t *)pbase2, (const uint32_t *)h1s, chunks, (unsigned)S1, nb2, h2s);
-            hipLaunchKernelGGL(k_ms_scatter, dim3((unsigned)P2), dim3(MS_THREADS), 0, st, (const uint2 *)pb, pa, (uint32_t *)nullptr, p2, (const uint32_t *)h2, (const uint32_t *)h2s);
-            // what is left of the bucket index: inside one wave per segment (k_ms_final), or -- segments longer than MS_SEG_LONG -- a third pass in pieces
-            hipLaunchKernelGGL(k_ms_piece_counts, dim3((unsigned)((H2 + MSM_THREADS) / MSM_THREADS)), dim3(MSM_THREADS), 0, st, (const uint32_t *)h2s, 1u, H2, MS_SEG_LONG, pcount);
-            VSP_TRY(exclusive_scan_w(ctx, wk, pcount, H2 + 1, pbase3, nullptr));
-            hipLaunchKernelGGL(k_ms_hist, dim3((unsigned)P3), dim3(MS_THREADS), 0, st, (const uint2 *)pa, p3, h3);
-            { size_t wg = (H2 + 3) / 4; if (wg > 65536) wg = 65536;
-              hipLaunchKernelGGL(k_ms_final, dim3((unsigned)wg), dim3(256), 0, st, (const uint2 *)pa, (const uint32_t *)h2s, H2, rb, (const uint32_t *)pbase3, h3, cnt, off, sorted); }
-            hipLaunchKernelGGL(k_ms_scatter, dim3((unsigned)P3), dim3(MS_THREADS), 0, st, (const uint2 *)pa, (uint2 *)nullptr, sorted, p3, (const uint32_t *)h3, (const uint32_t *)nullptr);
-            VSP_LAUNCH_CHECK();
-        } else if (wide_sort) {
-            // two passes: the LDS counting sort over the HIGH 15 bits of the bucket index (as a 16-bit window), then k_segment_sort over the low ones
-            MsmGeom gh = g; gh.c = 16; gh.B = 1u << 15; gh.lb = 0; gh.G = (size_t)g.Wr << 15;
-            unsigned nchunks = 256 / g.W; if (nchunks < 1) nchunks = 1;
-            while (nchunks > 1 && n / nchunks < 8192) nchunks >>= 1;
-            const size_t chunk_len = (n + nchunks - 1) / nchunks;
-            VSP_TRY(ensure_w(ctx, st, wk.digits, (size_t)g.W * n * 3));
-            VSP_TRY(ensure_w(ctx, st, wk.blockhist, (size_t)nchunks * g.W * gh.B * sizeof(uint32_t)));
-            VSP_TRY(ensure_w(ctx, st, wk.cnt_hi, (gh.G + 1) * 4));
-            VSP_TRY(ensure_w(ctx, st, wk.off_hi, (gh.G + 1) * 4));
-            VSP_TRY(ensure_w(ctx, st, wk.tmp_sorted, M * 4));
-            VSP_TRY(ensure_w(ctx, st, wk.tmp_lo, M));
-            uint16_t *hi = (uint16_t *)wk.digits.p; uint8_t *lo = (uint8_t *)(hi + (size_t)g.W * n);
-            uint32_t *blockhist = (uint32_t *)wk.blockhist.p, *cnt_hi = (uint32_t *)wk.cnt_hi.p, *off_hi = (uint32_t *)wk.off_hi.p;
-            const size_t lds_bytes = (size_t)gh.B * sizeof(uint32_t);
-            bool &attr_set = ctx->lds_attr_set[VSP_MSM_GROUP - 1];
-            if (!attr_set) {
-                VSP_HIP(hipFuncSetAttribute((const void *)k_count_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                VSP_HIP(hipFuncSetAttribute((const void *)k_scatter_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                attr_set = true;
-            }
-            hipLaunchKernelGGL(k_digits_wide, dim3(nblk), dim3(MSM_THREADS), 0, st, d_scalars, g, hi, lo);
-            hipLaunchKernelGGL(k_count_lds, dim3(nchunks * g.W), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)hi, gh, nchunks, chunk_len, blockhist);
-            hipLaunchKernelGGL(k_chunk_prefix, dim3((unsigned)((gh.G + MSM_THREADS - 1) / MSM_THREADS)), dim3(MSM_THREADS), 0, st, blockhist, g.single ? nchunks * g.W : nchunks, gh.G, cnt_hi, (uint32_t *)nullptr, gh.G);
-            VSP_LAUNCH_CHECK();
-            VSP_TRY(exclusive_scan_w(ctx, wk, cnt_hi, gh.G, off_hi, nullptr));
-            hipLaunchKernelGGL(k_scatter_lds, dim3(nchunks * g.W), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)hi, (const uint8_t *)nullptr, gh, nchunks, chunk_len,
-                               (const uint32_t *)blockhist, (const uint32_t *)off_hi, (uint32_t *)wk.tmp_sorted.p, (const uint8_t *)lo, (uint8_t *)wk.tmp_lo.p);
-            { size_t wg = (gh.G + 3) / 4; if (wg > 65536) wg = 65536;
-              hipLaunchKernelGGL(k_segment_sort, dim3((unsigned)wg), dim3(256), 0, st, (const uint32_t *)wk.tmp_sorted.p, (const uint8_t *)wk.tmp_lo.p, (const uint32_t *)off_hi,
-                                 gh.G, g.lb, cnt, off, sorted); }
-            VSP_LAUNCH_CHECK();
-        } else if (lds_sort) {
-            unsigned nchunks = 256 / g.W; if (nchunks < 1) nchunks = 1;
-            while (nchunks > 1 && n / nchunks < 8192) nchunks >>= 1;
-            const bool batch_single = g.single && g.K > 1;          // K bucket sets, each fed by its vector's Wk windows: their histograms must lie together
-            if (batch_single) nchunks = 1;
-            const size_t chunk_len = (n + nchunks - 1) / nchunks;
-            VSP_TRY(ensure_w(ctx, st, wk.digits, (size_t)g.W * n * sizeof(uint16_t) + (size_t)g.K * n));      // + one sign byte per scalar (endomorphism split), per vector of a batch
-            VSP_TRY(ensure_w(ctx, st, wk.blockhist, (size_t)nchunks * g.W * g.B * sizeof(uint32_t)));
-            uint16_t *digits = (uint16_t *)wk.digits.p; uint32_t *blockhist = (uint32_t *)wk.blockhist.p;
-            uint8_t *flips = (uint8_t *)(digits + (size_t)g.W * n);
-            const size_t lds_bytes = (size_t)g.B * sizeof(uint32_t);
-            bool &attr_set = ctx->lds_attr_set[VSP_MSM_GROUP - 1];      // per context (= per device) and per code object
-            if (!attr_set) {
-                VSP_HIP(hipFuncSetAttribute((const void *)k_count_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                VSP_HIP(hipFuncSetAttribute((const void *)k_scatter_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                attr_set = true;
-            }
-            if (fused_split) hipLaunchKernelGGL(k_glv_digits, dim3((unsigned)((n_orig + MSM_THREADS - 1) / MSM_THREADS), g.K), dim3(MSM_THREADS), 0, st, d_scalars_orig, n_orig, g, digits, flips);
-            else hipLaunchKernelGGL(k_digits, dim3(nblk, g.K), dim3(MSM_THREADS), 0, st, d_scalars, g, digits, flips);
-            hipLaunchKernelGGL(k_count_lds, dim3(nchunks * g.W), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)digits, g, nchunks, chunk_len, blockhist);
-            VSP_TRY(ensure_w(ctx, st, wk.blocksum, ((size_t)gblk + 2) * sizeof(uint32_t)));      // (the three-kernel scan shares this buffer and may have regrown it)
-            uint32_t *tilesum = (uint32_t *)wk.blocksum.p;
-            hipLaunchKernelGGL(k_chunk_prefix, dim3(gblk), dim3(MSM_THREADS), 0, st, blockhist, batch_single ? g.Wk : (g.single ? nchunks * g.W : nchunks), g.G, cnt,
-                               fused_scans ? tilesum : (uint32_t *)nullptr, batch_single ? (size_t)g.B : g.G);
-            VSP_LAUNCH_CHECK();
-            if (fused_scans) hipLaunchKernelGGL(k_scan_tiles256, dim3(gblk), dim3(MSM_THREADS), 0, st, (const uint32_t *)cnt, g.G, (const uint32_t *)tilesum, off, (uint32_t *)nullptr);
-            else VSP_TRY(exclusive_scan_w(ctx, wk, cnt, g.G, off, nullptr));
-            hipLaunchKernelGGL(k_scatter_lds, dim3(nchunks * g.W), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)digits, (const uint8_t *)flips, g, nchunks, chunk_len,
-                               (const uint32_t *)blockhist, (const uint32_t *)off, sorted, (const uint8_t *)nullptr, (uint8_t *)nullptr);
-            VSP_LAUNCH_CHECK();
-        } else {
-            VSP_HIP(hipMemsetAsync(cnt, 0, (g.G + 1) * 4, st));
-            hipLaunchKernelGGL(k_count, dim3(nblk), dim3(MSM_THREADS), 0, st, d_scalars, g, cnt);
-            VSP_LAUNCH_CHECK();
-            VSP_TRY(exclusive_scan_w(ctx, wk, cnt, g.G, off, cursor));
-            hipLaunchKernelGGL(k_scatter, dim3(nblk), dim3(MSM_THREADS), 0, st, d_scalars, g, cursor, sorted);
-            VSP_LAUNCH_CHECK();
-        }
-        VSP_TRY(ensure_w(ctx, st, wk.blocksum, ((size_t)gblk + 2) * sizeof(uint32_t)));
-        uint32_t *tilesum = (uint32_t *)wk.blocksum.p;
-        uint32_t *size_hist = (uint32_t *)wk.sizehist.p, *bin_cursor = size_hist + SZ_BINS;
-        uint32_t *redo0 = nullptr;                              // the accumulation's hand-back counter, cleared by k_plan when this launch goes on to accumulate over its own plan
-        if (!plan_only && (pre ? pre->table28 : plain_table28)) { VSP_TRY(ensure_w(ctx, st, wk.redo, (Smax + 1) * sizeof(uint32_t))); redo0 = (uint32_t *)wk.redo.p; }
-        hipLaunchKernelGGL(k_plan, dim3(gblk), dim3(MSM_THREADS), 0, st, (const uint32_t *)cnt, g.G, g.T, nsub, heavy, (uint32_t *)wk.medium.p, counters, fused_scans ? tilesum : (uint32_t *)nullptr,
-                           size_hist, 2u * SZ_BINS, redo0);
-        VSP_LAUNCH_CHECK();
-        if (fused_scans) hipLaunchKernelGGL(k_scan_tiles256, dim3(gblk), dim3(MSM_THREADS), 0, st, (const uint32_t *)nsub, g.G, (const uint32_t *)tilesum, suboff, (uint32_t *)nullptr);
-        else VSP_TRY(exclusive_scan_w(ctx, wk, nsub, g.G, suboff, nullptr));
-        uint32_t *part_bucket = (uint32_t *)wk.partbucket.p, *perm = (uint32_t *)wk.perm.p;
-        hipLaunchKernelGGL(k_partinfo, dim3(ablk), dim3(256), 0, st, (const uint32_t *)cnt, (const uint32_t *)suboff, g.G, g.T, part_bucket, size_hist);
-        hipLaunchKernelGGL(k_binscan, dim3(1), dim3(SZ_BINS), 0, st, (const uint32_t *)size_hist, bin_cursor);
-        hipLaunchKernelGGL(k_partsort, dim3(ablk), dim3(256), 0, st, (const uint32_t *)cnt, (const uint32_t *)suboff, (const uint32_t *)part_bucket, g.G, g.T, bin_cursor, perm);
-        VSP_LAUNCH_CHECK();
-        VSP_HIP(hipEventRecord(wk.plan_ready, st));
-    } else {
-        VSP_HIP(hipStreamWaitEvent(st, plan_from->plan_ready, 0));
-    }
-    if (plan_only) return VSP_OK;                           // the accumulation follows in a later launch over this slot's own plan
+// the LDS counting sort's two kernels take up to 128 KiB of LDS: allowed once per context (= per device) and per code object
+static int lds_sort_attrs(vsp_ctx *ctx) {
+    bool &attr_set = ctx->lds_attr_set[VSP_MSM_GROUP - 1];
+    if (attr_set) return VSP_OK;
+    VSP_HIP(hipFuncSetAttribute((const void *)k_count_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    VSP_HIP(hipFuncSetAttribute((const void *)k_scatter_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    attr_set = true;
+    return VSP_OK;
+}
+// chunks per window of the LDS counting sort: about 256 workgroups over all windows, none with fewer than 8192 scalars
+static unsigned lds_chunks(const MsmGeom &g, size_t n) {
+    unsigned nchunks = 256 / g.W; if (nchunks < 1) nchunks = 1;
+    while (nchunks > 1 && n / nchunks < 8192) nchunks >>= 1;
+    return nchunks;
+}
 
-    const void *table28 = pre ? pre->table28 : plain_table28;
+// staged sort: 8 + 8 bits through LDS tiles, the rest inside LDS (k_ms_*): every global write is a run of whole lines
+static int msm_sort_staged(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const MsmGeom &g) {
+    const hipStream_t st = L.st; const size_t M = L.M;
+    uint32_t *cnt = (uint32_t *)wk.cnt.p, *off = (uint32_t *)wk.off.p, *sorted = (uint32_t *)wk.sorted.p;
+    // the bits of the bucket index (c - 1): 8 for the first pass, rb <= 6 for the last step, the rest (1 .. 8) for the second pass;
+    // rb as large as keeps the last step's segments at ~1024 entries (2^23 points, c = 19: 2^13 segments per window, not 2^16
+    // of 128 entries each -- the last step paid per segment: 1.4 ms)
+    const unsigned parents = g.single ? 1u : g.W;
+    const size_t npp = g.single ? (size_t)g.W * L.n : L.n;
+    unsigned rb = g.c > 17 ? g.c - 17 : 0;          // (the staged sort forced below 17 bits, "msm_sort" = 2: no minimum)
+    { const unsigned hi = g.c - 10 < 6 ? g.c - 10 : 6; const unsigned lg = ceil_log2(npp / 1024 + 1);
+      const unsigned want = g.c - 1 > lg ? g.c - 1 - lg : 0; if (want > rb) rb = want; if (rb > hi) rb = hi; }
+    const unsigned bits2 = g.c - 9 - rb, nb2 = 1u << bits2;
+    if (bits2 < 1 || bits2 > 8) return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: staged sort: window size outside its range");
+    const unsigned chunks = (unsigned)((npp + MS_CHUNK - 1) / MS_CHUNK);
+    const size_t H1 = (size_t)parents * 257 * chunks, S1 = (size_t)parents * 256, H2 = S1 * nb2;
+    const size_t P2 = (M + MS_CHUNK - 1) / MS_CHUNK + S1;      // pieces of the second pass: at most one partial piece per segment
+    VSP_TRY(ensure_w(ctx, st, wk.pairs_a, M * sizeof(uint2)));
+    VSP_TRY(ensure_w(ctx, st, wk.pairs_b, M * sizeof(uint2)));
+    VSP_TRY(ensure_w(ctx, st, wk.ms_h1, (H1 + 1) * 4)); VSP_TRY(ensure_w(ctx, st, wk.ms_h1s, (H1 + 1) * 4));
+    const size_t P3 = (M + MS_CHUNK - 1) / MS_CHUNK + M / MS_SEG_LONG + 1;      // pieces of the third: only segments longer than MS_SEG_LONG have any
+    // ms_h2: the second pass's piece histograms | the third's | piece counts | pbase2 | pbase3
+    VSP_TRY(ensure_w(ctx, st, wk.ms_h2, (P2 * 256 + P3 * 64 + (H2 + 1) + (S1 + 1) + (H2 + 1)) * 4)); VSP_TRY(ensure_w(ctx, st, wk.ms_h2s, (H2 + 1) * 4));
+    uint2 *pa = (uint2 *)wk.pairs_a.p, *pb = (uint2 *)wk.pairs_b.p;
+    uint32_t *h1 = (uint32_t *)wk.ms_h1.p, *h1s = (uint32_t *)wk.ms_h1s.p, *h2 = (uint32_t *)wk.ms_h2.p, *h2s = (uint32_t *)wk.ms_h2s.p;
+    uint32_t *h3 = h2 + P2 * 256, *pcount = h3 + P3 * 64, *pbase2 = pcount + (H2 + 1), *pbase3 = pbase2 + (S1 + 1);
+    hipLaunchKernelGGL(k_ms_pairs, dim3(L.nblk), dim3(MSM_THREADS), 0, st, L.scalars, g, pa);
+    MsPass p1; p1.npp = npp; p1.parents = parents; p1.chunks = chunks; p1.seg = nullptr; p1.seg_stride = 0; p1.pbase = nullptr; p1.S = 0;
+    p1.shift = g.c - 9; p1.mask = 0xFFu; p1.bins = 256; p1.slots = 256;
+    MsPass p2 = p1; p2.seg = h1s; p2.seg_stride = chunks; p2.pbase = pbase2; p2.S = (unsigned)S1; p2.shift = rb; p2.mask = nb2 - 1u; p2.bins = nb2;
+    MsPass p3 = p1; p3.seg = h2s; p3.seg_stride = 1; p3.pbase = pbase3; p3.S = (unsigned)H2; p3.shift = 0; p3.mask = (1u << rb) - 1u; p3.bins = 1u << rb; p3.slots = 64;
+    hipLaunchKernelGGL(k_ms_hist, dim3(parents * chunks), dim3(MS_THREADS), 0, st, (const uint2 *)pa, p1, h1);
+    VSP_LAUNCH_CHECK();
+    VSP_TRY(exclusive_scan_w(ctx, wk, h1, H1, h1s, nullptr));
+    hipLaunchKernelGGL(k_ms_scatter, dim3(parents * chunks), dim3(MS_THREADS), 0, st, (const uint2 *)pa, pb, (uint32_t *)nullptr, p1, (const uint32_t *)h1s, (const uint32_t *)nullptr);
+    // second pass over the segments of the first ((parent, top 8 bits): h1s[segment * chunks] is where one starts; the parked entries
+    // follow the last one at h1s[S1 * chunks]), in pieces of MS_CHUNK elements
+    hipLaunchKernelGGL(k_ms_piece_counts, dim3((unsigned)((S1 + MSM_THREADS) / MSM_THREADS)), dim3(MSM_THREADS), 0, st, (const uint32_t *)h1s, chunks, S1, 0u, pcount);
+    VSP_TRY(exclusive_scan_w(ctx, wk, pcount, S1 + 1, pbase2, nullptr));
+    hipLaunchKernelGGL(k_ms_hist, dim3((unsigned)P2), dim3(MS_THREADS), 0, st, (const uint2 *)pb, p2, h2);
+    hipLaunchKernelGGL(k_ms_cursors, dim3((unsigned)S1), dim3(256), 0, st, h2, (const uint32_t *)pbase2, (const uint32_t *)h1s, chunks, (unsigned)S1, nb2, h2s);
+    hipLaunchKernelGGL(k_ms_scatter, dim3((unsigned)P2), dim3(MS_THREADS), 0, st, (const uint2 *)pb, pa, (uint32_t *)nullptr, p2, (const uint32_t *)h2, (const uint32_t *)h2s);
+    // what is left of the bucket index: inside one wave per segment (k_ms_final), or -- segments longer than MS_SEG_LONG -- a third pass in pieces
+    hipLaunchKernelGGL(k_ms_piece_counts, dim3((unsigned)((H2 + MSM_THREADS) / MSM_THREADS)), dim3(MSM_THREADS), 0, st, (const uint32_t *)h2s, 1u, H2, MS_SEG_LONG, pcount);
+    VSP_TRY(exclusive_scan_w(ctx, wk, pcount, H2 + 1, pbase3, nullptr));
+    hipLaunchKernelGGL(k_ms_hist, dim3((unsigned)P3), dim3(MS_THREADS), 0, st, (const uint2 *)pa, p3, h3);
+    { size_t wg = (H2 + 3) / 4; if (wg > 65536) wg = 65536;
+      hipLaunchKernelGGL(k_ms_final, dim3((unsigned)wg), dim3(256), 0, st, (const uint2 *)pa, (const uint32_t *)h2s, H2, rb, (const uint32_t *)pbase3, h3, cnt, off, sorted); }
+    hipLaunchKernelGGL(k_ms_scatter, dim3((unsigned)P3), dim3(MS_THREADS), 0, st, (const uint2 *)pa, (uint2 *)nullptr, sorted, p3, (const uint32_t *)h3, (const uint32_t *)nullptr);
+    VSP_LAUNCH_CHECK();
+    return VSP_OK;
+}
+
+// windows wider than 16 bits: the LDS counting sort over the HIGH 15 bits of the bucket index (as a 16-bit window), then k_segment_sort over the low ones
+static int msm_sort_wide(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const MsmGeom &g) {
+    const hipStream_t st = L.st; const size_t n = L.n;
+    MsmGeom gh = g; gh.c = 16; gh.B = 1u << 15; gh.lb = 0; gh.G = (size_t)g.Wr << 15;
+    const unsigned nchunks = lds_chunks(g, n);
+    const size_t chunk_len = (n + nchunks - 1) / nchunks;
+    VSP_TRY(ensure_w(ctx, st, wk.digits, (size_t)g.W * n * 3));
+    VSP_TRY(ensure_w(ctx, st, wk.blockhist, (size_t)nchunks * g.W * gh.B * sizeof(uint32_t)));
+    VSP_TRY(ensure_w(ctx, st, wk.cnt_hi, (gh.G + 1) * 4));
+    VSP_TRY(ensure_w(ctx, st, wk.off_hi, (gh.G + 1) * 4));
+    VSP_TRY(ensure_w(ctx, st, wk.tmp_sorted, L.M * 4));
+    VSP_TRY(ensure_w(ctx, st, wk.tmp_lo, L.M));
+    uint16_t *hi = (uint16_t *)wk.digits.p; uint8_t *lo = (uint8_t *)(hi + (size_t)g.W * n);
+    uint32_t *blockhist = (uint32_t *)wk.blockhist.p, *cnt_hi = (uint32_t *)wk.cnt_hi.p, *off_hi = (uint32_t *)wk.off_hi.p;
+    const size_t lds_bytes = (size_t)gh.B * sizeof(uint32_t);
+    VSP_TRY(lds_sort_attrs(ctx));
+    hipLaunchKernelGGL(k_digits_wide, dim3(L.nblk), dim3(MSM_THREADS), 0, st, L.scalars, g, hi, lo);
+    hipLaunchKernelGGL(k_count_lds, dim3(nchunks * g.W), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)hi, gh, nchunks, chunk_len, blockhist);
+    hipLaunchKernelGGL(k_chunk_prefix, dim3((unsigned)((gh.G + MSM_THREADS - 1) / MSM_THREADS)), dim3(MSM_THREADS), 0, st, blockhist, g.single ? nchunks * g.W : nchunks, gh.G, cnt_hi, (uint32_t *)nullptr, gh.G);
+    VSP_LAUNCH_CHECK();
+    VSP_TRY(exclusive_scan_w(ctx, wk, cnt_hi, gh.G, off_hi, nullptr));
+    hipLaunchKernelGGL(k_scatter_lds, dim3(nchunks * g.W), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)hi, (const uint8_t *)nullptr, gh, nchunks, chunk_len,
+                       (const uint32_t *)blockhist, (const uint32_t *)off_hi, (uint32_t *)wk.tmp_sorted.p, (const uint8_t *)lo, (uint8_t *)wk.tmp_lo.p);
+    { size_t wg = (gh.G + 3) / 4; if (wg > 65536) wg = 65536;
+      hipLaunchKernelGGL(k_segment_sort, dim3((unsigned)wg), dim3(256), 0, st, (const uint32_t *)wk.tmp_sorted.p, (const uint8_t *)wk.tmp_lo.p, (const uint32_t *)off_hi,
+                         gh.G, g.lb, (uint32_t *)wk.cnt.p, (uint32_t *)wk.off.p, (uint32_t *)wk.sorted.p); }
+    VSP_LAUNCH_CHECK();
+    return VSP_OK;
+}
+
+// the LDS counting sort (windows of at most 16 bits: large problems and every batch)
+static int msm_sort_lds(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const MsmGeom &g) {
+    const hipStream_t st = L.st; const size_t n = L.n;
+    uint32_t *cnt = (uint32_t *)wk.cnt.p, *off = (uint32_t *)wk.off.p;
+    const bool batch_single = g.single && g.K > 1;          // K bucket sets, each fed by its vector's Wk windows: their histograms must lie together
+    const unsigned nchunks = batch_single ? 1u : lds_chunks(g, n);
+    const size_t chunk_len = (n + nchunks - 1) / nchunks;
+    VSP_TRY(ensure_w(ctx, st, wk.digits, (size_t)g.W * n * sizeof(uint16_t) + (size_t)g.K * n));      // + one sign byte per scalar (endomorphism split), per vector of a batch
+    VSP_TRY(ensure_w(ctx, st, wk.blockhist, (size_t)nchunks * g.W * g.B * sizeof(uint32_t)));
+    uint16_t *digits = (uint16_t *)wk.digits.p; uint32_t *blockhist = (uint32_t *)wk.blockhist.p;
+    uint8_t *flips = (uint8_t *)(digits + (size_t)g.W * n);
+    const size_t lds_bytes = (size_t)g.B * sizeof(uint32_t);
+    VSP_TRY(lds_sort_attrs(ctx));
+    if (L.fused_split) hipLaunchKernelGGL(k_glv_digits, dim3((unsigned)((L.rq.n + MSM_THREADS - 1) / MSM_THREADS), g.K), dim3(MSM_THREADS), 0, st, L.rq.scalars, L.rq.n, g, digits, flips);
+    else hipLaunchKernelGGL(k_digits, dim3(L.nblk, g.K), dim3(MSM_THREADS), 0, st, L.scalars, g, digits, flips);
+    hipLaunchKernelGGL(k_count_lds, dim3(nchunks * g.W), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)digits, g, nchunks, chunk_len, blockhist);
+    VSP_TRY(ensure_w(ctx, st, wk.blocksum, ((size_t)L.gblk + 2) * sizeof(uint32_t)));      // (the three-kernel scan shares this buffer and may have regrown it)
+    uint32_t *tilesum = (uint32_t *)wk.blocksum.p;
+    hipLaunchKernelGGL(k_chunk_prefix, dim3(L.gblk), dim3(MSM_THREADS), 0, st, blockhist, batch_single ? g.Wk : (g.single ? nchunks * g.W : nchunks), g.G, cnt,
+                       L.fused_scans ? tilesum : (uint32_t *)nullptr, batch_single ? (size_t)g.B : g.G);
+    VSP_LAUNCH_CHECK();
+    if (L.fused_scans) hipLaunchKernelGGL(k_scan_tiles256, dim3(L.gblk), dim3(MSM_THREADS), 0, st, (const uint32_t *)cnt, g.G, (const uint32_t *)tilesum, off, (uint32_t *)nullptr);
+    else VSP_TRY(exclusive_scan_w(ctx, wk, cnt, g.G, off, nullptr));
+    hipLaunchKernelGGL(k_scatter_lds, dim3(nchunks * g.W), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)digits, (const uint8_t *)flips, g, nchunks, chunk_len,
+                       (const uint32_t *)blockhist, (const uint32_t *)off, (uint32_t *)wk.sorted.p, (const uint8_t *)nullptr, (uint8_t *)nullptr);
+    VSP_LAUNCH_CHECK();
+    return VSP_OK;
+}
+
+// the digit sort: the entries of every bucket together (cnt, off, sorted), by one of four sorts
+static int msm_digit_sort(vsp_ctx *ctx, MsmWork &wk, MsmLaunch &L, const MsmGeom &g) {
+    VSP_HIP(hipMemsetAsync(wk.counters.p, 0, 64, L.st));
+    // the two scans over the buckets in one kernel each (k_scan_tiles256) while a workgroup can add up the tile sums before its own
+    // cheaply: up to 4096 tiles of 256 buckets (2^20 buckets); beyond that the three-kernel scan.  Option "msm_fused_scans" = 0: never.
+    L.fused_scans = opt(ctx, "msm_fused_scans", 1) && L.gblk <= 4096;
+    const size_t n = L.n;
+    const bool staged = g.K == 1 && g.c >= 12 && g.c <= 23 && n >= 4096 && L.sort_mode != 1 && (L.sort_mode == 2 || (g.c >= 17 && n >= ((size_t)1 << 20)));
+    if (staged) return msm_sort_staged(ctx, wk, L, g);
+    if (g.c > 16 && n >= ((size_t)1 << 15)) return msm_sort_wide(ctx, wk, L, g);
+    if (g.c <= 16 && (n >= ((size_t)1 << 15) || g.K > 1)) return msm_sort_lds(ctx, wk, L, g);
+    // small problems: a global counting sort
+    uint32_t *cnt = (uint32_t *)wk.cnt.p, *cursor = (uint32_t *)wk.cursor.p;
+    VSP_HIP(hipMemsetAsync(cnt, 0, (g.G + 1) * 4, L.st));
+    hipLaunchKernelGGL(k_count, dim3(L.nblk), dim3(MSM_THREADS), 0, L.st, L.scalars, g, cnt);
+    VSP_LAUNCH_CHECK();
+    VSP_TRY(exclusive_scan_w(ctx, wk, cnt, g.G, (uint32_t *)wk.off.p, cursor));
+    hipLaunchKernelGGL(k_scatter, dim3(L.nblk), dim3(MSM_THREADS), 0, L.st, L.scalars, g, cursor, (uint32_t *)wk.sorted.p);
+    VSP_LAUNCH_CHECK();
+    return VSP_OK;
+}
+
+// the bucket plan over the sorted entries: parts of at most T points per bucket, ordered by size (k_plan .. k_partsort)
+static int msm_bucket_plan(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const MsmGeom &g) {
+    const hipStream_t st = L.st;
+    const uint32_t *cnt = (const uint32_t *)wk.cnt.p;
+    uint32_t *nsub = (uint32_t *)wk.nsub.p, *suboff = (uint32_t *)wk.suboff.p;
+    VSP_TRY(ensure_w(ctx, st, wk.blocksum, ((size_t)L.gblk + 2) * sizeof(uint32_t)));
+    uint32_t *tilesum = (uint32_t *)wk.blocksum.p;
+    uint32_t *size_hist = (uint32_t *)wk.sizehist.p, *bin_cursor = size_hist + SZ_BINS;
+    uint32_t *redo0 = nullptr;                              // the accumulation's hand-back counter, cleared by k_plan when this launch goes on to accumulate over its own plan
+    if (!L.rq.plan_only && L.table28) { VSP_TRY(ensure_w(ctx, st, wk.redo, (L.Smax + 1) * sizeof(uint32_t))); redo0 = (uint32_t *)wk.redo.p; }
+    hipLaunchKernelGGL(k_plan, dim3(L.gblk), dim3(MSM_THREADS), 0, st, cnt, g.G, g.T, nsub, (uint32_t *)wk.heavy.p, (uint32_t *)wk.medium.p, (uint32_t *)wk.counters.p,
+                       L.fused_scans ? tilesum : (uint32_t *)nullptr, size_hist, 2u * SZ_BINS, redo0);
+    VSP_LAUNCH_CHECK();
+    if (L.fused_scans) hipLaunchKernelGGL(k_scan_tiles256, dim3(L.gblk), dim3(MSM_THREADS), 0, st, (const uint32_t *)nsub, g.G, (const uint32_t *)tilesum, suboff, (uint32_t *)nullptr);
+    else VSP_TRY(exclusive_scan_w(ctx, wk, nsub, g.G, suboff, nullptr));
+    uint32_t *part_bucket = (uint32_t *)wk.partbucket.p, *perm = (uint32_t *)wk.perm.p;
+    hipLaunchKernelGGL(k_partinfo, dim3(L.ablk), dim3(256), 0, st, cnt, (const uint32_t *)suboff, g.G, g.T, part_bucket, size_hist);
+    hipLaunchKernelGGL(k_binscan, dim3(1), dim3(SZ_BINS), 0, st, (const uint32_t *)size_hist, bin_cursor);
+    hipLaunchKernelGGL(k_partsort, dim3(L.ablk), dim3(256), 0, st, cnt, (const uint32_t *)suboff, (const uint32_t *)part_bucket, g.G, g.T, bin_cursor, perm);
+    VSP_LAUNCH_CHECK();
+    VSP_HIP(hipEventRecord(wk.plan_ready, st));
+    return VSP_OK;
+}
+
+// accumulation over the plan (this slot's own or the shared one), then the bucket reduction (launch_tail)
+template <class F> static int msm_accumulate(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const MsmGeom &g) {
+    const Affine<F> *bases = (const Affine<F> *)L.rq.bases;
+    const hipStream_t st = L.st;
+    const MsmWork *pl = L.plan_from ? L.plan_from : &wk;
+    XYZZ<F> *buckets = (XYZZ<F> *)wk.buckets.p, *partials = (XYZZ<F> *)wk.partials.p, *winres = (XYZZ<F> *)wk.winres.p;
     // (the diagnostic build without hand-laid-out routines runs the multi-exponentiation on the generic 12 x 32-bit kernels only: the
     // 28-bit reduction kernels over portable products crash this toolchain's backend -- Machine Copy Propagation / post-RA pseudo
     // expansion segfault in k_dimsum<Fp28> / k_dimsum<Fp2x28>; the 28-bit and 29-bit FIELD forms stay covered by vsp_selftest_field,
@@ -2210,58 +2218,81 @@ static int msm_launch(vsp_ctx *ctx, MsmWork &wk, const Affine<F> *d_bases, const
 #else
     constexpr bool have28 = sizeof(F) != 0;
 #endif
-    bool ran28 = false;
-    if constexpr (have28) if (table28) {
-        ran28 = true;
+    if constexpr (have28) if (L.table28) {
         // 14 x 28-bit accumulation; bucket parts that meet an equal-x pair are listed and redone by the generic kernel
-        VSP_TRY(ensure_w(ctx, st, wk.redo, (Smax + 1) * sizeof(uint32_t)));
+        VSP_TRY(ensure_w(ctx, st, wk.redo, (L.Smax + 1) * sizeof(uint32_t)));
         uint32_t *redo = (uint32_t *)wk.redo.p;               // [0] = count, list from [1]
-        if (plan_from) VSP_HIP(hipMemsetAsync(redo, 0, sizeof(uint32_t), st));      // (k_plan cleared it when it ran in this launch)
-#if VSP_MSM_GROUP == 1
-        using F28 = Fp28; using Row28 = Affine28;
-#else
-        using F28 = Fp2x28; using Row28 = Affine28x2;
-#endif
+        if (L.plan_from) VSP_HIP(hipMemsetAsync(redo, 0, sizeof(uint32_t), st));      // (k_plan cleared it when it ran in this launch)
         // the bucket sums stay in the 28-bit form from here to the results per window; the parts the generic kernel redoes (equal-x
         // pairs) are written to the 12 x 32-bit arrays of the same indexing and, converted, to the 28-bit ones
         VSP_TRY(ensure_w(ctx, st, wk.buckets28, g.G * sizeof(XYZZ<F28>)));
-        VSP_TRY(ensure_w(ctx, st, wk.partials28, Smax * sizeof(XYZZ<F28>)));
-        VSP_TRY(ensure_w(ctx, st, wk.dims, (size_t)g.Wr * per_w * sizeof(XYZZ<F28>)));
+        VSP_TRY(ensure_w(ctx, st, wk.partials28, L.Smax * sizeof(XYZZ<F28>)));
+        VSP_TRY(ensure_w(ctx, st, wk.dims, (size_t)g.Wr * L.per_w * sizeof(XYZZ<F28>)));
         XYZZ<F28> *buckets28 = (XYZZ<F28> *)wk.buckets28.p, *partials28 = (XYZZ<F28> *)wk.partials28.p;
         VSP_HIP(hipEventRecord(wk.ev0, st));                  // ev0 .. ev1 bracket the accumulation kernel alone
 #if VSP_MSM_GROUP == 1
-        long use_asm = 1; { auto it = ctx->opts.find("msm_accum28_asm"); if (it != ctx->opts.end()) use_asm = it->second; }
+        long use_asm = opt(ctx, "msm_accum28_asm", 1);
 #if defined(VSP_PORTABLE_MUL)
         use_asm = 0;                                        // the diagnostic build without hand-laid-out routines: the C++ twin of the generated loop
 #endif
         if (!use_asm)
-            hipLaunchKernelGGL(k_accum28_cxx, dim3(ablk), dim3(MSM_THREADS), 0, st, (const Row28 *)table28, (const uint32_t *)pl->sorted.p,
+            hipLaunchKernelGGL(k_accum28_cxx, dim3(L.ablk), dim3(MSM_THREADS), 0, st, (const Row28 *)L.table28, (const uint32_t *)pl->sorted.p,
                                (const uint32_t *)pl->off.p, (const uint32_t *)pl->suboff.p, (const uint32_t *)pl->perm.p, (const uint32_t *)pl->partbucket.p,
                                g.G, g.T, buckets28, partials28, redo + 1, redo);
         else
 #endif
-        hipLaunchKernelGGL(k_accum28, dim3(ablk * LaneView<F>::LANES), dim3(MSM_THREADS), 0, st, (const Row28 *)table28, (const uint32_t *)pl->sorted.p,
+        hipLaunchKernelGGL(k_accum28, dim3(L.ablk * LaneView<F>::LANES), dim3(MSM_THREADS), 0, st, (const Row28 *)L.table28, (const uint32_t *)pl->sorted.p,
                            (const uint32_t *)pl->off.p, (const uint32_t *)pl->suboff.p, (const uint32_t *)pl->perm.p, (const uint32_t *)pl->partbucket.p,
                            g.G, g.T, buckets28, partials28, redo + 1, redo);
         VSP_HIP(hipEventRecord(wk.ev1, st));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_accum_redo<F>), dim3(ablk < 64 ? ablk : 64), dim3(MSM_THREADS), 0, st, d_bases, (const uint32_t *)pl->sorted.p,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_accum_redo<F>), dim3(L.ablk < 64 ? L.ablk : 64), dim3(MSM_THREADS), 0, st, bases, (const uint32_t *)pl->sorted.p,
                            (const uint32_t *)pl->off.p, (const uint32_t *)pl->suboff.p, (const uint32_t *)pl->partbucket.p, buckets, partials,
-                           (const uint32_t *)(redo + 1), (const uint32_t *)redo, glv, buckets28, partials28);
+                           (const uint32_t *)(redo + 1), (const uint32_t *)redo, L.rq.glv, buckets28, partials28);
         VSP_LAUNCH_CHECK();
         wk.dimbits = use_dimbits<F28>(ctx, g);
-        VSP_TRY(launch_tail<F28>(ctx, st, pl, g, buckets28, partials28, (XYZZ<F28> *)wk.dims.p, winres, (XYZZ<F> *)wk.h_pinned));
+        return launch_tail<F28>(ctx, st, pl, g, buckets28, partials28, (XYZZ<F28> *)wk.dims.p, winres, (XYZZ<F> *)wk.h_pinned);
     }
-    if (!ran28) {
-        VSP_HIP(hipEventRecord(wk.ev0, st));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_accum<F>), dim3(ablk * LaneView<F>::LANES), dim3(MSM_THREADS), 0, st, d_bases, (const uint32_t *)pl->sorted.p,
-                           (const uint32_t *)pl->off.p, (const uint32_t *)pl->suboff.p, (const uint32_t *)pl->perm.p, (const uint32_t *)pl->partbucket.p,
-                           g.G, g.T, buckets, partials);
-        VSP_HIP(hipEventRecord(wk.ev1, st));
-        VSP_LAUNCH_CHECK();
-        wk.dimbits = use_dimbits<F>(ctx, g);
-        VSP_TRY(launch_tail<F>(ctx, st, pl, g, buckets, partials, dims, winres, (XYZZ<F> *)wk.h_pinned));
-    }
-    VSP_HIP(hipEventRecord(wk.done, st));
+    VSP_HIP(hipEventRecord(wk.ev0, st));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_accum<F>), dim3(L.ablk * LaneView<F>::LANES), dim3(MSM_THREADS), 0, st, bases, (const uint32_t *)pl->sorted.p,
+                       (const uint32_t *)pl->off.p, (const uint32_t *)pl->suboff.p, (const uint32_t *)pl->perm.p, (const uint32_t *)pl->partbucket.p,
+                       g.G, g.T, buckets, partials);
+    VSP_HIP(hipEventRecord(wk.ev1, st));
+    VSP_LAUNCH_CHECK();
+    wk.dimbits = use_dimbits<F>(ctx, g);
+    return launch_tail<F>(ctx, st, pl, g, buckets, partials, (XYZZ<F> *)wk.dims.p, winres, (XYZZ<F> *)wk.h_pinned);
+}
+
+// one multi-exponentiation (common.h MsmRequest); plan_from: the work slot rq.plan_from names, or null
+template <class F>
+static int msm_launch(vsp_ctx *ctx, MsmWork &wk, const MsmRequest &rq, const MsmWork *plan_from) {
+    const size_t n = rq.n;
+    wk.active = false; wk.n = n;
+    if (n == 0) { wk.active = true; wk.empty = true; wk.g.K = rq.batch ? rq.batch : 1; return VSP_OK; }
+    wk.empty = false;
+    const unsigned batch = rq.batch ? rq.batch : 1;
+    // a batch (MsmGeom.K): plain bases, its own digit sort through the LDS counting sort, 16-bit windows at most
+    // (a shared plan must be a batch of the same vectors: the prover's A, B1 and B2 multiply by the same K witness vectors)
+    if (batch > 1 && rq.plan_only) return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: a batch plans and accumulates in one launch");
+    if (batch > 1 && plan_from && (plan_from->g.K != batch || plan_from->g.kstride != rq.stride || !plan_from->active || plan_from->empty))
+        return set_error(ctx, VSP_ERR_ARG, "msm: shared plan of another batch");
+    MsmLaunch L{};
+    L.rq = rq; L.rq.batch = batch; L.st = wk.stream; L.scalars = rq.scalars; L.n = n;
+    L.table28 = rq.pre ? rq.pre->table28 : rq.table28;
+    L.rq.glv = rq.glv && (rq.pre ? rq.pre->glv && rq.pre->table28 : rq.table28 != nullptr);      // the split needs the interleaved table
+    if (n >= ((size_t)1 << (L.rq.glv ? 30 : 31))) return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: n >= 2^31");
+    L.plan_from = plan_from && plan_from->glv == L.rq.glv ? plan_from : nullptr;      // a plan over split scalars serves only launches that split alike
+    wk.glv = L.rq.glv;
+    L.sort_mode = opt(ctx, "msm_sort", 0);
+    MsmGeom g; size_t n_eff = n;
+    VSP_TRY(msm_geometry<F>(ctx, wk, L, g, n_eff));
+    wk.g = g; wk.n_eff = n_eff;
+    VSP_TRY(msm_split_scalars(ctx, wk, L, g));
+    VSP_TRY(msm_buffers<F>(ctx, wk, L, g));
+    if (L.plan_from) VSP_HIP(hipStreamWaitEvent(L.st, L.plan_from->plan_ready, 0));
+    else { VSP_TRY(msm_digit_sort(ctx, wk, L, g)); VSP_TRY(msm_bucket_plan(ctx, wk, L, g)); }
+    if (rq.plan_only) return VSP_OK;                        // the accumulation follows in a later launch over this slot's own plan
+    VSP_TRY(msm_accumulate<F>(ctx, wk, L, g));
+    VSP_HIP(hipEventRecord(wk.done, L.st));
     wk.active = true;
     return VSP_OK;
 }
@@ -2329,22 +2360,21 @@ static int msm_finish_wait(vsp_ctx *ctx, MsmWork &wk, unsigned out_count, bool *
     ctx->stats["msm_bucket_sets"] = g.Wr;
     ctx->stats["msm_split"] = g.T;
     ctx->stats["msm_endomorphism_split"] = wk.glv ? 1 : 0;
-    { auto it = ctx->opts.find("msm_debug_counts");          // diagnostic: the plan's counts (a blocking read-back), only when asked for
-      if (it != ctx->opts.end() && it->second && wk.counters.p && wk.suboff.p) {
-          uint32_t c4[4] = {0, 0, 0, 0}, parts = 0;
-          if (hipMemcpy(c4, wk.counters.p, sizeof c4, hipMemcpyDeviceToHost) == hipSuccess &&
-              hipMemcpy(&parts, (const uint32_t *)wk.suboff.p + g.G, 4, hipMemcpyDeviceToHost) == hipSuccess) {
-              ctx->stats["msm_heavy_buckets"] = c4[0]; ctx->stats["msm_medium_buckets"] = c4[2]; ctx->stats["msm_parts"] = parts;
-              ctx->stats["msm_buckets"] = (double)g.G;
-          }
-      } }
+    if (opt(ctx, "msm_debug_counts", 0) && wk.counters.p && wk.suboff.p) {      // diagnostic: the plan's counts (a blocking read-back), only when asked for
+        uint32_t c4[4] = {0, 0, 0, 0}, parts = 0;
+        if (hipMemcpy(c4, wk.counters.p, sizeof c4, hipMemcpyDeviceToHost) == hipSuccess &&
+            hipMemcpy(&parts, (const uint32_t *)wk.suboff.p + g.G, 4, hipMemcpyDeviceToHost) == hipSuccess) {
+            ctx->stats["msm_heavy_buckets"] = c4[0]; ctx->stats["msm_medium_buckets"] = c4[2]; ctx->stats["msm_parts"] = parts;
+            ctx->stats["msm_buckets"] = (double)g.G;
+        }
+    }
     return VSP_OK;
 }
 template <class F, class HF> static void msm_fold(const MsmWork &wk, XYZZ<HF> *out) {
     const MsmGeom &g = wk.g;
     const XYZZ<HF> *wr = (const XYZZ<HF> *)wk.h_pinned;
     // Horner over bit positions: window w contributes D2 at c*w + q1 + q0, D1 at c*w + q0, D0 + Tot at c*w.  A batch: one chain per vector over
-    // its own windows [k Wk, (k + 1) Wk) (one bucket set per window: a batch never runs in the shared-set mode)
+    // its own windows [k Wk, (k + 1) Wk) (one bucket set per window), or over its one bucket set in the shared-set mode
     const unsigned per = g.single ? 1u : (g.K > 1 ? g.Wk : g.Wr);      // window results per vector (shared-set mode: its one bucket set)
     const bool dimbits_layout = wk.dimbits;
     host_parallel_for(g.K, [&, per, dimbits_layout](size_t kb) {
@@ -2401,6 +2431,13 @@ static int msm_precompute(vsp_ctx *ctx, Affine<F> *table, size_t n, unsigned c) 
 
 static MsmWork &slot(vsp_ctx *ctx, unsigned i) { return ctx->msm_work[i]; }
 
+// A batch reuses the plan of ANOTHER slot only.  A single launch may name its own slot: that is how the accumulation follows a plan-only launch.
+template <class F> static int launch_slot(vsp_ctx *ctx, unsigned slot_id, const MsmRequest &rq) {
+    if (slot_id >= VSP_MSM_SLOTS || rq.plan_from >= (int)VSP_MSM_SLOTS || (rq.batch && rq.plan_from == (int)slot_id)) return set_error(ctx, VSP_ERR_ARG, "msm: bad slot");
+    VSP_TRY(work_init(ctx, slot(ctx, slot_id), slot_id == 0 ? ctx->stream : nullptr));
+    return msm_launch<F>(ctx, slot(ctx, slot_id), rq, rq.plan_from >= 0 ? &slot(ctx, (unsigned)rq.plan_from) : nullptr);
+}
+
 }  // anonymous namespace
 
 #if VSP_MSM_GROUP == 1
@@ -2414,29 +2451,11 @@ int msm_g1_table28(vsp_ctx *ctx, const G1Affine *table, size_t count, void *d_ou
     VSP_LAUNCH_CHECK();
     return VSP_OK;
 }
-int msm_g1_launch(vsp_ctx *ctx, unsigned slot_id, const G1Affine *d_bases, const Fr *d_scalars, size_t n, int plan_from_slot, const MsmPre *pre,
-                  const void *plain_table28, bool glv) {
-    if (slot_id >= VSP_MSM_SLOTS) return set_error(ctx, VSP_ERR_ARG, "msm: bad slot");
-    VSP_TRY(work_init(ctx, slot(ctx, slot_id), slot_id == 0 ? ctx->stream : nullptr, false));
-    return msm_launch<Fp>(ctx, slot(ctx, slot_id), d_bases, d_scalars, n, plan_from_slot >= 0 ? &slot(ctx, (unsigned)plan_from_slot) : nullptr,
-                          plan_from_slot == VSP_MSM_DENSE, pre, plain_table28, glv, plan_from_slot == VSP_MSM_PLAN_ONLY);
-}
+int msm_g1_launch(vsp_ctx *ctx, unsigned slot_id, const MsmRequest &rq) { return launch_slot<Fp>(ctx, slot_id, rq); }
 int msm_g1_finish(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp> *out) { return msm_finish<Fp, HFp>(ctx, slot(ctx, slot_id), out); }
-// a batch of `batch` scalar vectors (vector k at d_scalars + k * stride) over the same plain bases: one sort, one accumulation, one reduction
-int msm_g1_launch_batch(vsp_ctx *ctx, unsigned slot_id, const G1Affine *d_bases, const Fr *d_scalars, size_t n, unsigned batch, size_t stride, bool dense,
-                        const void *plain_table28, bool glv, int plan_from_slot, const MsmPre *pre) {
-    if (slot_id >= VSP_MSM_SLOTS || plan_from_slot >= (int)VSP_MSM_SLOTS || plan_from_slot == (int)slot_id) return set_error(ctx, VSP_ERR_ARG, "msm: bad slot");
-    VSP_TRY(work_init(ctx, slot(ctx, slot_id), slot_id == 0 ? ctx->stream : nullptr, false));
-    return msm_launch<Fp>(ctx, slot(ctx, slot_id), d_bases, d_scalars, n, plan_from_slot >= 0 ? &slot(ctx, (unsigned)plan_from_slot) : nullptr, dense, pre, plain_table28,
-                          glv, false, batch, stride);
-}
 int msm_g1_finish_batch(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp> *out, unsigned batch) { return msm_finish<Fp, HFp>(ctx, slot(ctx, slot_id), out, batch); }
 int msm_g1_finish_wait(vsp_ctx *ctx, unsigned slot_id, bool *empty) { return msm_finish_wait<Fp, HFp>(ctx, slot(ctx, slot_id), 1, empty); }
 void msm_g1_fold(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp> *out) { msm_fold<Fp, HFp>(slot(ctx, slot_id), out); }
-int msm_g1_device(vsp_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, size_t n, XYZZ<HFp> *out) {
-    VSP_TRY(msm_g1_launch(ctx, 0, d_bases, d_scalars, n, -1, nullptr));
-    return msm_g1_finish(ctx, 0, out);
-}
 // the census kernel runs on the CONTEXT's stream (so it cannot be held up behind low-priority work); the slot picks it up
 // A stream for a work slot: the LOWEST priority -- work on the context's stream (the NTTs of witness_map, whose result gates the H
 // multi-exponentiation) gets compute units first.  (Option "msm_slot_normal_priority" = 1: the context's own priority instead -- the
@@ -2444,19 +2463,19 @@ int msm_g1_device(vsp_ctx *ctx, const G1Affine *d_bases, const Fr *d_scalars, si
 int msm_make_slot_stream(vsp_ctx *ctx, hipStream_t *out) {
     int least = 0, greatest = 0;
     VSP_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    long normal = 0; { auto it = ctx->opts.find("msm_slot_normal_priority"); if (it != ctx->opts.end()) normal = it->second; }
+    const long normal = opt(ctx, "msm_slot_normal_priority", 0);
     VSP_HIP(hipStreamCreateWithPriority(out, hipStreamNonBlocking, normal ? 0 : least));
     return VSP_OK;
 }
 int msm_slot_census(vsp_ctx *ctx, unsigned slot_id, const Fr *d_scalars, size_t n) {
     if (slot_id >= VSP_MSM_SLOTS) return set_error(ctx, VSP_ERR_ARG, "msm: bad slot");
-    VSP_TRY(work_init(ctx, slot(ctx, slot_id), slot_id == 0 ? ctx->stream : nullptr, false));
+    VSP_TRY(work_init(ctx, slot(ctx, slot_id), slot_id == 0 ? ctx->stream : nullptr));
     if (n == 0) return VSP_OK;
     return msm_census(ctx, slot(ctx, slot_id), d_scalars, n, ctx->stream);
 }
 int msm_slot_stream(vsp_ctx *ctx, unsigned slot_id, hipStream_t *out) {
     if (slot_id >= VSP_MSM_SLOTS) return set_error(ctx, VSP_ERR_ARG, "msm: bad slot");
-    VSP_TRY(work_init(ctx, slot(ctx, slot_id), slot_id == 0 ? ctx->stream : nullptr, false));
+    VSP_TRY(work_init(ctx, slot(ctx, slot_id), slot_id == 0 ? ctx->stream : nullptr));
     *out = slot(ctx, slot_id).stream;
     return VSP_OK;
 }
@@ -2467,7 +2486,7 @@ int msm_slot_use_stream(vsp_ctx *ctx, unsigned slot_id, hipStream_t stream_or_nu
     if (slot_id == 0 || slot_id >= VSP_MSM_SLOTS) return set_error(ctx, VSP_ERR_ARG, "msm: bad slot");
     MsmWork &wk = slot(ctx, slot_id);
     wk.stream = stream_or_null;                             // nullptr: the next work_init puts the own stream back (creating it if need be)
-    return stream_or_null ? work_init(ctx, wk, nullptr, false) : VSP_OK;
+    return stream_or_null ? work_init(ctx, wk, nullptr) : VSP_OK;
 }
 void msm_drain_slots(vsp_ctx *ctx) {
     for (unsigned i = 0; i < VSP_MSM_SLOTS; i++) {
@@ -2534,28 +2553,11 @@ int msm_g2_table28(vsp_ctx *ctx, const G2Affine *table, size_t count, void *d_ou
     VSP_LAUNCH_CHECK();
     return VSP_OK;
 }
-int msm_g2_launch(vsp_ctx *ctx, unsigned slot_id, const G2Affine *d_bases, const Fr *d_scalars, size_t n, int plan_from_slot, const MsmPre *pre,
-                  const void *plain_table28, bool glv) {
-    if (slot_id >= VSP_MSM_SLOTS) return set_error(ctx, VSP_ERR_ARG, "msm: bad slot");
-    VSP_TRY(work_init(ctx, slot(ctx, slot_id), slot_id == 0 ? ctx->stream : nullptr, false));
-    return msm_launch<Fp2>(ctx, slot(ctx, slot_id), d_bases, d_scalars, n, plan_from_slot >= 0 ? &slot(ctx, (unsigned)plan_from_slot) : nullptr,
-                           plan_from_slot == VSP_MSM_DENSE, pre, plain_table28, glv, plan_from_slot == VSP_MSM_PLAN_ONLY);
-}
+int msm_g2_launch(vsp_ctx *ctx, unsigned slot_id, const MsmRequest &rq) { return launch_slot<Fp2>(ctx, slot_id, rq); }
 int msm_g2_finish(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp2> *out) { return msm_finish<Fp2, HFp2>(ctx, slot(ctx, slot_id), out); }
-int msm_g2_launch_batch(vsp_ctx *ctx, unsigned slot_id, const G2Affine *d_bases, const Fr *d_scalars, size_t n, unsigned batch, size_t stride, bool dense,
-                        const void *plain_table28, bool glv, int plan_from_slot, const MsmPre *pre) {
-    if (slot_id >= VSP_MSM_SLOTS || plan_from_slot >= (int)VSP_MSM_SLOTS || plan_from_slot == (int)slot_id) return set_error(ctx, VSP_ERR_ARG, "msm: bad slot");
-    VSP_TRY(work_init(ctx, slot(ctx, slot_id), slot_id == 0 ? ctx->stream : nullptr, false));
-    return msm_launch<Fp2>(ctx, slot(ctx, slot_id), d_bases, d_scalars, n, plan_from_slot >= 0 ? &slot(ctx, (unsigned)plan_from_slot) : nullptr, dense, pre, plain_table28,
-                          glv, false, batch, stride);
-}
 int msm_g2_finish_batch(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp2> *out, unsigned batch) { return msm_finish<Fp2, HFp2>(ctx, slot(ctx, slot_id), out, batch); }
 int msm_g2_finish_wait(vsp_ctx *ctx, unsigned slot_id, bool *empty) { return msm_finish_wait<Fp2, HFp2>(ctx, slot(ctx, slot_id), 1, empty); }
 void msm_g2_fold(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp2> *out) { msm_fold<Fp2, HFp2>(slot(ctx, slot_id), out); }
-int msm_g2_device(vsp_ctx *ctx, const G2Affine *d_bases, const Fr *d_scalars, size_t n, XYZZ<HFp2> *out) {
-    VSP_TRY(msm_g2_launch(ctx, 0, d_bases, d_scalars, n, -1, nullptr));
-    return msm_g2_finish(ctx, 0, out);
-}
 int subgroup_check_g2(vsp_ctx *ctx, const G2Affine *d_mont, size_t n, uint32_t *d_flag) {
     if (!n) return VSP_OK;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_subgroup_check<Fp2>), dim3((unsigned)((2 * n + MSM_THREADS - 1) / MSM_THREADS)), dim3(MSM_THREADS), 0, ctx->stream, d_mont, n, d_flag);

@@ -480,8 +480,8 @@ static bool ntt29_known_answer_check(vsp_ctx *ctx) {
     const uint64_t g7[4] = {7, 0, 0, 0};
     void *d = nullptr;
     bool ran = false, same = true;
-    const bool had = ctx->opts.count("ntt_fr29") != 0; const long saved = had ? ctx->opts["ntt_fr29"] : 1;
     if (hipMalloc(&d, bytes) == hipSuccess) {
+        OptScope saved(ctx, {"ntt_fr29"});
         ran = true;
         for (int inverse = 0; inverse < 2 && ran; inverse++) {
             for (int path = 0; path < 2 && ran; path++) {
@@ -496,10 +496,9 @@ static bool ntt29_known_answer_check(vsp_ctx *ctx) {
         }
         hipFree(d);
     }
-    if (had) ctx->opts["ntt_fr29"] = saved; else ctx->opts.erase("ntt_fr29");
     hipGetLastError();
     if (!ran) { ctx->ntt29_checked = 0; ctx->stats["ntt_fr29_selfcheck"] = 0.0; return false; }      // could not run: no verdict, the 8 x 32-bit kernel this time
-    { auto it = ctx->opts.find("ntt_fr29_selfcheck_fault"); if (it != ctx->opts.end() && it->second) same = false; }      // test hook: exercise the fallback
+    if (opt(ctx, "ntt_fr29_selfcheck_fault", 0)) same = false;      // test hook: exercise the fallback
     ctx->ntt29_checked = same ? 1 : -1;
     ctx->stats["ntt_fr29_selfcheck"] = same ? 1.0 : -1.0;
     if (!same) { ctx->opts["ntt_fr29"] = 0; ctx->err = "ntt: the 29-bit-limb butterfly kernel failed its known-answer check; 8 x 32-bit kernel in use"; }
@@ -508,17 +507,14 @@ static bool ntt29_known_answer_check(vsp_ctx *ctx) {
 
 // callers that set tables up before their first transform (the step-domain glue) run the check first: it rebuilds tables for its own use
 void ntt_selfcheck_once(vsp_ctx *ctx) {
-    long want29 = 1; auto it = ctx->opts.find("ntt_fr29"); if (it != ctx->opts.end()) want29 = it->second;
-    if (want29 && ctx->ntt29_checked == 0) ntt29_known_answer_check(ctx);
+    if (opt(ctx, "ntt_fr29", 1) && ctx->ntt29_checked == 0) ntt29_known_answer_check(ctx);
 }
 
 // whether the 29-bit butterflies are in use on this context (runs their known-answer check when it has not run yet)
 bool ntt29_in_use(vsp_ctx *ctx) {
-    long want29 = 1; { auto it = ctx->opts.find("ntt_fr29"); if (it != ctx->opts.end()) want29 = it->second; }
-    if (!want29) return false;
+    if (!opt(ctx, "ntt_fr29", 1)) return false;
     if (ctx->ntt29_checked <= 0 && !ntt29_known_answer_check(ctx)) return false;
-    { auto it = ctx->opts.find("ntt_fr29"); if (it != ctx->opts.end()) want29 = it->second; }
-    return want29 != 0;
+    return opt(ctx, "ntt_fr29", 1) != 0;                    // (a failed check has just switched it off)
 }
 static int ntt_device_impl(vsp_ctx *ctx, const Fr *const *d_in, Fr *const *d_out, unsigned count, unsigned log_m, int inverse, const uint64_t *coset_g,
                            const HFr *extra_scale, const Fr *fuse_b, const Fr *fuse_c, size_t in_stride = 0, size_t out_stride = 0);
@@ -562,8 +558,7 @@ static int ntt_device_impl(vsp_ctx *ctx, const Fr *const *d_in, Fr *const *d_out
     }
     // the 29-bit path's known-answer check comes first: it runs transforms of its own, which may rebuild the twiddle and coset tables
     bool check29_ok = true;
-    { long want29 = 1; auto it = ctx->opts.find("ntt_fr29"); if (it != ctx->opts.end()) want29 = it->second;
-      if (want29 && ctx->ntt29_checked <= 0) check29_ok = ntt29_known_answer_check(ctx); }      // (2 = the check itself is running: not re-entered)
+    if (opt(ctx, "ntt_fr29", 1) && ctx->ntt29_checked <= 0) check29_ok = ntt29_known_answer_check(ctx);      // (2 = the check itself is running: not re-entered)
     VSP_TRY(ntt_ensure_twiddles(ctx, log_m));
     if (coset_g) VSP_TRY(ntt_ensure_coset_tables(ctx, log_m, coset_g));
     const size_t n = (size_t)1 << log_m;
@@ -578,7 +573,7 @@ static int ntt_device_impl(vsp_ctx *ctx, const Fr *const *d_in, Fr *const *d_out
             for (unsigned k = i + 1; k < npass; k++)
                 if ((stages[k] & 1) && stages[i] < NTT_MAX_STAGES && stages[k] > 1) { stages[i]++; stages[k]--; break; }
 
-    long use29 = 1; { auto it = ctx->opts.find("ntt_fr29"); if (it != ctx->opts.end()) use29 = it->second; }
+    long use29 = opt(ctx, "ntt_fr29", 1);
     if (use29 && !check29_ok) use29 = 0;
     if (!use29 && (count > 1 || fuse_b || d_in[0] != d_out[0])) return set_error(ctx, VSP_ERR_UNSUPPORTED, "ntt: batched / fused transforms need the 29-bit butterflies");
     Fr *scratch = nullptr;

@@ -135,7 +135,7 @@ namespace vsp {
 // the fixed-base tables of delta (common.h vsp_pk): built by the first proof over the key, 32 x 255 additions per group (~5 ms G1, ~15 ms G2);
 // option "prove_fixed_base" = 0 keeps the double-and-add multiplications of rounds 1-3
 static bool delta_tables(vsp_ctx *ctx, const vsp_pk *pk) {
-    { auto it = ctx->opts.find("prove_fixed_base"); if (it != ctx->opts.end() && it->second == 0) return false; }
+    if (opt(ctx, "prove_fixed_base", 1) == 0) return false;
     if (pk->tab_ready.load(std::memory_order_acquire)) return true;
     std::lock_guard<std::mutex> lock(pk->tab_mu);
     if (!pk->tab_ready.load(std::memory_order_relaxed)) {
@@ -336,7 +336,7 @@ static int prove_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk,
     // contexts; the other pairings lose (A,B2 | B1,L: 7.8 ms; all four on one stream: 7.3 ms).  Fewer concurrent witness chains leave the
     // transforms and the H accumulation -- the critical chain -- alone for longer.  Option "prove_witness_streams" = 0: the
     // slots' own streams.
-    long wstreams = 1; { auto it = ctx->opts.find("prove_witness_streams"); if (it != ctx->opts.end()) wstreams = it->second; }
+    const long wstreams = opt(ctx, "prove_witness_streams", 1);
     if (wstreams) {
         for (int k = 0; k < 2; k++) if (!ctx->prove_streams[k]) VSP_TRY(msm_make_slot_stream(ctx, &ctx->prove_streams[k]));
         VSP_TRY(msm_slot_use_stream(ctx, 1, ctx->prove_streams[0])); VSP_TRY(msm_slot_use_stream(ctx, 2, ctx->prove_streams[0]));
@@ -346,7 +346,7 @@ static int prove_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk,
     VSP_TRY(msm_slot_census(ctx, 4, dz + ni + 1, nv - ni));
     VSP_HIP(hipEventRecord(ctx->ev_aux, st));          // z resident and censuses queued
     // option "prove_h_first" (default 1): queue witness_map + H before the witness multi-exponentiations, or after (0)
-    long h_first = 1; { auto it = ctx->opts.find("prove_h_first"); if (it != ctx->opts.end()) h_first = it->second; }
+    const long h_first = opt(ctx, "prove_h_first", 1);
     {
         hipStream_t s1, s2, s3, s4;
         VSP_TRY(msm_slot_stream(ctx, 1, &s1)); VSP_TRY(msm_slot_stream(ctx, 2, &s2));
@@ -358,23 +358,26 @@ static int prove_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk,
     // Their counting sort needs 128 KiB of LDS per workgroup; queued after the transforms it finds every CU's LDS taken by NTT tiles and
     // then every wave slot taken by the H accumulation, and waits ~2 ms (kernel timeline).  Queued first it runs while the
     // GPU is idle -- measured: no gain (9.10 against 9.02 ms): the proof is bound by the sum of its kernels, not by that wait.
-    long plan_first = 0; { auto it = ctx->opts.find("prove_plan_first"); if (it != ctx->opts.end()) plan_first = it->second; }
-    int planA = -1, planL = -1;
+    const long plan_first = opt(ctx, "prove_plan_first", 0);
+    MsmRequest a(dz, nv + 1), l(dz + ni + 1, nv - ni), h(dH, m - 1);      // A_query (B_query G1 / G2 alike), L_query, H_query
+    h.dense = true;                                           // H coefficients are dense
     if (h_first && plan_first) {
-        VSP_TRY(launch_on_bases(ctx, 1, pk->A, 0, nv + 1, dz, VSP_MSM_PLAN_ONLY)); planA = 1;
-        VSP_TRY(launch_on_bases(ctx, 4, pk->L, 0, nv - ni, dz + ni + 1, VSP_MSM_PLAN_ONLY)); planL = 4;
+        MsmRequest plan_a = a, plan_l = l; plan_a.plan_only = plan_l.plan_only = true;
+        VSP_TRY(launch_on_bases(ctx, 1, pk->A, 0, plan_a)); a.plan_from = 1;
+        VSP_TRY(launch_on_bases(ctx, 4, pk->L, 0, plan_l)); l.plan_from = 4;
     }
     if (h_first) {
         VSP_TRY(witness_map_device(ctx, dA, dB, dC, &cs->dom, dH));
-        VSP_TRY(launch_on_bases(ctx, 0, pk->H, 0, m - 1, dH, VSP_MSM_DENSE));   // H coefficients are dense
+        VSP_TRY(launch_on_bases(ctx, 0, pk->H, 0, h));
     }
-    VSP_TRY(launch_on_bases(ctx, 1, pk->A, 0, nv + 1, dz, planA));
-    VSP_TRY(launch_on_bases(ctx, 3, pk->B2, 0, nv + 1, dz, pk->B2->pre_c == pk->A->pre_c ? 1 : -1));
-    VSP_TRY(launch_on_bases(ctx, 2, pk->B1, 0, nv + 1, dz, pk->B1->pre_c == pk->A->pre_c ? 1 : -1));
-    VSP_TRY(launch_on_bases(ctx, 4, pk->L, 0, nv - ni, dz + ni + 1, planL));
+    VSP_TRY(launch_on_bases(ctx, 1, pk->A, 0, a));
+    MsmRequest b = a;
+    b.plan_from = pk->B2->pre_c == pk->A->pre_c ? 1 : -1; VSP_TRY(launch_on_bases(ctx, 3, pk->B2, 0, b));
+    b.plan_from = pk->B1->pre_c == pk->A->pre_c ? 1 : -1; VSP_TRY(launch_on_bases(ctx, 2, pk->B1, 0, b));
+    VSP_TRY(launch_on_bases(ctx, 4, pk->L, 0, l));
     if (!h_first) {
         VSP_TRY(witness_map_device(ctx, dA, dB, dC, &cs->dom, dH));
-        VSP_TRY(launch_on_bases(ctx, 0, pk->H, 0, m - 1, dH, VSP_MSM_DENSE));
+        VSP_TRY(launch_on_bases(ctx, 0, pk->H, 0, h));
     }
     lap("prove_launch_ms");
     // what the second half needs: the key, the randomness, the SAVER term
@@ -403,7 +406,7 @@ static int prove_finish_impl(vsp_ctx *ctx, uint64_t A_out[12], uint64_t B_out[24
     uint64_t rs4[4]; host_store_canon(rs4, mul(rr, ss));
     XYZZ<HFp> r_delta, s_delta, neg_rs_delta, saver = XYZZ<HFp>::inf();
     XYZZ<HFp2> s_delta2;
-    long hthreads = 1; { auto it = ctx->opts.find("prove_host_threads"); if (it != ctx->opts.end()) hthreads = it->second; }
+    const long hthreads = opt(ctx, "prove_host_threads", 1);
     const unsigned T = hthreads ? 8u : 1u;
     const bool fixed = delta_tables(ctx, pk);                 // (round 4: at most 32 additions per multiple of delta instead of 255 doublings + ~127 additions)
     host_parallel_for(5, [&](size_t j) {
@@ -508,16 +511,18 @@ static int prove_batch_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_p
     VSP_TRY(msm_slot_use_stream(ctx, 1, ctx->prove_streams[0])); VSP_TRY(msm_slot_use_stream(ctx, 2, ctx->prove_streams[0]));
     VSP_TRY(msm_slot_use_stream(ctx, 3, ctx->prove_streams[1])); VSP_TRY(msm_slot_use_stream(ctx, 4, ctx->prove_streams[1]));
     VSP_TRY(witness_map_device_batch(ctx, abc, (unsigned)K, &cs->dom, dH));
-    VSP_TRY(launch_on_bases_batch(ctx, 0, pk->H, 0, m - 1, dH, (unsigned)K, m, true));           // H coefficients are dense
-    VSP_TRY(launch_on_bases_batch(ctx, 1, pk->A, 0, nv + 1, dz, (unsigned)K, zs, false));
+    MsmRequest h(dH, m - 1), a(dz, nv + 1), l(dz + ni + 1, nv - ni);      // as in prove_launch_impl, K vectors each
+    h.dense = true; h.batch = a.batch = l.batch = (unsigned)K; h.stride = m; a.stride = l.stride = zs;      // H coefficients are dense
+    VSP_TRY(launch_on_bases(ctx, 0, pk->H, 0, h));
+    VSP_TRY(launch_on_bases(ctx, 1, pk->A, 0, a));
     // A, B1 and B2 multiply by the same K witness vectors: one digit sort and bucket plan (A's) serves the three (option "prove_batch_share_plan")
-    long share = 1; { auto it = ctx->opts.find("prove_batch_share_plan"); if (it != ctx->opts.end()) share = it->second; }
+    const long share = opt(ctx, "prove_batch_share_plan", 1);
     const bool same_shape = pk->A->glv == pk->B1->glv && pk->A->glv == pk->B2->glv && (pk->A->d28 != nullptr) == (pk->B1->d28 != nullptr) && (pk->A->d28 != nullptr) == (pk->B2->d28 != nullptr) &&
                             pk->A->pre_c == pk->B1->pre_c && pk->A->pre_c == pk->B2->pre_c && pk->A->n == pk->B1->n && pk->A->n == pk->B2->n;
-    const int from_a = share && same_shape && nv + 1 > 0 ? 1 : -1;
-    VSP_TRY(launch_on_bases_batch(ctx, 3, pk->B2, 0, nv + 1, dz, (unsigned)K, zs, false, from_a));
-    VSP_TRY(launch_on_bases_batch(ctx, 2, pk->B1, 0, nv + 1, dz, (unsigned)K, zs, false, from_a));
-    VSP_TRY(launch_on_bases_batch(ctx, 4, pk->L, 0, nv - ni, dz + ni + 1, (unsigned)K, zs, false));
+    MsmRequest b = a; b.plan_from = share && same_shape && nv + 1 > 0 ? 1 : -1;
+    VSP_TRY(launch_on_bases(ctx, 3, pk->B2, 0, b));
+    VSP_TRY(launch_on_bases(ctx, 2, pk->B1, 0, b));
+    VSP_TRY(launch_on_bases(ctx, 4, pk->L, 0, l));
     lap("prove_batch_launch_ms");
     return VSP_OK;
 }
