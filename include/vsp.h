@@ -319,8 +319,9 @@ int vsp_groth16_prove_launch_packed(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_
  * gain nothing from it and its 2 GB table would miss the cache); bits 1..5 select A_query, B_query (G1), B_query (G2), H_query, L_query one by one.  The key owns its queries.
  * WHICH TO CHOOSE (measured, 2^20 constraints, 90 % boolean witness, MI355X): precompute = 0, the PLAIN key, holds 1.95 GB and proves in
  * 6.65 ms (194 proofs/s from one thread with two proofs in flight); precompute = 1 holds 19.2 GB and proves in 6.26 ms (203 proofs/s).  The
- * tables buy ~5 % for ten times the memory: keep the key plain unless single-proof latency at that size is what matters -- and
- * vsp_groth16_prove_batch, the way to prove many statements of one circuit, takes plain keys only. */
+ * tables buy ~5 % for ten times the memory: keep the key plain unless single-proof latency at that size is what matters.
+ * vsp_groth16_prove_batch, the way to prove many statements of one circuit, takes plain keys and keys whose tables have windows of at
+ * most 16 bits (not with option "msm_batch_tables" = 0); other keys are refused with VSP_ERR_UNSUPPORTED. */
 typedef struct vsp_keypair vsp_keypair;
 vsp_keypair *vsp_groth16_generate(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64_t toxic[20], int precompute);
 const vsp_pk *vsp_keypair_pk(const vsp_keypair *kp);

@@ -482,14 +482,21 @@ def groth16_prove(ctx, cs, pk, witness, r, s, saver_P1=None, saver_r_enc=None):
     return A, B, Cc, proof.tobytes()
 
 
-def groth16_prove_batch(ctx, cs, pk, witnesses, r, s):
-    """K proofs over one PLAIN key in one pass (vsp_groth16_prove_batch): witnesses [K, num_vars, 4], r / s [K, 4].
-    -> (A [K, 12], B [K, 24], C [K, 12], [proof bytes] * K); proof k is byte-identical to groth16_prove(witness_k, r_k, s_k)."""
+def _batch_inputs(cs, witnesses, r, s):
+    """witnesses [K, num_vars, 4], r / s [K, 4] as contiguous uint64 arrays -> (witnesses, r, s, K)"""
     witnesses = np.ascontiguousarray(witnesses, dtype=np.uint64)
     if witnesses.ndim != 3 or witnesses.shape[1:] != (cs.num_vars, 4):
         raise ValueError("prove_batch: witnesses must be [K, num_vars, 4]")
     K = witnesses.shape[0]
     r = np.ascontiguousarray(r, dtype=np.uint64).reshape(K, 4); s = np.ascontiguousarray(s, dtype=np.uint64).reshape(K, 4)
+    return witnesses, r, s, K
+
+
+def groth16_prove_batch(ctx, cs, pk, witnesses, r, s):
+    """K proofs over one key in one pass (vsp_groth16_prove_batch): witnesses [K, num_vars, 4], r / s [K, 4].  The key is plain, or has
+    tables of window multiples of at most 16 bits (refused otherwise, and with option msm_batch_tables = 0).
+    -> (A [K, 12], B [K, 24], C [K, 12], [proof bytes] * K); proof k is byte-identical to groth16_prove(witness_k, r_k, s_k)."""
+    witnesses, r, s, K = _batch_inputs(cs, witnesses, r, s)
     A = np.zeros((K, 12), np.uint64); B = np.zeros((K, 24), np.uint64); Cc = np.zeros((K, 12), np.uint64)
     proofs = np.zeros((K, 192), np.uint8)
     ctx.check(ctx.lib.vsp_groth16_prove_batch(ctx.h, cs.h, pk.h, _ptr(witnesses), K, _ptr(r), _ptr(s), _ptr(A), _ptr(B), _ptr(Cc), _ptr(proofs)))
@@ -498,11 +505,7 @@ def groth16_prove_batch(ctx, cs, pk, witnesses, r, s):
 
 def groth16_prove_batch_launch(ctx, cs, pk, witnesses, r, s):
     """first half of groth16_prove_batch: copy the witnesses, queue every kernel of the K proofs, return K (one batch in flight per context)"""
-    witnesses = np.ascontiguousarray(witnesses, dtype=np.uint64)
-    if witnesses.ndim != 3 or witnesses.shape[1:] != (cs.num_vars, 4):
-        raise ValueError("prove_batch: witnesses must be [K, num_vars, 4]")
-    K = witnesses.shape[0]
-    r = np.ascontiguousarray(r, dtype=np.uint64).reshape(K, 4); s = np.ascontiguousarray(s, dtype=np.uint64).reshape(K, 4)
+    witnesses, r, s, K = _batch_inputs(cs, witnesses, r, s)
     ctx.check(ctx.lib.vsp_groth16_prove_batch_launch(ctx.h, cs.h, pk.h, _ptr(witnesses), K, _ptr(r), _ptr(s)))
     ctx._prove_batch_count = K
     return K

@@ -185,12 +185,12 @@ vsp_ctx *vsp_create(int device_ordinal) {
 void vsp_destroy(vsp_ctx *ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->device);
-    if (ctx->prove.active || ctx->prove_batch.active) msm_drain_slots(ctx);      // a proof launched and never finished: wait its kernels out before their buffers go
+    if (ctx->prove.active) msm_drain_slots(ctx);      // a proof launched and never finished: wait its kernels out before their buffers go
     hipStreamSynchronize(ctx->stream);
     DevBuf *bufs[] = {&ctx->ntt.fwd, &ctx->ntt.inv, &ctx->ntt.pw_lo_f, &ctx->ntt.pw_hi_f, &ctx->ntt.pw_lo_i, &ctx->ntt.pw_hi_i, &ctx->ntt_scratch, &ctx->dom_scratch,
                       &ctx->ntt.fwd29, &ctx->ntt.inv29, &ctx->ntt.pw29[0], &ctx->ntt.pw29[1], &ctx->ntt.pw29[2], &ctx->ntt.pw29[3],
                       &ctx->msm_scalars, &ctx->val_flag, &ctx->fb_g1, &ctx->fb_g2, &ctx->fb_tmp, &ctx->fb_pre,
-                      &ctx->pr_z, &ctx->pr_a, &ctx->pr_b, &ctx->pr_c, &ctx->pr_h, &ctx->pr_pack, &ctx->pr_bz, &ctx->pr_babc, &ctx->pr_bh};
+                      &ctx->pr_z, &ctx->pr_abc, &ctx->pr_h, &ctx->pr_pack};
     for (DevBuf *b : bufs) free_buf(*b);
     msm_free_slots(ctx);
     if (ctx->h_fold) hipHostFree(ctx->h_fold);
@@ -571,11 +571,11 @@ int vsp_msm_resident_batch(vsp_ctx *ctx, const vsp_bases *bases, size_t first, s
     VSP_TRY(launch_on_bases(ctx, 0, bases, first, rq));
     if (bases->group == 1) {
         std::vector<XYZZ<HFp>> r(batch);
-        VSP_TRY(msm_g1_finish_batch(ctx, 0, r.data(), (unsigned)batch));
+        VSP_TRY(msm_g1_finish(ctx, 0, r.data(), (unsigned)batch));
         for (size_t k = 0; k < batch; k++) VSP_TRY((finish_affine<Fp, HFp>(r[k], out_affine + k * words, out_is_inf ? out_is_inf + k : nullptr)));
     } else {
         std::vector<XYZZ<HFp2>> r(batch);
-        VSP_TRY(msm_g2_finish_batch(ctx, 0, r.data(), (unsigned)batch));
+        VSP_TRY(msm_g2_finish(ctx, 0, r.data(), (unsigned)batch));
         for (size_t k = 0; k < batch; k++) VSP_TRY((finish_affine<Fp2, HFp2>(r[k], out_affine + k * words, out_is_inf ? out_is_inf + k : nullptr)));
     }
     return VSP_OK;
@@ -750,12 +750,12 @@ int vsp_witness_map_h_device(vsp_ctx *ctx, void *d_Az, void *d_Bz, void *d_Cz, u
 }
 static int witness_map_host(vsp_ctx *ctx, const vsp_domain *d, uint64_t *Az, uint64_t *Bz, uint64_t *Cz, uint64_t *H) {
     size_t bytes = d->m * 32;
-    VSP_TRY(ensure(ctx, ctx->pr_a, bytes)); VSP_TRY(ensure(ctx, ctx->pr_b, bytes));
-    VSP_TRY(ensure(ctx, ctx->pr_c, bytes)); VSP_TRY(ensure(ctx, ctx->pr_h, bytes));
-    VSP_HIP(hipMemcpyAsync(ctx->pr_a.p, Az, bytes, hipMemcpyHostToDevice, ctx->stream));
-    VSP_HIP(hipMemcpyAsync(ctx->pr_b.p, Bz, bytes, hipMemcpyHostToDevice, ctx->stream));
-    VSP_HIP(hipMemcpyAsync(ctx->pr_c.p, Cz, bytes, hipMemcpyHostToDevice, ctx->stream));
-    VSP_TRY(witness_map_device(ctx, (Fr *)ctx->pr_a.p, (Fr *)ctx->pr_b.p, (Fr *)ctx->pr_c.p, d, (Fr *)ctx->pr_h.p));
+    VSP_TRY(ensure(ctx, ctx->pr_abc, 3 * bytes)); VSP_TRY(ensure(ctx, ctx->pr_h, bytes));
+    Fr *dA = (Fr *)ctx->pr_abc.p, *dB = dA + d->m, *dC = dA + 2 * d->m;      // the prover's workspace, one witness
+    VSP_HIP(hipMemcpyAsync(dA, Az, bytes, hipMemcpyHostToDevice, ctx->stream));
+    VSP_HIP(hipMemcpyAsync(dB, Bz, bytes, hipMemcpyHostToDevice, ctx->stream));
+    VSP_HIP(hipMemcpyAsync(dC, Cz, bytes, hipMemcpyHostToDevice, ctx->stream));
+    VSP_TRY(witness_map_device(ctx, dA, dB, dC, d, (Fr *)ctx->pr_h.p));
     VSP_HIP(hipMemcpyAsync(H, ctx->pr_h.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     VSP_HIP(hipStreamSynchronize(ctx->stream));
     return VSP_OK;

@@ -139,13 +139,14 @@ struct vsp_ctx {
     int fp28_checked[2] = {0, 0};       // known-answer check of the 28-bit-limb accumulation kernels, per group: 0 not yet, 1 passed, -1 failed (kernel disabled)
     // fixed-base tables (generator multiples), built lazily
     vsp::DevBuf fb_g1, fb_g2, fb_tmp, fb_pre;
-    // prover workspaces
-    vsp::DevBuf pr_z, pr_a, pr_b, pr_c, pr_h, pr_pack;
-    vsp::DevBuf pr_bz, pr_babc, pr_bh;      // vsp_groth16_prove_batch: [K][num_vars + 1], [K][3][m], [K][m]
-    // a proof in flight between vsp_groth16_prove_launch and _finish (one per context)
-    struct { bool active = false; const vsp_pk *pk = nullptr; uint64_t r[4], s[4], P1[12], r_enc[4]; bool has_saver = false; } prove;
-    // a BATCH of proofs in flight between vsp_groth16_prove_batch_launch and _finish (one per context)
-    struct { bool active = false; const vsp_pk *pk = nullptr; size_t count = 0; std::vector<uint64_t> r, s; } prove_batch;
+    // prover workspaces for K witnesses (a single proof: K = 1): z [K][num_vars + 1], A z, B z, C z [K][3][m], H [K][m], the packed witness
+    vsp::DevBuf pr_z, pr_abc, pr_h, pr_pack;
+    // the proof or the batch of K proofs in flight between a launch and its finish (one per context): the key, r and s (K x 4 words), the
+    // SAVER term (single proofs only), the bytes of z the launch wrote
+    struct {
+        bool active = false, batch = false; const vsp_pk *pk = nullptr; size_t count = 0, z_bytes = 0; std::vector<uint64_t> r, s;
+        bool has_saver = false; uint64_t P1[12], r_enc[4];
+    } prove;
 };
 
 struct vsp_bases {
@@ -274,6 +275,10 @@ int domain_lagrange_device(vsp_ctx *ctx, const vsp_domain *d, const HFr &t, Fr *
 HFr domain_vanishing(const vsp_domain *d, const HFr &t);
 HFr domain_element(const vsp_domain *d, size_t idx);
 int witness_map_device(vsp_ctx *ctx, Fr *dA, Fr *dB, Fr *dC, const vsp_domain *d, Fr *dH);
+// vsp_groth16_prove with a hook (prover.hip): `overlap` runs on the host after every kernel is queued and before the first wait
+int prove_with_overlap(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witness, const uint64_t r[4], const uint64_t s[4],
+                       const uint64_t *saver_P1, const uint64_t *saver_r_enc, uint64_t A_out[12], uint64_t B_out[24], uint64_t C_out[12],
+                       uint8_t proof_out[192], const std::function<void()> *overlap);
 
 // MSM on device-resident Montgomery bases; result as host XYZZ (Montgomery, 64-bit limbs)
 int msm_g1_launch(vsp_ctx *ctx, unsigned slot, const MsmRequest &rq);
@@ -282,15 +287,13 @@ int msm_g1_precompute(vsp_ctx *ctx, G1Affine *table, size_t n, unsigned c);
 int msm_g2_precompute(vsp_ctx *ctx, G2Affine *table, size_t n, unsigned c);
 int msm_g1_table28(vsp_ctx *ctx, const G1Affine *table, size_t count, void *d_out /* count (glv: 2 count) rows of 128 bytes */, bool glv);
 int msm_g2_table28(vsp_ctx *ctx, const G2Affine *table, size_t count, void *d_out /* count (glv: 2 count) rows of 256 bytes */, bool glv);
-int msm_g1_finish(vsp_ctx *ctx, unsigned slot, XYZZ<HFp> *out);
-int msm_g2_finish(vsp_ctx *ctx, unsigned slot, XYZZ<HFp2> *out);
-// the results of a batch launch: one per vector
-int msm_g1_finish_batch(vsp_ctx *ctx, unsigned slot, XYZZ<HFp> *out, unsigned batch);
-int msm_g2_finish_batch(vsp_ctx *ctx, unsigned slot, XYZZ<HFp2> *out, unsigned batch);
+// the results of a launch: `count` of them, one per vector of its batch (1 for a launch without a batch)
+int msm_g1_finish(vsp_ctx *ctx, unsigned slot, XYZZ<HFp> *out, unsigned count = 1);
+int msm_g2_finish(vsp_ctx *ctx, unsigned slot, XYZZ<HFp2> *out, unsigned count = 1);
 // a finish in two halves: the wait (context state: caller's thread) and the fold of the window results (pure host arithmetic over the slot: any thread)
-int msm_g1_finish_wait(vsp_ctx *ctx, unsigned slot, bool *empty);
+int msm_g1_finish_wait(vsp_ctx *ctx, unsigned slot, unsigned count, bool *empty);
 void msm_g1_fold(vsp_ctx *ctx, unsigned slot, XYZZ<HFp> *out);
-int msm_g2_finish_wait(vsp_ctx *ctx, unsigned slot, bool *empty);
+int msm_g2_finish_wait(vsp_ctx *ctx, unsigned slot, unsigned count, bool *empty);
 void msm_g2_fold(vsp_ctx *ctx, unsigned slot, XYZZ<HFp2> *out);
 // rq over points [first, first + rq.n) of resident bases: fills in rq's bases, pre, table28 and glv
 int launch_on_bases(vsp_ctx *ctx, unsigned slot, const vsp_bases *bases, size_t first, MsmRequest rq);

@@ -2452,9 +2452,8 @@ int msm_g1_table28(vsp_ctx *ctx, const G1Affine *table, size_t count, void *d_ou
     return VSP_OK;
 }
 int msm_g1_launch(vsp_ctx *ctx, unsigned slot_id, const MsmRequest &rq) { return launch_slot<Fp>(ctx, slot_id, rq); }
-int msm_g1_finish(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp> *out) { return msm_finish<Fp, HFp>(ctx, slot(ctx, slot_id), out); }
-int msm_g1_finish_batch(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp> *out, unsigned batch) { return msm_finish<Fp, HFp>(ctx, slot(ctx, slot_id), out, batch); }
-int msm_g1_finish_wait(vsp_ctx *ctx, unsigned slot_id, bool *empty) { return msm_finish_wait<Fp, HFp>(ctx, slot(ctx, slot_id), 1, empty); }
+int msm_g1_finish(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp> *out, unsigned count) { return msm_finish<Fp, HFp>(ctx, slot(ctx, slot_id), out, count); }
+int msm_g1_finish_wait(vsp_ctx *ctx, unsigned slot_id, unsigned count, bool *empty) { return msm_finish_wait<Fp, HFp>(ctx, slot(ctx, slot_id), count, empty); }
 void msm_g1_fold(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp> *out) { msm_fold<Fp, HFp>(slot(ctx, slot_id), out); }
 // the census kernel runs on the CONTEXT's stream (so it cannot be held up behind low-priority work); the slot picks it up
 // A stream for a work slot: the LOWEST priority -- work on the context's stream (the NTTs of witness_map, whose result gates the H
@@ -2554,9 +2553,8 @@ int msm_g2_table28(vsp_ctx *ctx, const G2Affine *table, size_t count, void *d_ou
     return VSP_OK;
 }
 int msm_g2_launch(vsp_ctx *ctx, unsigned slot_id, const MsmRequest &rq) { return launch_slot<Fp2>(ctx, slot_id, rq); }
-int msm_g2_finish(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp2> *out) { return msm_finish<Fp2, HFp2>(ctx, slot(ctx, slot_id), out); }
-int msm_g2_finish_batch(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp2> *out, unsigned batch) { return msm_finish<Fp2, HFp2>(ctx, slot(ctx, slot_id), out, batch); }
-int msm_g2_finish_wait(vsp_ctx *ctx, unsigned slot_id, bool *empty) { return msm_finish_wait<Fp2, HFp2>(ctx, slot(ctx, slot_id), 1, empty); }
+int msm_g2_finish(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp2> *out, unsigned count) { return msm_finish<Fp2, HFp2>(ctx, slot(ctx, slot_id), out, count); }
+int msm_g2_finish_wait(vsp_ctx *ctx, unsigned slot_id, unsigned count, bool *empty) { return msm_finish_wait<Fp2, HFp2>(ctx, slot(ctx, slot_id), count, empty); }
 void msm_g2_fold(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp2> *out) { msm_fold<Fp2, HFp2>(slot(ctx, slot_id), out); }
 int subgroup_check_g2(vsp_ctx *ctx, const G2Affine *d_mont, size_t n, uint32_t *d_flag) {
     if (!n) return VSP_OK;

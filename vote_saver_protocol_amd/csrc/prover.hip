@@ -146,17 +146,65 @@ static bool delta_tables(vsp_ctx *ctx, const vsp_pk *pk) {
     }
     return true;
 }
-}  // namespace vsp
-extern "C" {
 
-// the witness as the caller hands it over: plain (num_vars x 4 canonical words), or packed (vsp_witness_pack)
-struct WitnessSrc { const uint64_t *plain; const uint64_t *class_words; const uint32_t *word_offsets; const uint64_t *dense; size_t n_dense; };
-static int prove_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const WitnessSrc &w, const uint64_t r[4], const uint64_t s[4],
-                             const uint64_t *saver_P1, const uint64_t *saver_r_enc);
-static int prove_finish_impl(vsp_ctx *ctx, uint64_t A_out[12], uint64_t B_out[24], uint64_t C_out[12], uint8_t proof_out[192], const std::function<void()> *overlap);
+// host time since the previous lap (or the construction), added to the vsp_get_stat counter the lap names
+struct HostLap {
+    vsp_ctx *ctx; double t = now();
+    static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    void operator()(const char *name) { const double t1 = now(); ctx->stats[name] += t1 - t; t = t1; }
+};
 
-}  // extern "C"
-namespace vsp {
+// ---- the Groth16 algebra of one proof on the host: the single prover and the batch call these, so their proofs agree byte for byte
+// k delta in G1 / G2: over the key's fixed-base tables (delta_tables; round 4: at most 32 additions per multiple instead of 255 doublings
+// + ~127 additions), or by double-and-add without them
+struct DeltaMul {
+    const vsp_pk *pk; bool fixed; XYZZ<HFp> d1; XYZZ<HFp2> d2;
+    DeltaMul(vsp_ctx *ctx, const vsp_pk *pk_) : pk(pk_), fixed(delta_tables(ctx, pk_)), d1(xyzz_from_affine(pk_->delta_g1)), d2(xyzz_from_affine(pk_->delta_g2)) {}
+    XYZZ<HFp> g1(const uint64_t k[4]) const { return fixed ? xyzz_mul_fixed(pk->tab1, k) : xyzz_mul_scalar(d1, k, 255); }
+    XYZZ<HFp2> g2(const uint64_t k[4]) const { return fixed ? xyzz_mul_fixed(pk->tab2, k) : xyzz_mul_scalar(d2, k, 255); }
+};
+static void rs_product(const uint64_t r[4], const uint64_t s[4], uint64_t rs[4]) { host_store_canon(rs, mul(host_load_canon<HFr>(r), host_load_canon<HFr>(s))); }
+// A = alpha + sum z_i A_i + r delta, B = beta + sum z_i B_i + s delta (G1 and G2) from the multi-exponentiations' results eA, eB1, eB2
+static XYZZ<HFp> proof_a(const vsp_pk *pk, XYZZ<HFp> eA, const XYZZ<HFp> &r_delta) { xyzz_madd(eA, pk->alpha_g1); xyzz_add(eA, r_delta); return eA; }
+static XYZZ<HFp> proof_b1(const vsp_pk *pk, XYZZ<HFp> eB1, const XYZZ<HFp> &s_delta) { xyzz_madd(eB1, pk->beta_g1); xyzz_add(eB1, s_delta); return eB1; }
+static XYZZ<HFp2> proof_b2(const vsp_pk *pk, XYZZ<HFp2> eB2, const XYZZ<HFp2> &s_delta2) { xyzz_madd(eB2, pk->beta_g2); xyzz_add(eB2, s_delta2); return eB2; }
+// C = sum h_i H_i + sum_{aux} z_i L_i + s A + r B1 - r s delta (+ r_enc P1; `saver` is infinity outside SAVER mode)
+static XYZZ<HFp> proof_c(XYZZ<HFp> eH, const XYZZ<HFp> &eL, const XYZZ<HFp> &s_gA, const XYZZ<HFp> &r_gB1, const XYZZ<HFp> &neg_rs_delta, const XYZZ<HFp> &saver) {
+    xyzz_add(eH, eL); xyzz_add(eH, s_gA); xyzz_add(eH, r_gB1); xyzz_add(eH, neg_rs_delta); xyzz_add(eH, saver);
+    return eH;
+}
+// proof k into the outputs (any may be null): A, B, C as canonical affine words, and the 192 compressed bytes
+static void store_proof(size_t k, const XYZZ<HFp> &gA, const XYZZ<HFp2> &gB2, const XYZZ<HFp> &gC, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out) {
+    uint64_t A12[12], B24[24], C12[12];
+    host_store_g1(A12, xyzz_to_affine(gA)); host_store_g2(B24, xyzz_to_affine(gB2)); host_store_g1(C12, xyzz_to_affine(gC));
+    if (A_out) memcpy(A_out + 12 * k, A12, sizeof A12);
+    if (B_out) memcpy(B_out + 24 * k, B24, sizeof B24);
+    if (C_out) memcpy(C_out + 12 * k, C12, sizeof C12);
+    if (proofs_out) { uint8_t *p = proofs_out + 192 * k; vsp_g1_compress(A12, p); vsp_g2_compress(B24, p + 48); vsp_g1_compress(C12, p + 144); }
+}
+
+// ---- the proof or the batch in flight on a context (ctx->prove), between a launch and its finish
+// the start both launches share: the checks, made before anything is queued (arguments present, nothing in flight, the K pairs (r, s) and
+// r_enc canonical, the key made for the constraint system), then the record the finish reads -- active once the launch body has succeeded
+static int prove_begin(vsp_ctx *ctx, bool batch, bool args_present, const vsp_r1cs *cs, const vsp_pk *pk, size_t K, const uint64_t *r, const uint64_t *s,
+                       const uint64_t *saver_P1, const uint64_t *saver_r_enc) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!args_present) return set_error(ctx, VSP_ERR_ARG, batch ? "prove_batch: null argument or a batch outside 1..64" : "prove: null argument");
+    if (ctx->prove.active) return set_error(ctx, VSP_ERR_ARG, "prove: a proof is already in flight on this context (finish it first)");
+    for (size_t k = 0; k < K; k++)
+        if (!fr_canonical(r + 4 * k) || !fr_canonical(s + 4 * k) || (saver_r_enc && !fr_canonical(saver_r_enc)))
+            return set_error(ctx, VSP_ERR_ARG, batch ? "prove: r and s must be canonical (< r)" : "prove: r, s and r_enc must be canonical (< r)");
+    const size_t nv = cs->num_vars;
+    if (pk->A->n != nv + 1 || pk->B1->n != nv + 1 || pk->B2->n != nv + 1 || pk->H->n + 1 != cs->dom.m || pk->L->n != nv - cs->num_inputs)
+        return set_error(ctx, VSP_ERR_ARG, "prove: proving key does not match the constraint system");
+    auto &p = ctx->prove;
+    p.batch = batch; p.pk = pk; p.count = K; p.z_bytes = K * (nv + 1) * sizeof(Fr);
+    p.r.assign(r, r + 4 * K); p.s.assign(s, s + 4 * K);
+    p.has_saver = saver_P1 && saver_r_enc;
+    if (p.has_saver) { memcpy(p.P1, saver_P1, 96); memcpy(p.r_enc, saver_r_enc, 32); }
+    return VSP_OK;
+}
+// the end of a failed launch and of every finish
 static void prove_cleanup(vsp_ctx *ctx, int rc) {
     if (rc != VSP_OK) {
         // an early return leaves multi-exponentiations in flight on their own streams, still reading the witness and H vectors:
@@ -166,19 +214,35 @@ static void prove_cleanup(vsp_ctx *ctx, int rc) {
         ctx->err = keep;
     }
     for (unsigned k = 1; k <= 4; k++) (void)msm_slot_use_stream(ctx, k, nullptr);      // the slots go back to their own streams
-    // the witness does not outlive the call in device memory
-    if (ctx->pr_z.p) hipMemsetAsync(ctx->pr_z.p, 0, ctx->pr_z.cap, ctx->stream);
+    // the call's copy of its witnesses, z = (1, witness) for each of the K, is zeroed; what was derived from them -- A z, B z, C z
+    // (pr_abc), the H coefficients (pr_h), the packed witness (pr_pack) -- stays resident until the next call overwrites it
+    const size_t zb = ctx->prove.z_bytes < ctx->pr_z.cap ? ctx->prove.z_bytes : ctx->pr_z.cap;
+    if (ctx->pr_z.p && zb) hipMemsetAsync(ctx->pr_z.p, 0, zb, ctx->stream);
     ctx->prove.active = false;
 }
+// the four witness multi-exponentiations as two chains on the prover's two low-priority streams: slots 1, 2 on one, 3, 4 on the other
+static int prove_use_streams(vsp_ctx *ctx) {
+    for (int k = 0; k < 2; k++) if (!ctx->prove_streams[k]) VSP_TRY(msm_make_slot_stream(ctx, &ctx->prove_streams[k]));
+    VSP_TRY(msm_slot_use_stream(ctx, 1, ctx->prove_streams[0])); VSP_TRY(msm_slot_use_stream(ctx, 2, ctx->prove_streams[0]));
+    VSP_TRY(msm_slot_use_stream(ctx, 3, ctx->prove_streams[1])); VSP_TRY(msm_slot_use_stream(ctx, 4, ctx->prove_streams[1]));
+    return VSP_OK;
+}
+}  // namespace vsp
+extern "C" {
+
+// the witness as the caller hands it over: plain (num_vars x 4 canonical words), or packed (vsp_witness_pack)
+struct WitnessSrc { const uint64_t *plain; const uint64_t *class_words; const uint32_t *word_offsets; const uint64_t *dense; size_t n_dense; };
+static int prove_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const WitnessSrc &w);
+static int prove_finish_impl(vsp_ctx *ctx, uint64_t A_out[12], uint64_t B_out[24], uint64_t C_out[12], uint8_t proof_out[192], const std::function<void()> *overlap);
+
+}  // extern "C"
+namespace vsp {
 static int prove_launch_checked(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const WitnessSrc &w, const uint64_t r[4], const uint64_t s[4],
                                 const uint64_t *saver_P1, const uint64_t *saver_r_enc) {
-    if (!ctx) return VSP_ERR_ARG;
-    if (!cs || !pk || !r || !s || (!w.plain && !(w.class_words && w.word_offsets && (w.dense || !w.n_dense)))) return set_error(ctx, VSP_ERR_ARG, "prove: null argument");
-    if (ctx->prove.active || ctx->prove_batch.active) return set_error(ctx, VSP_ERR_ARG, "prove: a proof is already in flight on this context (finish it first)");
-    if (!fr_canonical(r) || !fr_canonical(s) || (saver_r_enc && !fr_canonical(saver_r_enc)))
-        return set_error(ctx, VSP_ERR_ARG, "prove: r, s and r_enc must be canonical (< r)");
-    int rc = prove_launch_impl(ctx, cs, pk, w, r, s, saver_P1, saver_r_enc);
-    if (rc != VSP_OK) prove_cleanup(ctx, rc);
+    const bool args = cs && pk && r && s && (w.plain || (w.class_words && w.word_offsets && (w.dense || !w.n_dense)));
+    VSP_TRY(prove_begin(ctx, false, args, cs, pk, 1, r, s, saver_P1, saver_r_enc));
+    int rc = prove_launch_impl(ctx, cs, pk, w);
+    if (rc != VSP_OK) prove_cleanup(ctx, rc); else ctx->prove.active = true;
     return rc;
 }
 // the prover with a hook: `overlap` runs on the host after every kernel is queued and before the first wait -- the window in which
@@ -231,7 +295,7 @@ int vsp_groth16_prove_launch_packed(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_
 }
 int vsp_groth16_prove_finish(vsp_ctx *ctx, uint64_t A_out[12], uint64_t B_out[24], uint64_t C_out[12], uint8_t proof_out[192]) {
     if (!ctx) return VSP_ERR_ARG;
-    if (!ctx->prove.active) return set_error(ctx, VSP_ERR_ARG, "prove_finish: no proof in flight on this context");
+    if (!ctx->prove.active || ctx->prove.batch) return set_error(ctx, VSP_ERR_ARG, "prove_finish: no proof in flight on this context");
     int rc = prove_finish_impl(ctx, A_out, B_out, C_out, proof_out, nullptr);
     prove_cleanup(ctx, rc);
     return rc;
@@ -281,24 +345,17 @@ __global__ __launch_bounds__(256) void k_witness_expand(const uint64_t *class_wo
     z[2 * i] = lo; z[2 * i + 1] = hi;
 }
 
-static int prove_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const WitnessSrc &wsrc, const uint64_t r[4], const uint64_t s[4],
-                             const uint64_t *saver_P1, const uint64_t *saver_r_enc) {
+static int prove_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const WitnessSrc &wsrc) {
     const size_t nv = cs->num_vars, ni = cs->num_inputs, nc = cs->num_constraints;
     const size_t m = cs->dom.m;
-    if (pk->A->n != nv + 1 || pk->B1->n != nv + 1 || pk->B2->n != nv + 1 || pk->H->n + 1 != m || pk->L->n != nv - ni)
-        return set_error(ctx, VSP_ERR_ARG, "prove: proving key does not match the constraint system");
     VSP_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t_prev = now();
-    auto lap = [&](const char *name) { double t = now(); ctx->stats[name] += t - t_prev; t_prev = t; };
-    // z = (1, witness) canonical on device
+    HostLap lap{ctx};
+    // z = (1, witness) canonical on device; the workspace of a batch of one: A z, B z, C z one after the other in pr_abc
     VSP_TRY(ensure(ctx, ctx->pr_z, (nv + 1) * sizeof(Fr)));
-    VSP_TRY(ensure(ctx, ctx->pr_a, m * sizeof(Fr)));
-    VSP_TRY(ensure(ctx, ctx->pr_b, m * sizeof(Fr)));
-    VSP_TRY(ensure(ctx, ctx->pr_c, m * sizeof(Fr)));
+    VSP_TRY(ensure(ctx, ctx->pr_abc, 3 * m * sizeof(Fr)));
     VSP_TRY(ensure(ctx, ctx->pr_h, m * sizeof(Fr)));
-    Fr *dz = (Fr *)ctx->pr_z.p, *dA = (Fr *)ctx->pr_a.p, *dB = (Fr *)ctx->pr_b.p, *dC = (Fr *)ctx->pr_c.p, *dH = (Fr *)ctx->pr_h.p;
+    Fr *dz = (Fr *)ctx->pr_z.p, *dA = (Fr *)ctx->pr_abc.p, *dB = dA + m, *dC = dA + 2 * m, *dH = (Fr *)ctx->pr_h.p;
     const uint64_t one4[4] = {1, 0, 0, 0};
     VSP_HIP(hipMemcpyAsync(dz, one4, 32, hipMemcpyHostToDevice, st));
     if (wsrc.plain) VSP_HIP(hipMemcpyAsync(dz + 1, wsrc.plain, nv * 32, hipMemcpyHostToDevice, st));
@@ -336,12 +393,7 @@ static int prove_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk,
     // contexts; the other pairings lose (A,B2 | B1,L: 7.8 ms; all four on one stream: 7.3 ms).  Fewer concurrent witness chains leave the
     // transforms and the H accumulation -- the critical chain -- alone for longer.  Option "prove_witness_streams" = 0: the
     // slots' own streams.
-    const long wstreams = opt(ctx, "prove_witness_streams", 1);
-    if (wstreams) {
-        for (int k = 0; k < 2; k++) if (!ctx->prove_streams[k]) VSP_TRY(msm_make_slot_stream(ctx, &ctx->prove_streams[k]));
-        VSP_TRY(msm_slot_use_stream(ctx, 1, ctx->prove_streams[0])); VSP_TRY(msm_slot_use_stream(ctx, 2, ctx->prove_streams[0]));
-        VSP_TRY(msm_slot_use_stream(ctx, 3, ctx->prove_streams[1])); VSP_TRY(msm_slot_use_stream(ctx, 4, ctx->prove_streams[1]));
-    }
+    if (opt(ctx, "prove_witness_streams", 1)) VSP_TRY(prove_use_streams(ctx));
     VSP_TRY(msm_slot_census(ctx, 1, dz, nv + 1));
     VSP_TRY(msm_slot_census(ctx, 4, dz + ni + 1, nv - ni));
     VSP_HIP(hipEventRecord(ctx->ev_aux, st));          // z resident and censuses queued
@@ -380,41 +432,28 @@ static int prove_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk,
         VSP_TRY(launch_on_bases(ctx, 0, pk->H, 0, h));
     }
     lap("prove_launch_ms");
-    // what the second half needs: the key, the randomness, the SAVER term
-    ctx->prove.active = true; ctx->prove.pk = pk;
-    memcpy(ctx->prove.r, r, 32); memcpy(ctx->prove.s, s, 32);
-    ctx->prove.has_saver = saver_P1 && saver_r_enc;
-    if (ctx->prove.has_saver) { memcpy(ctx->prove.P1, saver_P1, 96); memcpy(ctx->prove.r_enc, saver_r_enc, 32); }
     return VSP_OK;
 }
 
 static int prove_finish_impl(vsp_ctx *ctx, uint64_t A_out[12], uint64_t B_out[24], uint64_t C_out[12], uint8_t proof_out[192], const std::function<void()> *overlap) {
     const vsp_pk *pk = ctx->prove.pk;
-    const uint64_t *r = ctx->prove.r, *s = ctx->prove.s;
-    const uint64_t *saver_P1 = ctx->prove.has_saver ? ctx->prove.P1 : nullptr, *saver_r_enc = ctx->prove.has_saver ? ctx->prove.r_enc : nullptr;
+    const uint64_t *r = ctx->prove.r.data(), *s = ctx->prove.s.data();
     VSP_HIP(hipSetDevice(ctx->device));
-    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t_prev = now();
-    auto lap = [&](const char *name) { double t = now(); ctx->stats[name] += t - t_prev; t_prev = t; };
-    XYZZ<HFp> eA = XYZZ<HFp>::inf(), eB1 = XYZZ<HFp>::inf(), eH = XYZZ<HFp>::inf(), eL = XYZZ<HFp>::inf(); XYZZ<HFp2> eB2 = XYZZ<HFp2>::inf();
+    HostLap lap{ctx};
     // host work that needs no MSM result, done while the GPU runs: the four multiples of delta on four host threads (round 4: at the real
     // circuit's size the HOST was the critical path of a proof -- 0.85 ms of scalar multiplications here and ~1 ms of Horner chains in the
     // five finishes below, one after the other, against ~1.5 ms of GPU work; tools/prove_phases.py)
-    XYZZ<HFp> dj = xyzz_from_affine(pk->delta_g1);
-    XYZZ<HFp2> dj2 = xyzz_from_affine(pk->delta_g2);
-    HFr rr = host_load_canon<HFr>(r), ss = host_load_canon<HFr>(s);
-    uint64_t rs4[4]; host_store_canon(rs4, mul(rr, ss));
+    uint64_t rs4[4]; rs_product(r, s, rs4);
     XYZZ<HFp> r_delta, s_delta, neg_rs_delta, saver = XYZZ<HFp>::inf();
     XYZZ<HFp2> s_delta2;
-    const long hthreads = opt(ctx, "prove_host_threads", 1);
-    const unsigned T = hthreads ? 8u : 1u;
-    const bool fixed = delta_tables(ctx, pk);                 // (round 4: at most 32 additions per multiple of delta instead of 255 doublings + ~127 additions)
+    const unsigned T = opt(ctx, "prove_host_threads", 1) ? 8u : 1u;
+    const DeltaMul delta(ctx, pk);
     host_parallel_for(5, [&](size_t j) {
-        if (j == 0) s_delta2 = fixed ? xyzz_mul_fixed(pk->tab2, s) : xyzz_mul_scalar(dj2, s, 255);                 // the G2 one is the longest: first
-        else if (j == 1) r_delta = fixed ? xyzz_mul_fixed(pk->tab1, r) : xyzz_mul_scalar(dj, r, 255);
-        else if (j == 2) s_delta = fixed ? xyzz_mul_fixed(pk->tab1, s) : xyzz_mul_scalar(dj, s, 255);
-        else if (j == 3) neg_rs_delta = xyzz_neg(fixed ? xyzz_mul_fixed(pk->tab1, rs4) : xyzz_mul_scalar(dj, rs4, 255));
-        else if (saver_P1 && saver_r_enc) saver = xyzz_mul_scalar_w4(xyzz_from_affine(host_load_g1(saver_P1)), saver_r_enc);
+        if (j == 0) s_delta2 = delta.g2(s);                   // the G2 one is the longest: first
+        else if (j == 1) r_delta = delta.g1(r);
+        else if (j == 2) s_delta = delta.g1(s);
+        else if (j == 3) neg_rs_delta = xyzz_neg(delta.g1(rs4));
+        else if (ctx->prove.has_saver) saver = xyzz_mul_scalar_w4(xyzz_from_affine(host_load_g1(ctx->prove.P1)), ctx->prove.r_enc);
     }, T);
     if (overlap && *overlap) (*overlap)();
     lap("prove_host_overlap_ms");
@@ -422,46 +461,25 @@ static int prove_finish_impl(vsp_ctx *ctx, uint64_t A_out[12], uint64_t B_out[24
     // thread: it touches the context) and a fold of the window results -- a Horner chain of a few hundred host group operations, 0.2 ms in G1,
     // 0.6 ms in G2 -- which runs on a thread of its own while this one waits for the next slot; s * A and r * B1, the two 255-bit scalar
     // multiplications of the assembly, follow their folds on the same threads.  Option "prove_host_threads" = 0: everything on this thread.
-    XYZZ<HFp> gA, gB1, s_gA, r_gB1;
+    XYZZ<HFp> eA = XYZZ<HFp>::inf(), eB1 = XYZZ<HFp>::inf(), eH = XYZZ<HFp>::inf(), eL = XYZZ<HFp>::inf(); XYZZ<HFp2> eB2 = XYZZ<HFp2>::inf();
+    XYZZ<HFp> gA, s_gA, r_gB1;
     XYZZ<HFp2> gB2;
     std::vector<std::thread> workers;
     auto run = [&](std::function<void()> f) { if (T > 1) workers.emplace_back(std::move(f)); else f(); };
-    auto join_all = [&]() { for (auto &w : workers) w.join(); workers.clear(); };
     int rc = VSP_OK; bool empty = false;
-    if ((rc = msm_g1_finish_wait(ctx, 1, &empty)) == VSP_OK) {
-        const bool e = empty;
-        run([&, e]() { if (!e) msm_g1_fold(ctx, 1, &eA); gA = eA; xyzz_madd(gA, pk->alpha_g1); xyzz_add(gA, r_delta); s_gA = xyzz_mul_scalar_w4(gA, s); });
-    }
-    if (rc == VSP_OK && (rc = msm_g1_finish_wait(ctx, 2, &empty)) == VSP_OK) {
-        const bool e = empty;
-        run([&, e]() { if (!e) msm_g1_fold(ctx, 2, &eB1); gB1 = eB1; xyzz_madd(gB1, pk->beta_g1); xyzz_add(gB1, s_delta); r_gB1 = xyzz_mul_scalar_w4(gB1, r); });
-    }
-    if (rc == VSP_OK && (rc = msm_g1_finish_wait(ctx, 4, &empty)) == VSP_OK) {
-        const bool e = empty;
-        run([&, e]() { if (!e) msm_g1_fold(ctx, 4, &eL); });
-    }
-    if (rc == VSP_OK && (rc = msm_g2_finish_wait(ctx, 3, &empty)) == VSP_OK) {
-        const bool e = empty;
-        run([&, e]() { if (!e) msm_g2_fold(ctx, 3, &eB2); gB2 = eB2; xyzz_madd(gB2, pk->beta_g2); xyzz_add(gB2, s_delta2); });
-    }
-    if (rc == VSP_OK && (rc = msm_g1_finish_wait(ctx, 0, &empty)) == VSP_OK && !empty) msm_g1_fold(ctx, 0, &eH);
-    join_all();
+    if ((rc = msm_g1_finish_wait(ctx, 1, 1, &empty)) == VSP_OK)
+        run([&, e = empty]() { if (!e) msm_g1_fold(ctx, 1, &eA); gA = proof_a(pk, eA, r_delta); s_gA = xyzz_mul_scalar_w4(gA, s); });
+    if (rc == VSP_OK && (rc = msm_g1_finish_wait(ctx, 2, 1, &empty)) == VSP_OK)
+        run([&, e = empty]() { if (!e) msm_g1_fold(ctx, 2, &eB1); r_gB1 = xyzz_mul_scalar_w4(proof_b1(pk, eB1, s_delta), r); });
+    if (rc == VSP_OK && (rc = msm_g1_finish_wait(ctx, 4, 1, &empty)) == VSP_OK)
+        run([&, e = empty]() { if (!e) msm_g1_fold(ctx, 4, &eL); });
+    if (rc == VSP_OK && (rc = msm_g2_finish_wait(ctx, 3, 1, &empty)) == VSP_OK)
+        run([&, e = empty]() { if (!e) msm_g2_fold(ctx, 3, &eB2); gB2 = proof_b2(pk, eB2, s_delta2); });
+    if (rc == VSP_OK && (rc = msm_g1_finish_wait(ctx, 0, 1, &empty)) == VSP_OK && !empty) msm_g1_fold(ctx, 0, &eH);
+    for (auto &w : workers) w.join();
     if (rc != VSP_OK) return rc;
     lap("prove_wait_ms");
-    // assembly: a handful of group operations
-    XYZZ<HFp> gC = eH; xyzz_add(gC, eL);
-    xyzz_add(gC, s_gA);
-    xyzz_add(gC, r_gB1);
-    xyzz_add(gC, neg_rs_delta);
-    xyzz_add(gC, saver);
-    Affine<HFp> a = xyzz_to_affine(gA), c = xyzz_to_affine(gC);
-    Affine<HFp2> b = xyzz_to_affine(gB2);
-    uint64_t A12[12], B24[24], C12[12];
-    host_store_g1(A12, a); host_store_g2(B24, b); host_store_g1(C12, c);
-    if (A_out) memcpy(A_out, A12, sizeof A12);
-    if (B_out) memcpy(B_out, B24, sizeof B24);
-    if (C_out) memcpy(C_out, C12, sizeof C12);
-    if (proof_out) { vsp_g1_compress(A12, proof_out); vsp_g2_compress(B24, proof_out + 48); vsp_g1_compress(C12, proof_out + 144); }
+    store_proof(0, gA, gB2, proof_c(eH, eL, s_gA, r_gB1, neg_rs_delta, saver), A_out, B_out, C_out, proof_out);      // a handful of group operations
     lap("prove_assembly_ms");
     ctx->stats["prove_calls"] += 1;
     return VSP_OK;
@@ -473,27 +491,18 @@ static int prove_finish_impl(vsp_ctx *ctx, uint64_t A_out[12], uint64_t B_out[24
 // from one context, ~900 / s from twelve.  K witnesses proved TOGETHER run the same number of launches K times as wide: one matvec, one
 // witness_map over 3 K transforms, and each of the five multi-exponentiations once over K scalar vectors (MsmGeom.K: separate bucket sets
 // per witness, the same base rows).  Every proof is byte-identical to vsp_groth16_prove's for the same (witness, r, s).
-// PLAIN key (vsp_groth16_generate with precompute = 0, or vsp_pk_create over plain bases): a batch has no use for tables of window multiples.
-static void prove_batch_cleanup(vsp_ctx *ctx, int rc) {
-    if (rc != VSP_OK) { std::string keep = ctx->err; msm_drain_slots(ctx); ctx->err = keep; }
-    for (unsigned k = 1; k <= 4; k++) (void)msm_slot_use_stream(ctx, k, nullptr);
-    if (ctx->pr_bz.p) hipMemsetAsync(ctx->pr_bz.p, 0, ctx->pr_bz.cap, ctx->stream);      // the witnesses do not outlive the call in device memory
-}
+// The key is plain (vsp_groth16_generate with precompute = 0, or vsp_pk_create over plain bases) or has tables of window multiples of at
+// most 16 bits (pre_c <= 16: one bucket set per witness and query -- worth it where the tables are small, i.e. at the real circuit's size);
+// other tables, or any table with option "msm_batch_tables" = 0, are refused with VSP_ERR_UNSUPPORTED.
 static int prove_batch_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witnesses, size_t K) {
     const size_t nv = cs->num_vars, ni = cs->num_inputs, nc = cs->num_constraints, m = cs->dom.m, zs = nv + 1;
-    if (pk->A->n != nv + 1 || pk->B1->n != nv + 1 || pk->B2->n != nv + 1 || pk->H->n + 1 != m || pk->L->n != nv - ni)
-        return set_error(ctx, VSP_ERR_ARG, "prove: proving key does not match the constraint system");
-    // (a key with tables of window multiples: one bucket set per witness and query, windows of 16 bits -- worth it where the tables are small, i.e. at
-    // the real circuit's size; option "msm_batch_tables" = 0 refuses such keys as rounds before the end of round 4 did)
     VSP_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t_prev = now();
-    auto lap = [&](const char *name) { double t = now(); ctx->stats[name] += t - t_prev; t_prev = t; };      // vsp_get_stat "prove_batch_*_ms": where a batch's time goes on the host
-    VSP_TRY(ensure(ctx, ctx->pr_bz, K * zs * sizeof(Fr)));
-    VSP_TRY(ensure(ctx, ctx->pr_babc, K * 3 * m * sizeof(Fr)));
-    VSP_TRY(ensure(ctx, ctx->pr_bh, K * m * sizeof(Fr)));
-    Fr *dz = (Fr *)ctx->pr_bz.p, *abc = (Fr *)ctx->pr_babc.p, *dH = (Fr *)ctx->pr_bh.p;
+    HostLap lap{ctx};                                         // vsp_get_stat "prove_batch_*_ms": where a batch's time goes on the host
+    VSP_TRY(ensure(ctx, ctx->pr_z, K * zs * sizeof(Fr)));
+    VSP_TRY(ensure(ctx, ctx->pr_abc, K * 3 * m * sizeof(Fr)));
+    VSP_TRY(ensure(ctx, ctx->pr_h, K * m * sizeof(Fr)));
+    Fr *dz = (Fr *)ctx->pr_z.p, *abc = (Fr *)ctx->pr_abc.p, *dH = (Fr *)ctx->pr_h.p;
     // z_k = (1, witness_k), canonical: the K ones from a small host array, the witnesses by one strided copy
     std::vector<uint64_t> ones(K * 4, 0); for (size_t k = 0; k < K; k++) ones[4 * k] = 1;
     VSP_HIP(hipMemcpy2DAsync(dz, zs * 32, ones.data(), 32, 32, K, hipMemcpyHostToDevice, st));
@@ -506,10 +515,7 @@ static int prove_batch_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_p
     }
     VSP_HIP(hipMemcpy2DAsync(abc + nc, 3 * m * sizeof(Fr), dz, zs * sizeof(Fr), (ni + 1) * sizeof(Fr), K, hipMemcpyDeviceToDevice, st));      // the rows "input_i * 0 = 0" of A
     VSP_HIP(hipStreamSynchronize(st));                       // `ones` goes out of scope; the copies above are queued from pageable memory anyway
-    // the four witness multi-exponentiations as two chains on the prover's two low-priority streams, the H chain on the context's (prove_launch_impl)
-    for (int k = 0; k < 2; k++) if (!ctx->prove_streams[k]) VSP_TRY(msm_make_slot_stream(ctx, &ctx->prove_streams[k]));
-    VSP_TRY(msm_slot_use_stream(ctx, 1, ctx->prove_streams[0])); VSP_TRY(msm_slot_use_stream(ctx, 2, ctx->prove_streams[0]));
-    VSP_TRY(msm_slot_use_stream(ctx, 3, ctx->prove_streams[1])); VSP_TRY(msm_slot_use_stream(ctx, 4, ctx->prove_streams[1]));
+    VSP_TRY(prove_use_streams(ctx));                         // the H chain on the context's stream (prove_launch_impl)
     VSP_TRY(witness_map_device_batch(ctx, abc, (unsigned)K, &cs->dom, dH));
     MsmRequest h(dH, m - 1), a(dz, nv + 1), l(dz + ni + 1, nv - ni);      // as in prove_launch_impl, K vectors each
     h.dense = true; h.batch = a.batch = l.batch = (unsigned)K; h.stride = m; a.stride = l.stride = zs;      // H coefficients are dense
@@ -526,94 +532,66 @@ static int prove_batch_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_p
     lap("prove_batch_launch_ms");
     return VSP_OK;
 }
-static int prove_batch_finish_impl(vsp_ctx *ctx, const vsp_pk *pk, size_t K, const uint64_t *r, const uint64_t *s,
-                                   uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out) {
-    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t_prev = now();
-    auto lap = [&](const char *name) { double t = now(); ctx->stats[name] += t - t_prev; t_prev = t; };
+static int prove_batch_finish_impl(vsp_ctx *ctx, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out) {
+    const vsp_pk *pk = ctx->prove.pk;
+    const size_t K = ctx->prove.count;
+    const uint64_t *r = ctx->prove.r.data(), *s = ctx->prove.s.data();
+    HostLap lap{ctx};
     VSP_HIP(hipSetDevice(ctx->device));
     // host work that needs no result: the delta multiples of every proof
-    XYZZ<HFp> dj = xyzz_from_affine(pk->delta_g1);
-    XYZZ<HFp2> dj2 = xyzz_from_affine(pk->delta_g2);
     std::vector<XYZZ<HFp>> r_delta(K), s_delta(K), neg_rs_delta(K);
     std::vector<XYZZ<HFp2>> s_delta2(K);
-    const bool fixed = delta_tables(ctx, pk);
+    const DeltaMul delta(ctx, pk);
     host_parallel_for(K, [&](size_t k) {
         const uint64_t *rk = r + 4 * k, *sk = s + 4 * k;
-        uint64_t rs4[4]; host_store_canon(rs4, mul(host_load_canon<HFr>(rk), host_load_canon<HFr>(sk)));
-        if (fixed) {
-            r_delta[k] = xyzz_mul_fixed(pk->tab1, rk); s_delta[k] = xyzz_mul_fixed(pk->tab1, sk);
-            neg_rs_delta[k] = xyzz_neg(xyzz_mul_fixed(pk->tab1, rs4));
-            s_delta2[k] = xyzz_mul_fixed(pk->tab2, sk);
-        } else {
-            r_delta[k] = xyzz_mul_scalar(dj, rk, 255); s_delta[k] = xyzz_mul_scalar(dj, sk, 255);
-            neg_rs_delta[k] = xyzz_neg(xyzz_mul_scalar(dj, rs4, 255));
-            s_delta2[k] = xyzz_mul_scalar(dj2, sk, 255);
-        }
+        uint64_t rs4[4]; rs_product(rk, sk, rs4);
+        r_delta[k] = delta.g1(rk); s_delta[k] = delta.g1(sk);
+        neg_rs_delta[k] = xyzz_neg(delta.g1(rs4));
+        s_delta2[k] = delta.g2(sk);
     });
     lap("prove_batch_delta_ms");
     std::vector<XYZZ<HFp>> eA(K), eB1(K), eH(K), eL(K);
     std::vector<XYZZ<HFp2>> eB2(K);
-    VSP_TRY(msm_g1_finish_batch(ctx, 1, eA.data(), (unsigned)K));
-    VSP_TRY(msm_g1_finish_batch(ctx, 2, eB1.data(), (unsigned)K));
-    VSP_TRY(msm_g1_finish_batch(ctx, 4, eL.data(), (unsigned)K));
-    VSP_TRY(msm_g2_finish_batch(ctx, 3, eB2.data(), (unsigned)K));
+    VSP_TRY(msm_g1_finish(ctx, 1, eA.data(), (unsigned)K));
+    VSP_TRY(msm_g1_finish(ctx, 2, eB1.data(), (unsigned)K));
+    VSP_TRY(msm_g1_finish(ctx, 4, eL.data(), (unsigned)K));
+    VSP_TRY(msm_g2_finish(ctx, 3, eB2.data(), (unsigned)K));
     lap("prove_batch_witness_finishes_ms");
-    // s * A and r * B1 of every proof inside the wait for the H chain (prove_finish_impl, prove_early_assembly)
+    // s * A and r * B1 of every proof inside the wait for the H chain, as prove_finish_impl does them
     std::vector<XYZZ<HFp>> gA(K), s_gA(K), r_gB1(K);
     host_parallel_for(K, [&](size_t k) {
-        gA[k] = eA[k]; xyzz_madd(gA[k], pk->alpha_g1); xyzz_add(gA[k], r_delta[k]);
+        gA[k] = proof_a(pk, eA[k], r_delta[k]);
         s_gA[k] = xyzz_mul_scalar_w4(gA[k], s + 4 * k);
-        XYZZ<HFp> gB1 = eB1[k]; xyzz_madd(gB1, pk->beta_g1); xyzz_add(gB1, s_delta[k]);
-        r_gB1[k] = xyzz_mul_scalar_w4(gB1, r + 4 * k);
+        r_gB1[k] = xyzz_mul_scalar_w4(proof_b1(pk, eB1[k], s_delta[k]), r + 4 * k);
     });
     lap("prove_batch_sA_rB1_ms");
-    VSP_TRY(msm_g1_finish_batch(ctx, 0, eH.data(), (unsigned)K));
+    VSP_TRY(msm_g1_finish(ctx, 0, eH.data(), (unsigned)K));
     lap("prove_batch_h_finish_ms");
     host_parallel_for(K, [&](size_t k) {
-        XYZZ<HFp2> gB2 = eB2[k]; xyzz_madd(gB2, pk->beta_g2); xyzz_add(gB2, s_delta2[k]);
-        XYZZ<HFp> gC = eH[k]; xyzz_add(gC, eL[k]);
-        xyzz_add(gC, s_gA[k]); xyzz_add(gC, r_gB1[k]); xyzz_add(gC, neg_rs_delta[k]);
-        Affine<HFp> a = xyzz_to_affine(gA[k]), c = xyzz_to_affine(gC);
-        Affine<HFp2> b = xyzz_to_affine(gB2);
-        uint64_t A12[12], B24[24], C12[12];
-        host_store_g1(A12, a); host_store_g2(B24, b); host_store_g1(C12, c);
-        if (A_out) memcpy(A_out + 12 * k, A12, sizeof A12);
-        if (B_out) memcpy(B_out + 24 * k, B24, sizeof B24);
-        if (C_out) memcpy(C_out + 12 * k, C12, sizeof C12);
-        if (proofs_out) { vsp_g1_compress(A12, proofs_out + 192 * k); vsp_g2_compress(B24, proofs_out + 192 * k + 48); vsp_g1_compress(C12, proofs_out + 192 * k + 144); }
+        store_proof(k, gA[k], proof_b2(pk, eB2[k], s_delta2[k]), proof_c(eH[k], eL[k], s_gA[k], r_gB1[k], neg_rs_delta[k], XYZZ<HFp>::inf()),
+                    A_out, B_out, C_out, proofs_out);
     });
     lap("prove_batch_assembly_ms");
     ctx->stats["prove_calls"] += (double)K;
     ctx->stats["prove_batches"] += 1;
     return VSP_OK;
 }
-static int prove_batch_launch_checked(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witnesses, size_t count, const uint64_t *r, const uint64_t *s) {
-    if (!ctx) return VSP_ERR_ARG;
-    if (!cs || !pk || !witnesses || !r || !s || count < 1 || count > 64) return set_error(ctx, VSP_ERR_ARG, "prove_batch: null argument or a batch outside 1..64");
-    if (ctx->prove.active || ctx->prove_batch.active) return set_error(ctx, VSP_ERR_ARG, "prove: a proof is already in flight on this context (finish it first)");
-    for (size_t k = 0; k < count; k++)
-        if (!fr_canonical(r + 4 * k) || !fr_canonical(s + 4 * k)) return set_error(ctx, VSP_ERR_ARG, "prove: r and s must be canonical (< r)");
-    int rc = prove_batch_launch_impl(ctx, cs, pk, witnesses, count);
-    if (rc != VSP_OK) { prove_batch_cleanup(ctx, rc); return rc; }
-    ctx->prove_batch.active = true; ctx->prove_batch.pk = pk; ctx->prove_batch.count = count;
-    ctx->prove_batch.r.assign(r, r + 4 * count); ctx->prove_batch.s.assign(s, s + 4 * count);
-    return VSP_OK;
-}
 int vsp_groth16_prove_batch_launch(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witnesses, size_t count, const uint64_t *r, const uint64_t *s) {
-    return prove_batch_launch_checked(ctx, cs, pk, witnesses, count, r, s);
+    VSP_TRY(prove_begin(ctx, true, cs && pk && witnesses && r && s && count >= 1 && count <= 64, cs, pk, count, r, s, nullptr, nullptr));
+    int rc = prove_batch_launch_impl(ctx, cs, pk, witnesses, count);
+    if (rc != VSP_OK) prove_cleanup(ctx, rc); else ctx->prove.active = true;
+    return rc;
 }
 int vsp_groth16_prove_batch_finish(vsp_ctx *ctx, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out) {
     if (!ctx) return VSP_ERR_ARG;
-    if (!ctx->prove_batch.active) return set_error(ctx, VSP_ERR_ARG, "prove_batch_finish: no batch in flight on this context");
-    int rc = prove_batch_finish_impl(ctx, ctx->prove_batch.pk, ctx->prove_batch.count, ctx->prove_batch.r.data(), ctx->prove_batch.s.data(), A_out, B_out, C_out, proofs_out);
-    ctx->prove_batch.active = false;
-    prove_batch_cleanup(ctx, rc);
+    if (!ctx->prove.active || !ctx->prove.batch) return set_error(ctx, VSP_ERR_ARG, "prove_batch_finish: no batch in flight on this context");
+    int rc = prove_batch_finish_impl(ctx, A_out, B_out, C_out, proofs_out);
+    prove_cleanup(ctx, rc);
     return rc;
 }
 int vsp_groth16_prove_batch(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witnesses, size_t count, const uint64_t *r, const uint64_t *s,
                             uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out) {
-    int rc = prove_batch_launch_checked(ctx, cs, pk, witnesses, count, r, s);
+    int rc = vsp_groth16_prove_batch_launch(ctx, cs, pk, witnesses, count, r, s);
     if (rc != VSP_OK) return rc;
     return vsp_groth16_prove_batch_finish(ctx, A_out, B_out, C_out, proofs_out);
 }

@@ -19,10 +19,6 @@
 
 namespace vsp {
 
-int prove_with_overlap(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witness, const uint64_t r[4], const uint64_t s[4],
-                       const uint64_t *saver_P1, const uint64_t *saver_r_enc, uint64_t A_out[12], uint64_t B_out[24], uint64_t C_out[12],
-                       uint8_t proof_out[192], const std::function<void()> *overlap);
-
 // k * P for a fixed P: table[w][d - 1] = d * 16^w * P (affine), 64 windows x 15 entries; a product is <= 64 mixed additions
 struct FixedBase {
     std::vector<Affine<HFp>> tab;
