@@ -9,6 +9,7 @@ This module keeps the same names and argument meaning with numpy arrays of canon
 uint64 limbs (Fr: [n,4], G1 affine: [n,12], G2 affine: [n,24]; infinity = all zero).  Every call goes
 through libvsp_hip.so; nothing here computes field or curve arithmetic on the CPU.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -37,6 +38,16 @@ def _u64(a, cols=None):
     if cols is not None:
         a = a.reshape(-1, cols)
     return a
+
+
+# per group: uint64 words of a canonical affine point and of a Jacobian record, and the suffix of the group's C entry points
+_Group = collections.namedtuple("_Group", "affine jacobian suffix")
+_GROUPS = {1: _Group(12, 18, "_g1"), 2: _Group(24, 36, "_g2")}
+
+
+def _group(group):
+    """the table row of `group`; every value other than 1 sizes as G2 (the library refuses a group it does not know)"""
+    return _GROUPS[1] if group == 1 else _GROUPS[2]
 
 
 class Context:
@@ -121,17 +132,15 @@ class Context:
 
     # ---- bases
     def upload_bases(self, bases, group=1):
-        cols = 12 if group == 1 else 24
-        bases = _u64(bases, cols)
-        fn = self.lib.vsp_bases_upload_g1 if group == 1 else self.lib.vsp_bases_upload_g2
-        h = fn(self.h, _ptr(bases), bases.shape[0])
+        gr = _group(group)
+        bases = _u64(bases, gr.affine)
+        h = getattr(self.lib, "vsp_bases_upload" + gr.suffix)(self.h, _ptr(bases), bases.shape[0])
         if not h:
             raise VspError("bases upload failed: " + self.last_error())
         return Bases(self, h, group)
 
     def bases_from_device(self, dptr, n, group=1):
-        fn = self.lib.vsp_bases_from_device_g1 if group == 1 else self.lib.vsp_bases_from_device_g2
-        h = fn(self.h, _ptr(dptr), n)
+        h = getattr(self.lib, "vsp_bases_from_device" + _group(group).suffix)(self.h, _ptr(dptr), n)
         if not h:
             raise VspError("bases_from_device failed: " + self.last_error())
         return Bases(self, h, group)
@@ -159,7 +168,7 @@ class Bases:
     def msm(self, d_scalars, n=None, first=0):
         """sum_i scalars[i] * bases[first+i]; d_scalars is a device pointer / torch tensor.  -> (affine, is_inf)."""
         n = self.n - first if n is None else n
-        out = np.zeros(12 if self.group == 1 else 24, np.uint64)
+        out = np.zeros(_group(self.group).affine, np.uint64)
         inf = C.c_int(0)
         self.ctx.check(self.ctx.lib.vsp_msm_resident(self.ctx.h, self.h, first, n, _ptr(d_scalars), _ptr(out), C.byref(inf)))
         return out, bool(inf.value)
@@ -169,7 +178,7 @@ class Bases:
         bytes.  -> (affine [batch, 12 | 24], is_inf [batch])."""
         n = self.n - first if n is None else n
         stride = n if stride is None else stride
-        out = np.zeros((batch, 12 if self.group == 1 else 24), np.uint64)
+        out = np.zeros((batch, _group(self.group).affine), np.uint64)
         inf = np.zeros(batch, np.int32)
         self.ctx.check(self.ctx.lib.vsp_msm_resident_batch(self.ctx.h, self.h, first, n, _ptr(d_scalars), batch, stride, _ptr(out), _ptr(inf)))
         return out, inf.astype(bool)
@@ -180,7 +189,7 @@ class Bases:
         self.ctx.check(self.ctx.lib.vsp_msm_launch(self.ctx.h, slot, self.h, first, n, _ptr(d_scalars)))
 
     def msm_finish_jacobian(self, slot):
-        out = np.zeros(18 if self.group == 1 else 36, np.uint64)
+        out = np.zeros(_group(self.group).jacobian, np.uint64)
         self.ctx.check(self.ctx.lib.vsp_msm_finish_jacobian(self.ctx.h, slot, _ptr(out)))
         return out
 
@@ -192,7 +201,7 @@ class Bases:
     def msm_jacobian(self, d_scalars, n=None, first=0):
         """Same, result as the Jacobian partial-sum record (18 / 36 uint64) ranks exchange."""
         n = self.n - first if n is None else n
-        out = np.zeros(18 if self.group == 1 else 36, np.uint64)
+        out = np.zeros(_group(self.group).jacobian, np.uint64)
         self.ctx.check(self.ctx.lib.vsp_msm_resident_jacobian(self.ctx.h, self.h, first, n, _ptr(d_scalars), _ptr(out)))
         return out
 
@@ -201,14 +210,13 @@ class Bases:
 def multiexp(ctx, bases, scalars, group=1):
     """algebra::multiexp<multiexp_method_BDLO12>: sum_i scalars[i] * bases[i] as an affine point
     (zero array = infinity).  bases [n,12|24], scalars [n,4], host arrays."""
-    cols = 12 if group == 1 else 24
-    bases, scalars = _u64(bases, cols), _u64(scalars, 4)
+    gr = _group(group)
+    bases, scalars = _u64(bases, gr.affine), _u64(scalars, 4)
     if bases.shape[0] != scalars.shape[0]:
         raise ValueError("multiexp: bases and scalars differ in length")   # the reference asserts equal ranges
-    out = np.zeros(cols, np.uint64)
+    out = np.zeros(gr.affine, np.uint64)
     inf = C.c_int(0)
-    fn = ctx.lib.vsp_msm_g1 if group == 1 else ctx.lib.vsp_msm_g2
-    ctx.check(fn(ctx.h, _ptr(bases), _ptr(scalars), bases.shape[0], _ptr(out), C.byref(inf)))
+    ctx.check(getattr(ctx.lib, "vsp_msm" + gr.suffix)(ctx.h, _ptr(bases), _ptr(scalars), bases.shape[0], _ptr(out), C.byref(inf)))
     return out
 
 
@@ -220,9 +228,8 @@ def multiexp_with_mixed_addition(ctx, bases, scalars, group=1):
 
 def fold_jacobian(ctx, records, group=1):
     """Fold Jacobian partial sums (the multi-GPU exchange records) into one affine point."""
-    cols = 18 if group == 1 else 36
-    records = _u64(records, cols)
-    out = np.zeros(12 if group == 1 else 24, np.uint64)
+    records = _u64(records, _group(group).jacobian)
+    out = np.zeros(_group(group).affine, np.uint64)
     inf = C.c_int(0)
     ctx.check(ctx.lib.vsp_fold_jacobian(ctx.h, group, _ptr(records), records.shape[0], _ptr(out), C.byref(inf)))
     return out
@@ -230,7 +237,7 @@ def fold_jacobian(ctx, records, group=1):
 
 def fold_jacobian_device(ctx, d_records, count, group=1, stream=None):
     """Fold `count` records that sit in device memory (the all-gather's output) behind the work already queued on `stream`."""
-    out = np.zeros(12 if group == 1 else 24, np.uint64)
+    out = np.zeros(_group(group).affine, np.uint64)
     inf = C.c_int(0)
     ctx.check(ctx.lib.vsp_fold_jacobian_device(ctx.h, group, _ptr(d_records), count, C.c_void_p(stream) if stream else None, _ptr(out), C.byref(inf)))
     return out
@@ -635,10 +642,9 @@ def saver_rerandomize(ctx, spk, delta_g2, rnd3, ct, proof_abc):
 
 def fixed_base_mul(ctx, d_scalars, n, group=1):
     """Generator-side batch_exp: device array out[i] = scalars[i] * generator (canonical affine).  Returns a device pointer."""
-    width = 96 if group == 1 else 192
-    d_out = ctx.dmalloc(max(n, 1) * width)
-    fn = ctx.lib.vsp_fixed_base_mul_g1 if group == 1 else ctx.lib.vsp_fixed_base_mul_g2
-    ctx.check(fn(ctx.h, _ptr(d_scalars), n, C.c_void_p(d_out)))
+    gr = _group(group)
+    d_out = ctx.dmalloc(max(n, 1) * 8 * gr.affine)
+    ctx.check(getattr(ctx.lib, "vsp_fixed_base_mul" + gr.suffix)(ctx.h, _ptr(d_scalars), n, C.c_void_p(d_out)))
     return d_out
 
 

@@ -1,5 +1,5 @@
 // extern "C" surface of libvsp_hip.so (declared in include/vsp.h): context, device memory, MSM / NTT /
-// witness_map entry points, Jacobian record folding and the ZCash point compression.
+// witness_map entry points and Jacobian record folding (the point compression lives with the other wire formats in wire.hip).
 #include "common.h"
 #include "fp28.h"
 #include "lane_view.h"
@@ -13,7 +13,7 @@ int set_hip_error(vsp_ctx *ctx, hipError_t e, const char *what, const char *file
     return VSP_ERR_HIP;
 }
 int set_error(vsp_ctx *ctx, int code, const char *msg) {
-    if (ctx) { ctx->err = msg; ctx->err_code = code; }
+    if (ctx) ctx->err = msg;
     return code;
 }
 int ensure(vsp_ctx *ctx, DevBuf &b, size_t bytes) {
@@ -29,28 +29,13 @@ int ensure(vsp_ctx *ctx, DevBuf &b, size_t bytes) {
 
 static void free_buf(DevBuf &b) { if (b.p) hipFree(b.p); b.p = nullptr; b.cap = 0; }
 
-static const uint64_t HALF_P[6] = {0xdcff7fffffffd555ULL, 0x0f55ffff58a9ffffULL, 0xb39869507b587b12ULL, 0xb23ba5c279c2895fULL, 0x258dd3db21a5d66bULL, 0x0d0088f51cbff34dULL};
-static bool fp_lex_larger(const uint64_t *y) {      // y > (p-1)/2
-    for (int i = 5; i >= 0; i--) { if (y[i] > HALF_P[i]) return true; if (y[i] < HALF_P[i]) return false; }
-    return false;
-}
-static bool limbs_zero(const uint64_t *a, int n) { uint64_t o = 0; for (int i = 0; i < n; i++) o |= a[i]; return o == 0; }
-static void be48(uint8_t *out, const uint64_t *l) { for (int i = 0; i < 6; i++) for (int b = 0; b < 8; b++) out[47 - (i * 8 + b)] = (uint8_t)(l[i] >> (8 * b)); }
-
-template <class F, class HF>
-static int finish_affine(const XYZZ<HF> &acc, uint64_t *out_affine, int *out_is_inf);
-template <> int finish_affine<Fp, HFp>(const XYZZ<HFp> &acc, uint64_t *out_affine, int *out_is_inf) {
-    Affine<HFp> a = xyzz_to_affine(acc);
-    if (out_affine) host_store_g1(out_affine, a);
+template <class HF> static int finish_affine(const XYZZ<HF> &acc, uint64_t *out_affine, int *out_is_inf) {
+    if (out_affine) host_store_affine(out_affine, xyzz_to_affine(acc));
     if (out_is_inf) *out_is_inf = is_inf(acc) ? 1 : 0;
     return VSP_OK;
 }
-template <> int finish_affine<Fp2, HFp2>(const XYZZ<HFp2> &acc, uint64_t *out_affine, int *out_is_inf) {
-    Affine<HFp2> a = xyzz_to_affine(acc);
-    if (out_affine) host_store_g2(out_affine, a);
-    if (out_is_inf) *out_is_inf = is_inf(acc) ? 1 : 0;
-    return VSP_OK;
-}
+// bytes of one row of a group's 28-bit-limb table
+static size_t row28_bytes(int group) { return with_group(group, [](auto g) { return sizeof(typename decltype(g)::Row28); }); }
 
 // elementwise field operations on canonical values (diagnostic entry point vsp_selftest_field)
 template <class F> __global__ __launch_bounds__(64) void k_selftest_field(int op, const F *a, const F *b, F *out, size_t n) {
@@ -148,19 +133,22 @@ int vsp_selftest_xyzz_add(vsp_ctx *ctx, int group, int form, const uint64_t *a, 
     if (!ctx) return VSP_ERR_ARG;
     if (!a || !b || !out || (group != 1 && group != 2) || (form != 0 && form != 1)) return set_error(ctx, VSP_ERR_ARG, "selftest: bad argument");
     VSP_HIP(hipSetDevice(ctx->device));
-    const size_t esz = group == 1 ? sizeof(XYZZ<Fp>) : sizeof(XYZZ<Fp2>);
-    DevBuf da, db, dc;
-    int rc = ensure(ctx, da, n * esz); if (rc == VSP_OK) rc = ensure(ctx, db, n * esz); if (rc == VSP_OK) rc = ensure(ctx, dc, n * esz);
-    if (rc == VSP_OK) {
-        hipMemcpyAsync(da.p, a, n * esz, hipMemcpyHostToDevice, ctx->stream);
-        hipMemcpyAsync(db.p, b, n * esz, hipMemcpyHostToDevice, ctx->stream);
-        if (group == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_selftest_xyzz_add<Fp, Fp28>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, form, (const XYZZ<Fp> *)da.p, (const XYZZ<Fp> *)db.p, (XYZZ<Fp> *)dc.p, n);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_selftest_xyzz_add<Fp2, Fp2x28>), dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, ctx->stream, form, (const XYZZ<Fp2> *)da.p, (const XYZZ<Fp2> *)db.p, (XYZZ<Fp2> *)dc.p, n);
-        hipMemcpyAsync(out, dc.p, n * esz, hipMemcpyDeviceToHost, ctx->stream);
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = set_error(ctx, VSP_ERR_HIP, "selftest: kernel failed");
-    }
-    free_buf(da); free_buf(db); free_buf(dc);
-    return rc;
+    return with_group(group, [&](auto g) {
+        using G = decltype(g); using P = XYZZ<typename G::F>;
+        const size_t esz = sizeof(P);
+        DevBuf da, db, dc;
+        int rc = ensure(ctx, da, n * esz); if (rc == VSP_OK) rc = ensure(ctx, db, n * esz); if (rc == VSP_OK) rc = ensure(ctx, dc, n * esz);
+        if (rc == VSP_OK) {
+            hipMemcpyAsync(da.p, a, n * esz, hipMemcpyHostToDevice, ctx->stream);
+            hipMemcpyAsync(db.p, b, n * esz, hipMemcpyHostToDevice, ctx->stream);
+            if constexpr (G::ID == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_selftest_xyzz_add<Fp, Fp28>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, form, (const P *)da.p, (const P *)db.p, (P *)dc.p, n);
+            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_selftest_xyzz_add<Fp2, Fp2x28>), dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, ctx->stream, form, (const P *)da.p, (const P *)db.p, (P *)dc.p, n);
+            hipMemcpyAsync(out, dc.p, n * esz, hipMemcpyDeviceToHost, ctx->stream);
+            if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = set_error(ctx, VSP_ERR_HIP, "selftest: kernel failed");
+        }
+        free_buf(da); free_buf(db); free_buf(dc);
+        return rc;
+    });
 }
 
 vsp_ctx *vsp_create(int device_ordinal) {
@@ -189,7 +177,7 @@ void vsp_destroy(vsp_ctx *ctx) {
     hipStreamSynchronize(ctx->stream);
     DevBuf *bufs[] = {&ctx->ntt.fwd, &ctx->ntt.inv, &ctx->ntt.pw_lo_f, &ctx->ntt.pw_hi_f, &ctx->ntt.pw_lo_i, &ctx->ntt.pw_hi_i, &ctx->ntt_scratch, &ctx->dom_scratch,
                       &ctx->ntt.fwd29, &ctx->ntt.inv29, &ctx->ntt.pw29[0], &ctx->ntt.pw29[1], &ctx->ntt.pw29[2], &ctx->ntt.pw29[3],
-                      &ctx->msm_scalars, &ctx->val_flag, &ctx->fb_g1, &ctx->fb_g2, &ctx->fb_tmp, &ctx->fb_pre,
+                      &ctx->msm_scalars, &ctx->val_flag, &ctx->fb_table[0], &ctx->fb_table[1], &ctx->fb_tmp, &ctx->fb_pre,
                       &ctx->pr_z, &ctx->pr_abc, &ctx->pr_h, &ctx->pr_pack};
     for (DevBuf *b : bufs) free_buf(*b);
     msm_free_slots(ctx);
@@ -291,13 +279,14 @@ int vsp_host_unregister(vsp_ctx *ctx, void *ptr) {
 //       over the reduction: the doubling branch of the full addition inside k_dimsum(_mixed), k_dimbits and the merges (round 4).
 // All five affine results must be identical.  On a mismatch the 28-bit kernels are switched off for this context ("msm_fp28" = 0:
 // every later multi-exponentiation takes the generic kernels).  Returns true when 28-bit tables may be used.
-static bool fp28_known_answer_check(vsp_ctx *ctx, int group) {
-    const int gi = group - 1;
+template <class G> static bool fp28_known_answer_check(vsp_ctx *ctx) {
+    using HF = typename G::HF;
+    const int gi = G::ID - 1;
     if (ctx->fp28_checked[gi] != 0) return ctx->fp28_checked[gi] > 0;
     if (ctx->msm_work[0].active) return true;                 // slot 0 busy (unusual): check at the next table instead
     const size_t n = 4096;
     std::vector<uint64_t> sc(2 * n * 4);                      // [0, n): the multiples that make the points; [n, 2n): the scalars of the check
-    uint64_t x = 0x9E3779B97F4A7C15ULL ^ (uint64_t)group;
+    uint64_t x = 0x9E3779B97F4A7C15ULL ^ (uint64_t)G::ID;
     auto next = [&]() { x += 0x9E3779B97F4A7C15ULL; uint64_t z = x; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL; z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL; return z ^ (z >> 31); };
     for (size_t i = 0; i < 2 * n; i++) {
         sc[4 * i] = next(); sc[4 * i + 1] = next(); sc[4 * i + 2] = next(); sc[4 * i + 3] = next() >> 2;     // < 2^254 < r
@@ -305,20 +294,20 @@ static bool fp28_known_answer_check(vsp_ctx *ctx, int group) {
     }
     // equal points and opposite points under equal scalars: the same bucket meets P + P (the doubling path of every addition routine, the
     // equal-x hand-back of the accumulation kernel) and P - P (the infinity paths) in all three pipelines
-    static const uint64_t R64[4] = {0xffffffff00000001ULL, 0x53bda402fffe5bfeULL, 0x3339d80809a1d805ULL, 0x73eda753299d7d48ULL};
     for (size_t i = 1; i < n; i++) {
         if (i % 16 == 5) for (int j = 0; j < 4; j++) sc[4 * i + j] = sc[4 * (i - 1) + j];                    // the same point twice
         else if (i % 16 == 9) {                                                                             // a point and its negative: r - k
             unsigned __int128 borrow = 0;
             for (int j = 0; j < 4; j++) {
-                const unsigned __int128 d = (unsigned __int128)R64[j] - sc[4 * (i - 1) + j] - borrow;
+                const unsigned __int128 d = (unsigned __int128)FrP64::MOD[j] - sc[4 * (i - 1) + j] - borrow;
                 sc[4 * i + j] = (uint64_t)d; borrow = (d >> 64) & 1;
             }
         } else continue;
         for (int j = 0; j < 4; j++) sc[4 * (n + i) + j] = sc[4 * (n + i - 1) + j];                           // ... under the same scalar
     }
     for (size_t i = n - 511; i < n; i++) for (int j = 0; j < 4; j++) sc[4 * i + j] = sc[4 * (n - 512) + j];  // one point 512 times, scalars as drawn
-    const size_t esz = group == 1 ? sizeof(G1Affine) : sizeof(G2Affine), row = group == 1 ? sizeof(Affine28) : sizeof(Affine28x2);
+    const size_t esz = sizeof(typename G::Point), row = sizeof(typename G::Row28);
+    const std::string sfx = "_g" + std::to_string(G::ID);        // of the stat names
     void *d_pts = nullptr, *t28 = nullptr;
     bool same = false, ran = false;
     OptScope saved(ctx, {"msm_split", "msm_dimbits", "msm_window_bits"});      // (the legs below set them; they come back at the return)
@@ -326,10 +315,9 @@ static bool fp28_known_answer_check(vsp_ctx *ctx, int group) {
         hipMemcpyAsync(ctx->msm_scalars.p, sc.data(), 2 * n * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
         hipStreamSynchronize(ctx->stream) == hipSuccess && hipMalloc(&d_pts, n * esz) == hipSuccess && hipMalloc(&t28, 2 * n * row) == hipSuccess) {
         const Fr *dk = (const Fr *)ctx->msm_scalars.p, *ds = dk + n;
-        int rc = group == 1 ? fixed_base_mul_g1(ctx, dk, n, d_pts) : fixed_base_mul_g2(ctx, dk, n, d_pts);
-        if (rc == VSP_OK) rc = group == 1 ? bases_to_mont_g1(ctx, d_pts, (G1Affine *)d_pts, n, 0, (uint32_t *)ctx->val_flag.p)
-                                          : bases_to_mont_g2(ctx, d_pts, (G2Affine *)d_pts, n, 0, (uint32_t *)ctx->val_flag.p);
-        if (rc == VSP_OK) rc = group == 1 ? msm_g1_table28(ctx, (const G1Affine *)d_pts, n, t28, true) : msm_g2_table28(ctx, (const G2Affine *)d_pts, n, t28, true);
+        int rc = fixed_base_mul<G>(ctx, dk, n, d_pts);
+        if (rc == VSP_OK) rc = bases_to_mont<G>(ctx, d_pts, (typename G::Point *)d_pts, n, 0, (uint32_t *)ctx->val_flag.p);
+        if (rc == VSP_OK) rc = msm_table28<G>(ctx, (const typename G::Point *)d_pts, n, t28, true);
         if (rc == VSP_OK && hipStreamSynchronize(ctx->stream) == hipSuccess) {
             ran = true;
             auto run = [&](const void *table, bool glv, long split, long dimbits, uint64_t *aff, int *inf, long wbits = 0) -> bool {
@@ -337,26 +325,20 @@ static bool fp28_known_answer_check(vsp_ctx *ctx, int group) {
                 if (split) ctx->opts["msm_split"] = split; else ctx->opts.erase("msm_split");
                 if (dimbits >= 0) ctx->opts["msm_dimbits"] = dimbits; else ctx->opts.erase("msm_dimbits");
                 MsmRequest rq(ds, n); rq.bases = d_pts; rq.dense = true; rq.table28 = table; rq.glv = glv;
-                if (group == 1) {
-                    XYZZ<HFp> r;
-                    if (msm_g1_launch(ctx, 0, rq) != VSP_OK || msm_g1_finish(ctx, 0, &r) != VSP_OK) return false;
-                    Affine<HFp> a = xyzz_to_affine(r); host_store_g1(aff, a); *inf = is_inf(r);
-                } else {
-                    XYZZ<HFp2> r;
-                    if (msm_g2_launch(ctx, 0, rq) != VSP_OK || msm_g2_finish(ctx, 0, &r) != VSP_OK) return false;
-                    Affine<HFp2> a = xyzz_to_affine(r); host_store_g2(aff, a); *inf = is_inf(r);
-                }
+                XYZZ<HF> r;
+                if (msm_slot_launch<G>(ctx, 0, rq) != VSP_OK || msm_slot_finish<G>(ctx, 0, &r) != VSP_OK) return false;
+                host_store_affine(aff, xyzz_to_affine(r)); *inf = is_inf(r);
                 return true;
             };
             uint64_t ra[24], rb[24], rc3[24], rd[24], re[24]; int ia = 0, ib = 0, ic = 0, id = 0, ie = 0;
             memset(ra, 0, sizeof ra); memset(rb, 0, sizeof rb); memset(rc3, 0, sizeof rc3); memset(rd, 0, sizeof rd); memset(re, 0, sizeof re);
-            const bool okr = run(t28, true, 0, -1, ra, &ia) && run(t28, true, 6, group == 1 ? 0 : 1, rb, &ib) && run(nullptr, false, 0, -1, rc3, &ic) &&
+            const bool okr = run(t28, true, 0, -1, ra, &ia) && run(t28, true, 6, G::ID == 1 ? 0 : 1, rb, &ib) && run(nullptr, false, 0, -1, rc3, &ic) &&
                              run(t28, true, 0, -1, rd, &id, 6) && run(t28, true, 0, -1, re, &ie, 12);
             same = okr && ia == ic && ib == ic && id == ic && ie == ic && !ic && memcmp(ra, rc3, sizeof ra) == 0 && memcmp(rb, rc3, sizeof rb) == 0 &&
                    memcmp(rd, rc3, sizeof rd) == 0 && memcmp(re, rc3, sizeof re) == 0;
             // which leg differed (stat "msm_fp28_selfcheck_detail_g1/2"): 1 = the default 28-bit pipeline, 2 = the split-bucket / other reduction
             // pipeline, 4 = a point at infinity where there should be none, 8 = a launch failed, 16 / 32 = the 6-bit / 12-bit window legs
-            ctx->stats[group == 1 ? "msm_fp28_selfcheck_detail_g1" : "msm_fp28_selfcheck_detail_g2"] =
+            ctx->stats["msm_fp28_selfcheck_detail" + sfx] =
                 (double)((okr ? 0 : 8) | ((ia != ic || memcmp(ra, rc3, sizeof ra)) ? 1 : 0) | ((ib != ic || memcmp(rb, rc3, sizeof rb)) ? 2 : 0) | (ic ? 4 : 0) |
                          ((id != ic || memcmp(rd, rc3, sizeof rd)) ? 16 : 0) | ((ie != ic || memcmp(re, rc3, sizeof re)) ? 32 : 0));
         }
@@ -364,10 +346,10 @@ static bool fp28_known_answer_check(vsp_ctx *ctx, int group) {
     if (d_pts) hipFree(d_pts);
     if (t28) hipFree(t28);
     hipGetLastError();
-    if (!ran) { ctx->stats[group == 1 ? "msm_fp28_selfcheck_g1" : "msm_fp28_selfcheck_g2"] = 0.0; return false; }      // could not run (out of memory): no verdict, no 28-bit table this time
+    if (!ran) { ctx->stats["msm_fp28_selfcheck" + sfx] = 0.0; return false; }      // could not run (out of memory): no verdict, no 28-bit table this time
     if (opt(ctx, "msm_fp28_selfcheck_fault", 0)) same = false;   // test hook: exercise the fallback
     ctx->fp28_checked[gi] = same ? 1 : -1;
-    ctx->stats[group == 1 ? "msm_fp28_selfcheck_g1" : "msm_fp28_selfcheck_g2"] = same ? 1.0 : -1.0;
+    ctx->stats["msm_fp28_selfcheck" + sfx] = same ? 1.0 : -1.0;
     if (!same) { ctx->opts["msm_fp28"] = 0; ctx->err = "msm: the 28-bit-limb kernels failed their known-answer check; generic kernels in use"; }
     return same;
 }
@@ -376,14 +358,14 @@ static bool fp28_known_answer_check(vsp_ctx *ctx, int group) {
 // layout: 2 count rows, (P_i, phi(P_i)) interleaved (option "msm_glv" = 0: off; 2: on for any size and WITHOUT the check -- the caller vouches)
 static bool glv_wanted(vsp_ctx *ctx, int group, size_t count, unsigned pre_c) {
     const long want = opt(ctx, "msm_fp28", 1), want_glv = opt(ctx, "msm_glv", 1);
-    const size_t row = group == 1 ? sizeof(Affine28) : sizeof(Affine28x2);
+    const size_t row = row28_bytes(group);
     // The split halves the bucket sets (and the host Horner chain) but doubles the table and the sort's input.  Measured
     // (tools/msm_sizes.py, bench.py; one in flight / three in flight, ms): G1 2^16 1.49 / 1.42 -> 1.35 / 0.80, G1 2^18 2.31 / 1.29 ->
     // 2.04 / 1.27, G1 2^20 4.24 / 3.35 -> 3.98 / 3.34, a 2^20-constraint proof 8.71 -> 8.45 ms (plain key: 9.98 -> 8.95);
     // G2 2^16 3.01 / 1.58 -> 2.67 / 1.40, G2 2^18 5.21 / 3.21 -> 5.56 / 2.90, G2 2^19 7.23 / 4.82 -> 8.28 / 5.58 (dense scalars:
     // the lane-pair merges of the split buckets cost more than the windows saved).  So: on while the doubled table is at most
     // 256 MB for G1 (2^20 points) and 128 MB for G2 (2^18 points); "msm_glv" = 2 forces it on, 0 switches it off.
-    const size_t glv_limit = group == 1 ? ((size_t)256 << 20) : ((size_t)128 << 20);
+    const size_t glv_limit = ((size_t)256 << 20) / group;      // 256 MB (G1), 128 MB (G2)
     return want && want_glv && pre_c == 0 && count >= 1024 && count < ((size_t)1 << 30) && (want_glv >= 2 || 2 * count * row <= glv_limit);
 }
 static void build_table28(vsp_ctx *ctx, vsp_bases *b, size_t count) {
@@ -391,8 +373,8 @@ static void build_table28(vsp_ctx *ctx, vsp_bases *b, size_t count) {
     b->glv = false;
     const long want = opt(ctx, "msm_fp28", 1), want_glv = opt(ctx, "msm_glv", 1);
     // "msm_fp28" = 2 (diagnostics: bisecting a failed check with tools/fuzz_msm.py): the 28-bit kernels WITHOUT the context-time check
-    if (!want || (want < 2 && !fp28_known_answer_check(ctx, b->group))) return;   // the check may have just switched "msm_fp28" off
-    const size_t row = b->group == 1 ? sizeof(Affine28) : sizeof(Affine28x2);
+    if (!want || (want < 2 && !with_group(b->group, [&](auto g) { return fp28_known_answer_check<decltype(g)>(ctx); }))) return;   // the check may have just switched "msm_fp28" off
+    const size_t row = row28_bytes(b->group);
     bool glv = glv_wanted(ctx, b->group, count, b->pre_c) && (b->in_subgroup > 0 || want_glv >= 2);
     if (b->pre_c && b->pre_split && want_glv && (b->in_subgroup > 0 || want_glv >= 2)) {
         // window multiples for dense scalars: the 128 / c windows of a split scalar, every row with its endomorphism image beside it
@@ -401,23 +383,28 @@ static void build_table28(vsp_ctx *ctx, vsp_bases *b, size_t count) {
     }
     void *t28 = nullptr;
     if (hipMalloc(&t28, count * row * (glv ? 2 : 1)) != hipSuccess) { hipGetLastError(); return; }
-    int rc = b->group == 1 ? msm_g1_table28(ctx, (const G1Affine *)b->d, count, t28, glv) : msm_g2_table28(ctx, (const G2Affine *)b->d, count, t28, glv);
+    int rc = with_group(b->group, [&](auto g) { using G = decltype(g); return msm_table28<G>(ctx, (const typename G::Point *)b->d, count, t28, glv); });
     if (rc == VSP_OK && hipStreamSynchronize(ctx->stream) == hipSuccess) { b->d28 = t28; b->glv = glv; }
     else { hipFree(t28); hipGetLastError(); }
 }
+// queue the subgroup check of plain resident bases: bit 2 of the context's validation word
+static int bases_subgroup_check(vsp_ctx *ctx, const vsp_bases *b) {
+    return with_group(b->group, [&](auto g) { using G = decltype(g); return subgroup_check<G>(ctx, (const typename G::Point *)b->d, b->n, (uint32_t *)ctx->val_flag.p); });
+}
 namespace vsp {
-vsp_bases *bases_create(vsp_ctx *ctx, int group, const void *src, bool src_on_device, size_t n, int trust) {
-    if (!ctx) return nullptr;
-    if (!src && n) { set_error(ctx, VSP_ERR_ARG, "bases: null pointer"); return nullptr; }
+int bases_create(vsp_ctx *ctx, int group, const void *src, bool src_on_device, size_t n, int trust, vsp_bases **out) {
+    *out = nullptr;
+    if (!ctx) return VSP_ERR_ARG;
+    if (!src && n) return set_error(ctx, VSP_ERR_ARG, "bases: null pointer");
     hipSetDevice(ctx->device);
-    size_t esz = group == 1 ? sizeof(G1Affine) : sizeof(G2Affine);
+    const size_t esz = point_bytes(group);
     vsp_bases *b = new vsp_bases();
     b->group = group; b->n = n;
-    if (hipMalloc(&b->d, n ? n * esz : 16) != hipSuccess) { set_error(ctx, VSP_ERR_NOMEM, "bases: hipMalloc failed"); delete b; return nullptr; }
+    if (hipMalloc(&b->d, n ? n * esz : 16) != hipSuccess) { delete b; return set_error(ctx, VSP_ERR_NOMEM, "bases: hipMalloc failed"); }
     if (n) {
         int rc;
         if (!src_on_device) {
-            if (hipMemcpyAsync(b->d, src, n * esz, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { set_error(ctx, VSP_ERR_HIP, "bases: H2D failed"); hipFree(b->d); delete b; return nullptr; }
+            if (hipMemcpyAsync(b->d, src, n * esz, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { hipFree(b->d); delete b; return set_error(ctx, VSP_ERR_HIP, "bases: H2D failed"); }
             src = b->d;                      // convert in place
         }
         // boundary validation (include/vsp.h): coordinates below p always; the curve equation unless option "bases_check_curve" = 0
@@ -430,15 +417,16 @@ vsp_bases *bases_create(vsp_ctx *ctx, int group, const void *src, bool src_on_de
         rc = ensure(ctx, ctx->val_flag, 16);
         if (rc == VSP_OK && hipMemsetAsync(ctx->val_flag.p, 0, 16, ctx->stream) != hipSuccess) rc = set_error(ctx, VSP_ERR_HIP, "bases: memset failed");
         if (rc == VSP_OK)
-            rc = group == 1 ? bases_to_mont_g1(ctx, src, (G1Affine *)b->d, n, (int)check_curve, (uint32_t *)ctx->val_flag.p)
-                            : bases_to_mont_g2(ctx, src, (G2Affine *)b->d, n, (int)check_curve, (uint32_t *)ctx->val_flag.p);
+            rc = with_group(group, [&](auto g) {
+                using G = decltype(g);
+                return bases_to_mont<G>(ctx, src, (typename G::Point *)b->d, n, (int)check_curve, (uint32_t *)ctx->val_flag.p);
+            });
         bool sub_checked = false;
         if (trust == BASES_OWN) b->in_subgroup = 1;
         // policy 2 covers every upload whose points the library did not make itself (caller's handles, one call's host buffers, key blobs),
         // with or without the curve check; policy 1 only the uploads that would get the endomorphism layout
         else if (rc == VSP_OK && (check_sub >= 2 || (trust == BASES_CALLER && check_curve && check_sub == 1 && glv_wanted(ctx, group, n, 0)))) {
-            rc = group == 1 ? subgroup_check_g1(ctx, (const G1Affine *)b->d, n, (uint32_t *)ctx->val_flag.p)
-                            : subgroup_check_g2(ctx, (const G2Affine *)b->d, n, (uint32_t *)ctx->val_flag.p);
+            rc = bases_subgroup_check(ctx, b);
             sub_checked = true;
         }
         if (rc == VSP_OK && (hipMemcpyAsync(&h_flag, ctx->val_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
@@ -453,22 +441,29 @@ vsp_bases *bases_create(vsp_ctx *ctx, int group, const void *src, bool src_on_de
                 if (check_sub >= 2) rc = set_error(ctx, VSP_ERR_ARG, "bases: a point is not in the order-r subgroup");
             }
         }
-        if (rc != VSP_OK) { hipFree(b->d); delete b; return nullptr; }
+        if (rc != VSP_OK) { hipFree(b->d); delete b; return rc; }
         if (n >= 1024) build_table28(ctx, b, n);       // best effort: without it the 12 x 32-bit kernel runs
     }
-    return b;
+    *out = b;
+    return VSP_OK;
 }
 }  // namespace vsp
+// caller's bases as a handle, or null with the reason in the context's error text
+static vsp_bases *bases_upload(vsp_ctx *ctx, int group, const void *src, bool src_on_device, size_t n) {
+    vsp_bases *b;
+    bases_create(ctx, group, src, src_on_device, n, BASES_CALLER, &b);
+    return b;
+}
 extern "C" {
-vsp_bases *vsp_bases_upload_g1(vsp_ctx *ctx, const uint64_t *bases, size_t n) { return bases_create(ctx, 1, bases, false, n, BASES_CALLER); }
-vsp_bases *vsp_bases_upload_g2(vsp_ctx *ctx, const uint64_t *bases, size_t n) { return bases_create(ctx, 2, bases, false, n, BASES_CALLER); }
-vsp_bases *vsp_bases_from_device_g1(vsp_ctx *ctx, const void *d_bases, size_t n) { return bases_create(ctx, 1, d_bases, true, n, BASES_CALLER); }
-vsp_bases *vsp_bases_from_device_g2(vsp_ctx *ctx, const void *d_bases, size_t n) { return bases_create(ctx, 2, d_bases, true, n, BASES_CALLER); }
+vsp_bases *vsp_bases_upload_g1(vsp_ctx *ctx, const uint64_t *bases, size_t n) { return bases_upload(ctx, 1, bases, false, n); }
+vsp_bases *vsp_bases_upload_g2(vsp_ctx *ctx, const uint64_t *bases, size_t n) { return bases_upload(ctx, 2, bases, false, n); }
+vsp_bases *vsp_bases_from_device_g1(vsp_ctx *ctx, const void *d_bases, size_t n) { return bases_upload(ctx, 1, d_bases, true, n); }
+vsp_bases *vsp_bases_from_device_g2(vsp_ctx *ctx, const void *d_bases, size_t n) { return bases_upload(ctx, 2, d_bases, true, n); }
 size_t vsp_bases_count(const vsp_bases *b) { return b ? b->n : 0; }
 size_t vsp_bases_device_bytes(const vsp_bases *b) {
     if (!b) return 0;
     const size_t slices = b->pre_c ? 255 / b->pre_c + 1 : 1, count = b->n * slices;
-    const size_t esz = b->group == 1 ? sizeof(G1Affine) : sizeof(G2Affine), row = b->group == 1 ? sizeof(Affine28) : sizeof(Affine28x2);
+    const size_t esz = point_bytes(b->group), row = row28_bytes(b->group);
     const size_t rows28 = (b->pre_c && b->glv) ? b->n * ((128 + b->pre_c - 1) / b->pre_c) * 2 : count * (b->glv ? 2 : 1);
     return (count ? count * esz : 16) + (b->d28 ? rows28 * row : 0);
 }
@@ -489,14 +484,24 @@ int launch_on_bases(vsp_ctx *ctx, unsigned slot, const vsp_bases *bases, size_t 
     if (slot < VSP_MSM_SLOTS) ctx->slot_group[slot] = bases->group;
     if (bases->pre_c && rq.batch && (!opt(ctx, "msm_batch_tables", 1) || bases->pre_c > 16))      // (a batch over the table: ONE bucket set per vector)
         return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: a batch over this table of window multiples is not supported (plain bases, or windows of at most 16 bits)");
-    const size_t row = bases->group == 1 ? sizeof(Affine28) : sizeof(Affine28x2), esz = bases->group == 1 ? sizeof(G1Affine) : sizeof(G2Affine);
+    const size_t row = row28_bytes(bases->group), esz = point_bytes(bases->group);
     MsmPre pre{bases->n, first, bases->pre_c, bases->d28, bases->glv};
     rq.glv = bases->glv;
     if (bases->pre_c) { rq.bases = bases->d; rq.pre = &pre; }
     else { rq.bases = (const char *)bases->d + first * esz; rq.table28 = bases->d28 ? (const char *)bases->d28 + first * row * (bases->glv ? 2 : 1) : nullptr; }
-    return bases->group == 1 ? msm_g1_launch(ctx, slot, rq) : msm_g2_launch(ctx, slot, rq);
+    return with_group(bases->group, [&](auto g) { return msm_slot_launch<decltype(g)>(ctx, slot, rq); });
 }
 }  // namespace vsp
+// vsp_msm_launch on slot 0 (its argument checks), its finish, then done(result) with the result in the group's host form
+template <class Fn> static int msm_resident_then(vsp_ctx *ctx, const vsp_bases *bases, size_t first, size_t n, const void *d_scalars, Fn &&done) {
+    VSP_TRY(vsp_msm_launch(ctx, 0, bases, first, n, d_scalars));
+    return with_group(bases->group, [&](auto g) {
+        XYZZ<typename decltype(g)::HF> a;
+        VSP_TRY(msm_slot_finish<decltype(g)>(ctx, 0, &a));
+        return done(a);
+    });
+}
+
 extern "C" {
 
 static int bases_precompute(vsp_ctx *ctx, vsp_bases *b, unsigned window_bits, bool split);
@@ -512,8 +517,7 @@ static int bases_precompute(vsp_ctx *ctx, vsp_bases *b, unsigned window_bits, bo
             VSP_HIP(hipSetDevice(ctx->device));
             VSP_TRY(ensure(ctx, ctx->val_flag, 16));
             VSP_HIP(hipMemsetAsync(ctx->val_flag.p, 0, 4, ctx->stream));
-            VSP_TRY(b->group == 1 ? subgroup_check_g1(ctx, (const G1Affine *)b->d, b->n, (uint32_t *)ctx->val_flag.p)
-                                  : subgroup_check_g2(ctx, (const G2Affine *)b->d, b->n, (uint32_t *)ctx->val_flag.p));
+            VSP_TRY(bases_subgroup_check(ctx, b));
             uint32_t h_flag = 0;
             VSP_HIP(hipMemcpyAsync(&h_flag, ctx->val_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
             VSP_HIP(hipStreamSynchronize(ctx->stream));
@@ -532,12 +536,12 @@ static int bases_precompute(vsp_ctx *ctx, vsp_bases *b, unsigned window_bits, bo
     if (b->n == 0) { b->pre_c = window_bits; b->pre_split = split; return VSP_OK; }
     VSP_HIP(hipSetDevice(ctx->device));
     const unsigned W = 255 / window_bits + 1;
-    const size_t esz = b->group == 1 ? sizeof(G1Affine) : sizeof(G2Affine);
+    const size_t esz = point_bytes(b->group);
     if ((size_t)W * b->n >= ((size_t)1 << 31)) return set_error(ctx, VSP_ERR_UNSUPPORTED, "precompute: table too large to index");
     void *table = nullptr;
     if (hipMalloc(&table, (size_t)W * b->n * esz) != hipSuccess) return set_error(ctx, VSP_ERR_NOMEM, "precompute: hipMalloc failed");
     VSP_HIP(hipMemcpyAsync(table, b->d, b->n * esz, hipMemcpyDeviceToDevice, ctx->stream));
-    int rc = b->group == 1 ? msm_g1_precompute(ctx, (G1Affine *)table, b->n, window_bits) : msm_g2_precompute(ctx, (G2Affine *)table, b->n, window_bits);
+    int rc = with_group(b->group, [&](auto g) { using G = decltype(g); return msm_precompute<G>(ctx, (typename G::Point *)table, b->n, window_bits); });
     if (rc != VSP_OK) { hipFree(table); return rc; }
     VSP_HIP(hipStreamSynchronize(ctx->stream));
     hipFree(b->d);
@@ -547,17 +551,8 @@ static int bases_precompute(vsp_ctx *ctx, vsp_bases *b, unsigned window_bits, bo
     return VSP_OK;
 }
 
-static int msm_resident_xyzz(vsp_ctx *ctx, const vsp_bases *bases, size_t first, size_t n, const void *d_scalars,
-                             XYZZ<HFp> *o1, XYZZ<HFp2> *o2) {
-    VSP_TRY(vsp_msm_launch(ctx, 0, bases, first, n, d_scalars));      // (its argument checks, on slot 0)
-    if (bases->group == 1) return msm_g1_finish(ctx, 0, o1);
-    return msm_g2_finish(ctx, 0, o2);
-}
-
 int vsp_msm_resident(vsp_ctx *ctx, const vsp_bases *bases, size_t first, size_t n, const void *d_scalars, uint64_t *out_affine, int *out_is_inf) {
-    XYZZ<HFp> a1; XYZZ<HFp2> a2;
-    VSP_TRY(msm_resident_xyzz(ctx, bases, first, n, d_scalars, &a1, &a2));
-    return bases->group == 1 ? finish_affine<Fp, HFp>(a1, out_affine, out_is_inf) : finish_affine<Fp2, HFp2>(a2, out_affine, out_is_inf);
+    return msm_resident_then(ctx, bases, first, n, d_scalars, [&](const auto &a) { return finish_affine(a, out_affine, out_is_inf); });
 }
 
 int vsp_msm_resident_batch(vsp_ctx *ctx, const vsp_bases *bases, size_t first, size_t n, const void *d_scalars, size_t batch, size_t stride,
@@ -566,35 +561,20 @@ int vsp_msm_resident_batch(vsp_ctx *ctx, const vsp_bases *bases, size_t first, s
     if (!bases || (!d_scalars && n) || !out_affine || batch < 1 || batch > 64 || (batch > 1 && stride < n)) return set_error(ctx, VSP_ERR_ARG, "msm: bad batch argument");
     if (first > bases->n || n > bases->n - first) return set_error(ctx, VSP_ERR_ARG, "msm: range outside the resident bases");
     VSP_HIP(hipSetDevice(ctx->device));
-    const size_t words = bases->group == 1 ? 12 : 24;
     MsmRequest rq((const Fr *)d_scalars, n); rq.batch = (unsigned)batch; rq.stride = stride;
     VSP_TRY(launch_on_bases(ctx, 0, bases, first, rq));
-    if (bases->group == 1) {
-        std::vector<XYZZ<HFp>> r(batch);
-        VSP_TRY(msm_g1_finish(ctx, 0, r.data(), (unsigned)batch));
-        for (size_t k = 0; k < batch; k++) VSP_TRY((finish_affine<Fp, HFp>(r[k], out_affine + k * words, out_is_inf ? out_is_inf + k : nullptr)));
-    } else {
-        std::vector<XYZZ<HFp2>> r(batch);
-        VSP_TRY(msm_g2_finish(ctx, 0, r.data(), (unsigned)batch));
-        for (size_t k = 0; k < batch; k++) VSP_TRY((finish_affine<Fp2, HFp2>(r[k], out_affine + k * words, out_is_inf ? out_is_inf + k : nullptr)));
-    }
-    return VSP_OK;
+    return with_group(bases->group, [&](auto g) -> int {
+        using G = decltype(g);
+        std::vector<XYZZ<typename G::HF>> r(batch);
+        VSP_TRY(msm_slot_finish<G>(ctx, 0, r.data(), (unsigned)batch));
+        for (size_t k = 0; k < batch; k++) VSP_TRY(finish_affine(r[k], out_affine + k * G::AFFINE_WORDS, out_is_inf ? out_is_inf + k : nullptr));
+        return VSP_OK;
+    });
 }
 
 int vsp_msm_resident_jacobian(vsp_ctx *ctx, const vsp_bases *bases, size_t first, size_t n, const void *d_scalars, uint64_t *out_jacobian) {
-    XYZZ<HFp> a1; XYZZ<HFp2> a2;
     if (!out_jacobian) return set_error(ctx, VSP_ERR_ARG, "msm: null output");
-    VSP_TRY(msm_resident_xyzz(ctx, bases, first, n, d_scalars, &a1, &a2));
-    if (bases->group == 1) {
-        Jacobian<HFp> j = xyzz_to_jacobian(a1);
-        host_store_canon(out_jacobian, j.X); host_store_canon(out_jacobian + 6, j.Y); host_store_canon(out_jacobian + 12, j.Z);
-    } else {
-        Jacobian<HFp2> j = xyzz_to_jacobian(a2);
-        host_store_canon(out_jacobian, j.X.c0); host_store_canon(out_jacobian + 6, j.X.c1);
-        host_store_canon(out_jacobian + 12, j.Y.c0); host_store_canon(out_jacobian + 18, j.Y.c1);
-        host_store_canon(out_jacobian + 24, j.Z.c0); host_store_canon(out_jacobian + 30, j.Z.c1);
-    }
-    return VSP_OK;
+    return msm_resident_then(ctx, bases, first, n, d_scalars, [&](const auto &a) -> int { host_store_jacobian(out_jacobian, xyzz_to_jacobian(a)); return VSP_OK; });
 }
 
 // ---- pipelined form: up to VSP_MSM_SLOTS multi-exponentiations in flight, each on its own stream ----
@@ -607,20 +587,13 @@ int vsp_msm_launch(vsp_ctx *ctx, unsigned slot, const vsp_bases *bases, size_t f
 }
 // the Jacobian record of a finished slot (18 / 36 canonical words); returns the words written
 static int finish_record(vsp_ctx *ctx, unsigned slot, uint64_t *out_jacobian, size_t *words) {
-    if (ctx->slot_group[slot] == 1) {
-        XYZZ<HFp> a; VSP_TRY(msm_g1_finish(ctx, slot, &a));
-        Jacobian<HFp> j = xyzz_to_jacobian(a);
-        host_store_canon(out_jacobian, j.X); host_store_canon(out_jacobian + 6, j.Y); host_store_canon(out_jacobian + 12, j.Z);
-        *words = 18;
-    } else {
-        XYZZ<HFp2> a; VSP_TRY(msm_g2_finish(ctx, slot, &a));
-        Jacobian<HFp2> j = xyzz_to_jacobian(a);
-        host_store_canon(out_jacobian, j.X.c0); host_store_canon(out_jacobian + 6, j.X.c1);
-        host_store_canon(out_jacobian + 12, j.Y.c0); host_store_canon(out_jacobian + 18, j.Y.c1);
-        host_store_canon(out_jacobian + 24, j.Z.c0); host_store_canon(out_jacobian + 30, j.Z.c1);
-        *words = 36;
-    }
-    return VSP_OK;
+    return with_group(ctx->slot_group[slot], [&](auto g) -> int {
+        using G = decltype(g);
+        XYZZ<typename G::HF> a; VSP_TRY(msm_slot_finish<G>(ctx, slot, &a));
+        host_store_jacobian(out_jacobian, xyzz_to_jacobian(a));
+        *words = G::JACOBIAN_WORDS;
+        return VSP_OK;
+    });
 }
 int vsp_msm_finish_jacobian(vsp_ctx *ctx, unsigned slot, uint64_t *out_jacobian) {
     if (!ctx) return VSP_ERR_ARG;
@@ -652,27 +625,13 @@ int vsp_msm_finish_jacobian_device(vsp_ctx *ctx, unsigned slot, void *d_out_jaco
 
 int vsp_fold_jacobian(vsp_ctx *ctx, int group, const uint64_t *records, size_t count, uint64_t *out_affine, int *out_is_inf) {
     if (!records && count) return set_error(ctx, VSP_ERR_ARG, "fold: null records");
-    if (group == 1) {
-        XYZZ<HFp> acc = XYZZ<HFp>::inf();
-        for (size_t i = 0; i < count; i++) {
-            const uint64_t *p = records + 18 * i;
-            Jacobian<HFp> j; j.X = host_load_canon<HFp>(p); j.Y = host_load_canon<HFp>(p + 6); j.Z = host_load_canon<HFp>(p + 12);
-            xyzz_add(acc, jacobian_to_xyzz(j));
-        }
-        return finish_affine<Fp, HFp>(acc, out_affine, out_is_inf);
-    } else if (group == 2) {
-        XYZZ<HFp2> acc = XYZZ<HFp2>::inf();
-        for (size_t i = 0; i < count; i++) {
-            const uint64_t *p = records + 36 * i;
-            Jacobian<HFp2> j;
-            j.X.c0 = host_load_canon<HFp>(p); j.X.c1 = host_load_canon<HFp>(p + 6);
-            j.Y.c0 = host_load_canon<HFp>(p + 12); j.Y.c1 = host_load_canon<HFp>(p + 18);
-            j.Z.c0 = host_load_canon<HFp>(p + 24); j.Z.c1 = host_load_canon<HFp>(p + 30);
-            xyzz_add(acc, jacobian_to_xyzz(j));
-        }
-        return finish_affine<Fp2, HFp2>(acc, out_affine, out_is_inf);
-    }
-    return set_error(ctx, VSP_ERR_ARG, "fold: group must be 1 or 2");
+    if (group != 1 && group != 2) return set_error(ctx, VSP_ERR_ARG, "fold: group must be 1 or 2");
+    return with_group(group, [&](auto g) {
+        using G = decltype(g); using HF = typename G::HF;
+        XYZZ<HF> acc = XYZZ<HF>::inf();
+        for (size_t i = 0; i < count; i++) xyzz_add(acc, jacobian_to_xyzz(host_load_jacobian<HF>(records + G::JACOBIAN_WORDS * i)));
+        return finish_affine(acc, out_affine, out_is_inf);
+    });
 }
 
 // Fold records that sit in DEVICE memory (the output of the all-gather): one asynchronous copy of count * 144 / 288 bytes into a pinned
@@ -684,7 +643,7 @@ int vsp_fold_jacobian_device(vsp_ctx *ctx, int group, const void *d_records, siz
     if (!d_records && count) return set_error(ctx, VSP_ERR_ARG, "fold: null records");
     if (count > 4096) return set_error(ctx, VSP_ERR_ARG, "fold: more than 4096 records");
     VSP_HIP(hipSetDevice(ctx->device));
-    const size_t bytes = count * (size_t)(group == 1 ? 144 : 288);
+    const size_t bytes = count * 8 * with_group(group, [](auto g) { return decltype(g)::JACOBIAN_WORDS; });
     if (bytes > ctx->h_fold_cap) {
         if (ctx->h_fold) { hipHostFree(ctx->h_fold); ctx->h_fold = nullptr; ctx->h_fold_cap = 0; }
         const size_t want = bytes < 8192 ? 8192 : bytes;
@@ -703,8 +662,8 @@ static int msm_host(vsp_ctx *ctx, int group, const uint64_t *bases, const uint64
     if (!ctx) return VSP_ERR_ARG;
     if ((!bases || !scalars) && n) return set_error(ctx, VSP_ERR_ARG, "msm: null argument");
     VSP_HIP(hipSetDevice(ctx->device));
-    vsp_bases *b = bases_create(ctx, group, bases, false, n, BASES_TRANSIENT);      // one call's bases: no endomorphism split, hence no subgroup check
-    if (!b) return ctx->err_code ? ctx->err_code : VSP_ERR_ARG;      // bases_create has said why (set_error)
+    vsp_bases *b = nullptr;
+    VSP_TRY(bases_create(ctx, group, bases, false, n, BASES_TRANSIENT, &b));      // one call's bases: no endomorphism split, hence no subgroup check
     int rc = ensure(ctx, ctx->msm_scalars, n * 32);
     if (rc == VSP_OK && n) {
         if (hipMemcpyAsync(ctx->msm_scalars.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = set_error(ctx, VSP_ERR_HIP, "msm: H2D of scalars failed");
@@ -861,132 +820,17 @@ size_t vsp_r1cs_domain_size(const vsp_r1cs *cs) { return cs ? cs->dom.m : 0; }
 int vsp_r1cs_domain_kind(const vsp_r1cs *cs) { return cs ? cs->dom.step : -1; }
 
 // ---- generator-side batch exponentiation ---------------------------------------------------------
-int vsp_fixed_base_mul_g1(vsp_ctx *ctx, const void *d_scalars, size_t n, void *d_out) {
+}  // extern "C"
+template <class G> static int fixed_base_mul_sync(vsp_ctx *ctx, const void *d_scalars, size_t n, void *d_out) {
     if (!ctx) return VSP_ERR_ARG;
     if ((!d_scalars || !d_out) && n) return set_error(ctx, VSP_ERR_ARG, "fixed_base_mul: null pointer");
     VSP_HIP(hipSetDevice(ctx->device));
-    VSP_TRY(fixed_base_mul_g1(ctx, (const Fr *)d_scalars, n, d_out));
+    VSP_TRY(fixed_base_mul<G>(ctx, (const Fr *)d_scalars, n, d_out));
     VSP_HIP(hipStreamSynchronize(ctx->stream));
     return VSP_OK;
 }
-int vsp_fixed_base_mul_g2(vsp_ctx *ctx, const void *d_scalars, size_t n, void *d_out) {
-    if (!ctx) return VSP_ERR_ARG;
-    if ((!d_scalars || !d_out) && n) return set_error(ctx, VSP_ERR_ARG, "fixed_base_mul: null pointer");
-    VSP_HIP(hipSetDevice(ctx->device));
-    VSP_TRY(fixed_base_mul_g2(ctx, (const Fr *)d_scalars, n, d_out));
-    VSP_HIP(hipStreamSynchronize(ctx->stream));
-    return VSP_OK;
-}
-
-// ---- ZCash compressed encoding (the wire format of reference bin/cli/src/data.bin[0:192]) ----------
-static bool canon_lt_p(const uint64_t *l) {
-    for (int i = 5; i >= 0; i--) { if (l[i] < FpP64::MOD[i]) return true; if (l[i] > FpP64::MOD[i]) return false; }
-    return false;
-}
-// VSP_ERR_ARG for a null pointer or a coordinate that is not canonical (>= p: its top bits would collide with the flag bits)
-int vsp_g1_compress(const uint64_t affine[12], uint8_t out[48]) {
-    if (!affine || !out) return VSP_ERR_ARG;
-    if (limbs_zero(affine, 12)) { memset(out, 0, 48); out[0] = 0xC0; return VSP_OK; }
-    if (!canon_lt_p(affine) || !canon_lt_p(affine + 6)) return VSP_ERR_ARG;
-    be48(out, affine);
-    out[0] |= 0x80;
-    if (fp_lex_larger(affine + 6)) out[0] |= 0x20;
-    return VSP_OK;
-}
-int vsp_g2_compress(const uint64_t affine[24], uint8_t out[96]) {
-    if (!affine || !out) return VSP_ERR_ARG;
-    if (limbs_zero(affine, 24)) { memset(out, 0, 96); out[0] = 0xC0; return VSP_OK; }
-    for (int k = 0; k < 4; k++) if (!canon_lt_p(affine + 6 * k)) return VSP_ERR_ARG;
-    be48(out, affine + 6);          // x.c1 first
-    be48(out + 48, affine);         // then x.c0
-    out[0] |= 0x80;
-    const uint64_t *y0 = affine + 12, *y1 = affine + 18;
-    bool larger = limbs_zero(y1, 6) ? fp_lex_larger(y0) : fp_lex_larger(y1);
-    if (larger) out[0] |= 0x20;
-    return VSP_OK;
-}
-
-
-// ---- decompression (the inverse of the above): x from the big-endian bytes, y = sqrt(x^3 + b) with the sign the flag names ----
-static void from_be48(uint64_t *l, const uint8_t *in) {
-    for (int i = 0; i < 6; i++) { uint64_t v = 0; for (int b = 0; b < 8; b++) v |= (uint64_t)in[47 - (i * 8 + b)] << (8 * b); l[i] = v; }
-}
-// a^((p+1)/4) -- the square root when a is a quadratic residue (p = 3 mod 4); returns false when it is not
-static bool fp_sqrt(const HFp &a, HFp &out) {
-    uint64_t e[6]; uint64_t carry = 1;                         // e = (p + 1) / 4
-    for (int i = 0; i < 6; i++) { uint64_t v = FpP64::MOD[i] + carry; carry = (v < carry) ? 1 : 0; e[i] = v; }
-    for (int i = 0; i < 6; i++) e[i] = (e[i] >> 2) | (i < 5 ? e[i + 1] << 62 : 0);
-    out = pow_limbs(a, e, 6);
-    return eq(sqr(out), a);
-}
-// square root in Fp2 = Fp[u]/(u^2+1) by the norm: returns false when a is not a square
-static bool fp2_sqrt(const HFp2 &a, HFp2 &out) {
-    if (is_zero(a.c1)) {
-        HFp r;
-        if (fp_sqrt(a.c0, r)) { out.c0 = r; out.c1 = HFp::zero(); return true; }
-        if (fp_sqrt(neg(a.c0), r)) { out.c0 = HFp::zero(); out.c1 = r; return true; }   // (r u)^2 = -r^2
-        return false;
-    }
-    HFp s;
-    if (!fp_sqrt(add(sqr(a.c0), sqr(a.c1)), s)) return false;
-    uint64_t two4[6] = {2, 0, 0, 0, 0, 0};
-    HFp half = inv(host_load_canon<HFp>(two4));
-    HFp t = mul(add(a.c0, s), half), x0;
-    if (!fp_sqrt(t, x0)) { t = mul(sub(a.c0, s), half); if (!fp_sqrt(t, x0)) return false; }
-    out.c0 = x0; out.c1 = mul(mul(a.c1, half), inv(x0));
-    return eq(sqr(out), a);
-}
-static const uint64_t R_LIMBS[4] = {0xffffffff00000001ULL, 0x53bda402fffe5bfeULL, 0x3339d80809a1d805ULL, 0x73eda753299d7d48ULL};
-
-int vsp_g1_decompress(const uint8_t in[48], int check_subgroup, uint64_t out_affine[12], int *out_is_inf) {
-    if (!in || !out_affine) return VSP_ERR_ARG;
-    if (!(in[0] & 0x80)) return VSP_ERR_ARG;                       // uncompressed form is not accepted
-    uint8_t buf[48]; memcpy(buf, in, 48); buf[0] &= 0x1f;
-    if (in[0] & 0x40) {                                            // infinity: every other bit must be clear
-        for (int i = 0; i < 48; i++) if (buf[i]) return VSP_ERR_ARG;
-        if (in[0] & 0x20) return VSP_ERR_ARG;
-        memset(out_affine, 0, 96); if (out_is_inf) *out_is_inf = 1; return VSP_OK;
-    }
-    uint64_t x4[6]; from_be48(x4, buf);
-    if (!canon_lt_p(x4)) return VSP_ERR_ARG;
-    HFp x = host_load_canon<HFp>(x4), y;
-    uint64_t four[6] = {4, 0, 0, 0, 0, 0};
-    if (!fp_sqrt(add(mul(sqr(x), x), host_load_canon<HFp>(four)), y)) return VSP_ERR_ARG;      // not on the curve
-    uint64_t y4[6]; host_store_canon(y4, y);
-    if (fp_lex_larger(y4) != ((in[0] & 0x20) != 0)) { y = neg(y); host_store_canon(y4, y); }
-    if (check_subgroup) {
-        Affine<HFp> p; p.x = x; p.y = y;
-        if (!is_inf(xyzz_mul_scalar(xyzz_from_affine(p), R_LIMBS, 255))) return VSP_ERR_ARG;
-    }
-    memcpy(out_affine, x4, 48); memcpy(out_affine + 6, y4, 48);
-    if (out_is_inf) *out_is_inf = 0;
-    return VSP_OK;
-}
-int vsp_g2_decompress(const uint8_t in[96], int check_subgroup, uint64_t out_affine[24], int *out_is_inf) {
-    if (!in || !out_affine) return VSP_ERR_ARG;
-    if (!(in[0] & 0x80)) return VSP_ERR_ARG;
-    uint8_t buf[96]; memcpy(buf, in, 96); buf[0] &= 0x1f;
-    if (in[0] & 0x40) {
-        for (int i = 0; i < 96; i++) if (buf[i]) return VSP_ERR_ARG;
-        if (in[0] & 0x20) return VSP_ERR_ARG;
-        memset(out_affine, 0, 192); if (out_is_inf) *out_is_inf = 1; return VSP_OK;
-    }
-    uint64_t x1[6], x0[6]; from_be48(x1, buf); from_be48(x0, buf + 48);      // x.c1 first, then x.c0
-    if (!canon_lt_p(x0) || !canon_lt_p(x1)) return VSP_ERR_ARG;
-    HFp2 x, y; x.c0 = host_load_canon<HFp>(x0); x.c1 = host_load_canon<HFp>(x1);
-    uint64_t four[6] = {4, 0, 0, 0, 0, 0};
-    HFp2 b; b.c0 = host_load_canon<HFp>(four); b.c1 = b.c0;                   // 4 (1 + u)
-    if (!fp2_sqrt(add(mul(sqr(x), x), b), y)) return VSP_ERR_ARG;
-    uint64_t y0[6], y1[6]; host_store_canon(y0, y.c0); host_store_canon(y1, y.c1);
-    bool larger = limbs_zero(y1, 6) ? fp_lex_larger(y0) : fp_lex_larger(y1);
-    if (larger != ((in[0] & 0x20) != 0)) { y = neg(y); host_store_canon(y0, y.c0); host_store_canon(y1, y.c1); }
-    if (check_subgroup) {
-        Affine<HFp2> p; p.x = x; p.y = y;
-        if (!is_inf(xyzz_mul_scalar(xyzz_from_affine(p), R_LIMBS, 255))) return VSP_ERR_ARG;
-    }
-    memcpy(out_affine, x0, 48); memcpy(out_affine + 6, x1, 48); memcpy(out_affine + 12, y0, 48); memcpy(out_affine + 18, y1, 48);
-    if (out_is_inf) *out_is_inf = 0;
-    return VSP_OK;
-}
+extern "C" {
+int vsp_fixed_base_mul_g1(vsp_ctx *ctx, const void *d_scalars, size_t n, void *d_out) { return fixed_base_mul_sync<G1>(ctx, d_scalars, n, d_out); }
+int vsp_fixed_base_mul_g2(vsp_ctx *ctx, const void *d_scalars, size_t n, void *d_out) { return fixed_base_mul_sync<G2>(ctx, d_scalars, n, d_out); }
 
 }  // extern "C"

@@ -18,6 +18,35 @@
 
 namespace vsp {
 
+// ---- the two groups: G1 over Fp, G2 over Fp2 (y^2 = x^3 + b, curve_b below) ----
+struct Affine28; struct Affine28x2;         // rows of the 28-bit-limb tables (fp28.h)
+template <int N> struct Group;
+template <> struct Group<1> {
+    static constexpr int ID = 1;
+    using F = Fp; using HF = HFp; using Point = Affine<Fp>; using Row28 = Affine28;     // device field, host field, device affine point, table row
+    static constexpr size_t AFFINE_WORDS = 12, JACOBIAN_WORDS = 18;                    // canonical 64-bit words of x | y and of X | Y | Z
+    static constexpr uint64_t GEN[12] = {0xfb3af00adb22c6bbULL, 0x6c55e83ff97a1aefULL, 0xa14e3a3f171bac58ULL, 0xc3688c4f9774b905ULL, 0x2695638c4fa9ac0fULL, 0x17f1d3a73197d794ULL,
+                                         0x0caa232946c5e7e1ULL, 0xd03cc744a2888ae4ULL, 0x00db18cb2c04b3edULL, 0xfcf5e095d5d00af6ULL, 0xa09e30ed741d8ae4ULL, 0x08b3f481e3aaa0f1ULL};
+};
+template <> struct Group<2> {
+    static constexpr int ID = 2;
+    using F = Fp2; using HF = HFp2; using Point = Affine<Fp2>; using Row28 = Affine28x2;
+    static constexpr size_t AFFINE_WORDS = 24, JACOBIAN_WORDS = 36;
+    static constexpr uint64_t GEN[24] = {0xd48056c8c121bdb8ULL, 0x0bac0326a805bbefULL, 0xb4510b647ae3d177ULL, 0xc6e47ad4fa403b02ULL, 0x260805272dc51051ULL, 0x024aa2b2f08f0a91ULL,
+                                         0xe5ac7d055d042b7eULL, 0x334cf11213945d57ULL, 0xb5da61bbdc7f5049ULL, 0x596bd0d09920b61aULL, 0x7dacd3a088274f65ULL, 0x13e02b6052719f60ULL,
+                                         0xe193548608b82801ULL, 0x923ac9cc3baca289ULL, 0x6d429a695160d12cULL, 0xadfd9baa8cbdd3a7ULL, 0x8cc9cdc6da2e351aULL, 0x0ce5d527727d6e11ULL,
+                                         0xaaa9075ff05f79beULL, 0x3f370d275cec1da1ULL, 0x267492ab572e99abULL, 0xcb3e287e85a763afULL, 0x32acd2b02bc28b99ULL, 0x0606c4a02ea734ccULL};
+};
+using G1 = Group<1>;
+using G2 = Group<2>;
+// f(G1{}) for group 1, f(G2{}) otherwise: the one place a group number becomes a type
+template <class Fn> inline decltype(auto) with_group(int group, Fn &&f) {
+    if (group == 1) return f(G1{});
+    return f(G2{});
+}
+// bytes of one device affine point of a group
+inline size_t point_bytes(int group) { return with_group(group, [](auto g) { return sizeof(typename decltype(g)::Point); }); }
+
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
@@ -94,7 +123,7 @@ struct MsmWork {
     size_t n = 0, n_eff = 0;
 };
 static constexpr unsigned VSP_MSM_SLOTS = 6;
-// one multi-exponentiation queued on a work slot (msm_g1_launch / msm_g2_launch)
+// one multi-exponentiation queued on a work slot (msm_slot_launch)
 struct MsmRequest {
     const void *bases = nullptr;        // Affine<Fp> / Affine<Fp2>, Montgomery form: the points, or with `pre` the table of window multiples
     const Fr *scalars = nullptr;
@@ -121,7 +150,6 @@ struct vsp_ctx {
     hipStream_t prove_streams[2] = {nullptr, nullptr};      // the prover's two witness chains (prover.hip), created on first use
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_aux = nullptr;
     std::string err;
-    int err_code = 0;                   // the code set_error last returned (callers that receive a null handle report it instead of guessing from the text)
     std::map<std::string, double> stats;
     std::map<std::string, long> opts;
     vsp::NttTables ntt;
@@ -137,8 +165,8 @@ struct vsp_ctx {
     void *h_fold = nullptr; size_t h_fold_cap = 0;      // pinned landing buffer of vsp_fold_jacobian_device (the ranks' records)
     vsp::DevBuf val_flag;               // one word: validation result of the last bases upload
     int fp28_checked[2] = {0, 0};       // known-answer check of the 28-bit-limb accumulation kernels, per group: 0 not yet, 1 passed, -1 failed (kernel disabled)
-    // fixed-base tables (generator multiples), built lazily
-    vsp::DevBuf fb_g1, fb_g2, fb_tmp, fb_pre;
+    // fixed-base tables of the generators (fb_table[group - 1]), built lazily, and the scratch of the batch exponentiation
+    vsp::DevBuf fb_table[2], fb_tmp, fb_pre;
     // prover workspaces for K witnesses (a single proof: K = 1): z [K][num_vars + 1], A z, B z, C z [K][3][m], H [K][m], the packed witness
     vsp::DevBuf pr_z, pr_abc, pr_h, pr_pack;
     // the proof or the batch of K proofs in flight between a launch and its finish (one per context): the key, r and s (K x 4 words), the
@@ -280,21 +308,17 @@ int prove_with_overlap(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const
                        const uint64_t *saver_P1, const uint64_t *saver_r_enc, uint64_t A_out[12], uint64_t B_out[24], uint64_t C_out[12],
                        uint8_t proof_out[192], const std::function<void()> *overlap);
 
-// MSM on device-resident Montgomery bases; result as host XYZZ (Montgomery, 64-bit limbs)
-int msm_g1_launch(vsp_ctx *ctx, unsigned slot, const MsmRequest &rq);
-int msm_g2_launch(vsp_ctx *ctx, unsigned slot, const MsmRequest &rq);
-int msm_g1_precompute(vsp_ctx *ctx, G1Affine *table, size_t n, unsigned c);
-int msm_g2_precompute(vsp_ctx *ctx, G2Affine *table, size_t n, unsigned c);
-int msm_g1_table28(vsp_ctx *ctx, const G1Affine *table, size_t count, void *d_out /* count (glv: 2 count) rows of 128 bytes */, bool glv);
-int msm_g2_table28(vsp_ctx *ctx, const G2Affine *table, size_t count, void *d_out /* count (glv: 2 count) rows of 256 bytes */, bool glv);
+// MSM on device-resident Montgomery bases (msm_impl.inc, instantiated for each group by msm_g1.hip / msm_g2.hip); result as host XYZZ
+// (Montgomery, 64-bit limbs)
+template <class G> int msm_slot_launch(vsp_ctx *ctx, unsigned slot, const MsmRequest &rq);
+template <class G> int msm_precompute(vsp_ctx *ctx, typename G::Point *table, size_t n, unsigned c);
+// count (glv: 2 count) rows of sizeof(G::Row28) bytes
+template <class G> int msm_table28(vsp_ctx *ctx, const typename G::Point *table, size_t count, void *d_out, bool glv);
 // the results of a launch: `count` of them, one per vector of its batch (1 for a launch without a batch)
-int msm_g1_finish(vsp_ctx *ctx, unsigned slot, XYZZ<HFp> *out, unsigned count = 1);
-int msm_g2_finish(vsp_ctx *ctx, unsigned slot, XYZZ<HFp2> *out, unsigned count = 1);
+template <class G> int msm_slot_finish(vsp_ctx *ctx, unsigned slot, XYZZ<typename G::HF> *out, unsigned count = 1);
 // a finish in two halves: the wait (context state: caller's thread) and the fold of the window results (pure host arithmetic over the slot: any thread)
-int msm_g1_finish_wait(vsp_ctx *ctx, unsigned slot, unsigned count, bool *empty);
-void msm_g1_fold(vsp_ctx *ctx, unsigned slot, XYZZ<HFp> *out);
-int msm_g2_finish_wait(vsp_ctx *ctx, unsigned slot, unsigned count, bool *empty);
-void msm_g2_fold(vsp_ctx *ctx, unsigned slot, XYZZ<HFp2> *out);
+template <class G> int msm_slot_finish_wait(vsp_ctx *ctx, unsigned slot, unsigned count, bool *empty);
+template <class G> void msm_slot_fold(vsp_ctx *ctx, unsigned slot, XYZZ<typename G::HF> *out);
 // rq over points [first, first + rq.n) of resident bases: fills in rq's bases, pre, table28 and glv
 int launch_on_bases(vsp_ctx *ctx, unsigned slot, const vsp_bases *bases, size_t first, MsmRequest rq);
 int msm_slot_stream(vsp_ctx *ctx, unsigned slot, hipStream_t *out);
@@ -304,36 +328,68 @@ int msm_slot_use_stream(vsp_ctx *ctx, unsigned slot, hipStream_t stream_or_null)
 int msm_make_slot_stream(vsp_ctx *ctx, hipStream_t *out);
 void msm_drain_slots(vsp_ctx *ctx);
 // d_flag: one device word, zeroed by the caller; bit 0 = coordinate >= p, bit 1 = point off the curve (only when check_curve)
-int bases_to_mont_g1(vsp_ctx *ctx, const void *d_canon, G1Affine *d_out, size_t n, int check_curve, uint32_t *d_flag);
-int bases_to_mont_g2(vsp_ctx *ctx, const void *d_canon, G2Affine *d_out, size_t n, int check_curve, uint32_t *d_flag);
+template <class G> int bases_to_mont(vsp_ctx *ctx, const void *d_canon, typename G::Point *d_out, size_t n, int check_curve, uint32_t *d_flag);
 // raises bit 2 of *d_flag when some point fails phi(P) = lambda P (the endomorphism split's precondition; msm_impl.inc k_subgroup_check)
-int subgroup_check_g1(vsp_ctx *ctx, const G1Affine *d_mont, size_t n, uint32_t *d_flag);
+template <class G> int subgroup_check(vsp_ctx *ctx, const typename G::Point *d_mont, size_t n, uint32_t *d_flag);
 int msm_diag_clock(vsp_ctx *ctx, int reset, double *ghz, double *waves);
 int ntt_diag_clock(vsp_ctx *ctx, int reset, double *ghz, double *waves);
-int subgroup_check_g2(vsp_ctx *ctx, const G2Affine *d_mont, size_t n, uint32_t *d_flag);
-// resident bases from canonical points; trust: BASES_CALLER = caller data (validated; the split only after the subgroup check),
+// resident bases from canonical points into *out; trust: BASES_CALLER = caller data (validated; the split only after the subgroup check),
 // BASES_OWN = points this library computed as multiples of a generator (in the subgroup by construction: no check),
 // BASES_TRANSIENT = bases of one host-buffer call, or bases about to get window multiples (no split, so no check: exact for any curve point)
 enum { BASES_CALLER = 0, BASES_OWN = 1, BASES_TRANSIENT = 2 };
-vsp_bases *bases_create(vsp_ctx *ctx, int group, const void *src, bool src_on_device, size_t n, int trust);
-int fixed_base_mul_g1(vsp_ctx *ctx, const Fr *d_scalars, size_t n, void *d_out);
-int fixed_base_mul_g2(vsp_ctx *ctx, const Fr *d_scalars, size_t n, void *d_out);
+int bases_create(vsp_ctx *ctx, int group, const void *src, bool src_on_device, size_t n, int trust, vsp_bases **out);
+// out[i] = scalars[i] * the group's generator, canonical affine (fixedbase_impl.inc, instantiated by fixedbase_g1.hip / fixedbase_g2.hip)
+template <class G> int fixed_base_mul(vsp_ctx *ctx, const Fr *d_scalars, size_t n, void *d_out);
 int upload_power_tables(vsp_ctx *ctx, const HFr &base, size_t hi_count, DevBuf &lo, DevBuf &hi);
 HFr host_omega(unsigned log_m);
 
-// canonical <-> host Montgomery helpers
+// canonical <-> host Montgomery helpers: one field element, an affine point (x | y) and a Jacobian record (X | Y | Z); HFp2 values
+// are c0 | c1, 6 words each
 template <class F> inline F host_load_canon(const uint64_t *p) { F t; memcpy(&t, p, sizeof(F)); return to_mont(t); }
 template <class F> inline void host_store_canon(uint64_t *p, const F &m) { F t = from_mont(m); memcpy(p, &t, sizeof(F)); }
-inline Affine<HFp> host_load_g1(const uint64_t *p) { Affine<HFp> a; a.x = host_load_canon<HFp>(p); a.y = host_load_canon<HFp>(p + 6); return a; }
-inline Affine<HFp2> host_load_g2(const uint64_t *p) {
-    Affine<HFp2> a;
-    a.x.c0 = host_load_canon<HFp>(p); a.x.c1 = host_load_canon<HFp>(p + 6);
-    a.y.c0 = host_load_canon<HFp>(p + 12); a.y.c1 = host_load_canon<HFp>(p + 18);
-    return a;
+template <class HF> inline Affine<HF> host_load_affine(const uint64_t *p) {
+    constexpr size_t w = sizeof(HF) / 8;
+    Affine<HF> a; a.x = host_load_canon<HF>(p); a.y = host_load_canon<HF>(p + w); return a;
 }
-inline void host_store_g1(uint64_t *p, const Affine<HFp> &a) { host_store_canon(p, a.x); host_store_canon(p + 6, a.y); }
-inline void host_store_g2(uint64_t *p, const Affine<HFp2> &a) {
-    host_store_canon(p, a.x.c0); host_store_canon(p + 6, a.x.c1); host_store_canon(p + 12, a.y.c0); host_store_canon(p + 18, a.y.c1);
+template <class HF> inline void host_store_affine(uint64_t *p, const Affine<HF> &a) {
+    constexpr size_t w = sizeof(HF) / 8;
+    host_store_canon(p, a.x); host_store_canon(p + w, a.y);
+}
+template <class HF> inline Jacobian<HF> host_load_jacobian(const uint64_t *p) {
+    constexpr size_t w = sizeof(HF) / 8;
+    Jacobian<HF> j; j.X = host_load_canon<HF>(p); j.Y = host_load_canon<HF>(p + w); j.Z = host_load_canon<HF>(p + 2 * w); return j;
+}
+template <class HF> inline void host_store_jacobian(uint64_t *p, const Jacobian<HF> &j) {
+    constexpr size_t w = sizeof(HF) / 8;
+    host_store_canon(p, j.X); host_store_canon(p + w, j.Y); host_store_canon(p + 2 * w, j.Z);
+}
+
+// ---- host codec helpers: canonical values as little-endian 64-bit limbs
+// nl limbs <-> nl * 8 big-endian bytes
+inline void be_from_limbs(uint8_t *o, const uint64_t *l, int nl) { for (int i = 0; i < nl; i++) for (int b = 0; b < 8; b++) o[nl * 8 - 1 - (i * 8 + b)] = (uint8_t)(l[i] >> (8 * b)); }
+inline void limbs_from_be(uint64_t *l, const uint8_t *p, int nl) {
+    for (int i = 0; i < nl; i++) { uint64_t v = 0; for (int b = 0; b < 8; b++) v |= (uint64_t)p[nl * 8 - 1 - (i * 8 + b)] << (8 * b); l[i] = v; }
+}
+inline bool limbs_zero(const uint64_t *l, int n) { uint64_t o = 0; for (int i = 0; i < n; i++) o |= l[i]; return o == 0; }
+// P::N limbs below the modulus P::MOD (FpP64: a coordinate below p; FrP64: a scalar below r)
+template <class P> inline bool below_mod(const uint64_t *l) {
+    for (int i = P::N - 1; i >= 0; i--) { if (l[i] < P::MOD[i]) return true; if (l[i] > P::MOD[i]) return false; }
+    return false;
+}
+// a host scalar as the kernels take it (the same Montgomery value on 32-bit limbs)
+inline Fr to_dev(const HFr &h) { Fr d; memcpy(&d, &h, sizeof(Fr)); return d; }
+inline HFr host_from_u64(uint64_t v) { uint64_t c[4] = {v, 0, 0, 0}; return host_load_canon<HFr>(c); }
+// the curve constant b of y^2 = x^3 + b: 4 (G1), 4 (1 + u) (G2)
+template <class HF> inline HF curve_b();
+template <> inline HFp curve_b<HFp>() { return dbl(dbl(HFp::one())); }
+template <> inline HFp2 curve_b<HFp2>() { HFp2 b; b.c0 = curve_b<HFp>(); b.c1 = b.c0; return b; }
+// `words` canonical words (whole Fp values) all below p
+inline bool coords_below_p(const uint64_t *l, size_t words) { for (size_t k = 0; k < words; k += 6) if (!below_mod<FpP64>(l + k)) return false; return true; }
+// canonical affine words of group G: every coordinate below p, and the point on the curve or all zero (infinity)
+template <class G> inline bool affine_valid(const uint64_t *p) {
+    if (!coords_below_p(p, G::AFFINE_WORDS)) return false;
+    const Affine<typename G::HF> a = host_load_affine<typename G::HF>(p);
+    return is_inf(a) || eq(sqr(a.y), add(mul(sqr(a.x), a.x), curve_b<typename G::HF>()));
 }
 
 static inline unsigned ceil_log2(size_t n) { unsigned l = 0; while (((size_t)1 << l) < n) l++; return l; }

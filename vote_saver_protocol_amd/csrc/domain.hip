@@ -148,8 +148,6 @@ __global__ __launch_bounds__(256) void k_fr_from_mont(Fr *a, size_t n) {
     if (i < n) a[i] = from_mont(a[i]);
 }
 
-static Fr dev(const HFr &h) { Fr d; memcpy(&d, &h, sizeof(Fr)); return d; }
-static HFr h_u64(uint64_t v) { uint64_t c[4] = {v, 0, 0, 0}; return host_load_canon<HFr>(c); }
 static HFr h_pow(const HFr &b, uint64_t e) { uint64_t ee[1] = {e}; return pow_limbs(b, ee, 1); }
 static const uint64_t G7[4] = {7, 0, 0, 0};
 
@@ -189,14 +187,14 @@ int domain_init(vsp_ctx *ctx, vsp_domain *d, size_t min_size) {
     if (!(pick_basic(d, min_size) || pick_step(d, min_size) || pick_basic(d, big + rounded) || pick_step(d, big + rounded)))
         return set_error(ctx, VSP_ERR_UNSUPPORTED, "make_evaluation_domain: no radix-2 family domain of this size");
     // divisors of divide_by_z_on_coset, coset generator 7
-    HFr g = h_u64(7);
+    HFr g = host_from_u64(7);
     if (!d->step) { d->zinv_const = inv(domain_vanishing(d, g)); return VSP_OK; }
     VSP_HIP(hipSetDevice(ctx->device));
     VSP_TRY(ntt_ensure_twiddles(ctx, d->log_big + 1));
     HFr omega = host_omega(d->log_big + 1);
     HFr Z0 = sub(h_pow(g, d->big_m), HFr::one());
     HFr w1 = h_pow(omega, d->small_m);
-    ZConsts k; k.c0 = dev(mul(h_pow(g, d->small_m), Z0)); k.c1 = dev(mul(w1, Z0));
+    ZConsts k; k.c0 = to_dev(mul(h_pow(g, d->small_m), Z0)); k.c1 = to_dev(mul(w1, Z0));
     size_t compr = d->big_m / d->small_m;
     VSP_TRY(ensure(ctx, d->zinv, compr * sizeof(Fr)));
     hipLaunchKernelGGL(k_zinv_table, dim3((unsigned)((compr + 63) / 64)), dim3(64), 0, ctx->stream, (Fr *)d->zinv.p, compr, d->small_m, d->big_m,
@@ -208,7 +206,7 @@ int domain_init(vsp_ctx *ctx, vsp_domain *d, size_t min_size) {
 }
 void domain_basic(vsp_domain *d, unsigned log_m) {
     d->m = d->big_m = (size_t)1 << log_m; d->small_m = 0; d->log_big = log_m; d->log_small = 0; d->step = 0;
-    d->zinv_const = inv(domain_vanishing(d, h_u64(7)));
+    d->zinv_const = inv(domain_vanishing(d, host_from_u64(7)));
 }
 int fr_from_mont_device(vsp_ctx *ctx, Fr *a, size_t n) {
     if (!n) return VSP_OK;
@@ -259,7 +257,7 @@ int domain_fft_device(vsp_ctx *ctx, const vsp_domain *d, Fr *a, int inverse, con
     VSP_TRY(fold(ctx, a, dv, ping, pong, small, compr, 1, (const Fr *)ctx->ntt.fwd.p, shift));
     PostConsts k;
     HFr scale = extra_scale ? *extra_scale : HFr::one();
-    k.scale = dev(scale); k.half = dev(mul(scale, inv(h_u64(2))));
+    k.scale = to_dev(scale); k.half = to_dev(mul(scale, inv(host_from_u64(2))));
     hipLaunchKernelGGL(k_step_post, dim3(blocks), dim3(256), 0, ctx->stream, a, (const Fr *)dv, (const Fr *)ctx->ntt.inv.p, shift, big, small,
                        coset_g ? (const Fr *)ctx->ntt.pw_lo_i.p : nullptr, coset_g ? (const Fr *)ctx->ntt.pw_hi_i.p : nullptr, extra_scale ? 1 : 0, k);
     VSP_LAUNCH_CHECK();
@@ -269,7 +267,7 @@ int domain_fft_device(vsp_ctx *ctx, const vsp_domain *d, Fr *a, int inverse, con
 int domain_divide_by_z_device(vsp_ctx *ctx, const vsp_domain *d, Fr *p) {
     size_t compr = d->step ? d->big_m / d->small_m : 1;
     hipLaunchKernelGGL(k_mul_zinv, dim3((unsigned)((d->m + 255) / 256)), dim3(256), 0, ctx->stream, p, d->m, d->step ? d->big_m : 0, compr - 1,
-                       d->step ? (const Fr *)d->zinv.p : nullptr, dev(d->zinv_const));
+                       d->step ? (const Fr *)d->zinv.p : nullptr, to_dev(d->zinv_const));
     VSP_LAUNCH_CHECK();
     return VSP_OK;
 }
@@ -286,22 +284,22 @@ int domain_lagrange_device(vsp_ctx *ctx, const vsp_domain *d, const HFr &t, Fr *
     int np = 0;
     if (!d->step) {
         HFr Z = sub(h_pow(t, d->m), HFr::one());
-        parts[np++] = {d->m, host_omega(d->log_big), t, mul(Z, inv(h_u64(d->m))), HFr::zero(), HFr::one(), 0, 0};
+        parts[np++] = {d->m, host_omega(d->log_big), t, mul(Z, inv(host_from_u64(d->m))), HFr::zero(), HFr::one(), 0, 0};
     } else {
         HFr omega = host_omega(d->log_big + 1), ts = mul(t, inv(omega));
         HFr ws = h_pow(omega, d->small_m);
         HFr Zb = sub(h_pow(t, d->big_m), HFr::one()), Zs = sub(h_pow(ts, d->small_m), HFr::one());
         HFr L0 = sub(h_pow(t, d->small_m), ws);
         HFr L1 = mul(Zb, inv(sub(h_pow(omega, d->big_m), HFr::one())));
-        parts[np++] = {d->big_m, sqr(omega), t, mul(mul(Zb, inv(h_u64(d->big_m))), L0), ws, HFr::one(), d->small_m, 0};
-        parts[np++] = {d->small_m, host_omega(d->log_small), ts, mul(mul(Zs, inv(h_u64(d->small_m))), L1), HFr::zero(), omega, 0, d->big_m};
+        parts[np++] = {d->big_m, sqr(omega), t, mul(mul(Zb, inv(host_from_u64(d->big_m))), L0), ws, HFr::one(), d->small_m, 0};
+        parts[np++] = {d->small_m, host_omega(d->log_small), ts, mul(mul(Zs, inv(host_from_u64(d->small_m))), L1), HFr::zero(), omega, 0, d->big_m};
     }
     for (int k = 0; k < np; k++) {
         const Part &p = parts[k];
         const size_t hi_count = p.n > ((size_t)1 << PW_LOG) ? (p.n >> PW_LOG) : 1;
         int rc = upload_power_tables(ctx, p.w, hi_count, lo, hi);
         if (rc != VSP_OK) return done(rc);
-        LagConsts kc; kc.x = dev(in_domain ? t : p.x); kc.coef = dev(in_domain ? p.mult : p.coef); kc.shift = dev(p.shift);
+        LagConsts kc; kc.x = to_dev(in_domain ? t : p.x); kc.coef = to_dev(in_domain ? p.mult : p.coef); kc.shift = to_dev(p.shift);
         LagConsts *kd = (LagConsts *)kbuf.p + k;
         if (hipMemcpyAsync(kd, &kc, sizeof kc, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
             return done(set_error(ctx, VSP_ERR_HIP, "lagrange: constants upload failed"));
@@ -348,7 +346,7 @@ int witness_map_device(vsp_ctx *ctx, Fr *dA, Fr *dB, Fr *dC, const vsp_domain *d
         extra = mul(d->zinv_const, extra);    // Z is constant on the coset of a basic domain: fold 1/Z(g) as well
     } else {
         hipLaunchKernelGGL(k_ab_minus_c_div, dim3(blocks), dim3(256), 0, ctx->stream, dH, (const Fr *)dA, (const Fr *)dB, (const Fr *)dC, m, d->big_m,
-                           d->big_m / d->small_m - 1, (const Fr *)d->zinv.p, dev(d->zinv_const));
+                           d->big_m / d->small_m - 1, (const Fr *)d->zinv.p, to_dev(d->zinv_const));
     }
     VSP_LAUNCH_CHECK();
     VSP_TRY(domain_fft_device(ctx, d, dH, 1, G7, &extra));

@@ -1,3 +1,6 @@
 // G1 instantiation of the generator-side batch exponentiation (see fixedbase_impl.inc)
-#define VSP_FB_GROUP 1
 #include "fixedbase_impl.inc"
+
+namespace vsp {
+template int fixed_base_mul<G1>(vsp_ctx *, const Fr *, size_t, void *);
+}  // namespace vsp

@@ -1,6 +1,6 @@
 // Generator-side fixed-base batch exponentiation (the Groth16 generator's batch_exp, reached from
 // bin/cli/include/nil/vote_saver/common.hpp:916-917): out[i] = scalars[i] * generator, as canonical affine points.
-// Implementation include: compiled once per group by fixedbase_g1.hip / fixedbase_g2.hip so the two build in parallel.
+// Implementation include: fixedbase_g1.hip / fixedbase_g2.hip each instantiate fixed_base_mul for their group, so the two build in parallel.
 #include "common.h"
 #include "lane_view.h"
 
@@ -83,14 +83,16 @@ static int build_fixed_table(vsp_ctx *ctx, const Affine<HF> &gen, DevBuf &dst) {
     return VSP_OK;
 }
 
-template <class F, class HF>
-static int fixed_base_mul(vsp_ctx *ctx, const Affine<HF> &gen, DevBuf &table, const Fr *d_scalars, size_t n, void *d_out) {
+}  // anonymous namespace
+
+template <class G> int fixed_base_mul(vsp_ctx *ctx, const Fr *d_scalars, size_t n, void *d_out) {
+    using F = typename G::F; using HF = typename G::HF;
     if (!n) return VSP_OK;
-    VSP_TRY((build_fixed_table<F, HF>(ctx, gen, table)));
+    VSP_TRY((build_fixed_table<F, HF>(ctx, host_load_affine<HF>(G::GEN), ctx->fb_table[G::ID - 1])));
     VSP_TRY(ensure(ctx, ctx->fb_tmp, n * sizeof(XYZZ<F>)));
     VSP_TRY(ensure(ctx, ctx->fb_pre, n * sizeof(F)));
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fixed_base<F>), dim3((unsigned)((n * LaneView<F>::LANES + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const Affine<F> *)table.p, d_scalars, n, (XYZZ<F> *)ctx->fb_tmp.p);
+                       (const Affine<F> *)ctx->fb_table[G::ID - 1].p, d_scalars, n, (XYZZ<F> *)ctx->fb_tmp.p);
     VSP_LAUNCH_CHECK();
     size_t chunks = (n + BA_CHUNK - 1) / BA_CHUNK;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_batch_affine<F>), dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, ctx->stream,
@@ -98,23 +100,5 @@ static int fixed_base_mul(vsp_ctx *ctx, const Affine<HF> &gen, DevBuf &table, co
     VSP_LAUNCH_CHECK();
     return VSP_OK;
 }
-}  // anonymous namespace
-
-#if VSP_FB_GROUP == 1
-static const uint64_t G1_GEN[12] = {0xfb3af00adb22c6bbULL, 0x6c55e83ff97a1aefULL, 0xa14e3a3f171bac58ULL, 0xc3688c4f9774b905ULL, 0x2695638c4fa9ac0fULL, 0x17f1d3a73197d794ULL,
-                                    0x0caa232946c5e7e1ULL, 0xd03cc744a2888ae4ULL, 0x00db18cb2c04b3edULL, 0xfcf5e095d5d00af6ULL, 0xa09e30ed741d8ae4ULL, 0x08b3f481e3aaa0f1ULL};
-int fixed_base_mul_g1(vsp_ctx *ctx, const Fr *d_scalars, size_t n, void *d_out) {
-    return fixed_base_mul<Fp, HFp>(ctx, host_load_g1(G1_GEN), ctx->fb_g1, d_scalars, n, d_out);
-}
-#else
-static const uint64_t G2_GEN[24] = {0xd48056c8c121bdb8ULL, 0x0bac0326a805bbefULL, 0xb4510b647ae3d177ULL, 0xc6e47ad4fa403b02ULL, 0x260805272dc51051ULL, 0x024aa2b2f08f0a91ULL,
-                                    0xe5ac7d055d042b7eULL, 0x334cf11213945d57ULL, 0xb5da61bbdc7f5049ULL, 0x596bd0d09920b61aULL, 0x7dacd3a088274f65ULL, 0x13e02b6052719f60ULL,
-                                    0xe193548608b82801ULL, 0x923ac9cc3baca289ULL, 0x6d429a695160d12cULL, 0xadfd9baa8cbdd3a7ULL, 0x8cc9cdc6da2e351aULL, 0x0ce5d527727d6e11ULL,
-                                    0xaaa9075ff05f79beULL, 0x3f370d275cec1da1ULL, 0x267492ab572e99abULL, 0xcb3e287e85a763afULL, 0x32acd2b02bc28b99ULL, 0x0606c4a02ea734ccULL};
-
-int fixed_base_mul_g2(vsp_ctx *ctx, const Fr *d_scalars, size_t n, void *d_out) {
-    return fixed_base_mul<Fp2, HFp2>(ctx, host_load_g2(G2_GEN), ctx->fb_g2, d_scalars, n, d_out);
-}
-#endif
 
 }  // namespace vsp

@@ -57,17 +57,8 @@ __global__ __launch_bounds__(256) void k_affine_from_mont_g2(const G2Affine *in,
     G2Affine p = in[i]; p.x = from_mont(p.x); p.y = from_mont(p.y); out[i] = p;
 }
 
-static Fr dev(const HFr &h) { Fr d; memcpy(&d, &h, sizeof(Fr)); return d; }
 // the generator's scratch holds functions of the toxic waste (powers of t, exponent vectors): zeroed before it goes back to the allocator
 static void free_dev(DevBuf &b) { if (b.p) { hipMemset(b.p, 0, b.cap); hipFree(b.p); } b.p = nullptr; b.cap = 0; }
-
-static const uint64_t G1_GEN_L[12] = {0xfb3af00adb22c6bbULL, 0x6c55e83ff97a1aefULL, 0xa14e3a3f171bac58ULL, 0xc3688c4f9774b905ULL, 0x2695638c4fa9ac0fULL, 0x17f1d3a73197d794ULL,
-                                      0x0caa232946c5e7e1ULL, 0xd03cc744a2888ae4ULL, 0x00db18cb2c04b3edULL, 0xfcf5e095d5d00af6ULL, 0xa09e30ed741d8ae4ULL, 0x08b3f481e3aaa0f1ULL};
-static const uint64_t G2_GEN_L[24] = {0xd48056c8c121bdb8ULL, 0x0bac0326a805bbefULL, 0xb4510b647ae3d177ULL, 0xc6e47ad4fa403b02ULL, 0x260805272dc51051ULL, 0x024aa2b2f08f0a91ULL,
-                                      0xe5ac7d055d042b7eULL, 0x334cf11213945d57ULL, 0xb5da61bbdc7f5049ULL, 0x596bd0d09920b61aULL, 0x7dacd3a088274f65ULL, 0x13e02b6052719f60ULL,
-                                      0xe193548608b82801ULL, 0x923ac9cc3baca289ULL, 0x6d429a695160d12cULL, 0xadfd9baa8cbdd3a7ULL, 0x8cc9cdc6da2e351aULL, 0x0ce5d527727d6e11ULL,
-                                      0xaaa9075ff05f79beULL, 0x3f370d275cec1da1ULL, 0x267492ab572e99abULL, 0xcb3e287e85a763afULL, 0x32acd2b02bc28b99ULL, 0x0606c4a02ea734ccULL};
-
 }  // anonymous namespace
 }  // namespace vsp
 
@@ -94,8 +85,8 @@ vsp_keypair *vsp_groth16_generate(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64
     if (is_zero(gamma) || is_zero(delta)) { set_error(ctx, VSP_ERR_ARG, "generate: gamma and delta must be non-zero"); return nullptr; }
     HFr Zt = domain_vanishing(&cs->dom, t);
     GenConsts k;
-    k.alpha = dev(alpha); k.beta = dev(beta);
-    k.gamma_inv = dev(inv(gamma)); k.delta_inv = dev(inv(delta)); k.zt_delta_inv = dev(mul(Zt, inv(delta)));
+    k.alpha = to_dev(alpha); k.beta = to_dev(beta);
+    k.gamma_inv = to_dev(inv(gamma)); k.delta_inv = to_dev(inv(delta)); k.zt_delta_inv = to_dev(mul(Zt, inv(delta)));
 
     DevBuf t_lo, t_hi, u, At, Bt, Ct, A_sc, B_sc, H_sc, L_sc, ABC_sc, pts, kbuf;
     vsp_keypair *kp = new vsp_keypair();
@@ -130,12 +121,10 @@ vsp_keypair *vsp_groth16_generate(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64
     struct Q { const Fr *sc; size_t n; int group; } qs[6] = {{(const Fr *)A_sc.p, ncols, 1}, {(const Fr *)B_sc.p, ncols, 1}, {(const Fr *)B_sc.p, ncols, 2},
                                                               {(const Fr *)H_sc.p, m - 1, 1}, {(const Fr *)L_sc.p, nv - ni, 1}, {(const Fr *)ABC_sc.p, ni + 1, 1}};
     for (int i = 0; i < 6; i++) {
-        size_t esz = qs[i].group == 1 ? sizeof(G1Affine) : sizeof(G2Affine);
-        if (ensure(ctx, pts, (qs[i].n ? qs[i].n : 1) * esz) != VSP_OK) return fail(nullptr);
-        int rc = qs[i].group == 1 ? fixed_base_mul_g1(ctx, qs[i].sc, qs[i].n, pts.p) : fixed_base_mul_g2(ctx, qs[i].sc, qs[i].n, pts.p);
-        if (rc != VSP_OK) return fail(nullptr);
-        kp->q[i] = bases_create(ctx, qs[i].group, pts.p, true, qs[i].n, BASES_OWN);      // multiples of the generators: in the subgroup by construction
-        if (!kp->q[i]) return fail(nullptr);
+        if (ensure(ctx, pts, (qs[i].n ? qs[i].n : 1) * point_bytes(qs[i].group)) != VSP_OK) return fail(nullptr);
+        if (with_group(qs[i].group, [&](auto g) { return fixed_base_mul<decltype(g)>(ctx, qs[i].sc, qs[i].n, pts.p); }) != VSP_OK) return fail(nullptr);
+        // multiples of the generators: in the subgroup by construction
+        if (bases_create(ctx, qs[i].group, pts.p, true, qs[i].n, BASES_OWN, &kp->q[i]) != VSP_OK) return fail(nullptr);
         // precompute: bit 0 = the recommended set A, B(G1), B(G2), L; bits 1..5 select A, B(G1), B(G2), H, L one by one.  H stays plain
         // in the recommended set: its scalars are dense, so the window size does not shrink, the bucket reduction over 16 window sets is
         // small beside 2^20 * 16 additions, and the plain 128 MB table is read out of the Infinity Cache where the 2 GB table of window
@@ -145,9 +134,9 @@ vsp_keypair *vsp_groth16_generate(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64
         if (pre_this && vsp_bases_precompute(ctx, kp->q[i], (unsigned)pre_window) != VSP_OK) return fail(nullptr);      // (0: by the query's size)
     }
     // single elements on the host
-    Affine<HFp> g1 = host_load_g1(G1_GEN_L); Affine<HFp2> g2 = host_load_g2(G2_GEN_L);
-    auto mul1 = [&](const uint64_t *sc, uint64_t *out) { host_store_g1(out, xyzz_to_affine(xyzz_mul_scalar(xyzz_from_affine(g1), sc, 255))); };
-    auto mul2 = [&](const uint64_t *sc, uint64_t *out) { host_store_g2(out, xyzz_to_affine(xyzz_mul_scalar(xyzz_from_affine(g2), sc, 255))); };
+    Affine<HFp> g1 = host_load_affine<HFp>(G1::GEN); Affine<HFp2> g2 = host_load_affine<HFp2>(G2::GEN);
+    auto mul1 = [&](const uint64_t *sc, uint64_t *out) { host_store_affine(out, xyzz_to_affine(xyzz_mul_scalar(xyzz_from_affine(g1), sc, 255))); };
+    auto mul2 = [&](const uint64_t *sc, uint64_t *out) { host_store_affine(out, xyzz_to_affine(xyzz_mul_scalar(xyzz_from_affine(g2), sc, 255))); };
     mul1(toxic + 4, kp->alpha_g1); mul1(toxic + 8, kp->beta_g1); mul1(toxic + 16, kp->delta_g1);
     mul2(toxic + 8, kp->beta_g2); mul2(toxic + 16, kp->delta_g2); mul2(toxic + 12, kp->gamma_g2); mul1(toxic + 12, kp->gamma_g1);
     kp->pk = vsp_pk_create(ctx, kp->alpha_g1, kp->beta_g1, kp->beta_g2, kp->delta_g1, kp->delta_g2, kp->q[0], kp->q[1], kp->q[2], kp->q[3], kp->q[4]);
@@ -181,7 +170,7 @@ int vsp_keypair_export(vsp_ctx *ctx, const vsp_keypair *kp, int which, uint64_t 
     const vsp_bases *b = kp->q[which];
     if (!b || !b->n) return VSP_OK;
     VSP_HIP(hipSetDevice(ctx->device));
-    size_t esz = b->group == 1 ? sizeof(G1Affine) : sizeof(G2Affine);
+    const size_t esz = point_bytes(b->group);
     DevBuf tmp;
     VSP_TRY(ensure(ctx, tmp, b->n * esz));
     unsigned blk = (unsigned)((b->n + 255) / 256);

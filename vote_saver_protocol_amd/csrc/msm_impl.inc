@@ -2406,9 +2406,21 @@ template <class F, class HF> static void msm_fold(const MsmWork &wk, XYZZ<HF> *o
     });
 }
 
+static MsmWork &slot(vsp_ctx *ctx, unsigned i) { return ctx->msm_work[i]; }
+
+// A batch reuses the plan of ANOTHER slot only.  A single launch may name its own slot: that is how the accumulation follows a plan-only launch.
+template <class F> static int launch_slot(vsp_ctx *ctx, unsigned slot_id, const MsmRequest &rq) {
+    if (slot_id >= VSP_MSM_SLOTS || rq.plan_from >= (int)VSP_MSM_SLOTS || (rq.batch && rq.plan_from == (int)slot_id)) return set_error(ctx, VSP_ERR_ARG, "msm: bad slot");
+    VSP_TRY(work_init(ctx, slot(ctx, slot_id), slot_id == 0 ? ctx->stream : nullptr));
+    return msm_launch<F>(ctx, slot(ctx, slot_id), rq, rq.plan_from >= 0 ? &slot(ctx, (unsigned)rq.plan_from) : nullptr);
+}
+
+}  // anonymous namespace
+
+// the entry points of common.h, defined once for both groups; msm_g1.hip / msm_g2.hip instantiate them for their group (VSP_MSM_GROUP)
 // table[w][i] = 2^(c*w) * table[0][i] for w = 1..W-1 (slice 0 already holds the bases); affine, Montgomery
-template <class F>
-static int msm_precompute(vsp_ctx *ctx, Affine<F> *table, size_t n, unsigned c) {
+template <class G> int msm_precompute(vsp_ctx *ctx, typename G::Point *table, size_t n, unsigned c) {
+    using F = typename G::F;
     const unsigned W = 255 / c + 1;
     hipStream_t st = ctx->stream;
     DevBuf tmp, pre;
@@ -2429,32 +2441,42 @@ static int msm_precompute(vsp_ctx *ctx, Affine<F> *table, size_t n, unsigned c) 
     return rc;
 }
 
-static MsmWork &slot(vsp_ctx *ctx, unsigned i) { return ctx->msm_work[i]; }
-
-// A batch reuses the plan of ANOTHER slot only.  A single launch may name its own slot: that is how the accumulation follows a plan-only launch.
-template <class F> static int launch_slot(vsp_ctx *ctx, unsigned slot_id, const MsmRequest &rq) {
-    if (slot_id >= VSP_MSM_SLOTS || rq.plan_from >= (int)VSP_MSM_SLOTS || (rq.batch && rq.plan_from == (int)slot_id)) return set_error(ctx, VSP_ERR_ARG, "msm: bad slot");
-    VSP_TRY(work_init(ctx, slot(ctx, slot_id), slot_id == 0 ? ctx->stream : nullptr));
-    return msm_launch<F>(ctx, slot(ctx, slot_id), rq, rq.plan_from >= 0 ? &slot(ctx, (unsigned)rq.plan_from) : nullptr);
-}
-
-}  // anonymous namespace
-
-#if VSP_MSM_GROUP == 1
-int msm_g1_precompute(vsp_ctx *ctx, G1Affine *table, size_t n, unsigned c) { return msm_precompute<Fp>(ctx, table, n, c); }
-int msm_g1_table28(vsp_ctx *ctx, const G1Affine *table, size_t count, void *d_out, bool glv) {
+template <class G> int msm_table28(vsp_ctx *ctx, const typename G::Point *table, size_t count, void *d_out, bool glv) {
     if (!count) return VSP_OK;
 #if defined(VSP_PORTABLE_MUL)
     return VSP_ERR_UNSUPPORTED;                              // the diagnostic build without hand-laid-out routines: generic kernels (no 28-bit table, no split)
 #endif
-    hipLaunchKernelGGL(k_table28, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, table, count, (Affine28 *)d_out, glv);
+    hipLaunchKernelGGL(k_table28, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, table, count, (Row28 *)d_out, glv);
     VSP_LAUNCH_CHECK();
     return VSP_OK;
 }
-int msm_g1_launch(vsp_ctx *ctx, unsigned slot_id, const MsmRequest &rq) { return launch_slot<Fp>(ctx, slot_id, rq); }
-int msm_g1_finish(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp> *out, unsigned count) { return msm_finish<Fp, HFp>(ctx, slot(ctx, slot_id), out, count); }
-int msm_g1_finish_wait(vsp_ctx *ctx, unsigned slot_id, unsigned count, bool *empty) { return msm_finish_wait<Fp, HFp>(ctx, slot(ctx, slot_id), count, empty); }
-void msm_g1_fold(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp> *out) { msm_fold<Fp, HFp>(slot(ctx, slot_id), out); }
+template <class G> int msm_slot_launch(vsp_ctx *ctx, unsigned slot_id, const MsmRequest &rq) { return launch_slot<typename G::F>(ctx, slot_id, rq); }
+template <class G> int msm_slot_finish(vsp_ctx *ctx, unsigned slot_id, XYZZ<typename G::HF> *out, unsigned count) {
+    return msm_finish<typename G::F, typename G::HF>(ctx, slot(ctx, slot_id), out, count);
+}
+template <class G> int msm_slot_finish_wait(vsp_ctx *ctx, unsigned slot_id, unsigned count, bool *empty) {
+    return msm_finish_wait<typename G::F, typename G::HF>(ctx, slot(ctx, slot_id), count, empty);
+}
+template <class G> void msm_slot_fold(vsp_ctx *ctx, unsigned slot_id, XYZZ<typename G::HF> *out) { msm_fold<typename G::F, typename G::HF>(slot(ctx, slot_id), out); }
+template <class G> int subgroup_check(vsp_ctx *ctx, const typename G::Point *d_mont, size_t n, uint32_t *d_flag) {
+    using F = typename G::F;
+    if (!n) return VSP_OK;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_subgroup_check<F>), dim3((unsigned)((LaneView<F>::LANES * n + MSM_THREADS - 1) / MSM_THREADS)), dim3(MSM_THREADS), 0, ctx->stream,
+                       d_mont, n, d_flag);
+    VSP_LAUNCH_CHECK();
+    return VSP_OK;
+}
+template <class G> int bases_to_mont(vsp_ctx *ctx, const void *d_canon, typename G::Point *d_out, size_t n, int check_curve, uint32_t *d_flag) {
+    using F = typename G::F;
+    if (!n) return VSP_OK;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bases_to_mont<F>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const Affine<F> *)d_canon, d_out, n, check_curve, d_flag);
+    VSP_LAUNCH_CHECK();
+    return VSP_OK;
+}
+
+// the group-independent entry points: compiled once, with G1
+#if VSP_MSM_GROUP == 1
 // the census kernel runs on the CONTEXT's stream (so it cannot be held up behind low-priority work); the slot picks it up
 // A stream for a work slot: the LOWEST priority -- work on the context's stream (the NTTs of witness_map, whose result gates the H
 // multi-exponentiation) gets compute units first.  (Option "msm_slot_normal_priority" = 1: the context's own priority instead -- the
@@ -2527,47 +2549,6 @@ int msm_diag_clock(vsp_ctx *ctx, int reset, double *ghz, double *waves) {
     (void)reset; if (ghz) *ghz = 0.0; if (waves) *waves = 0.0;
     return set_error(ctx, VSP_ERR_UNSUPPORTED, "diag_clock: this is not the diagnostic build (make diag -> libvsp_hip_diag.so)");
 #endif
-}
-int subgroup_check_g1(vsp_ctx *ctx, const G1Affine *d_mont, size_t n, uint32_t *d_flag) {
-    if (!n) return VSP_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_subgroup_check<Fp>), dim3((unsigned)((n + MSM_THREADS - 1) / MSM_THREADS)), dim3(MSM_THREADS), 0, ctx->stream, d_mont, n, d_flag);
-    VSP_LAUNCH_CHECK();
-    return VSP_OK;
-}
-int bases_to_mont_g1(vsp_ctx *ctx, const void *d_canon, G1Affine *d_out, size_t n, int check_curve, uint32_t *d_flag) {
-    if (!n) return VSP_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bases_to_mont<Fp>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const G1Affine *)d_canon, d_out, n, check_curve, d_flag);
-    VSP_LAUNCH_CHECK();
-    return VSP_OK;
-}
-#else
-int msm_g2_precompute(vsp_ctx *ctx, G2Affine *table, size_t n, unsigned c) { return msm_precompute<Fp2>(ctx, table, n, c); }
-int msm_g2_table28(vsp_ctx *ctx, const G2Affine *table, size_t count, void *d_out, bool glv) {
-    if (!count) return VSP_OK;
-#if defined(VSP_PORTABLE_MUL)
-    return VSP_ERR_UNSUPPORTED;                              // the diagnostic build without hand-laid-out routines: generic kernels (no 28-bit table, no split)
-#endif
-    hipLaunchKernelGGL(k_table28, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, table, count, (Affine28x2 *)d_out, glv);
-    VSP_LAUNCH_CHECK();
-    return VSP_OK;
-}
-int msm_g2_launch(vsp_ctx *ctx, unsigned slot_id, const MsmRequest &rq) { return launch_slot<Fp2>(ctx, slot_id, rq); }
-int msm_g2_finish(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp2> *out, unsigned count) { return msm_finish<Fp2, HFp2>(ctx, slot(ctx, slot_id), out, count); }
-int msm_g2_finish_wait(vsp_ctx *ctx, unsigned slot_id, unsigned count, bool *empty) { return msm_finish_wait<Fp2, HFp2>(ctx, slot(ctx, slot_id), count, empty); }
-void msm_g2_fold(vsp_ctx *ctx, unsigned slot_id, XYZZ<HFp2> *out) { msm_fold<Fp2, HFp2>(slot(ctx, slot_id), out); }
-int subgroup_check_g2(vsp_ctx *ctx, const G2Affine *d_mont, size_t n, uint32_t *d_flag) {
-    if (!n) return VSP_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_subgroup_check<Fp2>), dim3((unsigned)((2 * n + MSM_THREADS - 1) / MSM_THREADS)), dim3(MSM_THREADS), 0, ctx->stream, d_mont, n, d_flag);
-    VSP_LAUNCH_CHECK();
-    return VSP_OK;
-}
-int bases_to_mont_g2(vsp_ctx *ctx, const void *d_canon, G2Affine *d_out, size_t n, int check_curve, uint32_t *d_flag) {
-    if (!n) return VSP_OK;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bases_to_mont<Fp2>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const G2Affine *)d_canon, d_out, n, check_curve, d_flag);
-    VSP_LAUNCH_CHECK();
-    return VSP_OK;
 }
 #endif
 

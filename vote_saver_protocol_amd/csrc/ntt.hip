@@ -355,9 +355,7 @@ HFr host_omega(unsigned log_m) {
     for (unsigned i = log_m; i < 32; i++) w = sqr(w);
     return w;
 }
-static HFr host_from_u64(uint64_t v) { uint64_t c[4] = {v, 0, 0, 0}; return host_load_canon<HFr>(c); }
 
-static Fr to_dev(const HFr &h) { Fr d; memcpy(&d, &h, sizeof(Fr)); return d; }
 
 // lo[k] = base^k (k < 2^PW_LOG), hi[k] = base^(k << PW_LOG) (k < hi_count), Montgomery form
 int upload_power_tables(vsp_ctx *ctx, const HFr &base, size_t hi_count, DevBuf &lo, DevBuf &hi) {

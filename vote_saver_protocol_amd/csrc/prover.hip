@@ -30,11 +30,6 @@ __global__ __launch_bounds__(256) void k_fr_to_mont(Fr *a, size_t n) {
     if (i < n) a[i] = to_mont(a[i]);
 }
 
-// canonical Fr check on the host (4 x uint64 little-endian limbs below r)
-static bool fr_canonical(const uint64_t *k) {
-    for (int i = 3; i >= 0; i--) { if (k[i] < FrP64::MOD[i]) return true; if (k[i] > FrP64::MOD[i]) return false; }
-    return false;
-}
 
 }  // namespace vsp
 
@@ -67,7 +62,7 @@ vsp_r1cs *vsp_r1cs_upload(vsp_ctx *ctx, size_t num_constraints, size_t num_input
     for (int m = 0; m < 3; m++) {
         size_t nnz = rp[m][num_constraints];
         for (size_t e = 0; e < nnz; e++) if (ci[m][e] > num_vars) { set_error(ctx, VSP_ERR_ARG, "r1cs_upload: column out of range"); vsp_r1cs_free(ctx, cs); return nullptr; }
-        for (size_t e = 0; e < nnz; e++) if (!fr_canonical(co[m] + 4 * e)) { set_error(ctx, VSP_ERR_ARG, "r1cs_upload: a coefficient is not canonical (>= r)"); vsp_r1cs_free(ctx, cs); return nullptr; }
+        for (size_t e = 0; e < nnz; e++) if (!below_mod<FrP64>(co[m] + 4 * e)) { set_error(ctx, VSP_ERR_ARG, "r1cs_upload: a coefficient is not canonical (>= r)"); vsp_r1cs_free(ctx, cs); return nullptr; }
         bool ok = hipMalloc((void **)&cs->rp[m], (num_constraints + 1) * 4) == hipSuccess &&
                   hipMalloc((void **)&cs->ci[m], (nnz ? nnz : 1) * 4) == hipSuccess &&
                   hipMalloc(&cs->co[m], (nnz ? nnz : 1) * sizeof(Fr)) == hipSuccess;
@@ -124,8 +119,8 @@ vsp_pk *vsp_pk_create(vsp_ctx *ctx, const uint64_t alpha_g1[12], const uint64_t 
         set_error(ctx, VSP_ERR_ARG, "pk_create: bad argument"); return nullptr;
     }
     vsp_pk *pk = new vsp_pk();
-    pk->alpha_g1 = host_load_g1(alpha_g1); pk->beta_g1 = host_load_g1(beta_g1); pk->delta_g1 = host_load_g1(delta_g1);
-    pk->beta_g2 = host_load_g2(beta_g2); pk->delta_g2 = host_load_g2(delta_g2);
+    pk->alpha_g1 = host_load_affine<HFp>(alpha_g1); pk->beta_g1 = host_load_affine<HFp>(beta_g1); pk->delta_g1 = host_load_affine<HFp>(delta_g1);
+    pk->beta_g2 = host_load_affine<HFp2>(beta_g2); pk->delta_g2 = host_load_affine<HFp2>(delta_g2);
     pk->A = A_query; pk->B1 = B_query_g1; pk->B2 = B_query_g2; pk->H = H_query; pk->L = L_query;
     return pk;
 }
@@ -176,7 +171,7 @@ static XYZZ<HFp> proof_c(XYZZ<HFp> eH, const XYZZ<HFp> &eL, const XYZZ<HFp> &s_g
 // proof k into the outputs (any may be null): A, B, C as canonical affine words, and the 192 compressed bytes
 static void store_proof(size_t k, const XYZZ<HFp> &gA, const XYZZ<HFp2> &gB2, const XYZZ<HFp> &gC, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out) {
     uint64_t A12[12], B24[24], C12[12];
-    host_store_g1(A12, xyzz_to_affine(gA)); host_store_g2(B24, xyzz_to_affine(gB2)); host_store_g1(C12, xyzz_to_affine(gC));
+    host_store_affine(A12, xyzz_to_affine(gA)); host_store_affine(B24, xyzz_to_affine(gB2)); host_store_affine(C12, xyzz_to_affine(gC));
     if (A_out) memcpy(A_out + 12 * k, A12, sizeof A12);
     if (B_out) memcpy(B_out + 24 * k, B24, sizeof B24);
     if (C_out) memcpy(C_out + 12 * k, C12, sizeof C12);
@@ -192,7 +187,7 @@ static int prove_begin(vsp_ctx *ctx, bool batch, bool args_present, const vsp_r1
     if (!args_present) return set_error(ctx, VSP_ERR_ARG, batch ? "prove_batch: null argument or a batch outside 1..64" : "prove: null argument");
     if (ctx->prove.active) return set_error(ctx, VSP_ERR_ARG, "prove: a proof is already in flight on this context (finish it first)");
     for (size_t k = 0; k < K; k++)
-        if (!fr_canonical(r + 4 * k) || !fr_canonical(s + 4 * k) || (saver_r_enc && !fr_canonical(saver_r_enc)))
+        if (!below_mod<FrP64>(r + 4 * k) || !below_mod<FrP64>(s + 4 * k) || (saver_r_enc && !below_mod<FrP64>(saver_r_enc)))
             return set_error(ctx, VSP_ERR_ARG, batch ? "prove: r and s must be canonical (< r)" : "prove: r, s and r_enc must be canonical (< r)");
     const size_t nv = cs->num_vars;
     if (pk->A->n != nv + 1 || pk->B1->n != nv + 1 || pk->B2->n != nv + 1 || pk->H->n + 1 != cs->dom.m || pk->L->n != nv - cs->num_inputs)
@@ -453,7 +448,7 @@ static int prove_finish_impl(vsp_ctx *ctx, uint64_t A_out[12], uint64_t B_out[24
         else if (j == 1) r_delta = delta.g1(r);
         else if (j == 2) s_delta = delta.g1(s);
         else if (j == 3) neg_rs_delta = xyzz_neg(delta.g1(rs4));
-        else if (ctx->prove.has_saver) saver = xyzz_mul_scalar_w4(xyzz_from_affine(host_load_g1(ctx->prove.P1)), ctx->prove.r_enc);
+        else if (ctx->prove.has_saver) saver = xyzz_mul_scalar_w4(xyzz_from_affine(host_load_affine<HFp>(ctx->prove.P1)), ctx->prove.r_enc);
     }, T);
     if (overlap && *overlap) (*overlap)();
     lap("prove_host_overlap_ms");
@@ -467,15 +462,15 @@ static int prove_finish_impl(vsp_ctx *ctx, uint64_t A_out[12], uint64_t B_out[24
     std::vector<std::thread> workers;
     auto run = [&](std::function<void()> f) { if (T > 1) workers.emplace_back(std::move(f)); else f(); };
     int rc = VSP_OK; bool empty = false;
-    if ((rc = msm_g1_finish_wait(ctx, 1, 1, &empty)) == VSP_OK)
-        run([&, e = empty]() { if (!e) msm_g1_fold(ctx, 1, &eA); gA = proof_a(pk, eA, r_delta); s_gA = xyzz_mul_scalar_w4(gA, s); });
-    if (rc == VSP_OK && (rc = msm_g1_finish_wait(ctx, 2, 1, &empty)) == VSP_OK)
-        run([&, e = empty]() { if (!e) msm_g1_fold(ctx, 2, &eB1); r_gB1 = xyzz_mul_scalar_w4(proof_b1(pk, eB1, s_delta), r); });
-    if (rc == VSP_OK && (rc = msm_g1_finish_wait(ctx, 4, 1, &empty)) == VSP_OK)
-        run([&, e = empty]() { if (!e) msm_g1_fold(ctx, 4, &eL); });
-    if (rc == VSP_OK && (rc = msm_g2_finish_wait(ctx, 3, 1, &empty)) == VSP_OK)
-        run([&, e = empty]() { if (!e) msm_g2_fold(ctx, 3, &eB2); gB2 = proof_b2(pk, eB2, s_delta2); });
-    if (rc == VSP_OK && (rc = msm_g1_finish_wait(ctx, 0, 1, &empty)) == VSP_OK && !empty) msm_g1_fold(ctx, 0, &eH);
+    if ((rc = msm_slot_finish_wait<G1>(ctx, 1, 1, &empty)) == VSP_OK)
+        run([&, e = empty]() { if (!e) msm_slot_fold<G1>(ctx, 1, &eA); gA = proof_a(pk, eA, r_delta); s_gA = xyzz_mul_scalar_w4(gA, s); });
+    if (rc == VSP_OK && (rc = msm_slot_finish_wait<G1>(ctx, 2, 1, &empty)) == VSP_OK)
+        run([&, e = empty]() { if (!e) msm_slot_fold<G1>(ctx, 2, &eB1); r_gB1 = xyzz_mul_scalar_w4(proof_b1(pk, eB1, s_delta), r); });
+    if (rc == VSP_OK && (rc = msm_slot_finish_wait<G1>(ctx, 4, 1, &empty)) == VSP_OK)
+        run([&, e = empty]() { if (!e) msm_slot_fold<G1>(ctx, 4, &eL); });
+    if (rc == VSP_OK && (rc = msm_slot_finish_wait<G2>(ctx, 3, 1, &empty)) == VSP_OK)
+        run([&, e = empty]() { if (!e) msm_slot_fold<G2>(ctx, 3, &eB2); gB2 = proof_b2(pk, eB2, s_delta2); });
+    if (rc == VSP_OK && (rc = msm_slot_finish_wait<G1>(ctx, 0, 1, &empty)) == VSP_OK && !empty) msm_slot_fold<G1>(ctx, 0, &eH);
     for (auto &w : workers) w.join();
     if (rc != VSP_OK) return rc;
     lap("prove_wait_ms");
@@ -552,10 +547,10 @@ static int prove_batch_finish_impl(vsp_ctx *ctx, uint64_t *A_out, uint64_t *B_ou
     lap("prove_batch_delta_ms");
     std::vector<XYZZ<HFp>> eA(K), eB1(K), eH(K), eL(K);
     std::vector<XYZZ<HFp2>> eB2(K);
-    VSP_TRY(msm_g1_finish(ctx, 1, eA.data(), (unsigned)K));
-    VSP_TRY(msm_g1_finish(ctx, 2, eB1.data(), (unsigned)K));
-    VSP_TRY(msm_g1_finish(ctx, 4, eL.data(), (unsigned)K));
-    VSP_TRY(msm_g2_finish(ctx, 3, eB2.data(), (unsigned)K));
+    VSP_TRY(msm_slot_finish<G1>(ctx, 1, eA.data(), (unsigned)K));
+    VSP_TRY(msm_slot_finish<G1>(ctx, 2, eB1.data(), (unsigned)K));
+    VSP_TRY(msm_slot_finish<G1>(ctx, 4, eL.data(), (unsigned)K));
+    VSP_TRY(msm_slot_finish<G2>(ctx, 3, eB2.data(), (unsigned)K));
     lap("prove_batch_witness_finishes_ms");
     // s * A and r * B1 of every proof inside the wait for the H chain, as prove_finish_impl does them
     std::vector<XYZZ<HFp>> gA(K), s_gA(K), r_gB1(K);
@@ -565,7 +560,7 @@ static int prove_batch_finish_impl(vsp_ctx *ctx, uint64_t *A_out, uint64_t *B_ou
         r_gB1[k] = xyzz_mul_scalar_w4(proof_b1(pk, eB1[k], s_delta[k]), r + 4 * k);
     });
     lap("prove_batch_sA_rB1_ms");
-    VSP_TRY(msm_g1_finish(ctx, 0, eH.data(), (unsigned)K));
+    VSP_TRY(msm_slot_finish<G1>(ctx, 0, eH.data(), (unsigned)K));
     lap("prove_batch_h_finish_ms");
     host_parallel_for(K, [&](size_t k) {
         store_proof(k, gA[k], proof_b2(pk, eB2[k], s_delta2[k]), proof_c(eH[k], eL[k], s_gA[k], r_gB1[k], neg_rs_delta[k], XYZZ<HFp>::inf()),

@@ -57,32 +57,10 @@ struct FixedBase {
     }
 };
 
-static bool fr_canon(const uint64_t *k) {
-    for (int i = 3; i >= 0; i--) { if (k[i] < FrP64::MOD[i]) return true; if (k[i] > FrP64::MOD[i]) return false; }
-    return false;
-}
 static int bit_length(const uint64_t k[4]) {
     for (int i = 3; i >= 0; i--) if (k[i]) return 64 * i + 64 - __builtin_clzll(k[i]);
     return 0;
 }
-// canonical coordinates below p and the point on the curve (or infinity)
-static bool g1_valid(const uint64_t *p) {
-    auto below_p = [](const uint64_t *l) { for (int i = 5; i >= 0; i--) { if (l[i] < FpP64::MOD[i]) return true; if (l[i] > FpP64::MOD[i]) return false; } return false; };
-    if (!below_p(p) || !below_p(p + 6)) return false;
-    Affine<HFp> a = host_load_g1(p);
-    if (is_inf(a)) return true;
-    HFp four = dbl(dbl(HFp::one()));
-    return eq(sqr(a.y), add(mul(sqr(a.x), a.x), four));
-}
-static bool g2_valid(const uint64_t *p) {                      // coordinates below p, on y^2 = x^3 + 4 (1 + u) (all zero = infinity)
-    auto below_p = [](const uint64_t *l) { for (int i = 5; i >= 0; i--) { if (l[i] < FpP64::MOD[i]) return true; if (l[i] > FpP64::MOD[i]) return false; } return false; };
-    for (int k = 0; k < 4; k++) if (!below_p(p + 6 * k)) return false;
-    Affine<HFp2> a = host_load_g2(p);
-    if (is_inf(a)) return true;
-    HFp2 b; b.c0 = dbl(dbl(HFp::one())); b.c1 = b.c0;
-    return eq(sqr(a.y), add(mul(sqr(a.x), a.x), b));
-}
-
 }  // namespace vsp
 
 using namespace vsp;
@@ -117,32 +95,27 @@ int vsp_saver_keygen(vsp_ctx *ctx, size_t n, const uint64_t delta_g1[12], const 
                      const uint64_t *rnd, uint64_t *pk_out, uint64_t sk_out[4], uint64_t *vk_out) {
     // host only: ctx may be NULL (then there is no error text, only the status)
     if (!n || !delta_g1 || !gamma_g1 || !gamma_abc_g1 || !rnd || !pk_out || !sk_out || !vk_out) return set_error(ctx, VSP_ERR_ARG, "saver_keygen: null argument");
-    for (size_t i = 0; i < 3 * n + 2; i++) if (!fr_canon(rnd + 4 * i)) return set_error(ctx, VSP_ERR_ARG, "saver_keygen: a random value is not canonical (>= r)");
-    if (!g1_valid(delta_g1) || !g1_valid(gamma_g1)) return set_error(ctx, VSP_ERR_ARG, "saver_keygen: delta_g1 / gamma_g1 is not a curve point");
-    for (size_t i = 0; i <= n; i++) if (!g1_valid(gamma_abc_g1 + 12 * i)) return set_error(ctx, VSP_ERR_ARG, "saver_keygen: gamma_ABC_g1 entry is not a curve point");
+    for (size_t i = 0; i < 3 * n + 2; i++) if (!below_mod<FrP64>(rnd + 4 * i)) return set_error(ctx, VSP_ERR_ARG, "saver_keygen: a random value is not canonical (>= r)");
+    if (!affine_valid<G1>(delta_g1) || !affine_valid<G1>(gamma_g1)) return set_error(ctx, VSP_ERR_ARG, "saver_keygen: delta_g1 / gamma_g1 is not a curve point");
+    for (size_t i = 0; i <= n; i++) if (!affine_valid<G1>(gamma_abc_g1 + 12 * i)) return set_error(ctx, VSP_ERR_ARG, "saver_keygen: gamma_ABC_g1 entry is not a curve point");
     const uint64_t *s = rnd, *v = rnd + 4 * n, *t = rnd + 8 * n, *rho = rnd + 4 * (3 * n + 1);
     uint64_t *p_delta_s = pk_out + 12, *p_t_g1 = p_delta_s + 12 * n, *p_t_g2 = p_t_g1 + 12 * n, *p_dsum = p_t_g2 + 24 * (n + 1), *p_ginv = p_dsum + 12;
     memcpy(pk_out, delta_g1, 96);
-    FixedBase fd, fg; fd.build(host_load_g1(delta_g1)); fg.build(host_load_g1(gamma_g1));
-    // generator of G2 (public constant)
-    static const uint64_t G2_GEN[24] = {0xd48056c8c121bdb8ULL, 0x0bac0326a805bbefULL, 0xb4510b647ae3d177ULL, 0xc6e47ad4fa403b02ULL, 0x260805272dc51051ULL, 0x024aa2b2f08f0a91ULL,
-                                        0xe5ac7d055d042b7eULL, 0x334cf11213945d57ULL, 0xb5da61bbdc7f5049ULL, 0x596bd0d09920b61aULL, 0x7dacd3a088274f65ULL, 0x13e02b6052719f60ULL,
-                                        0xe193548608b82801ULL, 0x923ac9cc3baca289ULL, 0x6d429a695160d12cULL, 0xadfd9baa8cbdd3a7ULL, 0x8cc9cdc6da2e351aULL, 0x0ce5d527727d6e11ULL,
-                                        0xaaa9075ff05f79beULL, 0x3f370d275cec1da1ULL, 0x267492ab572e99abULL, 0xcb3e287e85a763afULL, 0x32acd2b02bc28b99ULL, 0x0606c4a02ea734ccULL};
-    XYZZ<HFp2> h = xyzz_from_affine(host_load_g2(G2_GEN));
-    auto g2mul = [&](const HFr &k, uint64_t *out) { uint64_t c[4]; host_store_canon(c, k); host_store_g2(out, xyzz_to_affine(xyzz_mul_scalar(h, c, 255))); };
+    FixedBase fd, fg; fd.build(host_load_affine<HFp>(delta_g1)); fg.build(host_load_affine<HFp>(gamma_g1));
+    XYZZ<HFp2> h = xyzz_from_affine(host_load_affine<HFp2>(G2::GEN));          // the generator of G2
+    auto g2mul = [&](const HFr &k, uint64_t *out) { uint64_t c[4]; host_store_canon(c, k); host_store_affine(out, xyzz_to_affine(xyzz_mul_scalar(h, c, 255))); };
     HFr sum_s = HFr::one(), sum_ts = host_load_canon<HFr>(t);
     for (size_t i = 0; i < n; i++) {
-        host_store_g1(p_delta_s + 12 * i, xyzz_to_affine(fd.mul_scalar(s + 4 * i)));
-        host_store_g1(p_t_g1 + 12 * i, xyzz_to_affine(xyzz_mul_scalar(xyzz_from_affine(host_load_g1(gamma_abc_g1 + 12 * (i + 1))), t + 4 * (i + 1), 255)));
+        host_store_affine(p_delta_s + 12 * i, xyzz_to_affine(fd.mul_scalar(s + 4 * i)));
+        host_store_affine(p_t_g1 + 12 * i, xyzz_to_affine(xyzz_mul_scalar(xyzz_from_affine(host_load_affine<HFp>(gamma_abc_g1 + 12 * (i + 1))), t + 4 * (i + 1), 255)));
         HFr si = host_load_canon<HFr>(s + 4 * i);
         sum_s = add(sum_s, si);
         sum_ts = add(sum_ts, mul(host_load_canon<HFr>(t + 4 * (i + 1)), si));
     }
     for (size_t j = 0; j <= n; j++) g2mul(host_load_canon<HFr>(t + 4 * j), p_t_g2 + 24 * j);
     uint64_t c4[4];
-    host_store_canon(c4, sum_ts); host_store_g1(p_dsum, xyzz_to_affine(fd.mul_scalar(c4)));
-    host_store_canon(c4, neg(sum_s)); host_store_g1(p_ginv, xyzz_to_affine(fg.mul_scalar(c4)));
+    host_store_canon(c4, sum_ts); host_store_affine(p_dsum, xyzz_to_affine(fd.mul_scalar(c4)));
+    host_store_canon(c4, neg(sum_s)); host_store_affine(p_ginv, xyzz_to_affine(fg.mul_scalar(c4)));
     memcpy(sk_out, rho, 32);
     HFr r_ = host_load_canon<HFr>(rho);
     g2mul(r_, vk_out);
@@ -157,20 +130,20 @@ int vsp_saver_keygen(vsp_ctx *ctx, size_t n, const uint64_t delta_g1[12], const 
 vsp_saver_pk *vsp_saver_pk_load(vsp_ctx *ctx, size_t n, const uint64_t *pk_in, const uint64_t *gamma_abc_g1) {
     if (!n || !pk_in || !gamma_abc_g1) { set_error(ctx, VSP_ERR_ARG, "saver_pk_load: null argument"); return nullptr; }
     const uint64_t *p_delta_s = pk_in + 12, *p_t_g1 = p_delta_s + 12 * n, *p_dsum = p_t_g1 + 12 * n + 24 * (n + 1), *p_ginv = p_dsum + 12;
-    for (size_t i = 0; i < 2 * n + 1; i++) if (!g1_valid(pk_in + 12 * i)) { set_error(ctx, VSP_ERR_ARG, "saver_pk_load: a G1 element of the key is not a curve point"); return nullptr; }
-    if (!g1_valid(p_dsum) || !g1_valid(p_ginv)) { set_error(ctx, VSP_ERR_ARG, "saver_pk_load: a G1 element of the key is not a curve point"); return nullptr; }
-    for (size_t i = 0; i <= n; i++) if (!g1_valid(gamma_abc_g1 + 12 * i)) { set_error(ctx, VSP_ERR_ARG, "saver_pk_load: gamma_ABC_g1 entry is not a curve point"); return nullptr; }
+    for (size_t i = 0; i < 2 * n + 1; i++) if (!affine_valid<G1>(pk_in + 12 * i)) { set_error(ctx, VSP_ERR_ARG, "saver_pk_load: a G1 element of the key is not a curve point"); return nullptr; }
+    if (!affine_valid<G1>(p_dsum) || !affine_valid<G1>(p_ginv)) { set_error(ctx, VSP_ERR_ARG, "saver_pk_load: a G1 element of the key is not a curve point"); return nullptr; }
+    for (size_t i = 0; i <= n; i++) if (!affine_valid<G1>(gamma_abc_g1 + 12 * i)) { set_error(ctx, VSP_ERR_ARG, "saver_pk_load: gamma_ABC_g1 entry is not a curve point"); return nullptr; }
     vsp_saver_pk *k = new vsp_saver_pk();
     k->n = n;
     k->words.assign(pk_in, pk_in + pk_words(n));
     k->gabc.assign(gamma_abc_g1, gamma_abc_g1 + 12 * (n + 1));
     k->X.resize(n + 2);
-    k->X[0].build(host_load_g1(pk_in));
-    for (size_t i = 0; i < n; i++) k->X[i + 1].build(host_load_g1(p_delta_s + 12 * i));
-    k->X[n + 1].build(host_load_g1(p_dsum));
-    k->P2.build(host_load_g1(p_ginv));
+    k->X[0].build(host_load_affine<HFp>(pk_in));
+    for (size_t i = 0; i < n; i++) k->X[i + 1].build(host_load_affine<HFp>(p_delta_s + 12 * i));
+    k->X[n + 1].build(host_load_affine<HFp>(p_dsum));
+    k->P2.build(host_load_affine<HFp>(p_ginv));
     k->G.resize(n); k->Y.resize(n);
-    for (size_t i = 0; i < n; i++) { k->G[i] = host_load_g1(gamma_abc_g1 + 12 * (i + 1)); k->Y[i] = host_load_g1(p_t_g1 + 12 * i); }
+    for (size_t i = 0; i < n; i++) { k->G[i] = host_load_affine<HFp>(gamma_abc_g1 + 12 * (i + 1)); k->Y[i] = host_load_affine<HFp>(p_t_g1 + 12 * i); }
     return k;
 }
 void vsp_saver_pk_free(vsp_ctx *, vsp_saver_pk *k) { delete k; }
@@ -183,23 +156,23 @@ int vsp_saver_encrypt(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1cs *cs,
     if (!spk || !cs || !pk || !msg || !witness || !r_enc || !r || !s || !ct_out) return set_error(ctx, VSP_ERR_ARG, "saver_encrypt: null argument");
     const size_t n = spk->n;
     if (cs->num_inputs < n) return set_error(ctx, VSP_ERR_ARG, "saver_encrypt: the constraint system has fewer public inputs than message blocks");
-    if (!fr_canon(r_enc)) return set_error(ctx, VSP_ERR_ARG, "saver_encrypt: r_enc must be canonical (< r)");
+    if (!below_mod<FrP64>(r_enc)) return set_error(ctx, VSP_ERR_ARG, "saver_encrypt: r_enc must be canonical (< r)");
     for (size_t i = 0; i < n; i++) {
-        if (!fr_canon(msg + 4 * i)) return set_error(ctx, VSP_ERR_ARG, "saver_encrypt: a message block is not canonical (>= r)");
+        if (!below_mod<FrP64>(msg + 4 * i)) return set_error(ctx, VSP_ERR_ARG, "saver_encrypt: a message block is not canonical (>= r)");
         // the message IS the first msg_size public inputs (common.hpp:1110-1135: m_block is allocated first)
         if (memcmp(msg + 4 * i, witness + 4 * i, 32) != 0) return set_error(ctx, VSP_ERR_ARG, "saver_encrypt: message differs from the first public inputs of the witness");
     }
     // ciphertext: c_0 = r X_0 | c_i = r X_i + m_i G_i | psi = r P_1 + sum m_i Y_i -- computed while the GPU proves
     std::function<void()> overlap = [&]() {
         XYZZ<HFp> psi = spk->X[n + 1].mul_scalar(r_enc);
-        host_store_g1(ct_out, xyzz_to_affine(spk->X[0].mul_scalar(r_enc)));
+        host_store_affine(ct_out, xyzz_to_affine(spk->X[0].mul_scalar(r_enc)));
         for (size_t i = 0; i < n; i++) {
             XYZZ<HFp> c = spk->X[i + 1].mul_scalar(r_enc);
             add_msg_term(c, spk->G[i], msg + 4 * i);
-            host_store_g1(ct_out + 12 * (i + 1), xyzz_to_affine(c));
+            host_store_affine(ct_out + 12 * (i + 1), xyzz_to_affine(c));
             add_msg_term(psi, spk->Y[i], msg + 4 * i);
         }
-        host_store_g1(ct_out + 12 * (n + 1), xyzz_to_affine(psi));
+        host_store_affine(ct_out + 12 * (n + 1), xyzz_to_affine(psi));
     };
     const uint64_t *p_ginv = spk->words.data() + 12 + 12 * n + 12 * n + 24 * (n + 1) + 12;
     return prove_with_overlap(ctx, cs, pk, witness, r, s, p_ginv, r_enc, A_out, B_out, C_out, proof_out, &overlap);
@@ -211,26 +184,26 @@ int vsp_saver_rerandomize(vsp_ctx *ctx, const vsp_saver_pk *spk, const uint64_t 
     if (!spk || !delta_g2 || !rnd || !ct || !A || !B || !C) return set_error(ctx, VSP_ERR_ARG, "saver_rerandomize: null argument");
     const size_t n = spk->n;
     const uint64_t *rp = rnd, *z1 = rnd + 4, *z2 = rnd + 8;
-    if (!fr_canon(rp) || !fr_canon(z1) || !fr_canon(z2)) return set_error(ctx, VSP_ERR_ARG, "saver_rerandomize: random values must be canonical (< r)");
+    if (!below_mod<FrP64>(rp) || !below_mod<FrP64>(z1) || !below_mod<FrP64>(z2)) return set_error(ctx, VSP_ERR_ARG, "saver_rerandomize: random values must be canonical (< r)");
     HFr a = host_load_canon<HFr>(z1), b = host_load_canon<HFr>(z2);
     if (is_zero(a)) return set_error(ctx, VSP_ERR_ARG, "saver_rerandomize: z1 must be invertible");
-    for (size_t i = 0; i < n + 2; i++) if (!g1_valid(ct + 12 * i)) return set_error(ctx, VSP_ERR_ARG, "saver_rerandomize: a ciphertext element is not a curve point");
-    if (!g1_valid(A) || !g1_valid(C) || !g2_valid(B)) return set_error(ctx, VSP_ERR_ARG, "saver_rerandomize: a proof element is not a curve point");
-    if (!g2_valid(delta_g2)) return set_error(ctx, VSP_ERR_ARG, "saver_rerandomize: delta_g2 is not a curve point");
+    for (size_t i = 0; i < n + 2; i++) if (!affine_valid<G1>(ct + 12 * i)) return set_error(ctx, VSP_ERR_ARG, "saver_rerandomize: a ciphertext element is not a curve point");
+    if (!affine_valid<G1>(A) || !affine_valid<G1>(C) || !affine_valid<G2>(B)) return set_error(ctx, VSP_ERR_ARG, "saver_rerandomize: a proof element is not a curve point");
+    if (!affine_valid<G2>(delta_g2)) return set_error(ctx, VSP_ERR_ARG, "saver_rerandomize: delta_g2 is not a curve point");
     uint64_t zi4[4], zz4[4];
     host_store_canon(zi4, inv(a)); host_store_canon(zz4, mul(a, b));
     // the four one-off scalar multiplications are independent: the two in G2 (the long ones) run beside the G1 work
-    Affine<HFp2> b_in = host_load_g2(B), d2 = host_load_g2(delta_g2);
+    Affine<HFp2> b_in = host_load_affine<HFp2>(B), d2 = host_load_affine<HFp2>(delta_g2);
     auto fB = std::async(std::launch::async, [&]() { return xyzz_mul_scalar(xyzz_from_affine(b_in), zi4, 255); });
     auto fD = std::async(std::launch::async, [&]() { return xyzz_mul_scalar(xyzz_from_affine(d2), z2, 255); });
-    Affine<HFp> a_in = host_load_g1(A);
+    Affine<HFp> a_in = host_load_affine<HFp>(A);
     auto fA = std::async(std::launch::async, [&]() { return xyzz_mul_scalar(xyzz_from_affine(a_in), z1, 255); });
     // ct_i += r' X_i: n + 2 fixed-base multiplications (64 mixed additions each), the upper half on another thread; all the G1
     // results of the call (n + 2 ciphertext elements, A, C) share ONE field inversion (prefix products of ZZZ) -- a Fermat
     // inversion per element was a third of the call
     std::vector<XYZZ<HFp>> pts(n + 4);
     auto ct_range = [&](size_t lo, size_t hi) {
-        for (size_t i = lo; i < hi; i++) { XYZZ<HFp> t = spk->X[i].mul_scalar(rp); xyzz_madd(t, host_load_g1(ct + 12 * i)); pts[i] = t; }
+        for (size_t i = lo; i < hi; i++) { XYZZ<HFp> t = spk->X[i].mul_scalar(rp); xyzz_madd(t, host_load_affine<HFp>(ct + 12 * i)); pts[i] = t; }
     };
     const size_t mid = (n + 2) / 2;
     auto fC = std::async(std::launch::async, [&]() { ct_range(mid, n + 2); });
@@ -238,7 +211,7 @@ int vsp_saver_rerandomize(vsp_ctx *ctx, const vsp_saver_pk *spk, const uint64_t 
     ct_range(0, mid);
     XYZZ<HFp> nC = spk->P2.mul_scalar(rp);
     xyzz_add(nC, zzA);
-    xyzz_madd(nC, host_load_g1(C));
+    xyzz_madd(nC, host_load_affine<HFp>(C));
     fC.get();
     pts[n + 2] = fA.get(); pts[n + 3] = nC;
     {
@@ -254,11 +227,11 @@ int vsp_saver_rerandomize(vsp_ctx *ctx, const vsp_saver_pk *spk, const uint64_t 
                 HFp zi = mul(zi3, pts[i].ZZ), zi2 = sqr(zi);
                 q.x = mul(pts[i].X, zi2); q.y = mul(pts[i].Y, zi3);
             }
-            host_store_g1(i < n + 2 ? ct + 12 * i : (i == n + 2 ? A : C), q);
+            host_store_affine(i < n + 2 ? ct + 12 * i : (i == n + 2 ? A : C), q);
         }
     }
     XYZZ<HFp2> nB = fB.get(); { XYZZ<HFp2> w = fD.get(); xyzz_add(nB, w); }
-    host_store_g2(B, xyzz_to_affine(nB));
+    host_store_affine(B, xyzz_to_affine(nB));
     if (proof_out) { vsp_g1_compress(A, proof_out); vsp_g2_compress(B, proof_out + 48); vsp_g1_compress(C, proof_out + 144); }
     return VSP_OK;
 }

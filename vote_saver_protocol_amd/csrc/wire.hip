@@ -19,6 +19,8 @@
 //               (vsp_r1cs_upload), because circuit construction is out of scope.
 // The proving-key loader is the part with a cost: the reference parses ~0.6 GB per vote at 2^20 constraints.  vsp_pk_from_blob copies the
 // raw bytes to the GPU once and converts there (byte order, infinity flags, curve check, Montgomery form, the 28-bit-limb table).
+// The ZCash point compression every compressed element goes through (vsp_g1/g2_compress, vsp_g1/g2_decompress) is here too, written
+// once for both groups.
 #include "common.h"
 
 namespace vsp {
@@ -63,15 +65,96 @@ __global__ __launch_bounds__(256) void k_g2_from_be(const uint8_t *src, size_t s
 
 static void put_be64(uint8_t *o, uint64_t v) { for (int i = 0; i < 8; i++) o[i] = (uint8_t)(v >> (56 - 8 * i)); }
 static uint64_t get_be64(const uint8_t *p) { uint64_t v = 0; for (int i = 0; i < 8; i++) v = (v << 8) | p[i]; return v; }
-static void be_from_limbs(uint8_t *o, const uint64_t *l, int nl) { for (int i = 0; i < nl; i++) for (int b = 0; b < 8; b++) o[nl * 8 - 1 - (i * 8 + b)] = (uint8_t)(l[i] >> (8 * b)); }
-static void limbs_from_be(uint64_t *l, const uint8_t *p, int nl) { for (int i = 0; i < nl; i++) { uint64_t v = 0; for (int b = 0; b < 8; b++) v |= (uint64_t)p[nl * 8 - 1 - (i * 8 + b)] << (8 * b); l[i] = v; } }
-static bool all_zero(const uint64_t *l, int n) { uint64_t o = 0; for (int i = 0; i < n; i++) o |= l[i]; return o == 0; }
-static void g1_uncompressed(uint8_t *o, const uint64_t *p) { if (all_zero(p, 12)) { memset(o, 0, 96); o[0] = 0x40; return; } be_from_limbs(o, p, 6); be_from_limbs(o + 48, p + 6, 6); }
-static void g2_uncompressed(uint8_t *o, const uint64_t *p) {
-    if (all_zero(p, 24)) { memset(o, 0, 192); o[0] = 0x40; return; }
-    be_from_limbs(o, p + 6, 6); be_from_limbs(o + 48, p, 6); be_from_limbs(o + 96, p + 18, 6); be_from_limbs(o + 144, p + 12, 6);
+// one coordinate of group G (G::AFFINE_WORDS / 2 canonical words; G2: c0 | c1) <-> its big-endian bytes, the highest coefficient first (G2: c1 | c0)
+template <class G> static void coord_to_be(uint8_t *o, const uint64_t *l) {
+    constexpr int m = (int)G::AFFINE_WORDS / 12;
+    for (int c = 0; c < m; c++) be_from_limbs(o + 48 * c, l + 6 * (m - 1 - c), 6);
 }
-static bool fr_below_r(const uint64_t *k) { for (int i = 3; i >= 0; i--) { if (k[i] < FrP64::MOD[i]) return true; if (k[i] > FrP64::MOD[i]) return false; } return false; }
+template <class G> static void coord_from_be(uint64_t *l, const uint8_t *o) {
+    constexpr int m = (int)G::AFFINE_WORDS / 12;
+    for (int c = 0; c < m; c++) limbs_from_be(l + 6 * (m - 1 - c), o + 48 * c, 6);
+}
+// ZCash uncompressed record: x | y big-endian, infinity = the flag 0x40 and nothing else
+template <class G> static void uncompressed(uint8_t *o, const uint64_t *p) {
+    constexpr size_t half = G::AFFINE_WORDS / 2;
+    if (limbs_zero(p, (int)G::AFFINE_WORDS)) { memset(o, 0, 16 * half); o[0] = 0x40; return; }
+    coord_to_be<G>(o, p); coord_to_be<G>(o + 8 * half, p + half);
+}
+
+// ---- ZCash compressed encoding (the wire format of reference bin/cli/src/data.bin[0:192)): x big-endian with three flag bits in its
+// first byte -- 0x80 compressed, 0x40 infinity (every other bit clear), 0x20 y is the larger of y and -y
+static const uint64_t HALF_P[6] = {0xdcff7fffffffd555ULL, 0x0f55ffff58a9ffffULL, 0xb39869507b587b12ULL, 0xb23ba5c279c2895fULL, 0x258dd3db21a5d66bULL, 0x0d0088f51cbff34dULL};
+static bool fp_lex_larger(const uint64_t *y) {      // y > (p-1)/2
+    for (int i = 5; i >= 0; i--) { if (y[i] > HALF_P[i]) return true; if (y[i] < HALF_P[i]) return false; }
+    return false;
+}
+// y larger than -y: its highest non-zero coefficient (G1: y itself) above (p - 1) / 2
+template <class G> static bool y_larger(const uint64_t *y) {
+    int c = (int)G::AFFINE_WORDS / 12 - 1;
+    while (c > 0 && limbs_zero(y + 6 * c, 6)) c--;
+    return fp_lex_larger(y + 6 * c);
+}
+// VSP_ERR_ARG for a null pointer or a coordinate that is not canonical (>= p: its top bits would collide with the flag bits)
+template <class G> static int compress(const uint64_t *affine, uint8_t *out) {
+    constexpr size_t half = G::AFFINE_WORDS / 2;
+    if (!affine || !out) return VSP_ERR_ARG;
+    if (limbs_zero(affine, (int)G::AFFINE_WORDS)) { memset(out, 0, 8 * half); out[0] = 0xC0; return VSP_OK; }
+    if (!coords_below_p(affine, G::AFFINE_WORDS)) return VSP_ERR_ARG;
+    coord_to_be<G>(out, affine);
+    out[0] |= 0x80;
+    if (y_larger<G>(affine + half)) out[0] |= 0x20;
+    return VSP_OK;
+}
+
+// ---- decompression (the inverse of the above): x from the big-endian bytes, y = sqrt(x^3 + b) with the sign the flag names ----
+// a^((p+1)/4) -- the square root when a is a quadratic residue (p = 3 mod 4); returns false when it is not
+static bool fp_sqrt(const HFp &a, HFp &out) {
+    uint64_t e[6]; uint64_t carry = 1;                         // e = (p + 1) / 4
+    for (int i = 0; i < 6; i++) { uint64_t v = FpP64::MOD[i] + carry; carry = (v < carry) ? 1 : 0; e[i] = v; }
+    for (int i = 0; i < 6; i++) e[i] = (e[i] >> 2) | (i < 5 ? e[i + 1] << 62 : 0);
+    out = pow_limbs(a, e, 6);
+    return eq(sqr(out), a);
+}
+// square root in Fp2 = Fp[u]/(u^2+1) by the norm: returns false when a is not a square
+static bool fp_sqrt(const HFp2 &a, HFp2 &out) {
+    if (is_zero(a.c1)) {
+        HFp r;
+        if (fp_sqrt(a.c0, r)) { out.c0 = r; out.c1 = HFp::zero(); return true; }
+        if (fp_sqrt(neg(a.c0), r)) { out.c0 = HFp::zero(); out.c1 = r; return true; }   // (r u)^2 = -r^2
+        return false;
+    }
+    HFp s;
+    if (!fp_sqrt(add(sqr(a.c0), sqr(a.c1)), s)) return false;
+    uint64_t two4[6] = {2, 0, 0, 0, 0, 0};
+    HFp half = inv(host_load_canon<HFp>(two4));
+    HFp t = mul(add(a.c0, s), half), x0;
+    if (!fp_sqrt(t, x0)) { t = mul(sub(a.c0, s), half); if (!fp_sqrt(t, x0)) return false; }
+    out.c0 = x0; out.c1 = mul(mul(a.c1, half), inv(x0));
+    return eq(sqr(out), a);
+}
+template <class G> static int decompress(const uint8_t *in, int check_subgroup, uint64_t *out_affine, int *out_is_inf) {
+    using HF = typename G::HF;
+    constexpr size_t half = G::AFFINE_WORDS / 2, bytes = 8 * half;
+    if (!in || !out_affine) return VSP_ERR_ARG;
+    if (!(in[0] & 0x80)) return VSP_ERR_ARG;                       // uncompressed form is not accepted
+    uint8_t buf[bytes]; memcpy(buf, in, bytes); buf[0] &= 0x1f;
+    if (in[0] & 0x40) {                                            // infinity: every other bit must be clear
+        for (size_t i = 0; i < bytes; i++) if (buf[i]) return VSP_ERR_ARG;
+        if (in[0] & 0x20) return VSP_ERR_ARG;
+        memset(out_affine, 0, 2 * bytes); if (out_is_inf) *out_is_inf = 1; return VSP_OK;
+    }
+    uint64_t xy[G::AFFINE_WORDS];                                  // canonical x | y
+    coord_from_be<G>(xy, buf);
+    if (!coords_below_p(xy, half)) return VSP_ERR_ARG;
+    Affine<HF> p; p.x = host_load_canon<HF>(xy);
+    if (!fp_sqrt(add(mul(sqr(p.x), p.x), curve_b<HF>()), p.y)) return VSP_ERR_ARG;      // not on the curve
+    host_store_canon(xy + half, p.y);
+    if (y_larger<G>(xy + half) != ((in[0] & 0x20) != 0)) { p.y = neg(p.y); host_store_canon(xy + half, p.y); }
+    if (check_subgroup && !is_inf(xyzz_mul_scalar(xyzz_from_affine(p), FrP64::MOD, 255))) return VSP_ERR_ARG;
+    memcpy(out_affine, xy, 2 * bytes);
+    if (out_is_inf) *out_is_inf = 0;
+    return VSP_OK;
+}
 
 }  // namespace vsp
 
@@ -79,11 +162,16 @@ using namespace vsp;
 
 extern "C" {
 
+int vsp_g1_compress(const uint64_t affine[12], uint8_t out[48]) { return compress<G1>(affine, out); }
+int vsp_g2_compress(const uint64_t affine[24], uint8_t out[96]) { return compress<G2>(affine, out); }
+int vsp_g1_decompress(const uint8_t in[48], int check_subgroup, uint64_t out_affine[12], int *out_is_inf) { return decompress<G1>(in, check_subgroup, out_affine, out_is_inf); }
+int vsp_g2_decompress(const uint8_t in[96], int check_subgroup, uint64_t out_affine[24], int *out_is_inf) { return decompress<G2>(in, check_subgroup, out_affine, out_is_inf); }
+
 // ---- scalar vectors (primary input, eid / sn / rt, voting result): common.hpp:476-485, 529-535 --------------------------------------
 size_t vsp_fr_vector_blob_size(size_t count) { return 8 + 32 * count; }
 int vsp_fr_vector_to_blob(const uint64_t *vals, size_t count, uint8_t *out) {
     if ((!vals && count) || !out) return VSP_ERR_ARG;
-    for (size_t i = 0; i < count; i++) if (!fr_below_r(vals + 4 * i)) return VSP_ERR_ARG;
+    for (size_t i = 0; i < count; i++) if (!below_mod<FrP64>(vals + 4 * i)) return VSP_ERR_ARG;
     put_be64(out, count);
     for (size_t i = 0; i < count; i++) be_from_limbs(out + 8 + 32 * i, vals + 4 * i, 4);
     return VSP_OK;
@@ -95,7 +183,7 @@ int vsp_fr_vector_from_blob(const uint8_t *blob, size_t len, uint64_t *vals_out,
     *count_out = (size_t)n;
     if (!vals_out) return VSP_OK;                                  // size query
     if (capacity < n) return VSP_ERR_ARG;
-    for (size_t i = 0; i < n; i++) { limbs_from_be(vals_out + 4 * i, blob + 8 + 32 * i, 4); if (!fr_below_r(vals_out + 4 * i)) return VSP_ERR_ARG; }
+    for (size_t i = 0; i < n; i++) { limbs_from_be(vals_out + 4 * i, blob + 8 + 32 * i, 4); if (!below_mod<FrP64>(vals_out + 4 * i)) return VSP_ERR_ARG; }
     return VSP_OK;
 }
 
@@ -182,8 +270,8 @@ int vsp_pk_to_blob(vsp_ctx *ctx, const vsp_keypair *kp, uint8_t *out) {
     if (!kp || !out) return set_error(ctx, VSP_ERR_ARG, "pk_to_blob: null argument");
     if (kp->q[1]->n != kp->q[2]->n) return set_error(ctx, VSP_ERR_ARG, "pk_to_blob: B_query halves differ in length");
     uint8_t *p = out;
-    g1_uncompressed(p, kp->alpha_g1); g1_uncompressed(p + 96, kp->beta_g1); g2_uncompressed(p + 192, kp->beta_g2);
-    g1_uncompressed(p + 384, kp->delta_g1); g2_uncompressed(p + 480, kp->delta_g2);
+    uncompressed<G1>(p, kp->alpha_g1); uncompressed<G1>(p + 96, kp->beta_g1); uncompressed<G2>(p + 192, kp->beta_g2);
+    uncompressed<G1>(p + 384, kp->delta_g1); uncompressed<G2>(p + 480, kp->delta_g2);
     p += PK_FIXED;
     std::vector<uint64_t> a, b;
     auto g1_section = [&](int which) -> int {
@@ -191,7 +279,7 @@ int vsp_pk_to_blob(vsp_ctx *ctx, const vsp_keypair *kp, uint8_t *out) {
         a.resize(12 * (n ? n : 1));
         VSP_TRY(vsp_keypair_export(ctx, kp, which, a.data()));
         put_be64(p, n); p += 8;
-        for (size_t i = 0; i < n; i++) g1_uncompressed(p + 96 * i, a.data() + 12 * i);
+        for (size_t i = 0; i < n; i++) uncompressed<G1>(p + 96 * i, a.data() + 12 * i);
         p += 96 * n;
         return VSP_OK;
     };
@@ -201,7 +289,7 @@ int vsp_pk_to_blob(vsp_ctx *ctx, const vsp_keypair *kp, uint8_t *out) {
         a.resize(12 * (n ? n : 1)); b.resize(24 * (n ? n : 1));
         VSP_TRY(vsp_keypair_export(ctx, kp, 1, a.data())); VSP_TRY(vsp_keypair_export(ctx, kp, 2, b.data()));
         put_be64(p, n); p += 8;
-        for (size_t i = 0; i < n; i++) { g2_uncompressed(p + 288 * i, b.data() + 24 * i); g1_uncompressed(p + 288 * i + 192, a.data() + 12 * i); }
+        for (size_t i = 0; i < n; i++) { uncompressed<G2>(p + 288 * i, b.data() + 24 * i); uncompressed<G1>(p + 288 * i + 192, a.data() + 12 * i); }
         p += 288 * n;
     }
     VSP_TRY(g1_section(3));
@@ -251,8 +339,7 @@ vsp_keypair *vsp_pk_from_blob(vsp_ctx *ctx, const uint8_t *blob, size_t len, int
             // curve check, Montgomery form, 28-bit table; wire bytes are caller data: the endomorphism layout only after the subgroup check
             // (a query that gets window multiples below never uses that layout: BASES_TRANSIENT skips the layout and its check)
             const bool pre_this = ((precompute & 1) && pt.q != 3) || ((precompute >> (pt.q + 1)) & 1);
-            kp->q[pt.q] = bases_create(ctx, pt.group, d_pts, true, n, pre_this ? BASES_TRANSIENT : BASES_CALLER);
-            ok = kp->q[pt.q] != nullptr;
+            ok = bases_create(ctx, pt.group, d_pts, true, n, pre_this ? BASES_TRANSIENT : BASES_CALLER, &kp->q[pt.q]) == VSP_OK;
         }
     }
     hipStreamSynchronize(st);
@@ -264,13 +351,15 @@ vsp_keypair *vsp_pk_from_blob(vsp_ctx *ctx, const uint8_t *blob, size_t len, int
     }
     if (ok) {
         // the five single elements on the host (uncompressed records; infinity is not a valid key element)
-        auto g1 = [&](const uint8_t *p, uint64_t *o) { if (p[0] & 0xC0) return false; uint8_t t[96]; memcpy(t, p, 96); limbs_from_be(o, t, 6); limbs_from_be(o + 6, t + 48, 6); return true; };
-        auto g2 = [&](const uint8_t *p, uint64_t *o) { if (p[0] & 0xC0) return false; limbs_from_be(o + 6, p, 6); limbs_from_be(o, p + 48, 6); limbs_from_be(o + 18, p + 96, 6); limbs_from_be(o + 12, p + 144, 6); return true; };
-        ok = g1(blob, kp->alpha_g1) && g1(blob + 96, kp->beta_g1) && g2(blob + 192, kp->beta_g2) && g1(blob + 384, kp->delta_g1) && g2(blob + 480, kp->delta_g2);
-        // validate them through the compression round trip (on the curve <=> decompress(compress(p)) == p)
-        auto on_curve1 = [&](const uint64_t *p) { uint8_t c[48]; uint64_t q[12]; int inf; return vsp_g1_compress(p, c) == VSP_OK && vsp_g1_decompress(c, 0, q, &inf) == VSP_OK && !memcmp(p, q, 96); };
-        auto on_curve2 = [&](const uint64_t *p) { uint8_t c[96]; uint64_t q[24]; int inf; return vsp_g2_compress(p, c) == VSP_OK && vsp_g2_decompress(c, 0, q, &inf) == VSP_OK && !memcmp(p, q, 192); };
-        ok = ok && on_curve1(kp->alpha_g1) && on_curve1(kp->beta_g1) && on_curve2(kp->beta_g2) && on_curve1(kp->delta_g1) && on_curve2(kp->delta_g2);
+        // (each validated: coordinates below p, on the curve)
+        auto load = [&](auto g, const uint8_t *p, uint64_t *o) {
+            using G = decltype(g);
+            if (p[0] & 0xC0) return false;
+            coord_from_be<G>(o, p); coord_from_be<G>(o + G::AFFINE_WORDS / 2, p + 4 * G::AFFINE_WORDS);
+            return affine_valid<G>(o);
+        };
+        ok = load(G1{}, blob, kp->alpha_g1) && load(G1{}, blob + 96, kp->beta_g1) && load(G2{}, blob + 192, kp->beta_g2) && load(G1{}, blob + 384, kp->delta_g1) &&
+             load(G2{}, blob + 480, kp->delta_g2);
         if (!ok) set_error(ctx, VSP_ERR_ARG, "pk_from_blob: a fixed key element is not a curve point in uncompressed form");
     }
     if (ok) {
