@@ -185,6 +185,34 @@ class R1CS:
             out.append((rp, ci[:nnz], co[:nnz]))
         return out
 
+    def resample_witness(self, seed, ballot=None, zero=False):
+        """Another satisfying assignment of this synthetic system (ref_r1cs_synth_ballot), computed in Python big integers from export():
+        fresh public inputs (ballot = (msg_size, vote): the first msg_size one-hot at vote), a fresh bit on every boolean row (A, B and C
+        name the same column) and, row by row, z_k = z_a * z_b on every product row.  zero=True: zero inputs and zero bits, so every wire
+        is zero -- A z is 1 at row nc only, B z = C z = 0 and H = 0.  -> uint64 [num_vars, 4]."""
+        import random
+        from bls12_381 import R
+        (_, ca, _), (_, cb, _), (_, cc, _) = self.export()
+        ni, nc = self.num_inputs, self.num_constraints
+        rng = random.Random(seed)
+        z = [1] + [0] * (ni + nc)
+        if not zero:
+            for k in range(1, ni + 1):
+                z[k] = rng.randrange(R)
+            if ballot:
+                msg_size, vote = ballot
+                for k in range(1, min(msg_size, ni) + 1):
+                    z[k] = int(k - 1 == vote)
+        for j in range(nc):
+            a, b, k = int(ca[j]), int(cb[j]), int(cc[j])
+            assert k == ni + 1 + j, "not a synthetic system: row j does not define variable ni + 1 + j"
+            if a == b == k:
+                z[k] = 0 if zero else rng.getrandbits(1)
+            else:
+                z[k] = z[a] * z[b] % R
+        v = np.array(z[1:], dtype=object)
+        return np.stack([((v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF).astype(np.uint64) for i in range(4)], axis=1)
+
     def is_satisfied(self, witness):
         return bool(lib().ref_r1cs_is_satisfied(self.h, _p(_u64(witness))))
 

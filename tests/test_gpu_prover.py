@@ -241,14 +241,13 @@ def test_prove_in_two_halves_and_from_a_packed_witness(cref):
 @pytest.mark.parametrize("nc,ni,K", [(10, 2, 3), (300, 5, 4), (2000, 30, 8), (5000, 3, 2)])
 def test_batch_of_proofs_is_byte_identical_to_single_proofs_and_the_oracle(ctx, cref, nc, ni, K):
     """vsp_groth16_prove_batch (round 4): K witnesses of one constraint system proved in one pass over a plain key -- every proof equals the
-    oracle's r1cs_gg_ppzksnark proof and vsp_groth16_prove's 192 bytes for the same (witness, r, s), under K different (r, s); over a key with
-    tables of window multiples too."""
+    oracle's r1cs_gg_ppzksnark proof and vsp_groth16_prove's 192 bytes for the same (witness, r, s), under K different witnesses and (r, s);
+    over a key with tables of window multiples too."""
     cs, wit0, kp, dcs, pk, q, r0, s0 = build(ctx, cref, nc, ni, seed=nc + K)
     gen = o.splitmix64(7 * nc + K)
     wits, rs, ss = [wit0], [r0], [s0]
     for k in range(1, K):
-        w = wit0.copy()                                         # the same witness under other randomness (different witnesses: the next test)
-        wits.append(w); rs.append(L(o.rand_fr(gen), 4)); ss.append(L(o.rand_fr(gen), 4))
+        wits.append(cs.resample_witness(1000 * nc + k)); rs.append(L(o.rand_fr(gen), 4)); ss.append(L(o.rand_fr(gen), 4))
     W = np.stack(wits); R = np.stack(rs); S = np.stack(ss)
     A, B, Cc, proofs = v.groth16_prove_batch(ctx, dcs, pk, W, R, S)
     for k in range(K):
@@ -307,10 +306,10 @@ def test_two_batches_in_flight_from_one_thread_over_two_contexts(ctx, cref):
     nc, ni, K = 900, 4, 3
     cs, wit0, kp, dcs, pk, q, r0, s0 = build(ctx, cref, nc, ni, seed=41)
     gen = o.splitmix64(4141)
-    def rand_batch():
-        return (np.ascontiguousarray(np.broadcast_to(wit0, (K,) + wit0.shape)), np.stack([L(o.rand_fr(gen), 4) for _ in range(K)]),
+    def rand_batch(b):
+        return (np.stack([cs.resample_witness(10 * b + k) for k in range(K)]), np.stack([L(o.rand_fr(gen), 4) for _ in range(K)]),
                 np.stack([L(o.rand_fr(gen), 4) for _ in range(K)]))
-    batches = [rand_batch() for _ in range(4)]
+    batches = [rand_batch(b) for b in range(4)]
     expect = [v.groth16_prove_batch(ctx, dcs, pk, *b)[3] for b in batches]
     with v.Context(0) as c1:
         with pytest.raises(v.VspError):
@@ -332,7 +331,7 @@ def test_two_batches_in_flight_from_one_thread_over_two_contexts(ctx, cref):
         got[2] = v.groth16_prove_batch_finish(ring[0])[3]
         got[3] = v.groth16_prove_batch_finish(ring[1])[3]
         assert got == expect
-        assert v.groth16_prove(c1, dcs, pk, wit0, batches[0][1][0], batches[0][2][0])[3] == expect[0][0]
+        assert v.groth16_prove(c1, dcs, pk, batches[0][0][0], batches[0][1][0], batches[0][2][0])[3] == expect[0][0]
     pk.free(); dcs.free(); [x.free() for x in q]; kp.free(); cs.free()
 
 
@@ -347,7 +346,7 @@ def test_contexts_that_proved_batches_return_their_device_memory(ctx, cref):
         return f.value
     nc, ni, K = 16000, 4, 16                                     # ~50 MB of batch buffers per context
     cs, wit0, kp, dcs, pk, q, r0, s0 = build(ctx, cref, nc, ni, seed=5)
-    W = np.ascontiguousarray(np.broadcast_to(wit0, (K,) + wit0.shape)); R = np.stack([r0] * K); S = np.stack([s0] * K)
+    W = np.stack([cs.resample_witness(k) for k in range(K)]); R = np.stack([r0] * K); S = np.stack([s0] * K)
     expect = v.groth16_prove_batch(ctx, dcs, pk, W, R, S)[3]
     seen = []
     for cycle in range(3):
@@ -368,9 +367,9 @@ def test_batch_prover_with_and_without_the_shared_digit_sort(ctx, cref):
     nc, ni, K = 3000, 5, 6
     cs, wit0, kp, dcs, pk, q, r0, s0 = build(ctx, cref, nc, ni, seed=23)
     gen = o.splitmix64(2323)
-    W = np.ascontiguousarray(np.broadcast_to(wit0, (K,) + wit0.shape))
+    W = np.stack([cs.resample_witness(k) for k in range(K)])
     R = np.stack([L(o.rand_fr(gen), 4) for _ in range(K)]); S = np.stack([L(o.rand_fr(gen), 4) for _ in range(K)])
-    singles = [v.groth16_prove(ctx, dcs, pk, wit0, R[k], S[k])[3] for k in range(K)]
+    singles = [v.groth16_prove(ctx, dcs, pk, W[k], R[k], S[k])[3] for k in range(K)]
     try:
         for share, dimbits in ((1, -1), (0, -1), (1, 0), (0, 0), (1, 1)):
             ctx.set_option("prove_batch_share_plan", share); ctx.set_option("msm_dimbits", dimbits)
@@ -390,16 +389,16 @@ def test_batch_over_a_generated_key_with_tables_on_all_five_queries(ctx, cref):
     tox = np.array([L(o.rand_fr(gen), 4) for _ in range(5)], dtype=np.uint64)
     dcs = v.R1CS(ctx, nc, ni, cs.num_vars, *cs.export())
     ref = cref.Keypair(cs, tox)
-    W = np.ascontiguousarray(np.broadcast_to(wit, (K,) + wit.shape))
+    W = np.stack([cs.resample_witness(k) for k in range(K)])
     R = np.stack([L(o.rand_fr(gen), 4) for _ in range(K)]); S = np.stack([L(o.rand_fr(gen), 4) for _ in range(K)])
     for window in (9, 14):
         kp = v.Keypair(ctx, dcs, tox, precompute=17, precompute_window=window)
         A, B, Cc, proofs = v.groth16_prove_batch(ctx, dcs, kp.pk, W, R, S)
         for k in range(K):
-            eA, eB, eC = ref.prove(wit, R[k], S[k])
+            eA, eB, eC = ref.prove(W[k], R[k], S[k])
             assert np.array_equal(A[k], eA) and np.array_equal(B[k], eB) and np.array_equal(Cc[k], eC), (window, k)
         v.groth16_prove_batch_launch(ctx, dcs, kp.pk, W, R, S)
         assert v.groth16_prove_batch_finish(ctx)[3] == proofs
-        assert v.groth16_prove(ctx, dcs, kp.pk, wit, R[0], S[0])[3] == proofs[0]
+        assert v.groth16_prove(ctx, dcs, kp.pk, W[0], R[0], S[0])[3] == proofs[0]
         kp.free()
     dcs.free(); ref.free(); cs.free()

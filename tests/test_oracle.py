@@ -182,3 +182,33 @@ def test_c_oracle_groth16_proof_verifies(cref, nc, ni):
     pub[1] = (pub[1] + 1) % o.R
     assert not pg.groth16_verify(vk, pub, proof)
     kp.free(); cs.free()
+
+
+@pytest.mark.parametrize("nc,ni,ballot", [(300, 5, None), (2000, 30, (25, 7)), (5000, 3, None)])
+def test_resampled_witnesses_of_one_system(cref, nc, ni, ballot):
+    """R1CS.resample_witness: fresh satisfying assignments of one synthetic system, as the batch prover's tests need them -- every one
+    satisfies the system, the same seed gives the same witness, different seeds give different witnesses and different H vectors
+    (witness_map), the ballot inputs are one-hot, and the zero member is all zero with H = 0 and A z = e_nc."""
+    cs, wit = cref.R1CS.synth(nc, ni, 9, ballot=ballot)
+    K = 6
+    wits = [cs.resample_witness(100 + k, ballot=None if ballot is None else (ballot[0], k)) for k in range(K)]
+    zero = cs.resample_witness(1, ballot=ballot, zero=True)
+    assert all(cs.is_satisfied(w) for w in wits + [zero])
+    assert np.array_equal(cs.resample_witness(100, ballot=None if ballot is None else (ballot[0], 0)), wits[0])
+    hs = [cs.witness_map(w) for w in wits + [wit]]
+    for a in range(K + 1):
+        for b in range(a):
+            assert not np.array_equal((wits + [wit])[a], (wits + [wit])[b]) and not np.array_equal(hs[a], hs[b]), (a, b)
+    assert all(h.any() for h in hs)
+    if ballot:
+        for k, w in enumerate(wits):
+            assert [I(w[i]) for i in range(ballot[0])] == [int(i == k) for i in range(ballot[0])]
+            assert all(I(w[i]) != 0 for i in range(ballot[0], ni))
+    # the boolean wires are bits, and both values occur
+    bits = [int(c) for c, a, b in zip(cs.export()[2][1], cs.export()[0][1], cs.export()[1][1]) if a == b == c]
+    assert {I(wits[0][k - 1]) for k in bits} == {0, 1}
+    assert not zero.any()
+    H, Az, Bz, Cz = cs.witness_map(zero, want_abc=True)
+    assert not H.any() and not Bz.any() and not Cz.any()
+    assert [k for k in range(cs.m) if Az[k].any()] == [nc] and I(Az[nc]) == 1
+    cs.free()

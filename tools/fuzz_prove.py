@@ -39,20 +39,21 @@ while time.time() - t0 < budget:
     ea, eb, ec = ref.prove(wit, r, s_, P1=P1, r_enc=renc)
     ok = ok and np.array_equal(pa, ea) and np.array_equal(pb, eb) and np.array_equal(pc, ec)
     if ok and rng.random() < 0.6:                             # the same statement(s) through the batch prover (plain and table keys; basic and step domains)
-        K = int(rng.integers(1, 7))
+        K = int(rng.integers(1, 65))                          # the API's 1..64 members, each with a witness of its own
+        W = np.stack([wit] + [cs.resample_witness(s + 10 + k, zero=rng.random() < 0.05) for k in range(1, K)])
         R = rand_fr_array(K, seed=s + 4); S = rand_fr_array(K, seed=s + 5)
         if rng.random() < 0.5:
-            bA, bB, bC, _ = v.groth16_prove_batch(ctx, dcs, kp.pk, np.stack([wit] * K), R, S)
+            bA, bB, bC, _ = v.groth16_prove_batch(ctx, dcs, kp.pk, W, R, S)
         else:                                                 # the two halves, a second batch in flight on a second context meanwhile
-            v.groth16_prove_batch_launch(ctx, dcs, kp.pk, np.stack([wit] * K), R, S)
-            v.groth16_prove_batch_launch(ctx2, dcs, kp.pk, np.stack([wit] * K), S, R)
+            v.groth16_prove_batch_launch(ctx, dcs, kp.pk, W, R, S)
+            v.groth16_prove_batch_launch(ctx2, dcs, kp.pk, W[::-1], S, R)
             bA, bB, bC, _ = v.groth16_prove_batch_finish(ctx)
             cA, cB, cC, _ = v.groth16_prove_batch_finish(ctx2)
-            xa, xb, xc = ref.prove(wit, S[K - 1], R[K - 1])
+            xa, xb, xc = ref.prove(W[0], S[K - 1], R[K - 1])
             ok = ok and np.array_equal(cA[K - 1], xa) and np.array_equal(cB[K - 1], xb) and np.array_equal(cC[K - 1], xc)
             kinds["two_halves"] = kinds.get("two_halves", 0) + 1
         for k in range(K):
-            xa, xb, xc = ref.prove(wit, R[k], S[k])
+            xa, xb, xc = ref.prove(W[k], R[k], S[k])
             ok = ok and np.array_equal(bA[k], xa) and np.array_equal(bB[k], xb) and np.array_equal(bC[k], xc)
         kinds["batched"] = kinds.get("batched", 0) + 1
         if pre: kinds["batched_table_key"] = kinds.get("batched_table_key", 0) + 1
