@@ -15,18 +15,23 @@ scalars/points, bit-exact vs multiexp), whole job, inputs resident in HBM, PLAIN
     ... bench.py --gpus N --scaling strong --total-log-n 26 --group g1    # BASELINE config 5: ONE 2^26-point problem, rank g holds chunk g
     ... bench.py --gpus N --scaling strong --total-log-n 24 --group g2
     ... bench.py ... --dump-outputs DIR                                   # also write the last timed step's result to DIR/<name>.npy
+    ... bench.py ... --full                                               # also run every check and secondary measurement below
 
-Without --scaling strong the per-GPU work is fixed (2^20 points per rank, "weak"); the default run additionally measures
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline line (`metric`, `value`, `unit`,
+`ms_per_step`, `config`, ...); it loads neither the oracle nor anything else the headline does not need.  Everything else runs after
+the timed steps with --full only (the --no-* options leave parts of it out):
+
+Without --scaling strong the per-GPU work is fixed (2^20 points per rank, "weak"); the full run additionally measures
 BASELINE config 5 (2^26 G1 + 2^24 G2 points split over the N ranks) -- `scaling_strong` at the top level of the line (and
 `extras.config5` in full) -- so the driver's N = 1, 2, 4, 8 lines carry the strong-scaling curve of that fixed problem next to the
 headline.  The sharded multi-exponentiation itself is the package's (vote_saver_protocol_amd/sharded.py); this file only generates the
 synthetic shards, times and verifies.
 
-Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel (bucket accumulation, k_accum28) with HIP events recorded on
-the launch stream, from a leg with ONE multi-exponentiation in flight (so nothing else shares the GPU with the kernel; the
-pipelined average is reported beside it); `cpu_baseline` times the oracle's serial BDLO12 (the reference algorithm, 1 thread like
-the reference build) on the same inputs, `cpu_baseline_all_cores` the same split in chunks over every host core (the `chunks`
-argument of multiexp) -- reported baselines only.  Nothing here reads /root/reference.
+Rank 0 prints ONE JSON line.  With --full, `verified_bit_exact` compares the result with the oracle's, `roofline` prices the dominant
+kernel (bucket accumulation, k_accum28) with HIP events recorded on the launch stream, from a leg with ONE multi-exponentiation in
+flight (so nothing else shares the GPU with the kernel; the pipelined average is reported beside it); `cpu_baseline` times the oracle's
+serial BDLO12 (the reference algorithm, 1 thread like the reference build) on the same inputs, `cpu_baseline_all_cores` the same split
+in chunks over every host core (the `chunks` argument of multiexp) -- reported baselines only.  Nothing here reads the reference project.
 """
 import argparse
 import glob
@@ -739,7 +744,7 @@ class ShardProblem:
     cheap -- and uniform 254-bit scalars, both generated on the device).  The multi-exponentiation over it is the package's
     vote_saver_protocol_amd.sharded.ShardedMsm."""
 
-    def __init__(self, ctx, v, torch, dev, group, total, world, rank, seed, sample=0):
+    def __init__(self, ctx, v, torch, dev, group, total, world, rank, seed, sample=0, check=True):
         self.ctx, self.v, self.group, self.total, self.world = ctx, v, group, total, world
         lo, hi = shard_bounds(total, world, rank)
         self.n = n = hi - lo
@@ -758,7 +763,7 @@ class ShardProblem:
             hb = np.zeros((m, 12 * group), np.uint64); ctx.d2h(hb, d_b)
             self.sample = (hb, self.d_s[:m].cpu().numpy().view(np.uint64).copy())
         ctx.dfree(d_b)
-        self.e_local = dot_mod_r_device(torch, k64, self.d_s)
+        self.e_local = dot_mod_r_device(torch, k64, self.d_s) if check else None      # the checker's sum: --full only
         del k64
 
     def free(self):
@@ -870,6 +875,10 @@ def main():
                     help="rehearsal on a box with fewer GPUs than ranks: rank g uses GPU g mod (GPUs present); forces --backend gloo (RCCL refuses two ranks on one GPU)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the result of the last one (the folded MSM point) to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else: the bit-exact check, the one-in-flight leg and roofline, the in-kernel "
+                         "clock, CPU baselines, the NTT / G2 / resident-key extras, the prover, config 5 and (N > 1) replica proving; the --no-* "
+                         "options and --force-replicas select among these.  Without it a run times the headline steps and prints that line only")
     args = ap.parse_args()
     if args.allow_shared_gpu:
         args.backend = "gloo"
@@ -968,7 +977,7 @@ def main():
         return sum(int(x) for x in to_ints(rows).tolist()) % R_MOD
 
     cref = o = gens = None
-    if rank == 0:
+    if rank == 0 and args.full:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import cref                                          # checker / CPU baseline only
         import bls12_381 as o
@@ -1080,26 +1089,30 @@ def main():
         lg_total = args.total_log_n or (26 if group == 1 else 24)
         total = 1 << lg_total
         prob = ShardProblem(ctx, v, torch, dev, group, total, world, rank, seed=77 + group,
-                            sample=0 if args.no_cpu_baseline else (1 << 20 if group == 1 else 1 << 17))
+                            sample=0 if (args.no_cpu_baseline or not args.full) else (1 << 20 if group == 1 else 1 << 17), check=args.full)
         ctx.stats_reset()
         elapsed, result = run_sharded(prob, args.steps, max(args.warmup, depth), exchange, barrier, depth)      # one warm-up per work slot: their multi-GB workspaces are allocated on first use
         if rank == 0 and args.dump_outputs:
             dump_outputs(args.dump_outputs, group, result)
         elapsed = allmax(elapsed)
-        pipe_ms = accum_stats()
         main_c, main_w, main_split = int(ctx.stat("msm_window_bits")), int(ctx.stat("msm_windows")), int(ctx.stat("msm_endomorphism_split"))
-        ctx.stats_reset()
-        ex_steps = max(2, args.steps // 4)
-        ex_elapsed, _ = run_sharded(prob, ex_steps, 1, exchange, barrier, 1)
-        ex_elapsed = allmax(ex_elapsed)
-        excl_ms = accum_stats()
-        e_tot = gather_e(prob.e_local)
-        if rank == 0:
-            verified = bool(np.array_equal(result, expected_point(group, e_tot)))
-            if prob.sample is not None:                      # every N: the CPU path timed on this box's host cores in the same run
-                cpu_baseline, cpu_all = cpu_baseline_legs(group, prob.sample[0], prob.sample[1])
-        barrier()
-        rl, rv = roofline_of(group, prob.n, main_w, excl_ms, ex_elapsed / ex_steps * 1e3, pipe_ms, main_split)
+        checks = {}
+        if args.full:
+            pipe_ms = accum_stats()
+            ctx.stats_reset()
+            ex_steps = max(2, args.steps // 4)
+            ex_elapsed, _ = run_sharded(prob, ex_steps, 1, exchange, barrier, 1)
+            ex_elapsed = allmax(ex_elapsed)
+            excl_ms = accum_stats()
+            e_tot = gather_e(prob.e_local)
+            if rank == 0:
+                verified = bool(np.array_equal(result, expected_point(group, e_tot)))
+                if prob.sample is not None:                      # every N: the CPU path timed on this box's host cores in the same run
+                    cpu_baseline, cpu_all = cpu_baseline_legs(group, prob.sample[0], prob.sample[1])
+            barrier()
+            rl, rv = roofline_of(group, prob.n, main_w, excl_ms, ex_elapsed / ex_steps * 1e3, pipe_ms, main_split)
+            checks = {"verified_bit_exact": verified, "latency_ms_one_in_flight": ex_elapsed / ex_steps * 1e3, "roofline": rl, "roofline_valu": rv,
+                      "cpu_baseline": cpu_baseline, "cpu_baseline_all_cores": cpu_all}
         out = {"metric": f"{args.group.upper()} MSM points/sec, one 2^{lg_total}-point problem sharded over the GPUs (BASELINE config 5)",
                "value": total * args.steps / elapsed, "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
@@ -1108,8 +1121,7 @@ def main():
                           "total_points": total, "points_per_gpu": prob.n, "window_bits": main_c, "windows": main_w, "msms_in_flight": depth,
                           "exchange_backend": exchange.backend, "ranks_seen_by_collective": ranks_seen, "gpus_visible": n_dev,
                           "runtime_env": {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES")}},
-               "verified_bit_exact": verified, "latency_ms_one_in_flight": ex_elapsed / ex_steps * 1e3, "roofline": rl, "roofline_valu": rv,
-               "cpu_baseline": cpu_baseline, "cpu_baseline_all_cores": cpu_all}
+               **checks}
         if rank == 0:
             os.write(real_stdout, (json.dumps(out) + "\n").encode())
         prob.free(); ctx.close()
@@ -1143,21 +1155,23 @@ def main():
     elapsed = allmax(elapsed)
     pipe_ms = accum_stats()
     main_c, main_w, main_split = int(ctx.stat("msm_window_bits")), int(ctx.stat("msm_windows")), int(ctx.stat("msm_endomorphism_split"))
-    # the same MSM with ONE in flight: latency of a single multi-exponentiation and the exclusive duration of its accumulation kernel
-    ctx.stats_reset()
-    ex_steps = max(4, args.steps // 2)
-    ex_elapsed, _ = run_sharded(head, ex_steps, 1, exchange, barrier, 1)
-    ex_elapsed = allmax(ex_elapsed)
-    excl_ms = accum_stats()
+    # everything below up to the JSON line runs with --full only (every rank sees the same flag, so the collectives still pair up)
+    if args.full:
+        # the same MSM with ONE in flight: latency of a single multi-exponentiation and the exclusive duration of its accumulation kernel
+        ctx.stats_reset()
+        ex_steps = max(4, args.steps // 2)
+        ex_elapsed, _ = run_sharded(head, ex_steps, 1, exchange, barrier, 1)
+        ex_elapsed = allmax(ex_elapsed)
+        excl_ms = accum_stats()
 
-    if rank == 0 and not args.no_diag_clock and not args.precompute:
+    if rank == 0 and args.full and not args.no_diag_clock and not args.precompute:
         try:
             clock_info = diag_clock_ghz(dev_index, d_bases_canon, n, d_s.data_ptr())
         except Exception as e:                               # a diagnostic: never take the bench line down
             print("bench.py: diagnostic clock leg failed: %r" % (e,), file=sys.stderr)
     # ---- untimed verification: sum over all ranks of (sum_i k_i s_i) * G must equal the folded result
-    e_tot = gather_e(int(sum((to_ints(ks) * to_ints(ss)).tolist()) % R_MOD))
-    if rank == 0:
+    e_tot = gather_e(int(sum((to_ints(ks) * to_ints(ss)).tolist()) % R_MOD)) if args.full else None
+    if rank == 0 and args.full:
         verified = bool(np.array_equal(result, expected_point(1, e_tot)))
 
         if not args.no_cpu_baseline:
@@ -1303,11 +1317,11 @@ def main():
     # =============================================================== proofs/s at N > 1: replica proving, every rank its own resident key
     # (N = 1: bench_prove above measures the same ring mode -- ONE host thread, three contexts, packed witness -- and much more)
     replicas = None
-    if (world > 1 or (args.force_replicas and use_dist)) and not args.no_prove:
+    if args.full and (world > 1 or (args.force_replicas and use_dist)) and not args.no_prove:
         replicas = replica_leg(args, v, torch, dist, coll_dev, rank, world, dev_index, barrier, allmax, cref, o)
 
     # =============================================================== BASELINE config 5 in the same run: 2^26 G1 + 2^24 G2 over the ranks
-    if not args.no_config5 and not (world == 1 and args.no_extras):
+    if args.full and not args.no_config5 and not (world == 1 and args.no_extras):
         c5 = {"scaling": "strong", "n_gpus": world, "msms_in_flight": depth}
         for group, lg in ((1, args.config5_log_g1), (2, args.config5_log_g2)):
             prob = ShardProblem(ctx, v, torch, dev, group, 1 << lg, world, rank, seed=55 + group)
@@ -1325,8 +1339,6 @@ def main():
         c5["exchange_backend"] = exchange.backend
         c5["ranks_seen_by_collective"] = ranks_seen
 
-    out_rl_inputs = (1, n, main_w, excl_ms, ex_elapsed / ex_steps * 1e3, pipe_ms, main_split)
-    rl, rv = roofline_of(*out_rl_inputs)
     out = {
         "metric": "G1 MSM points/sec at 2^20 (Groth16 prover hot path)",
         "value": n * world * args.steps / elapsed,
@@ -1350,15 +1362,13 @@ def main():
                    "bases_memory_bytes_per_point": (16 * (96 + 128)) if args.precompute else (96 + 2 * 128),
                    "precompute_once_s": precompute_s,
                    "runtime_env": {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES")}},
-        "verified_bit_exact": verified,
-        "latency_ms_one_in_flight": ex_elapsed / ex_steps * 1e3,
-        "roofline": rl,
-        "roofline_valu": rv,
-        "cpu_baseline": cpu_baseline,
-        "cpu_baseline_all_cores": cpu_all,
-        "exchange": {"backend": exchange.backend, "ranks_seen_by_collective": ranks_seen, "gpus_visible": n_dev,
-                     "records": "one Jacobian partial sum per rank and MSM (144 B G1 / 288 B G2), all-gathered, folded locally (vote_saver_protocol_amd/sharded.py)"},
     }
+    if args.full:
+        rl, rv = roofline_of(1, n, main_w, excl_ms, ex_elapsed / ex_steps * 1e3, pipe_ms, main_split)
+        out.update({"verified_bit_exact": verified, "latency_ms_one_in_flight": ex_elapsed / ex_steps * 1e3, "roofline": rl, "roofline_valu": rv,
+                    "cpu_baseline": cpu_baseline, "cpu_baseline_all_cores": cpu_all})
+    out["exchange"] = {"backend": exchange.backend, "ranks_seen_by_collective": ranks_seen, "gpus_visible": n_dev,
+                       "records": "one Jacobian partial sum per rank and MSM (144 B G1 / 288 B G2), all-gathered, folded locally (vote_saver_protocol_amd/sharded.py)"}
     if "config5" in extras:
         # BASELINE config 5 at the top level: ONE 2^26-point G1 and ONE 2^24-point G2 problem split over the N ranks of this run -- the driver's
         # N = 1, 2, 4, 8 lines give the strong-scaling curve (north_star: >= 6x at 8 GPUs) from these two figures

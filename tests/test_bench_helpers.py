@@ -96,6 +96,13 @@ def test_launcher_refuses_cleanly_without_gpus_and_never_imports_torch_first():
     assert r.returncode == 3 and r.stdout == "" and "nothing was launched" in r.stderr
 
 
+def test_full_is_an_option_of_its_own():
+    """`--full` (every check and secondary measurement after the timed steps) is accepted, and the help says what a run without it does"""
+    import subprocess, sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "Without it a run times the headline steps" in " ".join(r.stdout.split())
+
+
 def test_prove_ring_keeps_one_proof_in_flight_per_context_and_finishes_every_launch():
     """bench.prove_ring (the one-host-thread mode behind `secondary`): with a ring of C contexts, C - 1 proofs are in flight while one is
     awaited, every context holds at most one proof, launches and finishes alternate in ring order, and exactly total + C - 1 proofs run"""

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of the prefetching k_dimsum_mixed loop (option msm_dimsum_prefetch) on one box; why the portable build aborts
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
-for pf in 0 1 0 1; do VSP_OPTS=msm_dimsum_prefetch=$pf python bench.py --no-pipeline --no-extras --no-prove --no-cpu-baseline --no-config5 --no-diag-clock --steps 30 2>/dev/null | python -c "
+for pf in 0 1 0 1; do VSP_OPTS=msm_dimsum_prefetch=$pf python bench.py --full --no-pipeline --no-extras --no-prove --no-cpu-baseline --no-config5 --no-diag-clock --steps 30 2>/dev/null | python -c "
 import json,sys; j=json.loads(sys.stdin.read()); print('prefetch $pf: one in flight %.3f ms, accum %.3f' % (j['ms_per_step'], j['roofline']['avg_launch_ms']))"; done
 cd /tmp; export TMPDIR=/tmp
 for pf in 0 1; do VSP_OPTS=msm_dimsum_prefetch=$pf rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/r4k_pf$pf -o runc -- python3 $R/bench.py --no-pipeline --no-extras --no-prove --no-cpu-baseline --no-config5 --no-diag-clock --steps 30 > /dev/null 2>&1; grep "k_dimsum_mixed<vsp::Fp28" $R/gpurun_out/r4k_pf$pf/runc_kernel_stats.csv | cut -c1-60,150-260; done
