@@ -84,8 +84,9 @@ void vsp_stats_reset(vsp_ctx *ctx);
  * built on the host by the first proof over a key -- at most 32 additions per multiple; 0: double-and-add),
  * "prove_batch_share_plan" (default 1: in vsp_groth16_prove_batch the B1 and B2 multi-exponentiations take A's digit sort and bucket plan --
  * the three multiply by the same witness vectors; 0: each sorts for itself),
- * "witness_map_batched" (default 1: the three transforms of every step of witness_map in one launch per pass and the pointwise step inside
- * the last transform's first pass, basic domains on the 29-bit butterflies; 0: transform by transform), "msm_dimsum_lanes" (8/16/32/64 lanes per bucket-digit sum; 0 = chosen by the library),
+ * "witness_map_batched" (default 1: the three transforms of every step of witness_map -- 3 K in a batch of K proofs -- in one launch per
+ * pass and the pointwise step inside the last transform's first pass, basic domains on the 29-bit butterflies; 0: transform by transform,
+ * proof by proof), "msm_dimsum_lanes" (8/16/32/64 lanes per bucket-digit sum; 0 = chosen by the library),
  * "msm_dimsum_maxw" (256..4096, default 1024: waves the per-digit lane plan of the bucket reduction may fill; 2048 = two per SIMD),
  * "msm_dimsum_prefetch" (1: the bucket reduction requests the next bucket before the current addition; default 0, it spills), "msm_dimbits" (1 / 0: the last
  * step of the bucket reduction as plain subset sums folded by the host's doubling chain / as weighted sums on the GPU; default by group),

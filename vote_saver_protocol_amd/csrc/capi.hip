@@ -680,24 +680,42 @@ int vsp_msm_g2(vsp_ctx *ctx, const uint64_t *bases, const uint64_t *scalars, siz
 }
 
 // ---- NTT / witness_map ------------------------------------------------------------------------
+}  // extern "C"
+// the host-buffer form of a routine on the device: on the context's device, m canonical values in through its workspace pr_h (none when
+// `in` is null), run(pr_h), the m values there out to `out`, synchronised
+template <class Run> static int through_pr_h(vsp_ctx *ctx, const uint64_t *in, uint64_t *out, size_t m, Run &&run) {
+    VSP_HIP(hipSetDevice(ctx->device));
+    const size_t bytes = m * 32;
+    VSP_TRY(ensure(ctx, ctx->pr_h, bytes));
+    if (in) VSP_HIP(hipMemcpyAsync(ctx->pr_h.p, in, bytes, hipMemcpyHostToDevice, ctx->stream));
+    VSP_TRY(run((Fr *)ctx->pr_h.p));
+    VSP_HIP(hipMemcpyAsync(out, ctx->pr_h.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    VSP_HIP(hipStreamSynchronize(ctx->stream));
+    return VSP_OK;
+}
+// A z, B z, C z in through the prover's workspace of one witness (pr_abc), H out through pr_h
+static int witness_map_host(vsp_ctx *ctx, const vsp_domain *d, const uint64_t *Az, const uint64_t *Bz, const uint64_t *Cz, uint64_t *H) {
+    return through_pr_h(ctx, nullptr, H, d->m, [&](Fr *dH) {
+        const size_t m = d->m;
+        VSP_TRY(ensure(ctx, ctx->pr_abc, 3 * m * 32));
+        Fr *dA = (Fr *)ctx->pr_abc.p;
+        const uint64_t *src[3] = {Az, Bz, Cz};
+        for (int k = 0; k < 3; k++) VSP_HIP(hipMemcpyAsync(dA + k * m, src[k], m * 32, hipMemcpyHostToDevice, ctx->stream));
+        return witness_map_device(ctx, d, dA, dA + m, dA + 2 * m, 3 * m, 1, dH, m);
+    });
+}
+extern "C" {
 int vsp_ntt_fr_device(vsp_ctx *ctx, void *d_a, unsigned log_m, int inverse, const uint64_t coset_g[4]) {
     if (!ctx) return VSP_ERR_ARG;
     if (!d_a) return set_error(ctx, VSP_ERR_ARG, "ntt: null pointer");
     VSP_HIP(hipSetDevice(ctx->device));
-    return ntt_device(ctx, (Fr *)d_a, log_m, inverse, coset_g, nullptr);
+    return ntt_launch(ctx, NttRequest((Fr *)d_a, log_m, inverse, coset_g));
 }
 int vsp_ntt_fr(vsp_ctx *ctx, uint64_t *a, unsigned log_m, int inverse, const uint64_t coset_g[4]) {
     if (!ctx) return VSP_ERR_ARG;
     if (!a) return set_error(ctx, VSP_ERR_ARG, "ntt: null pointer");
     if (log_m > 28) return set_error(ctx, VSP_ERR_UNSUPPORTED, "ntt: log_m > 28");
-    VSP_HIP(hipSetDevice(ctx->device));
-    size_t bytes = ((size_t)1 << log_m) * 32;
-    VSP_TRY(ensure(ctx, ctx->pr_h, bytes));
-    VSP_HIP(hipMemcpyAsync(ctx->pr_h.p, a, bytes, hipMemcpyHostToDevice, ctx->stream));
-    VSP_TRY(ntt_device(ctx, (Fr *)ctx->pr_h.p, log_m, inverse, coset_g, nullptr));
-    VSP_HIP(hipMemcpyAsync(a, ctx->pr_h.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    VSP_HIP(hipStreamSynchronize(ctx->stream));
-    return VSP_OK;
+    return through_pr_h(ctx, a, a, (size_t)1 << log_m, [&](Fr *d_a) { return ntt_launch(ctx, NttRequest(d_a, log_m, inverse, coset_g)); });
 }
 int vsp_witness_map_h_device(vsp_ctx *ctx, void *d_Az, void *d_Bz, void *d_Cz, unsigned log_m, void *d_H) {
     if (!ctx) return VSP_ERR_ARG;
@@ -705,25 +723,12 @@ int vsp_witness_map_h_device(vsp_ctx *ctx, void *d_Az, void *d_Bz, void *d_Cz, u
     if (log_m > 28) return set_error(ctx, VSP_ERR_UNSUPPORTED, "witness_map: log_m > 28");
     VSP_HIP(hipSetDevice(ctx->device));
     vsp_domain d; domain_basic(&d, log_m);
-    return witness_map_device(ctx, (Fr *)d_Az, (Fr *)d_Bz, (Fr *)d_Cz, &d, (Fr *)d_H);
-}
-static int witness_map_host(vsp_ctx *ctx, const vsp_domain *d, uint64_t *Az, uint64_t *Bz, uint64_t *Cz, uint64_t *H) {
-    size_t bytes = d->m * 32;
-    VSP_TRY(ensure(ctx, ctx->pr_abc, 3 * bytes)); VSP_TRY(ensure(ctx, ctx->pr_h, bytes));
-    Fr *dA = (Fr *)ctx->pr_abc.p, *dB = dA + d->m, *dC = dA + 2 * d->m;      // the prover's workspace, one witness
-    VSP_HIP(hipMemcpyAsync(dA, Az, bytes, hipMemcpyHostToDevice, ctx->stream));
-    VSP_HIP(hipMemcpyAsync(dB, Bz, bytes, hipMemcpyHostToDevice, ctx->stream));
-    VSP_HIP(hipMemcpyAsync(dC, Cz, bytes, hipMemcpyHostToDevice, ctx->stream));
-    VSP_TRY(witness_map_device(ctx, dA, dB, dC, d, (Fr *)ctx->pr_h.p));
-    VSP_HIP(hipMemcpyAsync(H, ctx->pr_h.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    VSP_HIP(hipStreamSynchronize(ctx->stream));
-    return VSP_OK;
+    return witness_map_device(ctx, &d, (Fr *)d_Az, (Fr *)d_Bz, (Fr *)d_Cz, 0, 1, (Fr *)d_H, 0);
 }
 int vsp_witness_map_h(vsp_ctx *ctx, uint64_t *Az, uint64_t *Bz, uint64_t *Cz, unsigned log_m, uint64_t *H) {
     if (!ctx) return VSP_ERR_ARG;
     if (!Az || !Bz || !Cz || !H) return set_error(ctx, VSP_ERR_ARG, "witness_map: null pointer");
     if (log_m > 28) return set_error(ctx, VSP_ERR_UNSUPPORTED, "witness_map: log_m > 28");
-    VSP_HIP(hipSetDevice(ctx->device));
     vsp_domain d; domain_basic(&d, log_m);
     return witness_map_host(ctx, &d, Az, Bz, Cz, H);
 }
@@ -753,26 +758,15 @@ int vsp_domain_fft_device(vsp_ctx *ctx, const vsp_domain *d, void *d_a, int inve
 int vsp_domain_fft(vsp_ctx *ctx, const vsp_domain *d, uint64_t *a, int inverse, const uint64_t coset_g[4]) {
     if (!ctx) return VSP_ERR_ARG;
     if (!d || !a) return set_error(ctx, VSP_ERR_ARG, "domain_fft: null pointer");
-    VSP_HIP(hipSetDevice(ctx->device));
-    size_t bytes = d->m * 32;
-    VSP_TRY(ensure(ctx, ctx->pr_h, bytes));
-    VSP_HIP(hipMemcpyAsync(ctx->pr_h.p, a, bytes, hipMemcpyHostToDevice, ctx->stream));
-    VSP_TRY(domain_fft_device(ctx, d, (Fr *)ctx->pr_h.p, inverse, coset_g, nullptr));
-    VSP_HIP(hipMemcpyAsync(a, ctx->pr_h.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    VSP_HIP(hipStreamSynchronize(ctx->stream));
-    return VSP_OK;
+    return through_pr_h(ctx, a, a, d->m, [&](Fr *d_a) { return domain_fft_device(ctx, d, d_a, inverse, coset_g, nullptr); });
 }
 int vsp_domain_lagrange(vsp_ctx *ctx, const vsp_domain *d, const uint64_t t[4], uint64_t *out) {
     if (!ctx) return VSP_ERR_ARG;
     if (!d || !t || !out) return set_error(ctx, VSP_ERR_ARG, "domain_lagrange: null pointer");
-    VSP_HIP(hipSetDevice(ctx->device));
-    size_t bytes = d->m * 32;
-    VSP_TRY(ensure(ctx, ctx->pr_h, bytes));
-    VSP_TRY(domain_lagrange_device(ctx, d, host_load_canon<HFr>(t), (Fr *)ctx->pr_h.p));
-    VSP_TRY(fr_from_mont_device(ctx, (Fr *)ctx->pr_h.p, d->m));
-    VSP_HIP(hipMemcpyAsync(out, ctx->pr_h.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    VSP_HIP(hipStreamSynchronize(ctx->stream));
-    return VSP_OK;
+    return through_pr_h(ctx, nullptr, out, d->m, [&](Fr *u) {
+        VSP_TRY(domain_lagrange_device(ctx, d, host_load_canon<HFr>(t), u));
+        return fr_from_mont_device(ctx, u, d->m);
+    });
 }
 int vsp_domain_element(vsp_ctx *ctx, const vsp_domain *d, size_t idx, uint64_t out[4]) {
     if (!ctx) return VSP_ERR_ARG;
@@ -801,19 +795,11 @@ int vsp_domain_add_poly_z(vsp_ctx *ctx, const vsp_domain *d, const uint64_t coef
 int vsp_domain_divide_by_z_on_coset(vsp_ctx *ctx, const vsp_domain *d, uint64_t *P) {
     if (!ctx) return VSP_ERR_ARG;
     if (!d || !P) return set_error(ctx, VSP_ERR_ARG, "domain_divide_by_z_on_coset: null pointer");
-    VSP_HIP(hipSetDevice(ctx->device));
-    size_t bytes = d->m * 32;
-    VSP_TRY(ensure(ctx, ctx->pr_h, bytes));
-    VSP_HIP(hipMemcpyAsync(ctx->pr_h.p, P, bytes, hipMemcpyHostToDevice, ctx->stream));
-    VSP_TRY(domain_divide_by_z_device(ctx, d, (Fr *)ctx->pr_h.p));
-    VSP_HIP(hipMemcpyAsync(P, ctx->pr_h.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    VSP_HIP(hipStreamSynchronize(ctx->stream));
-    return VSP_OK;
+    return through_pr_h(ctx, P, P, d->m, [&](Fr *p) { return domain_divide_by_z_device(ctx, d, p); });
 }
 int vsp_domain_witness_map_h(vsp_ctx *ctx, const vsp_domain *d, uint64_t *Az, uint64_t *Bz, uint64_t *Cz, uint64_t *H) {
     if (!ctx) return VSP_ERR_ARG;
     if (!d || !Az || !Bz || !Cz || !H) return set_error(ctx, VSP_ERR_ARG, "witness_map: null pointer");
-    VSP_HIP(hipSetDevice(ctx->device));
     return witness_map_host(ctx, d, Az, Bz, Cz, H);
 }
 size_t vsp_r1cs_domain_size(const vsp_r1cs *cs) { return cs ? cs->dom.m : 0; }

@@ -141,6 +141,27 @@ struct MsmRequest {
     MsmRequest(const Fr *scalars_ = nullptr, size_t n_ = 0) : scalars(scalars_), n(n_) {}
 };
 
+// which butterflies run a transform: the 29-bit ones when ntt29_in_use says so, else the 8 x 32-bit ones; or one of the two forced
+enum NttPath { NTT_AUTO, NTT_FR29, NTT_FR32 };
+// `count` radix-2 transforms of 2^log_m canonical values in one launch per pass (ntt_launch).  Pointer form (strides 0): transform b
+// reads in[b] and writes out[b], count <= 3.  Strided form: transform b reads in[0] + b in_stride and writes out[0] + b out_stride,
+// count <= 65535.  Several transforms, out of place or fused, need the 29-bit butterflies.
+struct NttRequest {
+    const Fr *in[3] = {nullptr, nullptr, nullptr};
+    Fr *out[3] = {nullptr, nullptr, nullptr};
+    unsigned count = 1;
+    size_t in_stride = 0, out_stride = 0;
+    const Fr *fuse_b = nullptr, *fuse_c = nullptr;      // non-null: the first pass loads (in b - c) 2^-261, b and c following in_stride
+    unsigned log_m = 0;
+    int inverse = 0;
+    const uint64_t *coset_g = nullptr;                  // canonical coset generator (forward: a[i] g^i before; inverse: ginv^i after), or null
+    const HFr *extra_scale = nullptr;                   // host Montgomery: a constant multiplied into every output, or null
+    NttPath path = NTT_AUTO;
+    // one transform of d_a in place
+    NttRequest(Fr *d_a, unsigned log_m_, int inverse_ = 0, const uint64_t *coset_g_ = nullptr, const HFr *extra_scale_ = nullptr)
+        : log_m(log_m_), inverse(inverse_), coset_g(coset_g_), extra_scale(extra_scale_) { in[0] = d_a; out[0] = d_a; }
+};
+
 }  // namespace vsp
 
 struct vsp_ctx {
@@ -160,7 +181,7 @@ struct vsp_ctx {
     int slot_group[vsp::VSP_MSM_SLOTS] = {1, 1, 1, 1, 1, 1};
     bool lds_attr_set[2] = {false, false};
     bool ntt_attr_set = false;
-    int ntt29_checked = 0;              // known-answer check of k_ntt29_pass: 0 not yet, 1 passed, -1 failed (8 x 32-bit kernel in use), 2 running
+    int ntt29_checked = 0;              // known-answer check of k_ntt29_pass: 0 not yet (or could not run), 1 passed, -1 failed (8 x 32-bit kernel in use)
     vsp::DevBuf msm_scalars;
     void *h_fold = nullptr; size_t h_fold_cap = 0;      // pinned landing buffer of vsp_fold_jacobian_device (the ranks' records)
     vsp::DevBuf val_flag;               // one word: validation result of the last bases upload
@@ -239,8 +260,8 @@ namespace vsp {
 
 // option `name` of the context (vsp_set_option), or dflt when it was never set
 inline long opt(const vsp_ctx *ctx, const char *name, long dflt) { auto it = ctx->opts.find(name); return it != ctx->opts.end() ? it->second : dflt; }
-// the named options as they are at construction, present with a value or absent, put back when the scope ends (the known-answer
-// checks run their legs under settings of their own)
+// the named options as they are at construction, present with a value or absent, put back when the scope ends (the 28-bit known-answer
+// check runs its legs under settings of their own)
 class OptScope {
   public:
     OptScope(vsp_ctx *ctx, std::initializer_list<const char *> names) : ctx_(ctx) {
@@ -281,16 +302,9 @@ int ensure(vsp_ctx *ctx, DevBuf &b, size_t bytes);
 #define VSP_LAUNCH_CHECK() VSP_HIP(hipGetLastError())
 
 // ---- internal entry points (each implemented in its own .hip) ----
-int ntt_device(vsp_ctx *ctx, Fr *d_a, unsigned log_m, int inverse, const uint64_t *coset_g, const HFr *extra_scale);
-bool ntt29_in_use(vsp_ctx *ctx);
-int ntt_device_strided(vsp_ctx *ctx, Fr *base, unsigned count, size_t stride, unsigned log_m, int inverse, const uint64_t *coset_g, const HFr *extra_scale);
-int ntt_device_fused_abc_strided(vsp_ctx *ctx, const Fr *d_a, size_t off_b, size_t off_c, size_t in_stride, Fr *d_h, size_t out_stride, unsigned count, unsigned log_m,
-                                 int inverse, const uint64_t *coset_g, const HFr *extra_scale);
-int witness_map_device_batch(vsp_ctx *ctx, Fr *abc, unsigned count, const vsp_domain *d, Fr *dH);
-int ntt_device_batch(vsp_ctx *ctx, Fr *const *d_a, unsigned count, unsigned log_m, int inverse, const uint64_t *coset_g, const HFr *extra_scale);
-int ntt_device_fused_abc(vsp_ctx *ctx, const Fr *d_a, const Fr *d_b, const Fr *d_c, Fr *d_h, unsigned log_m, int inverse, const uint64_t *coset_g, const HFr *extra_scale);
+int ntt_launch(vsp_ctx *ctx, const NttRequest &rq);
+bool ntt29_in_use(vsp_ctx *ctx);                                // runs the 29-bit butterflies' known-answer check first: before any table set-up
 int ntt_ensure_twiddles(vsp_ctx *ctx, unsigned log_m);
-void ntt_selfcheck_once(vsp_ctx *ctx);                          // known-answer check of the 29-bit butterfly kernel, before any table set-up
 int ntt_ensure_coset_tables(vsp_ctx *ctx, unsigned log_m, const uint64_t *g4);
 // evaluation domains (domain.hip)
 int domain_init(vsp_ctx *ctx, vsp_domain *d, size_t min_size);      // make_evaluation_domain's choice + the coset divisors
@@ -302,7 +316,8 @@ int domain_divide_by_z_device(vsp_ctx *ctx, const vsp_domain *d, Fr *d_p);
 int domain_lagrange_device(vsp_ctx *ctx, const vsp_domain *d, const HFr &t, Fr *d_u /* m, Montgomery form */);
 HFr domain_vanishing(const vsp_domain *d, const HFr &t);
 HFr domain_element(const vsp_domain *d, size_t idx);
-int witness_map_device(vsp_ctx *ctx, Fr *dA, Fr *dB, Fr *dC, const vsp_domain *d, Fr *dH);
+// K witnesses: member k's A z, B z, C z at dA, dB, dC + k abc_stride (overwritten), its H at dH + k h_stride (domain.hip)
+int witness_map_device(vsp_ctx *ctx, const vsp_domain *d, Fr *dA, Fr *dB, Fr *dC, size_t abc_stride, unsigned K, Fr *dH, size_t h_stride);
 // vsp_groth16_prove with a hook (prover.hip): `overlap` runs on the host after every kernel is queued and before the first wait
 int prove_with_overlap(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witness, const uint64_t r[4], const uint64_t s[4],
                        const uint64_t *saver_P1, const uint64_t *saver_r_enc, uint64_t A_out[12], uint64_t B_out[24], uint64_t C_out[12],

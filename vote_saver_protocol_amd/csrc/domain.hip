@@ -230,9 +230,9 @@ HFr domain_element(const vsp_domain *d, size_t idx) {
 }
 
 int domain_fft_device(vsp_ctx *ctx, const vsp_domain *d, Fr *a, int inverse, const uint64_t *coset_g, const HFr *extra_scale) {
-    if (!d->step) return ntt_device(ctx, a, d->log_big, inverse, coset_g, extra_scale);
+    if (!d->step) return ntt_launch(ctx, NttRequest(a, d->log_big, inverse, coset_g, extra_scale));
     if (coset_g && !(coset_g[0] | coset_g[1] | coset_g[2] | coset_g[3])) return set_error(ctx, VSP_ERR_ARG, "fft: coset generator is zero");
-    ntt_selfcheck_once(ctx);
+    ntt29_in_use(ctx);                        // the known-answer check first: its transforms may rebuild the tables set up here
     const size_t big = d->big_m, small = d->small_m, compr = big / small;
     VSP_TRY(ntt_ensure_twiddles(ctx, d->log_big + 1));
     if (coset_g) VSP_TRY(ntt_ensure_coset_tables(ctx, d->log_big + 1, coset_g));
@@ -247,12 +247,12 @@ int domain_fft_device(vsp_ctx *ctx, const vsp_domain *d, Fr *a, int inverse, con
                            coset_g ? (const Fr *)ctx->ntt.pw_lo_f.p : nullptr, coset_g ? (const Fr *)ctx->ntt.pw_hi_f.p : nullptr);
         VSP_LAUNCH_CHECK();
         VSP_TRY(fold(ctx, dv, a + big, ping, pong, small, compr, 0, nullptr, 0));
-        VSP_TRY(ntt_device(ctx, a, d->log_big, 0, nullptr, extra_scale));
-        VSP_TRY(ntt_device(ctx, a + big, d->log_small, 0, nullptr, extra_scale));
+        VSP_TRY(ntt_launch(ctx, NttRequest(a, d->log_big, 0, nullptr, extra_scale)));
+        VSP_TRY(ntt_launch(ctx, NttRequest(a + big, d->log_small, 0, nullptr, extra_scale)));
         return VSP_OK;
     }
-    VSP_TRY(ntt_device(ctx, a, d->log_big, 1, nullptr, nullptr));
-    VSP_TRY(ntt_device(ctx, a + big, d->log_small, 1, nullptr, nullptr));
+    VSP_TRY(ntt_launch(ctx, NttRequest(a, d->log_big, 1)));
+    VSP_TRY(ntt_launch(ctx, NttRequest(a + big, d->log_small, 1)));
     const unsigned shift = ctx->ntt.log - 1 - d->log_big;      // after the transforms: their table may have been regenerated larger
     VSP_TRY(fold(ctx, a, dv, ping, pong, small, compr, 1, (const Fr *)ctx->ntt.fwd.p, shift));
     PostConsts k;
@@ -316,25 +316,10 @@ int domain_lagrange_device(vsp_ctx *ctx, const vsp_domain *d, const HFr &t, Fr *
     return done(VSP_OK);
 }
 
-// r1cs_to_qap::witness_map, d1 = d2 = d3 = 0:  H = icosetFFT( (cosetFFT(iFFT(A)) * cosetFFT(iFFT(B)) - cosetFFT(iFFT(C))) / Z on the coset )
-// dA, dB, dC: m canonical values each (overwritten); dH receives the m coefficients of H.
-int witness_map_device(vsp_ctx *ctx, Fr *dA, Fr *dB, Fr *dC, const vsp_domain *d, Fr *dH) {
+// r1cs_to_qap::witness_map of one witness as a sequence: 6 transforms, the pointwise kernel, the last transform
+static int witness_map_sequence(vsp_ctx *ctx, const vsp_domain *d, Fr *dA, Fr *dB, Fr *dC, Fr *dH) {
     const size_t m = d->m;
     Fr *v[3] = {dA, dB, dC};
-    { const long batched = opt(ctx, "witness_map_batched", 1);
-      if (batched && !d->step && m >= 2 && ntt29_in_use(ctx)) {
-        // basic radix-2 domain, 29-bit butterflies: the three inverse transforms as ONE launch per pass, the three coset transforms likewise, and
-        // the pointwise step A B - C inside the first pass of the last transform: 3 x passes launches instead of 7 x passes + 1, and the
-        // 128 bytes per element the pointwise kernel moved stay in registers.  (Option "witness_map_batched" = 0: the sequence below.)
-        unsigned log_m = 0; while (((size_t)1 << log_m) < m) log_m++;
-        VSP_TRY(ntt_device_batch(ctx, v, 3, log_m, 1, nullptr, nullptr));
-        VSP_TRY(ntt_device_batch(ctx, v, 3, log_m, 0, G7, nullptr));
-        // the fused load leaves (a b - c) 2^-261: 2^261 = 32 R goes into the scale with 1 / Z(g), constant on the coset of a basic domain
-        const uint64_t c32[4] = {32, 0, 0, 0};
-        HFr extra = mul(mul(HFr::r2(), host_load_canon<HFr>(c32)), d->zinv_const);
-        VSP_TRY(ntt_device_fused_abc(ctx, dA, dB, dC, dH, log_m, 1, G7, &extra));
-        return VSP_OK;
-      } }
     for (int k = 0; k < 3; k++) {
         VSP_TRY(domain_fft_device(ctx, d, v[k], 1, nullptr, nullptr));
         VSP_TRY(domain_fft_device(ctx, d, v[k], 0, G7, nullptr));
@@ -353,20 +338,33 @@ int witness_map_device(vsp_ctx *ctx, Fr *dA, Fr *dB, Fr *dC, const vsp_domain *d
     return VSP_OK;
 }
 
-// the same for `count` witnesses: abc holds [count][3][m] evaluation vectors (A z, B z, C z of witness k at abc + 3 k m), dH [count][m].
-// Basic domains on the 29-bit butterflies run 3 count transforms per launch; anything else takes the single form, witness by witness.
-int witness_map_device_batch(vsp_ctx *ctx, Fr *abc, unsigned count, const vsp_domain *d, Fr *dH) {
+// r1cs_to_qap::witness_map, d1 = d2 = d3 = 0:  H = icosetFFT( (cosetFFT(iFFT(A)) * cosetFFT(iFFT(B)) - cosetFFT(iFFT(C))) / Z on the coset )
+// for K witnesses.  Member k: A z, B z, C z at dA, dB, dC + k abc_stride, m canonical values each (overwritten); the m coefficients of its
+// H at dH + k h_stride.  A batch (K > 1) has the prover's layout [K][3][m]: dB = dA + m, dC = dA + 2 m, abc_stride = 3 m.
+int witness_map_device(vsp_ctx *ctx, const vsp_domain *d, Fr *dA, Fr *dB, Fr *dC, size_t abc_stride, unsigned K, Fr *dH, size_t h_stride) {
     const size_t m = d->m;
-    if (d->step || m < 2 || !ntt29_in_use(ctx)) {
-        for (unsigned k = 0; k < count; k++) VSP_TRY(witness_map_device(ctx, abc + (size_t)3 * k * m, abc + (size_t)(3 * k + 1) * m, abc + (size_t)(3 * k + 2) * m, d, dH + (size_t)k * m));
-        return VSP_OK;
+    if (K > 1 && (dB != dA + m || dC != dA + 2 * m || abc_stride != 3 * m)) return set_error(ctx, VSP_ERR_ARG, "witness_map: a batch needs the layout [K][3][m]");
+    if (opt(ctx, "witness_map_batched", 1) && !d->step && m >= 2 && ntt29_in_use(ctx)) {
+        // basic radix-2 domain, 29-bit butterflies: the 3 K inverse transforms as ONE launch per pass, the 3 K coset transforms likewise, and
+        // the pointwise step A B - C inside the first pass of the last transform: 3 x passes launches instead of K (7 x passes + 1), and the
+        // 128 bytes per element the pointwise kernel moved stay in registers.  (Option "witness_map_batched" = 0: the sequence, member by member.)
+        auto abc = [&](int inverse, const uint64_t *coset_g) {
+            NttRequest rq(dA, d->log_big, inverse, coset_g);
+            if (K == 1) { rq.count = 3; rq.in[1] = rq.out[1] = dB; rq.in[2] = rq.out[2] = dC; }
+            else { rq.count = 3 * K; rq.in_stride = rq.out_stride = m; }
+            return ntt_launch(ctx, rq);
+        };
+        VSP_TRY(abc(1, nullptr));
+        VSP_TRY(abc(0, G7));
+        // the fused load leaves (a b - c) 2^-261: 2^261 = 32 R goes into the scale with 1 / Z(g), constant on the coset of a basic domain
+        const uint64_t c32[4] = {32, 0, 0, 0};
+        const HFr extra = mul(mul(HFr::r2(), host_load_canon<HFr>(c32)), d->zinv_const);
+        NttRequest h(dA, d->log_big, 1, G7, &extra);
+        h.out[0] = dH; h.fuse_b = dB; h.fuse_c = dC;
+        if (K > 1) { h.count = K; h.in_stride = abc_stride; h.out_stride = h_stride; }
+        return ntt_launch(ctx, h);
     }
-    unsigned log_m = 0; while (((size_t)1 << log_m) < m) log_m++;
-    VSP_TRY(ntt_device_strided(ctx, abc, 3 * count, m, log_m, 1, nullptr, nullptr));
-    VSP_TRY(ntt_device_strided(ctx, abc, 3 * count, m, log_m, 0, G7, nullptr));
-    const uint64_t c32[4] = {32, 0, 0, 0};
-    HFr extra = mul(mul(HFr::r2(), host_load_canon<HFr>(c32)), d->zinv_const);
-    VSP_TRY(ntt_device_fused_abc_strided(ctx, abc, m, 2 * m, 3 * m, dH, m, count, log_m, 1, G7, &extra));
+    for (unsigned k = 0; k < K; k++) VSP_TRY(witness_map_sequence(ctx, d, dA + k * abc_stride, dB + k * abc_stride, dC + k * abc_stride, dH + k * h_stride));
     return VSP_OK;
 }
 

@@ -440,13 +440,10 @@ static int ntt29_ensure_tables(vsp_ctx *ctx, bool coset) {
     }
     return VSP_OK;
 }
-static Fr29 host_to_fr29_mont(const HFr &x) {          // host value (Montgomery, R = 2^256) -> canonical x * 2^261 mod r as 9 x 29-bit limbs
+// host value (Montgomery, R = 2^256) -> canonical x * 2^261 mod r as 9 x 29-bit limbs: the Montgomery form of the 29-bit kernels
+static Fr29 host_to_fr29_mont(const HFr &x) {
     uint64_t c[4]; host_store_canon(c, x);
-    HFr sh = host_load_canon<HFr>(c);                   // x again, to multiply by 2^261 = 2^256 * 2^5 through host arithmetic
-    HFr two = add(HFr::one(), HFr::one()), p32 = two;
-    for (int i = 0; i < 4; i++) p32 = add(p32, p32);      // 2^5
-    // 2^256 mod r in Montgomery form is R^2's reduction: to_mont(one's canonical R)...: simpler: multiply by 2 two hundred sixty-one times
-    HFr acc = sh;
+    HFr acc = host_load_canon<HFr>(c);                  // x again, through its canonical form
     for (int i = 0; i < 261; i++) acc = add(acc, acc);
     host_store_canon(c, acc);
     Fr29 r;
@@ -456,18 +453,16 @@ static Fr29 host_to_fr29_mont(const HFr &x) {          // host value (Montgomery
         if (w + 1 < 4) v |= (unsigned __int128)c[w + 1] << 64;
         r.l[i] = (uint32_t)(v >> s2) & (i < 8 ? 0x1FFFFFFFu : 0xFFFFFFFFu);
     }
-    (void)p32;
     return r;
 }
 
 // Known-answer check of the 29-bit-limb butterflies THROUGH k_ntt29_pass (its product, vsp_mm29, is a hand-laid-out routine with a private
 // calling convention: see the note at capi.hip fp28_known_answer_check).  Once per context, before the first transform on that path: a
 // 2^13-point vector (two passes: the lazy planes between passes, the first and the last pass) goes through a forward coset transform
-// and an inverse coset transform on k_ntt29_pass and on the 8 x 32-bit k_ntt_pass; the outputs must agree word for word.  On a
-// mismatch the context falls back to the 8 x 32-bit kernel ("ntt_fr29" = 0) for its lifetime.
-static bool ntt29_known_answer_check(vsp_ctx *ctx) {
-    if (ctx->ntt29_checked != 0) return ctx->ntt29_checked == 1;
-    ctx->ntt29_checked = 2;                                   // in progress: the transforms below must not re-enter
+// and an inverse coset transform on k_ntt29_pass and on the 8 x 32-bit k_ntt_pass, each path forced by its request; the outputs must
+// agree word for word.  On a mismatch the context falls back to the 8 x 32-bit kernel ("ntt_fr29" = 0) for its lifetime.  A check that
+// could not run leaves no verdict (ntt29_checked stays 0): the 8 x 32-bit kernel this time, the check again next time.
+static void ntt29_known_answer_check(vsp_ctx *ctx) {
     const unsigned lg = 13; const size_t n = (size_t)1 << lg, bytes = n * sizeof(Fr);
     std::vector<uint64_t> h(n * 4), o29(n * 4), o32(n * 4);
     uint64_t x = 0x243F6A8885A308D3ULL;
@@ -479,14 +474,14 @@ static bool ntt29_known_answer_check(vsp_ctx *ctx) {
     void *d = nullptr;
     bool ran = false, same = true;
     if (hipMalloc(&d, bytes) == hipSuccess) {
-        OptScope saved(ctx, {"ntt_fr29"});
         ran = true;
         for (int inverse = 0; inverse < 2 && ran; inverse++) {
             for (int path = 0; path < 2 && ran; path++) {
-                ctx->opts["ntt_fr29"] = path == 0 ? 1 : 0;
+                NttRequest rq((Fr *)d, lg, inverse, g7);
+                rq.path = path == 0 ? NTT_FR29 : NTT_FR32;
                 std::vector<uint64_t> &out = path == 0 ? o29 : o32;
                 ran = hipMemcpyAsync(d, h.data(), bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
-                      ntt_device(ctx, (Fr *)d, lg, inverse, g7, nullptr) == VSP_OK &&
+                      ntt_launch(ctx, rq) == VSP_OK &&
                       hipMemcpyAsync(out.data(), d, bytes, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
                       hipStreamSynchronize(ctx->stream) == hipSuccess;
             }
@@ -495,160 +490,97 @@ static bool ntt29_known_answer_check(vsp_ctx *ctx) {
         hipFree(d);
     }
     hipGetLastError();
-    if (!ran) { ctx->ntt29_checked = 0; ctx->stats["ntt_fr29_selfcheck"] = 0.0; return false; }      // could not run: no verdict, the 8 x 32-bit kernel this time
+    if (!ran) { ctx->stats["ntt_fr29_selfcheck"] = 0.0; return; }
     if (opt(ctx, "ntt_fr29_selfcheck_fault", 0)) same = false;      // test hook: exercise the fallback
     ctx->ntt29_checked = same ? 1 : -1;
     ctx->stats["ntt_fr29_selfcheck"] = same ? 1.0 : -1.0;
     if (!same) { ctx->opts["ntt_fr29"] = 0; ctx->err = "ntt: the 29-bit-limb butterfly kernel failed its known-answer check; 8 x 32-bit kernel in use"; }
-    return same;
 }
 
-// callers that set tables up before their first transform (the step-domain glue) run the check first: it rebuilds tables for its own use
-void ntt_selfcheck_once(vsp_ctx *ctx) {
-    if (opt(ctx, "ntt_fr29", 1) && ctx->ntt29_checked == 0) ntt29_known_answer_check(ctx);
-}
-
-// whether the 29-bit butterflies are in use on this context (runs their known-answer check when it has not run yet)
+// whether the 29-bit butterflies are in use on this context; runs their known-answer check when it has not run yet.  Callers that set
+// tables up (ntt_launch, the step-domain glue) ask this first: the check's own transforms may rebuild the twiddle and coset tables.
 bool ntt29_in_use(vsp_ctx *ctx) {
     if (!opt(ctx, "ntt_fr29", 1)) return false;
-    if (ctx->ntt29_checked <= 0 && !ntt29_known_answer_check(ctx)) return false;
-    return opt(ctx, "ntt_fr29", 1) != 0;                    // (a failed check has just switched it off)
+    if (ctx->ntt29_checked == 0) ntt29_known_answer_check(ctx);
+    return ctx->ntt29_checked == 1;
 }
-static int ntt_device_impl(vsp_ctx *ctx, const Fr *const *d_in, Fr *const *d_out, unsigned count, unsigned log_m, int inverse, const uint64_t *coset_g,
-                           const HFr *extra_scale, const Fr *fuse_b, const Fr *fuse_c, size_t in_stride = 0, size_t out_stride = 0);
-// d_a: n canonical Fr values in device memory, transformed in place.
-// extra_scale (optional, host Montgomery): an additional constant multiplied into every output.
-int ntt_device(vsp_ctx *ctx, Fr *d_a, unsigned log_m, int inverse, const uint64_t *coset_g, const HFr *extra_scale) {
-    const Fr *in[1] = {d_a}; Fr *out[1] = {d_a};
-    return ntt_device_impl(ctx, in, out, 1, log_m, inverse, coset_g, extra_scale, nullptr, nullptr);
-}
-// `count` (<= 3) transforms of one size in ONE launch per pass, in place (29-bit butterflies only: callers ask ntt29_in_use first)
-int ntt_device_batch(vsp_ctx *ctx, Fr *const *d_a, unsigned count, unsigned log_m, int inverse, const uint64_t *coset_g, const HFr *extra_scale) {
-    if (count < 1 || count > 3) return set_error(ctx, VSP_ERR_ARG, "ntt: batch of 1..3 transforms");
-    const Fr *in[3] = {d_a[0], count > 1 ? d_a[1] : nullptr, count > 2 ? d_a[2] : nullptr};
-    return ntt_device_impl(ctx, in, d_a, count, log_m, inverse, coset_g, extra_scale, nullptr, nullptr);
-}
-// d_h = transform of (a[i] b[i] - c[i]) 2^-261, the pointwise step fused into the first pass's load (29-bit butterflies only)
-int ntt_device_fused_abc(vsp_ctx *ctx, const Fr *d_a, const Fr *d_b, const Fr *d_c, Fr *d_h, unsigned log_m, int inverse, const uint64_t *coset_g, const HFr *extra_scale) {
-    const Fr *in[1] = {d_a}; Fr *out[1] = {d_h};
-    return ntt_device_impl(ctx, in, out, 1, log_m, inverse, coset_g, extra_scale, d_b, d_c);
-}
-// `count` transforms at base + b * stride, in place, one launch per pass (a batch of proofs: 3 K transforms; 29-bit butterflies only)
-int ntt_device_strided(vsp_ctx *ctx, Fr *base, unsigned count, size_t stride, unsigned log_m, int inverse, const uint64_t *coset_g, const HFr *extra_scale) {
-    if (count < 1 || count > 65535) return set_error(ctx, VSP_ERR_ARG, "ntt: batch size");
-    const Fr *in[1] = {base}; Fr *out[1] = {base};
-    return ntt_device_impl(ctx, in, out, count, log_m, inverse, coset_g, extra_scale, nullptr, nullptr, stride, stride);
-}
-// d_h + b out_stride = transform of (a b - c) 2^-261 with a = d_a + b in_stride, b = a + off_b, c = a + off_c
-int ntt_device_fused_abc_strided(vsp_ctx *ctx, const Fr *d_a, size_t off_b, size_t off_c, size_t in_stride, Fr *d_h, size_t out_stride, unsigned count, unsigned log_m,
-                                 int inverse, const uint64_t *coset_g, const HFr *extra_scale) {
-    if (count < 1 || count > 65535) return set_error(ctx, VSP_ERR_ARG, "ntt: batch size");
-    const Fr *in[1] = {d_a}; Fr *out[1] = {d_h};
-    return ntt_device_impl(ctx, in, out, count, log_m, inverse, coset_g, extra_scale, d_a + off_b, d_a + off_c, in_stride, out_stride);
-}
-static int ntt_device_impl(vsp_ctx *ctx, const Fr *const *d_in, Fr *const *d_out, unsigned count, unsigned log_m, int inverse, const uint64_t *coset_g,
-                           const HFr *extra_scale, const Fr *fuse_b, const Fr *fuse_c, size_t in_stride, size_t out_stride) {
-    Fr *d_a = d_out[0];
-    if (log_m > 28) return set_error(ctx, VSP_ERR_UNSUPPORTED, "ntt: log_m > 28");
-    if (coset_g) {
-        uint64_t z = coset_g[0] | coset_g[1] | coset_g[2] | coset_g[3];
-        if (!z) return set_error(ctx, VSP_ERR_ARG, "ntt: coset generator is zero");
-    }
-    // the 29-bit path's known-answer check comes first: it runs transforms of its own, which may rebuild the twiddle and coset tables
-    bool check29_ok = true;
-    if (opt(ctx, "ntt_fr29", 1) && ctx->ntt29_checked <= 0) check29_ok = ntt29_known_answer_check(ctx);      // (2 = the check itself is running: not re-entered)
-    VSP_TRY(ntt_ensure_twiddles(ctx, log_m));
-    if (coset_g) VSP_TRY(ntt_ensure_coset_tables(ctx, log_m, coset_g));
-    const size_t n = (size_t)1 << log_m;
 
-    // pass plan
-    unsigned npass = log_m <= NTT_TILE_LOG ? 1 : (log_m + NTT_MAX_STAGES - 1) / NTT_MAX_STAGES;
-    unsigned stages[8];
+// passes of at most NTT_MAX_STAGES stages each, as even as the stage count allows; returns their number
+static unsigned ntt_plan(unsigned log_m, unsigned stages[8]) {
+    const unsigned npass = log_m <= NTT_TILE_LOG ? 1 : (log_m + NTT_MAX_STAGES - 1) / NTT_MAX_STAGES;
     for (unsigned i = 0; i < npass; i++) stages[i] = log_m / npass + (i < log_m % npass ? 1 : 0);
     // radix-4 steps take stages two at a time: trade a stage between two odd passes (7 + 7 -> 8 + 6), earlier pass the larger
     for (unsigned i = 0; i + 1 < npass; i++)
         if (stages[i] & 1)
             for (unsigned k = i + 1; k < npass; k++)
                 if ((stages[k] & 1) && stages[i] < NTT_MAX_STAGES && stages[k] > 1) { stages[i]++; stages[k]--; break; }
+    return npass;
+}
 
-    long use29 = opt(ctx, "ntt_fr29", 1);
-    if (use29 && !check29_ok) use29 = 0;
-    if (!use29 && (count > 1 || fuse_b || d_in[0] != d_out[0])) return set_error(ctx, VSP_ERR_UNSUPPORTED, "ntt: batched / fused transforms need the 29-bit butterflies");
-    Fr *scratch = nullptr;
-    if (npass > 1) { VSP_TRY(ensure(ctx, ctx->ntt_scratch, (size_t)count * n * (use29 ? 36 : sizeof(Fr)))); scratch = (Fr *)ctx->ntt_scratch.p; }
+int ntt_launch(vsp_ctx *ctx, const NttRequest &rq) {
+    const bool strided = rq.in_stride || rq.out_stride;
+    if (strided && (rq.count < 1 || rq.count > 65535)) return set_error(ctx, VSP_ERR_ARG, "ntt: batch size");
+    if (!strided && (rq.count < 1 || rq.count > 3)) return set_error(ctx, VSP_ERR_ARG, "ntt: batch of 1..3 transforms");
+    if (rq.log_m > 28) return set_error(ctx, VSP_ERR_UNSUPPORTED, "ntt: log_m > 28");
+    if (rq.coset_g && !(rq.coset_g[0] | rq.coset_g[1] | rq.coset_g[2] | rq.coset_g[3])) return set_error(ctx, VSP_ERR_ARG, "ntt: coset generator is zero");
+    const bool use29 = rq.path == NTT_AUTO ? ntt29_in_use(ctx) : rq.path == NTT_FR29;
+    if (!use29 && (rq.count > 1 || rq.fuse_b || rq.in[0] != rq.out[0])) return set_error(ctx, VSP_ERR_UNSUPPORTED, "ntt: batched / fused transforms need the 29-bit butterflies");
+    VSP_TRY(ntt_ensure_twiddles(ctx, rq.log_m));
+    if (rq.coset_g) VSP_TRY(ntt_ensure_coset_tables(ctx, rq.log_m, rq.coset_g));
+    if (use29) VSP_TRY(ntt29_ensure_tables(ctx, rq.coset_g != nullptr));
+    const NttTables &t = ctx->ntt;
+    const size_t n = (size_t)1 << rq.log_m;
+    unsigned stages[8];
+    const unsigned npass = ntt_plan(rq.log_m, stages);
+    // between passes: lazy values in three planes, a slice per transform (29-bit), or canonical words (8 x 32-bit)
+    if (npass > 1) VSP_TRY(ensure(ctx, ctx->ntt_scratch, (size_t)rq.count * n * (use29 ? 36 : sizeof(Fr))));
 
     HFr scale = HFr::one();
-    bool have_scale = false;
-    if (inverse) { scale = inv(host_from_u64((uint64_t)n)); have_scale = true; }
-    if (extra_scale) { scale = mul(scale, *extra_scale); have_scale = true; }
+    if (rq.inverse) scale = inv(host_from_u64((uint64_t)n));
+    if (rq.extra_scale) scale = mul(scale, *rq.extra_scale);
+    const bool have_scale = rq.inverse || rq.extra_scale;
+    const bool coset_in = rq.coset_g && !rq.inverse, coset_out = rq.coset_g && rq.inverse;      // g^i at the first load, ginv^i at the last store
+    Fr29 scale29;
+    if (use29) scale29 = host_to_fr29_mont(scale);
+    const size_t tcount = (size_t)1 << (t.log - 1), L = (size_t)1 << PW_LOG, pn = (size_t)1 << t.pw_log, H = pn > L ? (pn >> PW_LOG) : 1;
+    const Planes29 lazy_in = planes_of(ctx->ntt_scratch, (size_t)rq.count * n);
+    const PlanesOut29 lazy_out = {(uint4 *)lazy_in.p0, (uint4 *)lazy_in.p1, (uint32_t *)lazy_in.p2};
+    Fr *scratch = (Fr *)ctx->ntt_scratch.p;
 
-    if (use29) {
-        // butterflies on 9 x 29-bit limbs (fr29.h); the scratch buffer holds lazy values in three planes between passes
-        VSP_TRY(ntt29_ensure_tables(ctx, coset_g != nullptr));
-        const size_t tcount = (size_t)1 << (ctx->ntt.log - 1);
-        const size_t L = (size_t)1 << PW_LOG, pn = (size_t)1 << ctx->ntt.pw_log, H = pn > L ? (pn >> PW_LOG) : 1;
-        Planes29 lazy_in = planes_of(ctx->ntt_scratch, (size_t)count * n);
-        PlanesOut29 lazy_out; lazy_out.p0 = (uint4 *)lazy_in.p0; lazy_out.p1 = (uint4 *)lazy_in.p1; lazy_out.p2 = (uint32_t *)lazy_in.p2;
-        unsigned s0 = 0;
-        for (unsigned i = 0; i < npass; i++) {
-            NttPass29Args p;
+    for (unsigned i = 0, s0 = 0; i < npass; s0 += stages[i], i++) {
+        const bool first = i == 0, last = i + 1 == npass;
+        const unsigned clog = npass == 1 ? 0 : NTT_TILE_LOG - stages[i];
+        if (!first && s0 < clog) return set_error(ctx, VSP_ERR_UNSUPPORTED, "ntt: pass plan");
+        auto common = [&](auto &p) {          // the fields both pass kernels read alike
             memset(&p, 0, sizeof p);
-            p.log_n = log_m; p.s0 = s0; p.s1 = s0 + stages[i];
-            p.tlog = ctx->ntt.log;
-            p.first = (i == 0); p.last = (i == npass - 1);
-            p.clog = npass == 1 ? 0 : NTT_TILE_LOG - stages[i];
-            p.tw = planes_of(inverse ? ctx->ntt.inv29 : ctx->ntt.fwd29, tcount);
-            p.premul = (p.first && coset_g && !inverse) ? 1 : 0;
-            p.postmul = (p.last && inverse && coset_g) ? 2 : 1;                    // the last pass always multiplies: by the scale or by one
-            if (p.premul) { p.pw_lo = planes_of(ctx->ntt.pw29[0], L); p.pw_hi = planes_of(ctx->ntt.pw29[1], H); }
-            if (p.postmul == 2) { p.pw_lo = planes_of(ctx->ntt.pw29[2], L); p.pw_hi = planes_of(ctx->ntt.pw29[3], H); }
-            p.scale = host_to_fr29_mont(scale);
-            if (in_stride || out_stride) { p.in[0] = d_in[0]; p.out[0] = d_out[0]; p.in_stride = in_stride; p.out_stride = out_stride; }
-            else for (unsigned b = 0; b < count; b++) { p.in[b] = d_in[b]; p.out[b] = d_out[b]; }
-            if (p.first) { p.fuse_b = fuse_b; p.fuse_c = fuse_c; }
-            if (!p.first && p.s0 < p.clog) return set_error(ctx, VSP_ERR_UNSUPPORTED, "ntt: pass plan");
-            const unsigned tile_log = stages[i] + p.clog;
-            hipLaunchKernelGGL(k_ntt29_pass, dim3((unsigned)(n >> tile_log), count), dim3(NTT_THREADS), 0, ctx->stream, lazy_in, lazy_out, p);
-            VSP_LAUNCH_CHECK();
-            s0 = p.s1;
+            p.log_n = rq.log_m; p.s0 = s0; p.s1 = s0 + stages[i]; p.clog = clog; p.tlog = t.log;
+            p.first = first; p.last = last; p.premul = first && coset_in;
+        };
+        const dim3 grid((unsigned)(n >> (stages[i] + clog)), rq.count);
+        if (use29) {
+            NttPass29Args p; common(p);
+            p.postmul = last && coset_out ? 2 : 1;                  // the last pass always multiplies: by the scale or by one
+            p.tw = planes_of(rq.inverse ? t.inv29 : t.fwd29, tcount);
+            if (p.premul) { p.pw_lo = planes_of(t.pw29[0], L); p.pw_hi = planes_of(t.pw29[1], H); }
+            if (p.postmul == 2) { p.pw_lo = planes_of(t.pw29[2], L); p.pw_hi = planes_of(t.pw29[3], H); }
+            p.scale = scale29;
+            for (int b = 0; b < 3; b++) { p.in[b] = rq.in[b]; p.out[b] = rq.out[b]; }
+            p.in_stride = rq.in_stride; p.out_stride = rq.out_stride;
+            if (first) { p.fuse_b = rq.fuse_b; p.fuse_c = rq.fuse_c; }
+            hipLaunchKernelGGL(k_ntt29_pass, grid, dim3(NTT_THREADS), 0, ctx->stream, lazy_in, lazy_out, p);
+        } else {
+            NttPassArgs p; common(p);
+            p.postmul = !last ? 0 : coset_out ? 2 : have_scale ? 1 : 0;      // without a scale the last pass stores as it is
+            p.tw = (const Fr *)(rq.inverse ? t.inv.p : t.fwd.p);
+            if (p.premul) { p.pw_lo = (const Fr *)t.pw_lo_f.p; p.pw_hi = (const Fr *)t.pw_hi_f.p; }
+            if (p.postmul == 2) { p.pw_lo = (const Fr *)t.pw_lo_i.p; p.pw_hi = (const Fr *)t.pw_hi_i.p; }
+            p.scale = to_dev(scale);
+            hipLaunchKernelGGL(k_ntt_pass, grid, dim3(NTT_THREADS), 0, ctx->stream, first ? rq.in[0] : scratch, last ? rq.out[0] : scratch, p);
         }
-        ctx->stats["ntt_passes"] = (double)npass;
-        ctx->stats["ntt_fr29"] = 1;
-        return VSP_OK;
-    }
-    ctx->stats["ntt_fr29"] = 0;
-
-    unsigned s0 = 0;
-    for (unsigned i = 0; i < npass; i++) {
-        NttPassArgs p;
-        memset(&p, 0, sizeof p);
-        p.log_n = log_m; p.s0 = s0; p.s1 = s0 + stages[i];
-        p.tlog = ctx->ntt.log;
-        p.first = (i == 0); p.last = (i == npass - 1);
-        p.clog = npass == 1 ? 0 : NTT_TILE_LOG - stages[i];
-        p.tw = (const Fr *)(inverse ? ctx->ntt.inv.p : ctx->ntt.fwd.p);
-        p.premul = (p.first && coset_g && !inverse) ? 1 : 0;
-        p.postmul = 0;
-        if (p.last) {
-            if (inverse && coset_g) p.postmul = 2;
-            else if (have_scale) p.postmul = 1;
-        }
-        if (p.premul) { p.pw_lo = (const Fr *)ctx->ntt.pw_lo_f.p; p.pw_hi = (const Fr *)ctx->ntt.pw_hi_f.p; }
-        if (p.postmul == 2) { p.pw_lo = (const Fr *)ctx->ntt.pw_lo_i.p; p.pw_hi = (const Fr *)ctx->ntt.pw_hi_i.p; }
-        p.scale = to_dev(scale);
-        if (!p.first && p.s0 < p.clog) return set_error(ctx, VSP_ERR_UNSUPPORTED, "ntt: pass plan");
-        const Fr *src = (i == 0) ? d_a : scratch;
-        Fr *dst = (npass == 1 || i == npass - 1) ? d_a : scratch;
-        unsigned tile_log = stages[i] + p.clog;
-        unsigned blocks = (unsigned)(n >> tile_log);
-        hipLaunchKernelGGL(k_ntt_pass, dim3(blocks), dim3(NTT_THREADS), 0, ctx->stream, src, dst, p);
         VSP_LAUNCH_CHECK();
-        s0 = p.s1;
-    }
-    if (log_m == 0 && have_scale) {
-        // m = 1: the transform is the identity; only an explicit extra scale would matter (not used)
     }
     ctx->stats["ntt_passes"] = (double)npass;
+    ctx->stats["ntt_fr29"] = use29 ? 1 : 0;
     return VSP_OK;
 }
 

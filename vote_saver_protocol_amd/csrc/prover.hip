@@ -414,7 +414,7 @@ static int prove_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk,
         VSP_TRY(launch_on_bases(ctx, 4, pk->L, 0, plan_l)); l.plan_from = 4;
     }
     if (h_first) {
-        VSP_TRY(witness_map_device(ctx, dA, dB, dC, &cs->dom, dH));
+        VSP_TRY(witness_map_device(ctx, &cs->dom, dA, dB, dC, 3 * m, 1, dH, m));
         VSP_TRY(launch_on_bases(ctx, 0, pk->H, 0, h));
     }
     VSP_TRY(launch_on_bases(ctx, 1, pk->A, 0, a));
@@ -423,7 +423,7 @@ static int prove_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk,
     b.plan_from = pk->B1->pre_c == pk->A->pre_c ? 1 : -1; VSP_TRY(launch_on_bases(ctx, 2, pk->B1, 0, b));
     VSP_TRY(launch_on_bases(ctx, 4, pk->L, 0, l));
     if (!h_first) {
-        VSP_TRY(witness_map_device(ctx, dA, dB, dC, &cs->dom, dH));
+        VSP_TRY(witness_map_device(ctx, &cs->dom, dA, dB, dC, 3 * m, 1, dH, m));
         VSP_TRY(launch_on_bases(ctx, 0, pk->H, 0, h));
     }
     lap("prove_launch_ms");
@@ -511,7 +511,7 @@ static int prove_batch_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_p
     VSP_HIP(hipMemcpy2DAsync(abc + nc, 3 * m * sizeof(Fr), dz, zs * sizeof(Fr), (ni + 1) * sizeof(Fr), K, hipMemcpyDeviceToDevice, st));      // the rows "input_i * 0 = 0" of A
     VSP_HIP(hipStreamSynchronize(st));                       // `ones` goes out of scope; the copies above are queued from pageable memory anyway
     VSP_TRY(prove_use_streams(ctx));                         // the H chain on the context's stream (prove_launch_impl)
-    VSP_TRY(witness_map_device_batch(ctx, abc, (unsigned)K, &cs->dom, dH));
+    VSP_TRY(witness_map_device(ctx, &cs->dom, abc, abc + m, abc + 2 * m, 3 * m, (unsigned)K, dH, m));
     MsmRequest h(dH, m - 1), a(dz, nv + 1), l(dz + ni + 1, nv - ni);      // as in prove_launch_impl, K vectors each
     h.dense = true; h.batch = a.batch = l.batch = (unsigned)K; h.stride = m; a.stride = l.stride = zs;      // H coefficients are dense
     VSP_TRY(launch_on_bases(ctx, 0, pk->H, 0, h));
