@@ -30,7 +30,7 @@ def test_makefile_carries_the_soundness_flags():
     assert re.search(r"^CXXFLAGS \?= .*\$\(SOUND\)", mk, re.M)
     dry = subprocess.run(["make", "-n", "-B", "-C", CSRC, "BUILD=/tmp/vsp_dry_build", "OUT=/tmp/vsp_dry.so"], capture_output=True, text=True)
     cmds = [l for l in dry.stdout.split("\n") if "hipcc" in l and " -c " in l]
-    assert len(cmds) >= 11 and all("-enable-misched=0" in c and "-verify-machineinstrs" in c for c in cmds), dry.stdout[-2000:]
+    assert len(cmds) >= 12 and all("-enable-misched=0" in c and "-verify-machineinstrs" in c for c in cmds), dry.stdout[-2000:]
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")

@@ -149,14 +149,17 @@ def test_fp28_kernel_known_answer_check_and_fallback(cref):
     table; a failed check switches the context to the generic kernel, results unchanged."""
     c = v.Context(0)
     try:
+        # the caller's tuning options reach none of the check's legs (each pins its own), and the caller's launches keep them
+        c.set_option("msm_window_bits", 10); c.set_option("msm_split", 64); c.set_option("msm_dimbits", 0)
         n = 3000
         bases = cref.g1_batch_mul_gen(rand_fr_array(n, 21)); ss = rand_fr_array(n, 22)
         b2 = cref.g2_batch_mul_gen(rand_fr_array(1100, 23))
         exp = cref.msm_g1(bases, ss)
         assert np.array_equal(v.multiexp(c, bases, ss, 1), exp)
-        assert c.stat("msm_fp28_selfcheck_g1") == 1.0
+        assert c.stat("msm_fp28_selfcheck_g1") == 1.0 and c.stat("msm_fp28_selfcheck_detail_g1") == 0
+        assert c.stat("msm_window_bits") == 10 and c.stat("msm_split") == 64
         B2 = c.upload_bases(b2, 2)
-        assert c.stat("msm_fp28_selfcheck_g2") == 1.0
+        assert c.stat("msm_fp28_selfcheck_g2") == 1.0 and c.stat("msm_fp28_selfcheck_detail_g2") == 0
         B2.free()
     finally:
         c.close()

@@ -1,5 +1,5 @@
-// extern "C" surface of libvsp_hip.so (declared in include/vsp.h): context, device memory, MSM / NTT /
-// witness_map entry points and Jacobian record folding (the point compression lives with the other wire formats in wire.hip).
+// extern "C" surface of libvsp_hip.so (declared in include/vsp.h): context, device memory, MSM / NTT / witness_map entry points and
+// Jacobian record folding (resident bases live in bases.hip, the point compression with the other wire formats in wire.hip).
 #include "common.h"
 #include "fp28.h"
 #include "lane_view.h"
@@ -34,8 +34,6 @@ template <class HF> static int finish_affine(const XYZZ<HF> &acc, uint64_t *out_
     if (out_is_inf) *out_is_inf = is_inf(acc) ? 1 : 0;
     return VSP_OK;
 }
-// bytes of one row of a group's 28-bit-limb table
-static size_t row28_bytes(int group) { return with_group(group, [](auto g) { return sizeof(typename decltype(g)::Row28); }); }
 
 // elementwise field operations on canonical values (diagnostic entry point vsp_selftest_field)
 template <class F> __global__ __launch_bounds__(64) void k_selftest_field(int op, const F *a, const F *b, F *out, size_t n) {
@@ -263,235 +261,8 @@ int vsp_host_unregister(vsp_ctx *ctx, void *ptr) {
     return VSP_OK;
 }
 
-// ---- bases ------------------------------------------------------------------------------------
-}  // extern "C"
-// Known-answer check of the hand-laid-out field routines THROUGH the kernels that use them (their products are entered with a private
-// calling convention the compiler's hazard recogniser and register allocator cannot see into; field-level selftests run them in another
-// code arrangement).  Once per context and group, before the first 28-bit table is used, over points the LIBRARY generates (4096
-// multiples of the generator: in the subgroup by construction, independent of whatever the caller uploads): the same multi-exponentiation
-//   (a) through k_accum28 over the endomorphism layout, the 28-bit merges (k_merge_a, k_merge2: its scalars hold zeros and ones, so one
-//       bucket is split in tens of parts), k_dimsum and k_dimbits / k_dimweight -- the default plan;
-//   (b) the same with short bucket parts forced ("msm_split" = 6: every bucket is cut in several parts, the merges' full additions run
-//       thousands of times) and the other last step of the bucket reduction;
-//   (c) through the generic 12 x 32-bit kernels, no split;
-//   (d), (e) the default plan again with 6-bit and with 12-bit windows: other digit splits (q0, q1) of the bucket reduction, other lane counts
-//       per sum in k_dimsum_mixed, and -- the last 512 points being ONE point under 512 different scalars -- bucket sums that coincide all
-//       over the reduction: the doubling branch of the full addition inside k_dimsum(_mixed), k_dimbits and the merges (round 4).
-// All five affine results must be identical.  On a mismatch the 28-bit kernels are switched off for this context ("msm_fp28" = 0:
-// every later multi-exponentiation takes the generic kernels).  Returns true when 28-bit tables may be used.
-template <class G> static bool fp28_known_answer_check(vsp_ctx *ctx) {
-    using HF = typename G::HF;
-    const int gi = G::ID - 1;
-    if (ctx->fp28_checked[gi] != 0) return ctx->fp28_checked[gi] > 0;
-    if (ctx->msm_work[0].active) return true;                 // slot 0 busy (unusual): check at the next table instead
-    const size_t n = 4096;
-    std::vector<uint64_t> sc(2 * n * 4);                      // [0, n): the multiples that make the points; [n, 2n): the scalars of the check
-    uint64_t x = 0x9E3779B97F4A7C15ULL ^ (uint64_t)G::ID;
-    auto next = [&]() { x += 0x9E3779B97F4A7C15ULL; uint64_t z = x; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL; z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL; return z ^ (z >> 31); };
-    for (size_t i = 0; i < 2 * n; i++) {
-        sc[4 * i] = next(); sc[4 * i + 1] = next(); sc[4 * i + 2] = next(); sc[4 * i + 3] = next() >> 2;     // < 2^254 < r
-        if (i >= n && i % 7 == 3) { sc[4 * i] &= 1; sc[4 * i + 1] = sc[4 * i + 2] = sc[4 * i + 3] = 0; }     // zeros and ones among the check's scalars
-    }
-    // equal points and opposite points under equal scalars: the same bucket meets P + P (the doubling path of every addition routine, the
-    // equal-x hand-back of the accumulation kernel) and P - P (the infinity paths) in all three pipelines
-    for (size_t i = 1; i < n; i++) {
-        if (i % 16 == 5) for (int j = 0; j < 4; j++) sc[4 * i + j] = sc[4 * (i - 1) + j];                    // the same point twice
-        else if (i % 16 == 9) {                                                                             // a point and its negative: r - k
-            unsigned __int128 borrow = 0;
-            for (int j = 0; j < 4; j++) {
-                const unsigned __int128 d = (unsigned __int128)FrP64::MOD[j] - sc[4 * (i - 1) + j] - borrow;
-                sc[4 * i + j] = (uint64_t)d; borrow = (d >> 64) & 1;
-            }
-        } else continue;
-        for (int j = 0; j < 4; j++) sc[4 * (n + i) + j] = sc[4 * (n + i - 1) + j];                           // ... under the same scalar
-    }
-    for (size_t i = n - 511; i < n; i++) for (int j = 0; j < 4; j++) sc[4 * i + j] = sc[4 * (n - 512) + j];  // one point 512 times, scalars as drawn
-    const size_t esz = sizeof(typename G::Point), row = sizeof(typename G::Row28);
-    const std::string sfx = "_g" + std::to_string(G::ID);        // of the stat names
-    void *d_pts = nullptr, *t28 = nullptr;
-    bool same = false, ran = false;
-    OptScope saved(ctx, {"msm_split", "msm_dimbits", "msm_window_bits"});      // (the legs below set them; they come back at the return)
-    if (ensure(ctx, ctx->msm_scalars, 2 * n * 32) == VSP_OK && ensure(ctx, ctx->val_flag, 16) == VSP_OK &&
-        hipMemcpyAsync(ctx->msm_scalars.p, sc.data(), 2 * n * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
-        hipStreamSynchronize(ctx->stream) == hipSuccess && hipMalloc(&d_pts, n * esz) == hipSuccess && hipMalloc(&t28, 2 * n * row) == hipSuccess) {
-        const Fr *dk = (const Fr *)ctx->msm_scalars.p, *ds = dk + n;
-        int rc = fixed_base_mul<G>(ctx, dk, n, d_pts);
-        if (rc == VSP_OK) rc = bases_to_mont<G>(ctx, d_pts, (typename G::Point *)d_pts, n, 0, (uint32_t *)ctx->val_flag.p);
-        if (rc == VSP_OK) rc = msm_table28<G>(ctx, (const typename G::Point *)d_pts, n, t28, true);
-        if (rc == VSP_OK && hipStreamSynchronize(ctx->stream) == hipSuccess) {
-            ran = true;
-            auto run = [&](const void *table, bool glv, long split, long dimbits, uint64_t *aff, int *inf, long wbits = 0) -> bool {
-                if (wbits) ctx->opts["msm_window_bits"] = wbits; else ctx->opts.erase("msm_window_bits");
-                if (split) ctx->opts["msm_split"] = split; else ctx->opts.erase("msm_split");
-                if (dimbits >= 0) ctx->opts["msm_dimbits"] = dimbits; else ctx->opts.erase("msm_dimbits");
-                MsmRequest rq(ds, n); rq.bases = d_pts; rq.dense = true; rq.table28 = table; rq.glv = glv;
-                XYZZ<HF> r;
-                if (msm_slot_launch<G>(ctx, 0, rq) != VSP_OK || msm_slot_finish<G>(ctx, 0, &r) != VSP_OK) return false;
-                host_store_affine(aff, xyzz_to_affine(r)); *inf = is_inf(r);
-                return true;
-            };
-            uint64_t ra[24], rb[24], rc3[24], rd[24], re[24]; int ia = 0, ib = 0, ic = 0, id = 0, ie = 0;
-            memset(ra, 0, sizeof ra); memset(rb, 0, sizeof rb); memset(rc3, 0, sizeof rc3); memset(rd, 0, sizeof rd); memset(re, 0, sizeof re);
-            const bool okr = run(t28, true, 0, -1, ra, &ia) && run(t28, true, 6, G::ID == 1 ? 0 : 1, rb, &ib) && run(nullptr, false, 0, -1, rc3, &ic) &&
-                             run(t28, true, 0, -1, rd, &id, 6) && run(t28, true, 0, -1, re, &ie, 12);
-            same = okr && ia == ic && ib == ic && id == ic && ie == ic && !ic && memcmp(ra, rc3, sizeof ra) == 0 && memcmp(rb, rc3, sizeof rb) == 0 &&
-                   memcmp(rd, rc3, sizeof rd) == 0 && memcmp(re, rc3, sizeof re) == 0;
-            // which leg differed (stat "msm_fp28_selfcheck_detail_g1/2"): 1 = the default 28-bit pipeline, 2 = the split-bucket / other reduction
-            // pipeline, 4 = a point at infinity where there should be none, 8 = a launch failed, 16 / 32 = the 6-bit / 12-bit window legs
-            ctx->stats["msm_fp28_selfcheck_detail" + sfx] =
-                (double)((okr ? 0 : 8) | ((ia != ic || memcmp(ra, rc3, sizeof ra)) ? 1 : 0) | ((ib != ic || memcmp(rb, rc3, sizeof rb)) ? 2 : 0) | (ic ? 4 : 0) |
-                         ((id != ic || memcmp(rd, rc3, sizeof rd)) ? 16 : 0) | ((ie != ic || memcmp(re, rc3, sizeof re)) ? 32 : 0));
-        }
-    }
-    if (d_pts) hipFree(d_pts);
-    if (t28) hipFree(t28);
-    hipGetLastError();
-    if (!ran) { ctx->stats["msm_fp28_selfcheck" + sfx] = 0.0; return false; }      // could not run (out of memory): no verdict, no 28-bit table this time
-    if (opt(ctx, "msm_fp28_selfcheck_fault", 0)) same = false;   // test hook: exercise the fallback
-    ctx->fp28_checked[gi] = same ? 1 : -1;
-    ctx->stats["msm_fp28_selfcheck" + sfx] = same ? 1.0 : -1.0;
-    if (!same) { ctx->opts["msm_fp28"] = 0; ctx->err = "msm: the 28-bit-limb kernels failed their known-answer check; generic kernels in use"; }
-    return same;
-}
-// the points once more on 14 x 28-bit limbs for the accumulation kernel (fp28.h); option "msm_fp28" = 0 switches it off.
-// Plain bases (no window multiples) whose points are known to satisfy phi(P) = lambda P (vsp_bases.in_subgroup) get the endomorphism
-// layout: 2 count rows, (P_i, phi(P_i)) interleaved (option "msm_glv" = 0: off; 2: on for any size and WITHOUT the check -- the caller vouches)
-static bool glv_wanted(vsp_ctx *ctx, int group, size_t count, unsigned pre_c) {
-    const long want = opt(ctx, "msm_fp28", 1), want_glv = opt(ctx, "msm_glv", 1);
-    const size_t row = row28_bytes(group);
-    // The split halves the bucket sets (and the host Horner chain) but doubles the table and the sort's input.  Measured
-    // (tools/msm_sizes.py, bench.py; one in flight / three in flight, ms): G1 2^16 1.49 / 1.42 -> 1.35 / 0.80, G1 2^18 2.31 / 1.29 ->
-    // 2.04 / 1.27, G1 2^20 4.24 / 3.35 -> 3.98 / 3.34, a 2^20-constraint proof 8.71 -> 8.45 ms (plain key: 9.98 -> 8.95);
-    // G2 2^16 3.01 / 1.58 -> 2.67 / 1.40, G2 2^18 5.21 / 3.21 -> 5.56 / 2.90, G2 2^19 7.23 / 4.82 -> 8.28 / 5.58 (dense scalars:
-    // the lane-pair merges of the split buckets cost more than the windows saved).  So: on while the doubled table is at most
-    // 256 MB for G1 (2^20 points) and 128 MB for G2 (2^18 points); "msm_glv" = 2 forces it on, 0 switches it off.
-    const size_t glv_limit = ((size_t)256 << 20) / group;      // 256 MB (G1), 128 MB (G2)
-    return want && want_glv && pre_c == 0 && count >= 1024 && count < ((size_t)1 << 30) && (want_glv >= 2 || 2 * count * row <= glv_limit);
-}
-static void build_table28(vsp_ctx *ctx, vsp_bases *b, size_t count) {
-    if (b->d28) { hipFree(b->d28); b->d28 = nullptr; }
-    b->glv = false;
-    const long want = opt(ctx, "msm_fp28", 1), want_glv = opt(ctx, "msm_glv", 1);
-    // "msm_fp28" = 2 (diagnostics: bisecting a failed check with tools/fuzz_msm.py): the 28-bit kernels WITHOUT the context-time check
-    if (!want || (want < 2 && !with_group(b->group, [&](auto g) { return fp28_known_answer_check<decltype(g)>(ctx); }))) return;   // the check may have just switched "msm_fp28" off
-    const size_t row = row28_bytes(b->group);
-    bool glv = glv_wanted(ctx, b->group, count, b->pre_c) && (b->in_subgroup > 0 || want_glv >= 2);
-    if (b->pre_c && b->pre_split && want_glv && (b->in_subgroup > 0 || want_glv >= 2)) {
-        // window multiples for dense scalars: the 128 / c windows of a split scalar, every row with its endomorphism image beside it
-        glv = true;
-        count = b->n * ((128 + b->pre_c - 1) / b->pre_c);
-    }
-    void *t28 = nullptr;
-    if (hipMalloc(&t28, count * row * (glv ? 2 : 1)) != hipSuccess) { hipGetLastError(); return; }
-    int rc = with_group(b->group, [&](auto g) { using G = decltype(g); return msm_table28<G>(ctx, (const typename G::Point *)b->d, count, t28, glv); });
-    if (rc == VSP_OK && hipStreamSynchronize(ctx->stream) == hipSuccess) { b->d28 = t28; b->glv = glv; }
-    else { hipFree(t28); hipGetLastError(); }
-}
-// queue the subgroup check of plain resident bases: bit 2 of the context's validation word
-static int bases_subgroup_check(vsp_ctx *ctx, const vsp_bases *b) {
-    return with_group(b->group, [&](auto g) { using G = decltype(g); return subgroup_check<G>(ctx, (const typename G::Point *)b->d, b->n, (uint32_t *)ctx->val_flag.p); });
-}
-namespace vsp {
-int bases_create(vsp_ctx *ctx, int group, const void *src, bool src_on_device, size_t n, int trust, vsp_bases **out) {
-    *out = nullptr;
-    if (!ctx) return VSP_ERR_ARG;
-    if (!src && n) return set_error(ctx, VSP_ERR_ARG, "bases: null pointer");
-    hipSetDevice(ctx->device);
-    const size_t esz = point_bytes(group);
-    vsp_bases *b = new vsp_bases();
-    b->group = group; b->n = n;
-    if (hipMalloc(&b->d, n ? n * esz : 16) != hipSuccess) { delete b; return set_error(ctx, VSP_ERR_NOMEM, "bases: hipMalloc failed"); }
-    if (n) {
-        int rc;
-        if (!src_on_device) {
-            if (hipMemcpyAsync(b->d, src, n * esz, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) { hipFree(b->d); delete b; return set_error(ctx, VSP_ERR_HIP, "bases: H2D failed"); }
-            src = b->d;                      // convert in place
-        }
-        // boundary validation (include/vsp.h): coordinates below p always; the curve equation unless option "bases_check_curve" = 0
-        const long check_curve = opt(ctx, "bases_check_curve", 1);
-        // the subgroup (option "bases_check_subgroup"): 1 (default) = checked where the endomorphism split would be used -- bases that fail
-        // keep the plain layout, whose result is exact for ANY curve point (like the reference's generic multiexp); 2 = always checked, a
-        // failing upload is refused; 0 = never checked, and then never split unless "msm_glv" = 2 (the caller vouches for the points)
-        const long check_sub = opt(ctx, "bases_check_subgroup", 1);
-        uint32_t h_flag = 0;
-        rc = ensure(ctx, ctx->val_flag, 16);
-        if (rc == VSP_OK && hipMemsetAsync(ctx->val_flag.p, 0, 16, ctx->stream) != hipSuccess) rc = set_error(ctx, VSP_ERR_HIP, "bases: memset failed");
-        if (rc == VSP_OK)
-            rc = with_group(group, [&](auto g) {
-                using G = decltype(g);
-                return bases_to_mont<G>(ctx, src, (typename G::Point *)b->d, n, (int)check_curve, (uint32_t *)ctx->val_flag.p);
-            });
-        bool sub_checked = false;
-        if (trust == BASES_OWN) b->in_subgroup = 1;
-        // policy 2 covers every upload whose points the library did not make itself (caller's handles, one call's host buffers, key blobs),
-        // with or without the curve check; policy 1 only the uploads that would get the endomorphism layout
-        else if (rc == VSP_OK && (check_sub >= 2 || (trust == BASES_CALLER && check_curve && check_sub == 1 && glv_wanted(ctx, group, n, 0)))) {
-            rc = bases_subgroup_check(ctx, b);
-            sub_checked = true;
-        }
-        if (rc == VSP_OK && (hipMemcpyAsync(&h_flag, ctx->val_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                             hipStreamSynchronize(ctx->stream) != hipSuccess)) rc = set_error(ctx, VSP_ERR_HIP, "bases: conversion failed");
-        if (rc == VSP_OK && (h_flag & 3u))
-            rc = set_error(ctx, VSP_ERR_ARG, (h_flag & 1u) ? "bases: a coordinate is not canonical (>= p)" : "bases: a point is not on the curve");
-        if (rc == VSP_OK && sub_checked) {
-            ctx->stats["bases_subgroup_checks"] += 1;
-            b->in_subgroup = (h_flag & 4u) ? -1 : 1;
-            if (h_flag & 4u) {
-                ctx->stats["bases_outside_subgroup"] += 1;
-                if (check_sub >= 2) rc = set_error(ctx, VSP_ERR_ARG, "bases: a point is not in the order-r subgroup");
-            }
-        }
-        if (rc != VSP_OK) { hipFree(b->d); delete b; return rc; }
-        if (n >= 1024) build_table28(ctx, b, n);       // best effort: without it the 12 x 32-bit kernel runs
-    }
-    *out = b;
-    return VSP_OK;
-}
-}  // namespace vsp
-// caller's bases as a handle, or null with the reason in the context's error text
-static vsp_bases *bases_upload(vsp_ctx *ctx, int group, const void *src, bool src_on_device, size_t n) {
-    vsp_bases *b;
-    bases_create(ctx, group, src, src_on_device, n, BASES_CALLER, &b);
-    return b;
-}
-extern "C" {
-vsp_bases *vsp_bases_upload_g1(vsp_ctx *ctx, const uint64_t *bases, size_t n) { return bases_upload(ctx, 1, bases, false, n); }
-vsp_bases *vsp_bases_upload_g2(vsp_ctx *ctx, const uint64_t *bases, size_t n) { return bases_upload(ctx, 2, bases, false, n); }
-vsp_bases *vsp_bases_from_device_g1(vsp_ctx *ctx, const void *d_bases, size_t n) { return bases_upload(ctx, 1, d_bases, true, n); }
-vsp_bases *vsp_bases_from_device_g2(vsp_ctx *ctx, const void *d_bases, size_t n) { return bases_upload(ctx, 2, d_bases, true, n); }
-size_t vsp_bases_count(const vsp_bases *b) { return b ? b->n : 0; }
-size_t vsp_bases_device_bytes(const vsp_bases *b) {
-    if (!b) return 0;
-    const size_t slices = b->pre_c ? 255 / b->pre_c + 1 : 1, count = b->n * slices;
-    const size_t esz = point_bytes(b->group), row = row28_bytes(b->group);
-    const size_t rows28 = (b->pre_c && b->glv) ? b->n * ((128 + b->pre_c - 1) / b->pre_c) * 2 : count * (b->glv ? 2 : 1);
-    return (count ? count * esz : 16) + (b->d28 ? rows28 * row : 0);
-}
-void vsp_bases_free(vsp_ctx *ctx, vsp_bases *b) {
-    if (!b) return;
-    if (ctx) { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
-    if (b->d) hipFree(b->d);
-    if (b->d28) hipFree(b->d28);
-    delete b;
-}
-
 // ---- MSM ----------------------------------------------------------------------------------------
 }  // extern "C"
-namespace vsp {
-// queue the multi-exponentiation rq over points [first, first + rq.n) of resident bases on a work slot: plain bases or a table of window
-// multiples, one scalar vector or a batch
-int launch_on_bases(vsp_ctx *ctx, unsigned slot, const vsp_bases *bases, size_t first, MsmRequest rq) {
-    if (slot < VSP_MSM_SLOTS) ctx->slot_group[slot] = bases->group;
-    if (bases->pre_c && rq.batch && (!opt(ctx, "msm_batch_tables", 1) || bases->pre_c > 16))      // (a batch over the table: ONE bucket set per vector)
-        return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: a batch over this table of window multiples is not supported (plain bases, or windows of at most 16 bits)");
-    const size_t row = row28_bytes(bases->group), esz = point_bytes(bases->group);
-    MsmPre pre{bases->n, first, bases->pre_c, bases->d28, bases->glv};
-    rq.glv = bases->glv;
-    if (bases->pre_c) { rq.bases = bases->d; rq.pre = &pre; }
-    else { rq.bases = (const char *)bases->d + first * esz; rq.table28 = bases->d28 ? (const char *)bases->d28 + first * row * (bases->glv ? 2 : 1) : nullptr; }
-    return with_group(bases->group, [&](auto g) { return msm_slot_launch<decltype(g)>(ctx, slot, rq); });
-}
-}  // namespace vsp
 // vsp_msm_launch on slot 0 (its argument checks), its finish, then done(result) with the result in the group's host form
 template <class Fn> static int msm_resident_then(vsp_ctx *ctx, const vsp_bases *bases, size_t first, size_t n, const void *d_scalars, Fn &&done) {
     VSP_TRY(vsp_msm_launch(ctx, 0, bases, first, n, d_scalars));
@@ -503,53 +274,6 @@ template <class Fn> static int msm_resident_then(vsp_ctx *ctx, const vsp_bases *
 }
 
 extern "C" {
-
-static int bases_precompute(vsp_ctx *ctx, vsp_bases *b, unsigned window_bits, bool split);
-int vsp_bases_precompute(vsp_ctx *ctx, vsp_bases *b, unsigned window_bits) { return bases_precompute(ctx, b, window_bits, false); }
-int vsp_bases_precompute_split(vsp_ctx *ctx, vsp_bases *b, unsigned window_bits) { return bases_precompute(ctx, b, window_bits, true); }
-static int bases_precompute(vsp_ctx *ctx, vsp_bases *b, unsigned window_bits, bool split) {
-    if (!ctx) return VSP_ERR_ARG;
-    if (!b) return set_error(ctx, VSP_ERR_ARG, "precompute: null bases");
-    if (split && b->pre_c == 0) {
-        // the endomorphism rows need the order-r subgroup (include/vsp.h "bases_check_subgroup"): bases that were not checked at upload are checked now
-        const long want_glv = opt(ctx, "msm_glv", 1);
-        if (b->in_subgroup == 0 && want_glv == 1 && b->n) {
-            VSP_HIP(hipSetDevice(ctx->device));
-            VSP_TRY(ensure(ctx, ctx->val_flag, 16));
-            VSP_HIP(hipMemsetAsync(ctx->val_flag.p, 0, 4, ctx->stream));
-            VSP_TRY(bases_subgroup_check(ctx, b));
-            uint32_t h_flag = 0;
-            VSP_HIP(hipMemcpyAsync(&h_flag, ctx->val_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-            VSP_HIP(hipStreamSynchronize(ctx->stream));
-            ctx->stats["bases_subgroup_checks"] += 1;
-            b->in_subgroup = (h_flag & 4u) ? -1 : 1;
-            if (h_flag & 4u) ctx->stats["bases_outside_subgroup"] += 1;
-        }
-    }
-    if (window_bits == 0) {                     // automatic: about n * W / 2^(c-1) = 256 points per shared bucket
-        unsigned lg = ceil_log2(b->n ? b->n : 1);
-        window_bits = lg < 11 ? 8 : (lg - 3 > 16 ? 16 : lg - 3);
-    }
-    if (window_bits < 8 || window_bits > 22) return set_error(ctx, VSP_ERR_ARG, "precompute: window_bits must be 8..22");
-    if (b->pre_c == window_bits) return VSP_OK;
-    if (b->pre_c) return set_error(ctx, VSP_ERR_ARG, "precompute: bases already precomputed for another window size");
-    if (b->n == 0) { b->pre_c = window_bits; b->pre_split = split; return VSP_OK; }
-    VSP_HIP(hipSetDevice(ctx->device));
-    const unsigned W = 255 / window_bits + 1;
-    const size_t esz = point_bytes(b->group);
-    if ((size_t)W * b->n >= ((size_t)1 << 31)) return set_error(ctx, VSP_ERR_UNSUPPORTED, "precompute: table too large to index");
-    void *table = nullptr;
-    if (hipMalloc(&table, (size_t)W * b->n * esz) != hipSuccess) return set_error(ctx, VSP_ERR_NOMEM, "precompute: hipMalloc failed");
-    VSP_HIP(hipMemcpyAsync(table, b->d, b->n * esz, hipMemcpyDeviceToDevice, ctx->stream));
-    int rc = with_group(b->group, [&](auto g) { using G = decltype(g); return msm_precompute<G>(ctx, (typename G::Point *)table, b->n, window_bits); });
-    if (rc != VSP_OK) { hipFree(table); return rc; }
-    VSP_HIP(hipStreamSynchronize(ctx->stream));
-    hipFree(b->d);
-    b->d = table; b->pre_c = window_bits;
-    b->pre_split = split;                                    // only now: a refused or failed call leaves the handle as it was (bases outside the subgroup get the ordinary table: build_table28 decides)
-    build_table28(ctx, b, (size_t)W * b->n);
-    return VSP_OK;
-}
 
 int vsp_msm_resident(vsp_ctx *ctx, const vsp_bases *bases, size_t first, size_t n, const void *d_scalars, uint64_t *out_affine, int *out_is_inf) {
     return msm_resident_then(ctx, bases, first, n, d_scalars, [&](const auto &a) { return finish_affine(a, out_affine, out_is_inf); });

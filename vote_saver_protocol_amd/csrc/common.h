@@ -123,6 +123,9 @@ struct MsmWork {
     size_t n = 0, n_eff = 0;
 };
 static constexpr unsigned VSP_MSM_SLOTS = 6;
+// what options "msm_window_bits", "msm_split" and "msm_dimbits" choose, pinned for one launch: window bits (0 = automatic), bucket part
+// length (0 = automatic), the bucket reduction's last step (1 = k_dimbits, 0 = k_dimweight, -1 = by group)
+struct MsmTuning { long window_bits = 0, split = 0, dimbits = -1; };
 // one multi-exponentiation queued on a work slot (msm_slot_launch)
 struct MsmRequest {
     const void *bases = nullptr;        // Affine<Fp> / Affine<Fp2>, Montgomery form: the points, or with `pre` the table of window multiples
@@ -138,6 +141,7 @@ struct MsmRequest {
     bool glv = false;                   // table28 (or pre->table28) holds (P_i, phi(P_i)) interleaved: split the scalars k = k1 + k2 lambda
     unsigned batch = 0;                 // 0: one scalar vector; K >= 1: a batch (MsmGeom.K), vector k at scalars + k * stride, one result each
     size_t stride = 0;
+    const MsmTuning *tuning = nullptr;  // null: the options
     MsmRequest(const Fr *scalars_ = nullptr, size_t n_ = 0) : scalars(scalars_), n(n_) {}
 };
 
@@ -260,18 +264,20 @@ namespace vsp {
 
 // option `name` of the context (vsp_set_option), or dflt when it was never set
 inline long opt(const vsp_ctx *ctx, const char *name, long dflt) { auto it = ctx->opts.find(name); return it != ctx->opts.end() ? it->second : dflt; }
-// the named options as they are at construction, present with a value or absent, put back when the scope ends (the 28-bit known-answer
-// check runs its legs under settings of their own)
-class OptScope {
-  public:
-    OptScope(vsp_ctx *ctx, std::initializer_list<const char *> names) : ctx_(ctx) {
-        for (const char *name : names) { auto it = ctx->opts.find(name); saved_.push_back({name, it != ctx->opts.end(), it != ctx->opts.end() ? it->second : 0}); }
-    }
-    ~OptScope() { for (const Saved &s : saved_) { if (s.had) ctx_->opts[s.name] = s.value; else ctx_->opts.erase(s.name); } }
-    OptScope(const OptScope &) = delete; OptScope &operator=(const OptScope &) = delete;
-  private:
-    struct Saved { std::string name; bool had; long value; };
-    vsp_ctx *ctx_; std::vector<Saved> saved_;
+// the verdict of a known-answer check (bases.hip fp28_known_answer_check, ntt.hip ntt29_known_answer_check): state and stat 1 when the
+// results matched, -1 when not -- option `fault` (a test hook) makes a match a mismatch.  A mismatch sets option `off` to 0 (the generic
+// kernels for the context's lifetime: beside vsp_set_option, the only write to the option map) and the error text to msg
+inline bool record_verdict(vsp_ctx *ctx, int &state, bool same, const char *fault, const std::string &stat, const char *off, const char *msg) {
+    if (opt(ctx, fault, 0)) same = false;
+    state = same ? 1 : -1;
+    ctx->stats[stat] = same ? 1.0 : -1.0;
+    if (!same) { ctx->opts[off] = 0; ctx->err = msg; }
+    return same;
+}
+// splitmix64: the known-answer checks' inputs
+struct SplitMix64 {
+    uint64_t x;
+    uint64_t operator()() { x += 0x9E3779B97F4A7C15ULL; uint64_t z = x; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL; z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL; return z ^ (z >> 31); }
 };
 int set_hip_error(vsp_ctx *ctx, hipError_t e, const char *what, const char *file, int line);
 // f(0) .. f(n - 1) on up to `max_threads` host threads (the host steps of a BATCH: the Horner chains over the window results of K

@@ -1681,18 +1681,18 @@ __global__ __launch_bounds__(MSM_THREADS, AccumWaves<F>::W) void k_subgroup_chec
     if (inf2 || !ex || !ey) atomicOr(flag, 4u);
 }
 
-// the bit-decomposed last step (k_dimbits) or the weighted one (k_dimweight): option "msm_dimbits" 1 / 0 forces either, default by group
-template <class FT> static bool use_dimbits(vsp_ctx *ctx, const MsmGeom &g) {
+// the bit-decomposed last step (k_dimbits) or the weighted one (k_dimweight): `forced` (MsmTuning.dimbits) 1 / 0 forces either, -1 by group
+template <class FT> static bool use_dimbits(long forced, const MsmGeom &g) {
     // room for 25 records per window in the slot's pinned buffer: the initial buffer for one vector (52 windows of 5 bits: no), the grown one
     // for a batch (msm_buffers grows it up to 64 MiB: K x Wk windows; k_dimweight's 16-addition chains took a fifth of a batch prover's kernel time)
     const size_t cap = g.K > 1 ? ((size_t)64 << 20) : MsmWork::PINNED_BYTES;
-    const long forced = opt(ctx, "msm_dimbits", -1);
     const bool want = forced >= 0 ? forced != 0 : (LaneView<FT>::LANES == 1 || g.Wr <= 2 || g.c > 16);      // wide windows: digits of 2^10 values and more only k_dimbits takes
     return want && (size_t)g.Wr * DIMBITS_STRIDE * sizeof(XYZZ<typename WinOut<FT>::type>) <= cap;
 }
-// merges + bucket reduction over the bucket sums of field FT (F, or Fp28 on the G1 28-bit path); winres in the host's form
+// merges + bucket reduction over the bucket sums of field FT (F, or Fp28 on the G1 28-bit path); winres in the host's form; dimbits: the
+// last step (use_dimbits)
 template <class FT>
-static int launch_tail(vsp_ctx *ctx, hipStream_t st, const MsmWork *pl, const MsmGeom &g, XYZZ<FT> *buckets, XYZZ<FT> *partials, XYZZ<FT> *dims,
+static int launch_tail(vsp_ctx *ctx, hipStream_t st, const MsmWork *pl, const MsmGeom &g, bool dimbits, XYZZ<FT> *buckets, XYZZ<FT> *partials, XYZZ<FT> *dims,
                        XYZZ<typename WinOut<FT>::type> *winres, XYZZ<typename WinOut<FT>::type> *winres_host) {
     using F = FT;
     constexpr unsigned NT = MsmBlock<F>::NT;
@@ -1747,7 +1747,7 @@ static int launch_tail(vsp_ctx *ctx, hipStream_t st, const MsmWork *pl, const Ms
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dimsum<F, (LL == 64 ? 64u : 32u)>), grid, dim3(64), 0, st, (const XYZZ<F> *)buckets, g, dims);
     }
     VSP_LAUNCH_CHECK();
-    if (use_dimbits<FT>(ctx, g)) {
+    if (dimbits) {
         // the results go straight into the slot's pinned host buffer (device-visible): no copy operation behind the kernel.  (A 29 KB
         // device-to-host copy per multi-exponentiation rides the DMA engines, behind the 32 MB witness upload of whichever proof another
         // context has just started: two contexts proved no faster than one.)
@@ -1760,9 +1760,9 @@ static int launch_tail(vsp_ctx *ctx, hipStream_t st, const MsmWork *pl, const Ms
 }
 
 // ------------------------------------------------------------------------------------------------
-// n: scalars that are neither 0 nor 1 (twice that with the endomorphism split: half-length scalars); windows: how many windows c bits need
-static unsigned pick_window_bits(vsp_ctx *ctx, size_t n, bool glv) {
-    const long forced = opt(ctx, "msm_window_bits", 0);
+// n: scalars that are neither 0 nor 1 (twice that with the endomorphism split: half-length scalars); windows: how many windows c bits need;
+// forced: MsmTuning.window_bits
+static unsigned pick_window_bits(vsp_ctx *ctx, long forced, size_t n, bool glv) {
     if (forced >= 2 && forced <= 23) return (unsigned)forced;
     unsigned L = ceil_log2(n ? n : 1);
     // mean bucket load n / 2^(c-1) of about 32 points balances the accumulation against the
@@ -1896,6 +1896,7 @@ struct MsmLaunch {
     const void *table28;                // the bases (or table) on 28-bit limbs, or null
     const Fr *scalars; size_t n;        // what the sort reads: with the endomorphism split 2 rq.n half-length scalars (k_glv_split)
     long sort_mode;                     // option "msm_sort": 1 never staged, 2 staged whenever c >= 17
+    MsmTuning tune;                     // the request's, or the options'
     bool fused_split, fused_scans, dimbits;      // dimbits: the bucket reduction's last step is k_dimbits (which decides how wide a digit may be)
     size_t M, Smax;                     // upper bounds on sorted entries and on bucket parts
     unsigned per_w, nblk, gblk, ablk;
@@ -1932,7 +1933,7 @@ template <class F> static int msm_geometry(vsp_ctx *ctx, MsmWork &wk, MsmLaunch 
         }
         wk.census_pending = false;
         if (glv) n_eff *= 2;                                  // two half-length scalars per counted scalar
-        g.c = pre ? pre->c : pick_window_bits(ctx, n_eff, glv);
+        g.c = pre ? pre->c : pick_window_bits(ctx, L.tune.window_bits, n_eff, glv);
         g.sbits = glv ? 128u : 255u;
         // 255-bit scalars: 255 / c + 1 windows cover the bits plus the carry of the signed recoding; split halves are magnitudes below
         // 2^127: ceil(128 / c) windows, and the top window's spare bit absorbs the carry
@@ -1948,7 +1949,7 @@ template <class F> static int msm_geometry(vsp_ctx *ctx, MsmWork &wk, MsmLaunch 
         g.single = pre ? 1u : 0u; g.idx_stride = pre ? (uint32_t)(pre->stride * imul) : 0u; g.idx_first = pre ? (uint32_t)(pre->first * imul) : 0u;
         g.Wr = pre ? g.K : g.W;                                // bucket sets: one per vector over a table of window multiples, else one per window
         g.G = (size_t)g.Wr * g.B;
-        const long t = opt(ctx, "msm_split", 0);
+        const long t = L.tune.split;
         if (pre) {
             // one bucket set: ~n_eff*W/B points per bucket; parts of T points, about 2^18 of them to fill the GPU evenly
             size_t est = n_eff * g.W / ((size_t)1 << 18);
@@ -1975,8 +1976,7 @@ template <class F> static int msm_geometry(vsp_ctx *ctx, MsmWork &wk, MsmLaunch 
     }
     g.bd = 8;
     // per group: a shared plan carries the window size, not the digit split.  Which last step the bucket reduction takes decides how wide a digit may be
-    MsmGeom probe = g; probe.q0 = probe.q1 = probe.q2 = 0;
-    L.dimbits = L.table28 ? use_dimbits<F28>(ctx, probe) : use_dimbits<F>(ctx, probe);
+    L.dimbits = L.table28 ? use_dimbits<F28>(L.tune.dimbits, g) : use_dimbits<F>(L.tune.dimbits, g);
     split_digits<F>(g, L.dimbits);
     return VSP_OK;
 }
@@ -2209,6 +2209,7 @@ template <class F> static int msm_accumulate(vsp_ctx *ctx, MsmWork &wk, const Ms
     const hipStream_t st = L.st;
     const MsmWork *pl = L.plan_from ? L.plan_from : &wk;
     XYZZ<F> *buckets = (XYZZ<F> *)wk.buckets.p, *partials = (XYZZ<F> *)wk.partials.p, *winres = (XYZZ<F> *)wk.winres.p;
+    wk.dimbits = L.dimbits;
     // (the diagnostic build without hand-laid-out routines runs the multi-exponentiation on the generic 12 x 32-bit kernels only: the
     // 28-bit reduction kernels over portable products crash this toolchain's backend -- Machine Copy Propagation / post-RA pseudo
     // expansion segfault in k_dimsum<Fp28> / k_dimsum<Fp2x28>; the 28-bit and 29-bit FIELD forms stay covered by vsp_selftest_field,
@@ -2249,8 +2250,7 @@ template <class F> static int msm_accumulate(vsp_ctx *ctx, MsmWork &wk, const Ms
                            (const uint32_t *)pl->off.p, (const uint32_t *)pl->suboff.p, (const uint32_t *)pl->partbucket.p, buckets, partials,
                            (const uint32_t *)(redo + 1), (const uint32_t *)redo, L.rq.glv, buckets28, partials28);
         VSP_LAUNCH_CHECK();
-        wk.dimbits = use_dimbits<F28>(ctx, g);
-        return launch_tail<F28>(ctx, st, pl, g, buckets28, partials28, (XYZZ<F28> *)wk.dims.p, winres, (XYZZ<F> *)wk.h_pinned);
+        return launch_tail<F28>(ctx, st, pl, g, L.dimbits, buckets28, partials28, (XYZZ<F28> *)wk.dims.p, winres, (XYZZ<F> *)wk.h_pinned);
     }
     VSP_HIP(hipEventRecord(wk.ev0, st));
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_accum<F>), dim3(L.ablk * LaneView<F>::LANES), dim3(MSM_THREADS), 0, st, bases, (const uint32_t *)pl->sorted.p,
@@ -2258,8 +2258,7 @@ template <class F> static int msm_accumulate(vsp_ctx *ctx, MsmWork &wk, const Ms
                        g.G, g.T, buckets, partials);
     VSP_HIP(hipEventRecord(wk.ev1, st));
     VSP_LAUNCH_CHECK();
-    wk.dimbits = use_dimbits<F>(ctx, g);
-    return launch_tail<F>(ctx, st, pl, g, buckets, partials, (XYZZ<F> *)wk.dims.p, winres, (XYZZ<F> *)wk.h_pinned);
+    return launch_tail<F>(ctx, st, pl, g, L.dimbits, buckets, partials, (XYZZ<F> *)wk.dims.p, winres, (XYZZ<F> *)wk.h_pinned);
 }
 
 // one multi-exponentiation (common.h MsmRequest); plan_from: the work slot rq.plan_from names, or null
@@ -2283,6 +2282,7 @@ static int msm_launch(vsp_ctx *ctx, MsmWork &wk, const MsmRequest &rq, const Msm
     L.plan_from = plan_from && plan_from->glv == L.rq.glv ? plan_from : nullptr;      // a plan over split scalars serves only launches that split alike
     wk.glv = L.rq.glv;
     L.sort_mode = opt(ctx, "msm_sort", 0);
+    L.tune = rq.tuning ? *rq.tuning : MsmTuning{opt(ctx, "msm_window_bits", 0), opt(ctx, "msm_split", 0), opt(ctx, "msm_dimbits", -1)};
     MsmGeom g; size_t n_eff = n;
     VSP_TRY(msm_geometry<F>(ctx, wk, L, g, n_eff));
     wk.g = g; wk.n_eff = n_eff;

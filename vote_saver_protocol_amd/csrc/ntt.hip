@@ -457,7 +457,7 @@ static Fr29 host_to_fr29_mont(const HFr &x) {
 }
 
 // Known-answer check of the 29-bit-limb butterflies THROUGH k_ntt29_pass (its product, vsp_mm29, is a hand-laid-out routine with a private
-// calling convention: see the note at capi.hip fp28_known_answer_check).  Once per context, before the first transform on that path: a
+// calling convention: see the note at bases.hip fp28_known_answer_check).  Once per context, before the first transform on that path: a
 // 2^13-point vector (two passes: the lazy planes between passes, the first and the last pass) goes through a forward coset transform
 // and an inverse coset transform on k_ntt29_pass and on the 8 x 32-bit k_ntt_pass, each path forced by its request; the outputs must
 // agree word for word.  On a mismatch the context falls back to the 8 x 32-bit kernel ("ntt_fr29" = 0) for its lifetime.  A check that
@@ -465,8 +465,7 @@ static Fr29 host_to_fr29_mont(const HFr &x) {
 static void ntt29_known_answer_check(vsp_ctx *ctx) {
     const unsigned lg = 13; const size_t n = (size_t)1 << lg, bytes = n * sizeof(Fr);
     std::vector<uint64_t> h(n * 4), o29(n * 4), o32(n * 4);
-    uint64_t x = 0x243F6A8885A308D3ULL;
-    auto next = [&]() { x += 0x9E3779B97F4A7C15ULL; uint64_t z = x; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL; z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL; return z ^ (z >> 31); };
+    SplitMix64 next{0x243F6A8885A308D3ULL};
     for (size_t i = 0; i < n; i++) { h[4 * i] = next(); h[4 * i + 1] = next(); h[4 * i + 2] = next(); h[4 * i + 3] = next() >> 2; }
     h[0] = h[1] = h[2] = h[3] = 0;                            // a zero and r - 1 among them
     h[4] = 0xffffffff00000000ULL; h[5] = 0x53bda402fffe5bfeULL; h[6] = 0x3339d80809a1d805ULL; h[7] = 0x73eda753299d7d48ULL;
@@ -491,10 +490,8 @@ static void ntt29_known_answer_check(vsp_ctx *ctx) {
     }
     hipGetLastError();
     if (!ran) { ctx->stats["ntt_fr29_selfcheck"] = 0.0; return; }
-    if (opt(ctx, "ntt_fr29_selfcheck_fault", 0)) same = false;      // test hook: exercise the fallback
-    ctx->ntt29_checked = same ? 1 : -1;
-    ctx->stats["ntt_fr29_selfcheck"] = same ? 1.0 : -1.0;
-    if (!same) { ctx->opts["ntt_fr29"] = 0; ctx->err = "ntt: the 29-bit-limb butterfly kernel failed its known-answer check; 8 x 32-bit kernel in use"; }
+    record_verdict(ctx, ctx->ntt29_checked, same, "ntt_fr29_selfcheck_fault", "ntt_fr29_selfcheck", "ntt_fr29",
+                   "ntt: the 29-bit-limb butterfly kernel failed its known-answer check; 8 x 32-bit kernel in use");
 }
 
 // whether the 29-bit butterflies are in use on this context; runs their known-answer check when it has not run yet.  Callers that set
