@@ -104,7 +104,7 @@ struct MsmWork {
     DevBuf cnt, off, cursor, nsub, suboff, blocksum, sorted, heavy, counters, digits, blockhist, partbucket, perm, sizehist;
     DevBuf buckets, partials, dims, winres, medium, redo;
     DevBuf buckets28, partials28;          // G1: bucket sums in the 14 x 28-bit form (fp28.h XYZZ<Fp28>)
-    DevBuf pairs_a, pairs_b, ms_h1, ms_h1s, ms_h2, ms_h2s;      // staged sort of large wide-window problems (msm_impl.inc k_ms_*)
+    DevBuf pairs_a, pairs_b, ms_h1, ms_h1s, ms_h2, ms_h2s;      // staged sort of large wide-window problems (msm_sort.hip k_ms_*)
     DevBuf tmp_sorted, tmp_lo, off_hi, cnt_hi;      // windows wider than 16 bits: the entries ordered by the high 15 bits of the bucket index, their low bits, the segment offsets
     DevBuf glv_scalars;                  // endomorphism split: 2n half-length scalars k1_i, k2_i (interleaved)
     bool glv = false;                    // this launch runs over the split scalars and the interleaved (P, phi(P)) table
@@ -144,6 +144,24 @@ struct MsmRequest {
     const MsmTuning *tuning = nullptr;  // null: the options
     MsmRequest(const Fr *scalars_ = nullptr, size_t n_ = 0) : scalars(scalars_), n(n_) {}
 };
+// what the stages of one msm_launch share: the request as the kernels see it and the sizes its geometry gives
+struct MsmLaunch {
+    MsmRequest rq;                      // the caller's, with batch >= 1 and glv only where the interleaved table is there
+    hipStream_t st;
+    const MsmWork *plan_from;           // the work whose digit sort / bucket plan this launch reuses, or null
+    const void *table28;                // the bases (or table) on 28-bit limbs, or null
+    const Fr *scalars; size_t n;        // what the sort reads: with the endomorphism split 2 rq.n half-length scalars (k_glv_split)
+    long sort_mode;                     // option "msm_sort": 1 never staged, 2 staged whenever c >= 17
+    MsmTuning tune;                     // the request's, or the options'
+    bool fused_split, fused_scans, dimbits;      // dimbits: the bucket reduction's last step is k_dimbits (which decides how wide a digit may be)
+    size_t M, Smax;                     // upper bounds on sorted entries and on bucket parts
+    unsigned per_w, nblk, gblk, ablk;
+};
+// what the sort / plan side (msm_sort.hip) and the group side (msm_impl.inc) of the pipeline both use: threads per workgroup; bins of the
+// counting sort of bucket parts by size (k_partinfo .. k_partsort); points per part of a bucket of s points cut into `parts` parts
+static constexpr unsigned MSM_THREADS = 256;
+static constexpr unsigned SZ_BINS = 1024;
+__device__ __forceinline__ uint32_t part_len(uint32_t s, uint32_t parts) { return (s + parts - 1) / parts; }
 
 // which butterflies run a transform: the 29-bit ones when ntt29_in_use says so, else the 8 x 32-bit ones; or one of the two forced
 enum NttPath { NTT_AUTO, NTT_FR29, NTT_FR32 };
@@ -183,7 +201,7 @@ struct vsp_ctx {
     // MSM work slots (slot 0 runs on the context's stream; the others own a stream each)
     vsp::MsmWork msm_work[vsp::VSP_MSM_SLOTS];
     int slot_group[vsp::VSP_MSM_SLOTS] = {1, 1, 1, 1, 1, 1};
-    bool lds_attr_set[2] = {false, false};
+    bool lds_attr_set = false;
     bool ntt_attr_set = false;
     int ntt29_checked = 0;              // known-answer check of k_ntt29_pass: 0 not yet (or could not run), 1 passed, -1 failed (8 x 32-bit kernel in use)
     vsp::DevBuf msm_scalars;
@@ -329,8 +347,17 @@ int prove_with_overlap(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const
                        const uint64_t *saver_P1, const uint64_t *saver_r_enc, uint64_t A_out[12], uint64_t B_out[24], uint64_t C_out[12],
                        uint8_t proof_out[192], const std::function<void()> *overlap);
 
-// MSM on device-resident Montgomery bases (msm_impl.inc, instantiated for each group by msm_g1.hip / msm_g2.hip); result as host XYZZ
-// (Montgomery, 64-bit limbs)
+// MSM on device-resident Montgomery bases; result as host XYZZ (Montgomery, 64-bit limbs).  The templates over the group: msm_impl.inc,
+// instantiated by msm_g1.hip / msm_g2.hip.  Everything without a template parameter is group-independent and defined once, in
+// msm_sort.hip (but msm_diag_clock: msm_g1.hip, beside the kernel whose stamps it reads).
+inline MsmWork &slot(vsp_ctx *ctx, unsigned i) { return ctx->msm_work[i]; }
+// the stages of one launch that msm_sort.hip owns; msm_launch<F> (msm_impl.inc) calls them between its own
+int ensure_w(vsp_ctx *ctx, hipStream_t st, DevBuf &b, size_t bytes);      // b holds at least `bytes` (grow only; waits for st before it frees)
+int work_init(vsp_ctx *ctx, MsmWork &wk, hipStream_t stream_or_null);
+int msm_census(vsp_ctx *ctx, MsmWork &wk, const Fr *d_scalars, size_t n, hipStream_t on_stream = nullptr, unsigned batch = 1, size_t batch_stride = 0);
+int msm_split_scalars(vsp_ctx *ctx, MsmWork &wk, MsmLaunch &L, const MsmGeom &g);
+int msm_digit_sort(vsp_ctx *ctx, MsmWork &wk, MsmLaunch &L, const MsmGeom &g);
+int msm_bucket_plan(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const MsmGeom &g);
 template <class G> int msm_slot_launch(vsp_ctx *ctx, unsigned slot, const MsmRequest &rq);
 template <class G> int msm_precompute(vsp_ctx *ctx, typename G::Point *table, size_t n, unsigned c);
 // count (glv: 2 count) rows of sizeof(G::Row28) bytes
