@@ -396,6 +396,46 @@ int vsp_g2_compress(const uint64_t affine[24], uint8_t out[96]);
 int vsp_g1_decompress(const uint8_t in[48], int check_subgroup, uint64_t out_affine[12], int *out_is_inf);
 int vsp_g2_decompress(const uint8_t in[96], int check_subgroup, uint64_t out_affine[24], int *out_is_inf);
 
+/* ---- batch decompression of G1 points on the GPU ------------------------------------------------
+ * n ZCash-compressed points (48 bytes each, back to back) -> canonical affine limbs and one status byte per point:
+ *     0      accepted
+ *     bit 0  malformed encoding: the compressed flag (0x80) is missing, an infinity record (0x40) has a payload or a sign bit, or x >= p
+ *     bit 1  x^3 + 4 is not a square: no point of the curve has this x
+ *     bit 2  not in the order-r subgroup (only with check_subgroup != 0; the endomorphism test of "bases_check_subgroup")
+ * A point is accepted exactly when vsp_g1_decompress accepts the same 48 bytes.  A rejected point and infinity (0xC0 00..) are
+ * written as all-zero limbs.  The return value is VSP_OK whatever the verdicts are: VSP_ERR_* is for bad arguments (a null pointer,
+ * also with n = 0) and HIP failures only.  One lane per point: the square root is a fixed chain of 481 field products (csrc/fp_sqrt.h).
+ * Any n: the points go through the device in pieces of at most 2^21 (see the workspace bound below). */
+int vsp_g1_decompress_batch(vsp_ctx *ctx, const uint8_t *in /* host n x 48 */, size_t n, int check_subgroup,
+                            uint64_t *out_affine /* host n x 12, canonical */, uint8_t *status_out /* host n */);
+
+/* ---- tally: the aggregation of common.hpp:1193-1216 (repeated by every verifier at :1257-1279) ----
+ * process_encrypted_input_mode_tally_admin_phase deserialises up to 1 << tree_depth ciphertext blobs one after the other and adds
+ * them component by component into ct_agg; everything after that is pairing work on the ONE aggregated ciphertext.  A tally handle
+ * holds the ct_len = msg_size + 2 running sums (host memory; the device workspaces belong to the context).
+ * vsp_tally_add_blobs takes `count` ballots lying back to back, each a G1 vector blob exactly as vsp_g1_vector_to_blob writes it
+ * (8-byte big-endian count, then ct_len compressed points: 8 + 48 ct_len bytes), decodes and checks every point on the GPU and adds
+ * every ACCEPTED ballot to the running sums.  A ballot's status is the OR of the status bytes of its points (as above), bit 0 also
+ * for a count header that differs from ct_len; a rejected ballot contributes none of its components, its well-formed ones included.
+ * status_out (count bytes) and accepted_out (ballots this call accepted) may be NULL; t and blobs may not (VSP_ERR_ARG, also with count = 0).  The reference aborts on the first bad blob:
+ * a caller who wants that compares *accepted_out with count.  With check_subgroup = 0 curve points outside the subgroup are
+ * accepted, and the sums are still the exact curve sums (the additions are generic).
+ * vsp_tally_result returns the ct_len sums as canonical affine points (infinity all zero) and the number of ballots accepted since
+ * the handle was created or last reset; it may be called at any time and adding may go on afterwards.  No accepted ballot: all
+ * infinity and 0.  The result is canonical, so it does not depend on how the ballots were split over calls.
+ * Workspace bound: a call with many ballots runs in pieces of at most 2^21 points (2^16 ballots of 27 points take 170 MB decoded),
+ * at least one ballot: raw bytes, Montgomery-form points, status bytes and partial sums of one piece stay below 400 MB of the
+ * context's grow-only workspaces whatever `count` is.  Stage times (HIP events, summed since vsp_stats_reset): vsp_get_stat
+ * "tally_decode_ms", "tally_subgroup_ms", "tally_sum_ms".  Option "tally_chunk_points" (default 2^21) sets the piece size. */
+typedef struct vsp_tally vsp_tally;
+vsp_tally *vsp_tally_create(vsp_ctx *ctx, size_t ct_len /* msg_size + 2; 1..1024 */);
+void vsp_tally_free(vsp_ctx *ctx, vsp_tally *t);
+int vsp_tally_add_blobs(vsp_ctx *ctx, vsp_tally *t, const uint8_t *blobs /* host, count x (8 + 48 ct_len), packed */,
+                        size_t count, int check_subgroup, uint8_t *status_out /* count, may be NULL */,
+                        size_t *accepted_out /* may be NULL */);
+int vsp_tally_result(vsp_ctx *ctx, const vsp_tally *t, uint64_t *ct_out /* host ct_len x 12 */, uint64_t *ballots_out /* may be NULL */);
+int vsp_tally_reset(vsp_ctx *ctx, vsp_tally *t);
+
 /* ---- wire formats of the reference's marshaling_policy (common.hpp:168-203 option::big_endian) --------------------
  * PROVISIONAL where marked: the marshalling sources are absent submodules, and only the proof bytes, the scalar vectors and the head of
  * the verification key (4 bytes, the GT element, three points) are pinned by files of the reference.  The tail of the verification key

@@ -680,6 +680,58 @@ def g2_decompress(data, check_subgroup=True):
     return out
 
 
+def g1_decompress_batch(ctx, data, check_subgroup=True):
+    """n x 48 ZCash-compressed bytes -> (points [n,12], status [n]) on the GPU.  status 0 = accepted; bit 0 malformed encoding, bit 1
+    no curve point has this x, bit 2 outside the order-r subgroup (only with check_subgroup).  Rejected points and infinity are all zero."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    if buf.shape[0] % 48:
+        raise ValueError("g1_decompress_batch: the input is not a whole number of 48-byte points")
+    n = buf.shape[0] // 48
+    out = np.zeros((n, 12), np.uint64); status = np.zeros(n, np.uint8)
+    ctx.check(ctx.lib.vsp_g1_decompress_batch(ctx.h, _ptr(buf), n, int(check_subgroup), _ptr(out), _ptr(status)))
+    return out, status
+
+
+class Tally:
+    """The aggregation of the tally (common.hpp:1193-1216, repeated by every verifier at :1257-1279): ct_len = msg_size + 2 running sums
+    of ciphertext components over the ballots added so far (vsp_tally)."""
+
+    def __init__(self, ctx, ct_len):
+        self.ctx = ctx
+        self.ct_len = int(ct_len)
+        self.h = ctx.lib.vsp_tally_create(ctx.h, self.ct_len)
+        if not self.h:
+            raise VspError("vsp_tally_create failed: " + ctx.last_error())
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.vsp_tally_free(self.ctx.h, self.h)
+            self.h = None
+
+    def add_blobs(self, blobs, check_subgroup=True):
+        """blobs: the ballots' G1 vector blobs back to back as one bytes object, or a list of per-ballot blobs (8 + 48 ct_len bytes each).
+        Adds every accepted ballot; returns (status [count] uint8, accepted)."""
+        data = bytes(blobs) if isinstance(blobs, (bytes, bytearray, memoryview)) else b"".join(bytes(b) for b in blobs)
+        size = 8 + 48 * self.ct_len
+        if len(data) % size:
+            raise ValueError(f"Tally.add_blobs: the input is not a whole number of {size}-byte ballots")
+        count = len(data) // size
+        status = np.zeros(count, np.uint8); accepted = C.c_size_t(0)
+        if count:
+            buf = np.frombuffer(data, dtype=np.uint8)
+            self.ctx.check(self.ctx.lib.vsp_tally_add_blobs(self.ctx.h, self.h, _ptr(buf), count, int(check_subgroup), _ptr(status), C.byref(accepted)))
+        return status, accepted.value
+
+    def result(self):
+        """(ct [ct_len,12] canonical affine sums, infinity all zero; ballots accepted since creation or the last reset)"""
+        ct = np.zeros((self.ct_len, 12), np.uint64); ballots = C.c_uint64(0)
+        self.ctx.check(self.ctx.lib.vsp_tally_result(self.ctx.h, self.h, _ptr(ct), C.byref(ballots)))
+        return ct, ballots.value
+
+    def reset(self):
+        self.ctx.check(self.ctx.lib.vsp_tally_reset(self.ctx.h, self.h))
+
+
 # ---- wire formats (f.2): the big-endian blobs of the reference's marshaling_policy (common.hpp:168-203, 462-485, 749-799) ---------
 def fr_vector_to_blob(vals):
     """serialize a scalar vector (primary input, eid, sn, rt, voting result): 8-byte count + 32-byte big-endian elements"""

@@ -210,6 +210,10 @@ struct vsp_ctx {
     int fp28_checked[2] = {0, 0};       // known-answer check of the 28-bit-limb accumulation kernels, per group: 0 not yet, 1 passed, -1 failed (kernel disabled)
     // fixed-base tables of the generators (fb_table[group - 1]), built lazily, and the scratch of the batch exponentiation
     vsp::DevBuf fb_table[2], fb_tmp, fb_pre;
+    // the tally's chunk (tally.hip): raw blobs, decoded points, a status byte per point and per ballot, the blocks' partial sums; the
+    // stage timers, created on first use
+    vsp::DevBuf tally_raw, tally_pts, tally_pstatus, tally_bstatus, tally_partials;
+    hipEvent_t tally_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     // prover workspaces for K witnesses (a single proof: K = 1): z [K][num_vars + 1], A z, B z, C z [K][3][m], H [K][m], the packed witness
     vsp::DevBuf pr_z, pr_abc, pr_h, pr_pack;
     // the proof or the batch of K proofs in flight between a launch and its finish (one per context): the key, r and s (K x 4 words), the
@@ -377,8 +381,9 @@ int msm_make_slot_stream(vsp_ctx *ctx, hipStream_t *out);
 void msm_drain_slots(vsp_ctx *ctx);
 // d_flag: one device word, zeroed by the caller; bit 0 = coordinate >= p, bit 1 = point off the curve (only when check_curve)
 template <class G> int bases_to_mont(vsp_ctx *ctx, const void *d_canon, typename G::Point *d_out, size_t n, int check_curve, uint32_t *d_flag);
-// raises bit 2 of *d_flag when some point fails phi(P) = lambda P (the endomorphism split's precondition; msm_impl.inc k_subgroup_check)
-template <class G> int subgroup_check(vsp_ctx *ctx, const typename G::Point *d_mont, size_t n, uint32_t *d_flag);
+// raises bit 2 of *d_flag when some point fails phi(P) = lambda P (the endomorphism split's precondition; msm_impl.inc k_subgroup_check).
+// With d_status (n bytes, one per point) the verdict is per point instead: bit 2 of d_status[i] is raised and *d_flag is not touched
+template <class G> int subgroup_check(vsp_ctx *ctx, const typename G::Point *d_mont, size_t n, uint32_t *d_flag, uint8_t *d_status = nullptr);
 int msm_diag_clock(vsp_ctx *ctx, int reset, double *ghz, double *waves);
 int ntt_diag_clock(vsp_ctx *ctx, int reset, double *ghz, double *waves);
 // resident bases from canonical points into *out; trust: BASES_CALLER = caller data (validated; the split only after the subgroup check),
@@ -438,6 +443,26 @@ template <class G> inline bool affine_valid(const uint64_t *p) {
     if (!coords_below_p(p, G::AFFINE_WORDS)) return false;
     const Affine<typename G::HF> a = host_load_affine<typename G::HF>(p);
     return is_inf(a) || eq(sqr(a.y), add(mul(sqr(a.x), a.x), curve_b<typename G::HF>()));
+}
+
+// ---- device codec helpers (wire.hip, tally.hip, msm_impl.inc)
+// 48 big-endian bytes (12 words) -> 12 little-endian 32-bit limbs; the three flag bits of the first byte are cleared
+__device__ __forceinline__ Fp fp_from_be(const uint32_t *w, bool first) {
+    Fp r;
+#pragma unroll
+    for (int j = 0; j < 12; j++) r.l[j] = __builtin_bswap32(w[11 - j]);
+    if (first) r.l[11] &= 0x1FFFFFFFu;
+    return r;
+}
+// a canonical value below p
+__device__ __forceinline__ bool canon_below_p(const Fp &a) {
+    bool lt = false, gt = false;
+#pragma unroll
+    for (int i = Fp::N - 1; i >= 0; i--) {
+        lt = lt || (!gt && a.l[i] < FpP32::MOD[i]);
+        gt = gt || (!lt && a.l[i] > FpP32::MOD[i]);
+    }
+    return lt;
 }
 
 static inline unsigned ceil_log2(size_t n) { unsigned l = 0; while (((size_t)1 << l) < n) l++; return l; }

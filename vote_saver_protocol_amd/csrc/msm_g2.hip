@@ -9,6 +9,6 @@ template int msm_slot_launch<G2>(vsp_ctx *, unsigned, const MsmRequest &);
 template int msm_slot_finish<G2>(vsp_ctx *, unsigned, XYZZ<G2::HF> *, unsigned);
 template int msm_slot_finish_wait<G2>(vsp_ctx *, unsigned, unsigned, bool *);
 template void msm_slot_fold<G2>(vsp_ctx *, unsigned, XYZZ<G2::HF> *);
-template int subgroup_check<G2>(vsp_ctx *, const G2::Point *, size_t, uint32_t *);
+template int subgroup_check<G2>(vsp_ctx *, const G2::Point *, size_t, uint32_t *, uint8_t *);
 template int bases_to_mont<G2>(vsp_ctx *, const void *, G2::Point *, size_t, int, uint32_t *);
 }  // namespace vsp

@@ -712,15 +712,6 @@ __global__ __launch_bounds__(64, AccumWaves<F>::W) void k_dimbits(const XYZZ<F> 
 //   flag bit 0: a coordinate is not canonical (>= p);  bit 1 (check_curve): a point is not on y^2 = x^3 + b
 // (b = 4 for G1, 4 (1 + u) for G2; all-zero = infinity is accepted).  Subgroup membership is NOT checked here -- a scalar
 // multiplication by r per point; vsp_g1_decompress / vsp_g2_decompress offer it for points that arrive as wire bytes.
-__device__ __forceinline__ bool canon_below_p(const Fp &a) {
-    bool lt = false, gt = false;
-#pragma unroll
-    for (int i = Fp::N - 1; i >= 0; i--) {
-        lt = lt || (!gt && a.l[i] < FpP32::MOD[i]);
-        gt = gt || (!lt && a.l[i] > FpP32::MOD[i]);
-    }
-    return lt;
-}
 __device__ __forceinline__ bool canon_below_p(const Fp2 &a) { return canon_below_p(a.c0) && canon_below_p(a.c1); }
 __device__ __forceinline__ Fp curve_b_mont(const Fp &) { Fp four = Fp::one(); four = dbl(dbl(four)); return four; }
 __device__ __forceinline__ Fp2 curve_b_mont(const Fp2 &) { Fp2 b; b.c0 = dbl(dbl(Fp::one())); b.c1 = b.c0; return b; }
@@ -746,7 +737,8 @@ template <class F> __global__ __launch_bounds__(256) void k_bases_to_mont(const 
 // (k1 + k2 lambda) P = k1 P + k2 phi(P), and the fold-back by lambda^2 + lambda + 1 = r is sound because (phi^2 + phi + 1) P = O holds on the
 // whole curve, hence r P = O.  (It is also the known fast membership test of this curve family: phi(P) = -z^2 P for the other cube root.)
 // lambda P = |z| (|z| P) - P with |z| = 0xd201000000010000 (Hamming weight 6): 126 doublings and 11 additions per point -- about 45 us of
-// one lane's time, 20-30 ms for 2^20 G1 points, once per uploaded key.  flag bit 2 is raised for any point that fails.
+// one lane's time, 20-30 ms for 2^20 G1 points, once per uploaded key.  flag bit 2 is raised for any point that fails; with `status`
+// (one byte per point, non-null) bit 2 of the failing point's byte is raised instead.
 static constexpr uint64_t BLS_ABS_Z = 0xd201000000010000ULL;
 // the three group operations as REAL calls on memory temporaries: inlined side by side, the generic formulas crash this toolchain's
 // machine scheduler next to the fixed-register product routine (as fp28.h notes for its cold branch); a one-off check can afford the calls
@@ -754,7 +746,7 @@ template <class E> __device__ __noinline__ void sgc_dbl(XYZZ<E> *a) { *a = xyzz_
 template <class E> __device__ __noinline__ void sgc_madd(XYZZ<E> *a, const Affine<E> *p, bool negate) { XYZZ<E> t = *a; xyzz_madd(t, *p, negate); *a = t; }
 template <class E> __device__ __noinline__ void sgc_add(XYZZ<E> *a, const XYZZ<E> *q) { XYZZ<E> t = *a; xyzz_add(t, *q); *a = t; }
 template <class F>
-__global__ __launch_bounds__(MSM_THREADS, AccumWaves<F>::W) void k_subgroup_check(const Affine<F> *__restrict__ bases, size_t n, uint32_t *flag) {
+__global__ __launch_bounds__(MSM_THREADS, AccumWaves<F>::W) void k_subgroup_check(const Affine<F> *__restrict__ bases, size_t n, uint32_t *flag, uint8_t *status) {
     using LV = LaneView<F>; using E = typename LV::E;
     const size_t i = gid<F>();
     if (i >= n) return;                                     // both lanes of a pair leave together
@@ -774,7 +766,10 @@ __global__ __launch_bounds__(MSM_THREADS, AccumWaves<F>::W) void k_subgroup_chec
     const bool inf2 = is_inf(t2);
     const bool ex = is_zero(sub(lx, t2.X));
     const bool ey = is_zero(sub(ly, t2.Y));
-    if (inf2 || !ex || !ey) atomicOr(flag, 4u);
+    if (inf2 || !ex || !ey) {
+        if (status) status[i] |= 4u;                        // a verdict per point (tally.hip); the lanes of a pair write the same byte
+        else atomicOr(flag, 4u);
+    }
 }
 
 // the bit-decomposed last step (k_dimbits) or the weighted one (k_dimweight): `forced` (MsmTuning.dimbits) 1 / 0 forces either, -1 by group
@@ -1270,11 +1265,11 @@ template <class G> int msm_slot_finish_wait(vsp_ctx *ctx, unsigned slot_id, unsi
     return msm_finish_wait<typename G::F, typename G::HF>(ctx, slot(ctx, slot_id), count, empty);
 }
 template <class G> void msm_slot_fold(vsp_ctx *ctx, unsigned slot_id, XYZZ<typename G::HF> *out) { msm_fold<typename G::F, typename G::HF>(slot(ctx, slot_id), out); }
-template <class G> int subgroup_check(vsp_ctx *ctx, const typename G::Point *d_mont, size_t n, uint32_t *d_flag) {
+template <class G> int subgroup_check(vsp_ctx *ctx, const typename G::Point *d_mont, size_t n, uint32_t *d_flag, uint8_t *d_status) {
     using F = typename G::F;
     if (!n) return VSP_OK;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_subgroup_check<F>), dim3((unsigned)((LaneView<F>::LANES * n + MSM_THREADS - 1) / MSM_THREADS)), dim3(MSM_THREADS), 0, ctx->stream,
-                       d_mont, n, d_flag);
+                       d_mont, n, d_flag, d_status);
     VSP_LAUNCH_CHECK();
     return VSP_OK;
 }

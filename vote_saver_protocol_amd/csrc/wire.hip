@@ -25,14 +25,6 @@
 
 namespace vsp {
 
-// 48 big-endian bytes (12 words) -> 12 little-endian 32-bit limbs; the three flag bits of the first byte are cleared
-__device__ __forceinline__ Fp fp_from_be(const uint32_t *w, bool first) {
-    Fp r;
-#pragma unroll
-    for (int j = 0; j < 12; j++) r.l[j] = __builtin_bswap32(w[11 - j]);
-    if (first) r.l[11] &= 0x1FFFFFFFu;
-    return r;
-}
 // ZCash uncompressed records -> canonical affine points (infinity flag -> all zero).  flag bit 2: a record is malformed -- it claims to be
 // compressed (0x80), carries the sign bit that only the compressed form has (0x20), or is an infinity record (0x40) with a non-zero payload
 __device__ __forceinline__ bool record_rest_zero(const uint32_t *w, unsigned words) {
