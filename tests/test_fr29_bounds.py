@@ -6,49 +6,18 @@
     intermediate is checked (no 32-bit limb wraps in either direction, every subtrahend is dominated by the 2r constant, every
     product operand stays below 2^261) and the result is the plain big-integer DFT;
  2. a worst-case propagation (value bound and per-limb bound) through the butterfly, showing that 11 radix-4 steps from a canonical
-    input (the deepest transform the pass plan allows is 2^28: 14 steps -- checked too) keep every constraint.
-No GPU needed; tests/test_gpu_ntt.py and tests/test_gpu_domain.py compare the kernels with the oracle's transforms bit for bit."""
-import os
+    input (the deepest transform the pass plan allows is 2^28: 14 steps -- checked too) keep every constraint;
+ 3. the transform's FIRST stage as the kernel runs it -- its twiddle is one, so the loaded values themselves are subtrahends -- for
+    each of the three loads (plain, coset-premultiplied, witness_map's fused a b - c), in the propagation and in the exact model at
+    the two ends of the fused load's range.
+The model itself is oracle/fr29_model.py (tests/test_gpu_ntt_structured.py crafts its inputs with it).  No GPU needed; tests/test_gpu_ntt.py and tests/test_gpu_domain.py compare the kernels with the oracle's transforms bit for bit."""
 import random
-import re
 
 import pytest
 
 import bls12_381 as o
-from conftest import ROOT
-
-R = o.R
-W, N = 29, 9
-MASK = (1 << W) - 1
-RP = 1 << (W * N)                      # R' = 2^261
-
-
-def _consts():
-    text = open(os.path.join(ROOT, "vote_saver_protocol_amd", "csrc", "mont_asm_gfx950.h")).read()
-    return {name: [int(x.strip().rstrip("u"), 16) for x in body.split(",")]
-            for name, body in re.findall(r"static constexpr uint32_t (FR29_\w+)\[9\] = \{([^}]*)\};", text)}
-
-
-K = _consts()
-RL, K2 = K["FR29_R"], K["FR29_K2_L1"]
-
-
-def val(l):
-    return sum(x << (W * i) for i, x in enumerate(l))
-
-
-def tight(v):
-    assert 0 <= v < 1 << (W * (N - 1) + 32)
-    return [(v >> (W * i)) & MASK for i in range(N - 1)] + [v >> (W * (N - 1))]
-
-
-class Bound(AssertionError):
-    pass
-
-
-def need(c, msg):
-    if not c:
-        raise Bound(msg)
+from fr29_model import (B, K, K2, K4, LOW_TRIPLE, MASK, N, R, RL, RP, W, Bound, add29, b_add, b_mul, b_norm, b_sub, b_transform, brev,
+                        csub29, first_stage_sources, fused_load, high_triple, mm29, model_ntt, norm29, radix4, sub29, tight, tw, val)
 
 
 def test_constants():
@@ -59,103 +28,6 @@ def test_constants():
     assert val(K["FR29_K4_L1"]) == 4 * R
     # the top limb of 2r (after lending one unit) dominates the top limb of anything below 1.9 r
     assert K2[-1] >= (19 * R // 10) >> (W * (N - 1))
-
-
-def mm29(a, b):
-    for x in (a, b):
-        need(all(0 <= t < 1 << 32 for t in x), "operand limb outside 32 bits")
-    need(val(a) < RP and val(b) < RP, "operand not below 2^261")
-    m, r, acc = [0] * N, [0] * N, 0
-    for k in range(2 * N - 1):
-        for i in range(max(0, k - N + 1), min(k, N - 1) + 1):
-            acc += a[i] * b[k - i]
-        for i in (range(0, k) if k < N else range(k - N + 1, N)):
-            acc += m[i] * RL[k - i]
-        if k < N:
-            m[k] = ((-acc) & 0xFFFFFFFF) & MASK                             # v_sub_u32 tmp, 0, lo ; v_and_b32
-            acc += m[k] * RL[0]
-            need(acc & MASK == 0, "Montgomery column not cleared")
-        else:
-            r[k - N] = acc & MASK
-        need(acc < 1 << 64, "column %d overflows the 64-bit accumulator" % k)
-        acc >>= W
-    need(acc < 1 << 32, "top limb overflows")
-    r[N - 1] = acc
-    need(val(r) * RP == val(a) * val(b) + val(m) * R, "not (a b + m r) / R'")
-    need(val(r) < val(a) * val(b) // RP + R + 1 and all(x <= MASK for x in r[:-1]), "output not tight / above a b / R' + r")
-    return r
-
-
-def add29(a, b):
-    r = [x + y for x, y in zip(a, b)]
-    need(all(t < 1 << 32 for t in r), "sum wraps")
-    return r
-
-
-def sub29(a, b):
-    r = []
-    for i in range(N):
-        need(a[i] + K2[i] < 1 << 32, "a + 2r wraps")
-        need(a[i] + K2[i] - b[i] >= 0, "a + 2r - b borrows in limb %d" % i)
-        r.append(a[i] + K2[i] - b[i])
-    return r
-
-
-def norm29(a):
-    r, c = [], 0
-    for i in range(N - 1):
-        t = a[i] + c
-        need(t < 1 << 32, "carry pass wraps")
-        r.append(t & MASK); c = t >> W
-    need(a[N - 1] + c < 1 << 32, "carry pass wraps the top limb")
-    return r + [a[N - 1] + c]
-
-
-def csub29(v):
-    need(val(v) < 2 * R, "conditional subtraction of a value >= 2r")
-    return tight(val(v) - R) if val(v) >= R else list(v)
-
-
-def tw(x):
-    return tight(x * RP % R)
-
-
-def radix4(x, w1, w2, w3, s_zero=False):
-    x0, x1, x2, x3 = x
-    if not s_zero:
-        x1, x3 = mm29(x1, w1), mm29(x3, w1)
-    a0, a1, a2, a3 = add29(x0, x1), sub29(x0, x1), add29(x2, x3), sub29(x2, x3)
-    a2, a3 = mm29(a2, w2), mm29(a3, w3)
-    return [norm29(add29(a0, a2)), norm29(add29(a1, a3)), norm29(sub29(a0, a2)), norm29(sub29(a1, a3))]
-
-
-def model_ntt(vals, log_n):
-    """radix-2 decimation in time exactly as k_ntt29_pass steps it (an odd stage count starts with one radix-2 stage, then radix-4
-    steps), one 'pass' over the whole array, values lazy throughout, canonical at the end through the product with the Montgomery one"""
-    n = 1 << log_n
-    omega = o.fr_root_of_unity(log_n)
-    a = [tight(vals[int(format(i, "0%db" % log_n)[::-1], 2)] if log_n else vals[i]) for i in range(n)]
-    t = 0
-    if log_n & 1:
-        for q in range(n // 2):
-            u, v = a[2 * q], a[2 * q + 1]
-            a[2 * q], a[2 * q + 1] = norm29(add29(u, v)), norm29(sub29(u, v))
-        t = 1
-    while t < log_n:
-        h = 1 << t
-        for q in range(n // 4):
-            mid_lo = q & (h - 1)
-            mid0 = ((q >> t) << (t + 2)) | mid_lo
-            e = [mid0, mid0 + h, mid0 + 2 * h, mid0 + 3 * h]
-            w1 = tw(pow(omega, mid_lo << (log_n - 1 - t), R))
-            w2 = tw(pow(omega, mid_lo << (log_n - 2 - t), R))
-            w3 = tw(pow(omega, (mid_lo + h) << (log_n - 2 - t), R))
-            out = radix4([a[i] for i in e], w1, w2, w3, s_zero=(t == 0))
-            for i, v in zip(e, out):
-                a[i] = v
-        t += 2
-    worst = max(val(v) for v in a)
-    return [val(csub29(mm29(v, K["FR29_ONE"]))) for v in a], worst
 
 
 @pytest.mark.parametrize("log_n", [1, 2, 3, 6, 7])
@@ -180,47 +52,6 @@ def test_product_column_bound_at_the_loosest_operands():
 
 
 # ------------------------------------------------------------------------------------------------ worst-case propagation
-class B:
-    def __init__(self, v, l):
-        self.v, self.l = int(v), list(l)          # value < v, limb i < l[i]
-
-    @staticmethod
-    def tight(v):
-        v = int(v)
-        return B(v, [1 << W] * (N - 1) + [(v >> (W * (N - 1))) + 1])
-
-
-def b_mul(a, b):
-    worst, carry = 0, 0
-    for k in range(2 * N - 1):
-        col = carry
-        for i in range(max(0, k - N + 1), min(k, N - 1) + 1):
-            col += (a.l[i] - 1) * (b.l[k - i] - 1)
-        for i in (range(0, k + 1) if k < N else range(k - N + 1, N)):
-            col += MASK * RL[k - i]
-        worst = max(worst, col); carry = col >> W
-    need(worst < 1 << 64, "worst-case column sum reaches 2^64")
-    need(a.v <= RP and b.v <= RP, "product operand may reach 2^261")
-    return B.tight(a.v * b.v // RP + R + 1)
-
-
-def b_add(a, b):
-    l = [x + y - 1 for x, y in zip(a.l, b.l)]
-    need(all(x <= 1 << 32 for x in l), "sum may wrap")
-    return B(a.v + b.v, l)
-
-
-def b_sub(a, b):
-    need(all(K2[i] >= b.l[i] - 1 for i in range(N)), "2r does not dominate the subtrahend's limbs")
-    need(all(a.l[i] - 1 + K2[i] < 1 << 32 for i in range(N)), "a + 2r may wrap")
-    return B(a.v + 2 * R, [a.l[i] + K2[i] for i in range(N)])
-
-
-def b_norm(a):
-    need(all(x <= (1 << 32) - 8 for x in a.l), "carry pass may wrap")
-    return B.tight(a.v)
-
-
 @pytest.mark.parametrize("steps", [11, 14])
 def test_bounds_are_inductive_over_a_whole_transform(steps):
     """from a canonical input (or a coset-shifted one: a product output below 1.02 r) through `steps` radix-4 steps -- 11 for 2^22,
@@ -275,3 +106,88 @@ def test_fused_pointwise_load_of_witness_map_stays_inside_the_lazy_domain():
             outs = [b_norm(b_add(a0, p2)), b_norm(b_add(a1, p3)), b_norm(b_sub(a0, p2)), b_norm(b_sub(a1, p3))]
             V = B.tight(max(x.v for x in outs))
         assert V.v < RP and b_mul(V, w).v < 2 * R
+
+
+# ------------------------------------------------------------------------------------------------ the first stage, as the kernel runs it
+FUSED_BOUND = int(3.03 * R)              # test_fused_pointwise_load_of_witness_map_stays_inside_the_lazy_domain: the fused load stays below
+
+
+@pytest.mark.parametrize("steps", [11, 14])
+@pytest.mark.parametrize("odd", [False, True])
+def test_first_stage_of_the_plain_and_the_premultiplied_load(steps, odd):
+    """the first stage skips its twiddle product (the twiddle is one), so x1, x3 (radix-4) or v (the radix-2 stage of an odd stage
+    count) are subtrahends as loaded.  A plain load is canonical and a coset-premultiplied one is a product output below 1.02 r: 2r
+    dominates both, and the growth is no more than the later steps'."""
+    w = B.tight(R)
+    canonical = B.tight(R)
+    premultiplied = b_mul(B.tight(R), b_mul(w, w))                        # v * (pw_lo * pw_hi): both products of canonical operands
+    assert premultiplied.v < 1.02 * R
+    for V in (canonical, premultiplied):
+        trace = b_transform(V, steps, odd=odd)
+        assert trace[0] <= 5.02 and trace[-1] <= 1.02 + 4 * len(trace)    # + 4r per stage, the first included
+
+
+@pytest.mark.parametrize("odd", [False, True])
+def test_first_stage_with_2r_rejects_the_fused_load(odd):
+    """REGRESSION of the finding: the fused load is a lazy value up to 3.02 r, not a product output; a first stage that subtracts it
+    against 2r (the kernel before sub29k4) breaks the bound discipline -- 2r's top limb does not dominate it."""
+    with pytest.raises(Bound, match="2r does not dominate"):
+        b_transform(B.tight(FUSED_BOUND), 11, odd=odd, k_first=K2)
+    lo, hi = fused_load(*LOW_TRIPLE), fused_load(*high_triple())
+    with pytest.raises(Bound, match="borrows in limb 8"):
+        sub29(lo, hi)
+    assert hi[-1] > K2[-1] + lo[-1]
+
+
+@pytest.mark.parametrize("steps", [11, 14])
+@pytest.mark.parametrize("odd", [False, True])
+def test_first_stage_with_4r_accepts_the_fused_load(steps, odd):
+    """the fixed first stage (k_ntt29_pass with FUSED: sub29k4) subtracts the raw fused values against the redundant 4r.  4r dominates
+    3.03 r limb by limb; the stage grows more than a later one (a0 = x0 + x1 has no product on x1: 3.03 r -> 9.03 r instead of + 4r,
+    and -> 7.03 r through the radix-2 stage), and the deepest plan -- 14 radix-4 steps, 2^28 -- still ends below 2^261 = 70.4 r with
+    its last product below 2r."""
+    assert all(k >= l - 1 for k, l in zip(K4, B.tight(FUSED_BOUND).l)) and all(x < 1 << 31 for x in K4)
+    trace = b_transform(B.tight(FUSED_BOUND), steps, odd=odd, k_first=K4)
+    assert trace[0] <= (7.04 if odd else 9.04)
+    assert trace[-1] <= trace[0] + 4 * (len(trace) - 1) + 0.01 and trace[-1] < 64
+
+
+def _extreme_fused_inputs(log_n, run):
+    """canonical (a, b, c) per natural-order position: the low / high triple laid out so that the values the first stage combines take
+    every pattern -- group q of run `run` gets pattern (q + run * groups) mod 16, bit j deciding x_j"""
+    lo, hi = LOW_TRIPLE, high_triple()
+    groups = first_stage_sources(log_n)
+    trip = [None] * (1 << log_n)
+    for q, src in enumerate(groups):
+        pattern = (q + run * len(groups)) % 16
+        for j, i in enumerate(src):
+            trip[i] = hi if pattern >> j & 1 else lo
+    return trip
+
+
+@pytest.mark.parametrize("log_n", [2, 3, 6, 7])
+def test_exact_model_transform_of_extreme_fused_inputs(log_n):
+    """witness_map's last transform in the exact model, from the two ends of the fused load's range (r + 1 and above 3.0 r) in every
+    low / high pattern over a first-stage butterfly -- all 16 over (x0, x1, x2, x3), which hold the 4 over the radix-2 stage's (u, v):
+    no bound is broken with the 4r first stage and the result is the plain inverse DFT of (a b - c) / 2^261; with the 2r first stage
+    the model raises."""
+    lo, hi = fused_load(*LOW_TRIPLE), fused_load(*high_triple())
+    assert val(lo) == R + 1 and val(hi) >= 3 * R and val(hi) < FUSED_BOUND
+    n = 1 << log_n
+    groups = n // 4
+    omega_inv = pow(o.fr_root_of_unity(log_n), -1, R)
+    rinv, ninv = pow(RP, -1, R), pow(n, -1, R)
+    seen = set()
+    for run in range(max(1, 16 // groups)):
+        trip = _extreme_fused_inputs(log_n, run)
+        for q, src in enumerate(first_stage_sources(log_n)):
+            seen.add(tuple(trip[i] is not LOW_TRIPLE for i in src))
+        loaded = [fused_load(*t) for t in trip]
+        got, worst = model_ntt(loaded, log_n, omega=omega_inv, k_first=K4, scale=ninv, loaded=True)
+        plain = [(a * b - c) * rinv % R for a, b, c in trip]
+        assert got == [x * ninv % R for x in o.dft_naive(plain, omega_inv)]
+        assert worst < ((7.03 + 4 * (log_n // 2)) if log_n & 1 else (9.03 + 4 * (log_n // 2 - 1))) * R   # the first stage, then + 4r per step
+        if any(trip[src[1]] is not LOW_TRIPLE and trip[src[0]] is LOW_TRIPLE for src in first_stage_sources(log_n)):
+            with pytest.raises(Bound, match="borrows in limb 8"):
+                model_ntt(loaded, log_n, omega=omega_inv, k_first=K2, scale=ninv, loaded=True)
+    assert len(seen) == 16

@@ -1,5 +1,6 @@
 """GPU: the kernels' Montgomery arithmetic (hand-scheduled v_mad_u64_u32 product, add, sub, inverse) against the
-golden field vectors (edge values 0, 1, p-1, ...) and against python big-int arithmetic on random values."""
+golden field vectors (edge values 0, 1, p-1, ...) and against python big-int arithmetic on random values; the lazy limb forms
+(14 x 28-bit Fp of the G1 accumulation, 9 x 29-bit Fr of the NTT butterflies) likewise."""
 import ctypes as C
 
 import numpy as np
@@ -73,6 +74,35 @@ def test_fp28_lazy_field_against_big_integers(ctx):
     assert ints(run(ctx, 0, 10, a, b), nl) == [x * (y - x) % mod for x, y in zip(A, B)]
     assert ints(run(ctx, 0, 11, a, b), nl) == [(-y) * x % mod for x, y in zip(A, B)]
     assert ints(run(ctx, 0, 12, a, b), nl) == [(x * (y - x) - y * x) % mod for x, y in zip(A, B)]
+
+
+def test_fr29_lazy_field_against_big_integers(ctx):
+    """The 9 x 29-bit field of the NTT butterflies (carry-free product through both register maps of the routine, limb-wise addition,
+    the lazy subtraction against the redundant 2r, the carry pass, the conditional subtraction): round trip, product, and the
+    butterfly's own chain x + x y - y^2, on edge values and random ones."""
+    mod, nl = o.R, 4
+    g = load_golden("field.json")["fr"]
+    A = [int(c["a"], 16) for c in g]; B = [int(c["b"], 16) for c in g]
+    edge = [0, 1, 2, mod - 1, mod - 2, (mod - 1) // 2, (1 << 254) - 1, (1 << 29) - 1, 1 << 29, (1 << 58) - 1]
+    for x in edge:
+        for y in edge:
+            A.append(x); B.append(y)
+    rng = np.random.default_rng(29)
+    for _ in range(20000):
+        A.append(int.from_bytes(rng.bytes(40), "little") % mod); B.append(int.from_bytes(rng.bytes(40), "little") % mod)
+    for k in range(0, 255):                            # limbs of all ones / single bits around every 29-bit boundary
+        if k % 29 in (0, 1, 2, 27, 28) or k % 32 in (0, 31):
+            A.append(((1 << k) - 1) % mod); B.append((mod - (1 << k)) % mod)
+            A.append((1 << k) % mod); B.append(((1 << k) - 1) % mod)
+    assert all(0 <= x < mod for x in A + B)
+    a, b = limbs_arr(A, nl), limbs_arr(B, nl)
+    assert ints(run(ctx, 1, 6, a, b), nl) == A
+    assert ints(run(ctx, 1, 7, a, b), nl) == [x * y % mod for x, y in zip(A, B)]
+    assert ints(run(ctx, 1, 8, a, b), nl) == [x * y % mod for x, y in zip(A, B)]
+    assert ints(run(ctx, 1, 9, a, b), nl) == [(x + x * y - y * y) % mod for x, y in zip(A, B)]
+    out = np.zeros_like(a)
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    assert ctx.lib.vsp_selftest_field(ctx.h, 1, 10, p(a), p(b), p(out), 4) != 0      # Fr has no op above 9
 
 
 @pytest.mark.parametrize("group", [1, 2])

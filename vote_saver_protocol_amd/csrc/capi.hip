@@ -2,6 +2,7 @@
 // Jacobian record folding (resident bases live in bases.hip, the point compression with the other wire formats in wire.hip).
 #include "common.h"
 #include "fp28.h"
+#include "fr29.h"
 #include "lane_view.h"
 
 namespace vsp {
@@ -72,6 +73,30 @@ __global__ __launch_bounds__(64) void k_selftest_fp28(int op, const Fp *a, const
 #endif
 }
 
+// the 9 x 29-bit lazy field of the NTT butterflies (fr29.h), on canonical inputs, canonical out:
+//   op 6 round trip through the limb form, 7 x y through vsp_mm29 (y brought to the R' = 2^261 Montgomery form the way fr29_from_mont256
+//   makes the tables) and the conditional subtraction, 8 the same through vsp_mm29q (the routine's second register map), 9 x + x y - y^2
+//   through add29, sub29, norm29 and the product with the Montgomery one that leaves the lazy domain: the butterfly's own chain
+__global__ __launch_bounds__(64) void k_selftest_fr29(int op, const Fr *a, const Fr *b, Fr *out, size_t n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Fr29 x = fr29_from_words(a[i]), y = fr29_from_words(b[i]), r;
+    const Fr29 ym = csub29(mul29(y, fr29_const(FR29_R2)));                  // y R'^2 / R' = y R', below 2r -> canonical
+    switch (op) {
+        case 6: r = x; break;
+        case 7: r = csub29(mul29(x, ym)); break;
+        case 8: r = csub29(mul29q(x, ym)); break;
+        default: {                                                          // op 9
+            Fr29 xy = mul29(x, ym), yy = mul29q(y, ym);                     // product outputs below 1.02 r
+            Fr29 s = norm29(sub29(add29(x, xy), yy));                       // x + x y + 2r - y^2, below 4.03 r
+            r = csub29(mul29(s, fr29_const(FR29_ONE)));
+        } break;
+    }
+    out[i] = fr29_to_words(r);
+#endif
+}
+
 // The full addition of two bucket sums (curve.h / fp28.h xyzz_add) on its own, in each of the four forms the merges and the bucket
 // reduction run it in (diagnostic entry point vsp_selftest_xyzz_add): canonical X, Y, ZZ, ZZZ in, canonical out.  Lanes of one wave take
 // different paths (ordinary sum, doubling, cancellation, infinity on either side) as the test orders its cases -- the divergence the
@@ -108,7 +133,7 @@ extern "C" {
 
 int vsp_selftest_field(vsp_ctx *ctx, int field, int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n) {
     if (!ctx) return VSP_ERR_ARG;
-    if (!a || !b || !out || (field != 0 && field != 1) || op < 0 || op > 12 || (op > 5 && field != 0)) return set_error(ctx, VSP_ERR_ARG, "selftest: bad argument");
+    if (!a || !b || !out || (field != 0 && field != 1) || op < 0 || op > (field == 0 ? 12 : 9)) return set_error(ctx, VSP_ERR_ARG, "selftest: bad argument");
     VSP_HIP(hipSetDevice(ctx->device));
     size_t esz = field == 0 ? sizeof(Fp) : sizeof(Fr);
     DevBuf da, db, dc;
@@ -118,6 +143,7 @@ int vsp_selftest_field(vsp_ctx *ctx, int field, int op, const uint64_t *a, const
         hipMemcpyAsync(db.p, b, n * esz, hipMemcpyHostToDevice, ctx->stream);
         unsigned blocks = (unsigned)((n + 63) / 64);
         if (field == 0 && op > 5) hipLaunchKernelGGL(k_selftest_fp28, dim3(blocks), dim3(64), 0, ctx->stream, op, (const Fp *)da.p, (const Fp *)db.p, (Fp *)dc.p, n);
+        else if (op > 5) hipLaunchKernelGGL(k_selftest_fr29, dim3(blocks), dim3(64), 0, ctx->stream, op, (const Fr *)da.p, (const Fr *)db.p, (Fr *)dc.p, n);
         else if (field == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_selftest_field<Fp>), dim3(blocks), dim3(64), 0, ctx->stream, op, (const Fp *)da.p, (const Fp *)db.p, (Fp *)dc.p, n);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_selftest_field<Fr>), dim3(blocks), dim3(64), 0, ctx->stream, op, (const Fr *)da.p, (const Fr *)db.p, (Fr *)dc.p, n);
         hipMemcpyAsync(out, dc.p, n * esz, hipMemcpyDeviceToHost, ctx->stream);

@@ -12,10 +12,17 @@
 //   twiddles     Montgomery with R' = 2^261, canonical (< r), tight: mul29(x, w R') = x w + (multiple of r), below x r / 2^261 + r
 //   products     operand limb bounds 2^Ea, 2^Eb with Ea + Eb <= 60 (a twiddle is tight, so a data operand may carry limbs up to 2^31);
 //                output tight, value < 1.65 r for a data operand below 46 r
-//   a - b        = a + K2 - b limb by limb, K2 = 2r with every limb but the top raised by 2^29: b must be a product output (tight,
-//                < 1.65 r < 2r), so no limb goes negative
-//   growth       a radix-4 step takes the bound V of its inputs to V + 4r; 11 steps from 1.02 r stay below 46 r
-// tests/test_fr29_bounds.py checks these bounds with an exact model of the routine and a worst-case propagation.
+//   a - b        = a + K2 - b limb by limb, K2 = 2r with every limb but the top raised by 2^29: b must be tight and below 1.9 r (K2's
+//                top limb, after lending one unit, dominates that of 1.9 r): a product output (< 1.65 r for a data operand below 46 r,
+//                < 1.9 r below 63 r), a canonical input, or a coset-premultiplied one (< 1.02 r) -- so no limb goes negative
+//   a - b (4r)   = a + K4 - b, K4 = 4r in the same redundant form (sub29k4): b tight and below 3.9 r.  Only the FIRST stage of a
+//                transform whose first pass computes its own input (a b - c) / 2^261 (witness_map's last transform) needs it: that
+//                stage's twiddle is one, so the loaded value -- lazy, in (r, 3.03 r), no product output -- is itself the subtrahend
+//   growth       a radix-4 step takes the bound V of its inputs to V + 4r; 11 steps from 1.02 r stay below 46 r, 14 (2^28) below 58 r
+//                fused load: the first step takes 3.03 r to 9.03 r (x0 + x1 has no product on x1, and 4r is lent instead of 2r), a
+//                leading radix-2 stage to 7.03 r; + 4r per later step: 14 steps end below 63.1 r < 2^261, the last product below 1.9 r
+// tests/test_fr29_bounds.py checks these bounds with an exact model of the routine and a worst-case propagation that steps the first
+// stage as the kernel does.
 #pragma once
 #include "field.h"
 
@@ -102,11 +109,18 @@ __device__ __forceinline__ Fr29 add29(const Fr29 &a, const Fr29 &b) {
     for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + b.l[i];
     return r;
 }
-// a + 2r - b, b a product output
+// a + 2r - b, b a product output (or a canonical / premultiplied input): tight and below 1.9 r
 __device__ __forceinline__ Fr29 sub29(const Fr29 &a, const Fr29 &b) {
     Fr29 r;
 #pragma unroll
     for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + FR29_K2_L1[i] - b.l[i];
+    return r;
+}
+// a + 4r - b, b tight and below 3.9 r: the fused load's lazy value as the first stage's subtrahend
+__device__ __forceinline__ Fr29 sub29k4(const Fr29 &a, const Fr29 &b) {
+    Fr29 r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.l[i] = a.l[i] + FR29_K4_L1[i] - b.l[i];
     return r;
 }
 // carry pass: limbs below 2^32 - 8 -> tight, same value

@@ -1021,8 +1021,8 @@ template <class F> static int msm_accumulate(vsp_ctx *ctx, MsmWork &wk, const Ms
     wk.dimbits = L.dimbits;
     // (the diagnostic build without hand-laid-out routines runs the multi-exponentiation on the generic 12 x 32-bit kernels only: the
     // 28-bit reduction kernels over portable products crash this toolchain's backend -- Machine Copy Propagation / post-RA pseudo
-    // expansion segfault in k_dimsum<Fp28> / k_dimsum<Fp2x28>; the 28-bit and 29-bit FIELD forms stay covered by vsp_selftest_field,
-    // vsp_selftest_xyzz_add and the transforms)
+    // expansion segfault in k_dimsum<Fp28> / k_dimsum<Fp2x28>; the FIELD forms stay covered there: the 28-bit one by vsp_selftest_field
+    // (Fp, ops 6..12) and vsp_selftest_xyzz_add, the 29-bit one by vsp_selftest_field (Fr, ops 6..9) and the transforms)
 #if defined(VSP_PORTABLE_MUL)
     constexpr bool have28 = sizeof(F) == 0;
 #else

@@ -243,27 +243,37 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt29_pass(Planes29 in_lazy, Pl
 
     const unsigned lo_part = p.first ? 0u : ((lo_hi << p.clog));
     unsigned t = 0;
+    // the transform's first stage (s == 0) has the twiddle one and no product: the values as LOADED are its subtrahends.  A plain load is
+    // canonical and a premultiplied one a product output -- sub29's 2r covers them; the fused load leaves a lazy value up to 3.03 r, which
+    // needs the redundant 4r (sub29k4; fr29.h).  A per-pass constant picks a copy of the stage, as for the first pair of products below.
+    const bool fused_first = p.first && p.fuse_b != nullptr;
     if (K & 1) {
         const unsigned s = p.s0;
-        for (unsigned bf = tid; bf < (tile >> 1); bf += NTT_THREADS) {
-            unsigned c = bf & (C - 1), q = bf >> p.clog;
-            unsigned e0 = (q << (1 + p.clog)) | c, e1 = e0 + C;
-            Fr29 u = lds_load29(pl0, pl1, pl2, e0), v = lds_load29(pl0, pl1, pl2, e1);
-            if (s > 0) v = mul29(v, ld29(p.tw, (size_t)(p.first ? 0u : (lo_part | c)) << (p.tlog - 1 - s)));
-            lds_store29(pl0, pl1, pl2, e0, norm29(add29(u, v)));
-            lds_store29(pl0, pl1, pl2, e1, norm29(sub29(u, v)));       // s == 0 only in the first pass: v is a canonical input there
-        }
+        auto stage = [&](auto fused_load) {
+            constexpr bool FUSED = decltype(fused_load)::value;
+            for (unsigned bf = tid; bf < (tile >> 1); bf += NTT_THREADS) {
+                unsigned c = bf & (C - 1), q = bf >> p.clog;
+                unsigned e0 = (q << (1 + p.clog)) | c, e1 = e0 + C;
+                Fr29 u = lds_load29(pl0, pl1, pl2, e0), v = lds_load29(pl0, pl1, pl2, e1);
+                if (!FUSED && s > 0) v = mul29(v, ld29(p.tw, (size_t)(p.first ? 0u : (lo_part | c)) << (p.tlog - 1 - s)));
+                lds_store29(pl0, pl1, pl2, e0, norm29(add29(u, v)));
+                lds_store29(pl0, pl1, pl2, e1, norm29(FUSED ? sub29k4(u, v) : sub29(u, v)));       // s == 0 only in the first pass: v is a loaded input there
+            }
+        };
+        if (s == 0 && fused_first) stage(std::true_type{}); else stage(std::false_type{});
         __syncthreads();
         t = 1;
     }
     for (; t < K; t += 2) {
         const unsigned s = p.s0 + t;
         const unsigned h = 1u << t;
-        // the first pair of products exists from stage 1 on (stage 0's twiddle is one).  Two copies of the loop, not a branch inside it:
+        // the first pair of products exists from stage 1 on (stage 0's twiddle is one).  Copies of the loop, not a branch inside it:
         // a value that is "the loaded x1 or the product" is ONE register set for the compiler, which then loads x1 into the routine's
         // result registers and copies it to the operand registers before every call (nine copies per product, section 3.2 of DESIGN.md)
-        auto group = [&](unsigned g, auto with_first_pair) {
+        auto group = [&](unsigned g, auto with_first_pair, auto fused_load) {
             constexpr bool TW1 = decltype(with_first_pair)::value;
+            constexpr bool FUSED = decltype(fused_load)::value;           // stage 0 of a fused load: raw subtrahends up to 3.03 r
+            static_assert(!(TW1 && FUSED), "a product output never needs the 4r subtraction");
             unsigned c = g & (C - 1), q = g >> p.clog;
             unsigned mid_lo = q & (h - 1);
             unsigned mid0 = ((q >> t) << (t + 2)) | mid_lo;
@@ -275,7 +285,7 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt29_pass(Planes29 in_lazy, Pl
                 x1 = mul29(x1, w1); x3 = mul29q(x3, w1);
             }
             Fr29 x0 = lds_load29(pl0, pl1, pl2, e0), x2 = lds_load29(pl0, pl1, pl2, e2);
-            Fr29 a0 = add29(x0, x1), a1 = sub29(x0, x1), a2 = add29(x2, x3), a3 = sub29(x2, x3);
+            Fr29 a0 = add29(x0, x1), a1 = FUSED ? sub29k4(x0, x1) : sub29(x0, x1), a2 = add29(x2, x3), a3 = FUSED ? sub29k4(x2, x3) : sub29(x2, x3);
             a2 = mul29(a2, ld29(p.tw, (((size_t)mid_lo << p.s0) | off) << (p.tlog - 2 - s)));
             a3 = mul29q(a3, ld29(p.tw, (((size_t)(mid_lo + h) << p.s0) | off) << (p.tlog - 2 - s)));
             lds_store29(pl0, pl1, pl2, e0, norm29(add29(a0, a2)));
@@ -283,8 +293,9 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt29_pass(Planes29 in_lazy, Pl
             lds_store29(pl0, pl1, pl2, e2, norm29(sub29(a0, a2)));
             lds_store29(pl0, pl1, pl2, e3, norm29(sub29(a1, a3)));
         };
-        if (s > 0) for (unsigned g = tid; g < (tile >> 2); g += NTT_THREADS) group(g, std::true_type{});
-        else for (unsigned g = tid; g < (tile >> 2); g += NTT_THREADS) group(g, std::false_type{});
+        if (s > 0) for (unsigned g = tid; g < (tile >> 2); g += NTT_THREADS) group(g, std::true_type{}, std::false_type{});
+        else if (fused_first) for (unsigned g = tid; g < (tile >> 2); g += NTT_THREADS) group(g, std::false_type{}, std::true_type{});
+        else for (unsigned g = tid; g < (tile >> 2); g += NTT_THREADS) group(g, std::false_type{}, std::false_type{});
         __syncthreads();
     }
 
@@ -578,6 +589,7 @@ int ntt_launch(vsp_ctx *ctx, const NttRequest &rq) {
     }
     ctx->stats["ntt_passes"] = (double)npass;
     ctx->stats["ntt_fr29"] = use29 ? 1 : 0;
+    ctx->stats["ntt_fused_load"] = rq.fuse_b ? 1 : 0;      // the first pass computed its own input (witness_map's last transform)
     return VSP_OK;
 }
 
