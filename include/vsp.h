@@ -412,6 +412,32 @@ int vsp_g2_decompress(const uint8_t in[96], int check_subgroup, uint64_t out_aff
 int vsp_g1_decompress_batch(vsp_ctx *ctx, const uint8_t *in /* host n x 48 */, size_t n, int check_subgroup,
                             uint64_t *out_affine /* host n x 12, canonical */, uint8_t *status_out /* host n */);
 
+/* ---- batch decompression of G2 points and of proofs on the GPU -----------------------------------
+ * vsp_g2_decompress_batch is the G2 counterpart of the above: n ZCash-compressed G2 points (96 bytes each: x.c1 | x.c0 big-endian, the
+ * flag bits in the first byte) -> canonical affine limbs (x.c0 | x.c1 | y.c0 | y.c1) and one status byte per point with the same bits:
+ *     bit 0  malformed encoding (flag rules as for G1; a coefficient of x >= p)
+ *     bit 1  x^3 + 4 (1 + u) is not a square in Fp2: no point of the twist has this x
+ *     bit 2  not in the order-r subgroup (only with check_subgroup != 0; the same endomorphism test over Fp2)
+ * A point is accepted exactly when vsp_g2_decompress accepts the same 96 bytes; a rejected point and infinity are all-zero limbs.
+ * One lane per point: the root in Fp2 is two fixed chains, 976 field products with the curve equation and the sign rule
+ * (csrc/fp2_sqrt.h), where the host function walks four generic square-and-multiply loops.
+ * vsp_proof_from_blob_batch decodes n proof blobs lying back to back (A (48) | B (96) | C (48): the layout vsp_proof_to_blob writes and
+ * data.bin[0:192) pins).  Proof k's status is the OR of its three points' status bytes in bits 0..2; bits 4, 5, 6 are set when A, B, C
+ * respectively was rejected.  A proof is accepted (status 0) exactly when vsp_proof_from_blob accepts the same 192 bytes (infinity
+ * members are accepted, as there); all three outputs of a rejected proof are all-zero limbs, its well-formed members included.  Any of
+ * A_out, B_out, C_out may be NULL (that member is still decoded and checked); blobs and status_out may not.
+ * Both: VSP_OK whatever the verdicts are; VSP_ERR_ARG for a null pointer, also with n = 0; VSP_ERR_HIP as elsewhere.  Any n: the work
+ * runs in pieces of at most "tally_chunk_points" points (default 2^21; a proof counts three, at least one proof per piece).
+ * Workspace bound per piece: 96 raw + 192 decoded + 1 status byte per G2 point (578 MiB at 2^21 points); 192 raw + 2 x 96 + 192 decoded
+ * + 4 status bytes per proof (387 MiB at 2^21 / 3 proofs), of the context's grow-only workspaces whatever n is.  Stage times (HIP
+ * events, summed since vsp_stats_reset): vsp_get_stat "g2_decode_ms", "g2_subgroup_ms"; the G1 members of proofs are added to
+ * "tally_decode_ms" and "tally_subgroup_ms". */
+int vsp_g2_decompress_batch(vsp_ctx *ctx, const uint8_t *in /* host n x 96 */, size_t n, int check_subgroup,
+                            uint64_t *out_affine /* host n x 24, canonical */, uint8_t *status_out /* host n */);
+int vsp_proof_from_blob_batch(vsp_ctx *ctx, const uint8_t *blobs /* host n x 192, back to back */, size_t n, int check_subgroup,
+                              uint64_t *A_out /* n x 12 */, uint64_t *B_out /* n x 24 */, uint64_t *C_out /* n x 12 */,
+                              uint8_t *status_out /* n */);
+
 /* ---- tally: the aggregation of common.hpp:1193-1216 (repeated by every verifier at :1257-1279) ----
  * process_encrypted_input_mode_tally_admin_phase deserialises up to 1 << tree_depth ciphertext blobs one after the other and adds
  * them component by component into ct_agg; everything after that is pairing work on the ONE aggregated ciphertext.  A tally handle

@@ -120,6 +120,8 @@ PROTOTYPES = {
     "vsp_g1_decompress": (_I, [_P, _I, _P, _P]),
     "vsp_g2_decompress": (_I, [_P, _I, _P, _P]),
     "vsp_g1_decompress_batch": (_I, [_P, _P, _SZ, _I, _P, _P]),
+    "vsp_g2_decompress_batch": (_I, [_P, _P, _SZ, _I, _P, _P]),
+    "vsp_proof_from_blob_batch": (_I, [_P, _P, _SZ, _I, _P, _P, _P, _P]),
     "vsp_tally_create": (_P, [_P, _SZ]),
     "vsp_tally_free": (None, [_P, _P]),
     "vsp_tally_add_blobs": (_I, [_P, _P, _P, _SZ, _I, _P, _P]),

@@ -692,6 +692,32 @@ def g1_decompress_batch(ctx, data, check_subgroup=True):
     return out, status
 
 
+def g2_decompress_batch(ctx, data, check_subgroup=True):
+    """n x 96 ZCash-compressed bytes -> (points [n,24], status [n]) on the GPU.  status 0 = accepted; bit 0 malformed encoding, bit 1
+    no point of the twist has this x, bit 2 outside the order-r subgroup (only with check_subgroup).  Rejected points and infinity are
+    all zero."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    if buf.shape[0] % 96:
+        raise ValueError("g2_decompress_batch: the input is not a whole number of 96-byte points")
+    n = buf.shape[0] // 96
+    out = np.zeros((n, 24), np.uint64); status = np.zeros(n, np.uint8)
+    ctx.check(ctx.lib.vsp_g2_decompress_batch(ctx.h, _ptr(buf), n, int(check_subgroup), _ptr(out), _ptr(status)))
+    return out, status
+
+
+def proofs_from_blob_batch(ctx, data, check_subgroup=True):
+    """n x 192 bytes of proof blobs (A | B | C, back to back) -> (A [n,12], B [n,24], C [n,12], status [n]) on the GPU.  status 0 =
+    accepted; bits 0..2 are the OR of the three points' status bits (as g1_decompress_batch), bits 4, 5, 6 say that A, B, C was
+    rejected.  Every member of a rejected proof is all zero."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    if buf.shape[0] % 192:
+        raise ValueError("proofs_from_blob_batch: the input is not a whole number of 192-byte proofs")
+    n = buf.shape[0] // 192
+    A = np.zeros((n, 12), np.uint64); B = np.zeros((n, 24), np.uint64); Cc = np.zeros((n, 12), np.uint64); status = np.zeros(n, np.uint8)
+    ctx.check(ctx.lib.vsp_proof_from_blob_batch(ctx.h, _ptr(buf), n, int(check_subgroup), _ptr(A), _ptr(B), _ptr(Cc), _ptr(status)))
+    return A, B, Cc, status
+
+
 class Tally:
     """The aggregation of the tally (common.hpp:1193-1216, repeated by every verifier at :1257-1279): ct_len = msg_size + 2 running sums
     of ciphertext components over the ballots added so far (vsp_tally)."""

@@ -214,6 +214,9 @@ struct vsp_ctx {
     // stage timers, created on first use
     vsp::DevBuf tally_raw, tally_pts, tally_pstatus, tally_bstatus, tally_partials;
     hipEvent_t tally_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // the G2 points of a chunk of proofs or of vsp_g2_decompress_batch (tally.hip) with their status bytes, and the two stages' timers
+    vsp::DevBuf g2_pts, g2_pstatus;
+    hipEvent_t g2_ev[3] = {nullptr, nullptr, nullptr};
     // prover workspaces for K witnesses (a single proof: K = 1): z [K][num_vars + 1], A z, B z, C z [K][3][m], H [K][m], the packed witness
     vsp::DevBuf pr_z, pr_abc, pr_h, pr_pack;
     // the proof or the batch of K proofs in flight between a launch and its finish (one per context): the key, r and s (K x 4 words), the
