@@ -43,7 +43,8 @@ enum {
                               * multi-exponentiation / proof finishes), a base coordinate >= p or a base off the curve (at upload) */
     VSP_ERR_HIP = -2,        /* a HIP runtime call failed; vsp_last_error() has the text */
     VSP_ERR_NOMEM = -3,
-    VSP_ERR_UNSUPPORTED = -4 /* e.g. log_m > 28 */
+    VSP_ERR_UNSUPPORTED = -4, /* e.g. log_m > 28 */
+    VSP_ERR_UNSATISFIED = -5  /* option "prove_check_witness": a witness does not satisfy the constraint system; no proof was written for it */
 };
 
 /* ---- context ------------------------------------------------------------------------------- */
@@ -102,7 +103,9 @@ void vsp_stats_reset(vsp_ctx *ctx);
  * multi-exponentiation -- a blocking read-back); "msm_sort" (0: by size; 1: never the staged sort of large wide-window problems;
  * 2: the staged sort for every window of 12 bits and more), "msm_wide_windows" (0: never more than 16 bits per window), "msm_fold" (0: 255-bit
  * scalars are not folded to min(k, r - k) where the window width divides 255), "msm_fused_split" (0: the endomorphism split and the digit
- * extraction run as two kernels over the scalars instead of one), "msm_fused_scans" (0: the bucket scans take three kernels each).
+ * extraction run as two kernels over the scalars instead of one), "msm_fused_scans" (0: the bucket scans take three kernels each),
+ * "prove_check_witness" (default 0; 1: every prover entry point checks its witnesses against the constraint system and refuses the ones
+ * that fail -- "witness check" below).
  *
  * Runtime environment.  Results never depend on it.  GPU_MAX_HW_QUEUES (HIP runtime, read once when the runtime starts; default 4
  * hardware queues per stream priority): one proof's latency does not depend on it (the prover's two chains take their queues when the
@@ -254,6 +257,48 @@ void vsp_r1cs_free(vsp_ctx *ctx, vsp_r1cs *cs);
 /* the domain r1cs_to_qap uses for this system: make_evaluation_domain(num_constraints + num_inputs + 1); H_query has size - 1 bases */
 size_t vsp_r1cs_domain_size(const vsp_r1cs *cs);
 int vsp_r1cs_domain_kind(const vsp_r1cs *cs);                  /* 0 basic_radix2, 1 step_radix2 */
+
+/* ---- witness check: bp.is_satisfied(), the gate in front of the prover (common.hpp:1109-1128) ---------------------------------
+ * Does z = (1, witness) satisfy (A z)[i] (B z)[i] = (C z)[i] in Fr for every row i < num_constraints?  vsp_r1cs_check_batch answers for
+ * `count` witnesses (num_vars x 4 words each, one after the other) with one status byte per witness:
+ *     0      satisfied
+ *     bit 0  the witness holds a value that is not canonical (>= r), in a wire of a constraint or in one that no constraint names
+ *     bit 1  some constraint does not hold
+ * first_bad_row_out[k] (may be NULL) is the lowest failing row of witness k, or num_constraints when none fails; bad_rows_out[k] (may be
+ * NULL) the number of failing rows.  Both are deterministic.  For a witness with bit 0 the rows are judged on the value reduced mod r:
+ * bit 1, first_bad_row and bad_rows are then unspecified beyond first_bad_row <= num_constraints and bad_rows <= num_constraints.  Rows
+ * num_constraints .. m - 1 of the domain (the "input_i * 0 = 0" rows, the padding) are not part of the system and are not checked; a
+ * system with num_constraints = 0 is satisfied by every canonical witness.
+ * The return value is VSP_OK whatever the verdicts are: VSP_ERR_ARG is for a null pointer (also with count = 0) and for a context with a
+ * proof in flight (the check uses the prover's workspace), VSP_ERR_HIP as elsewhere.  vsp_r1cs_is_satisfied is the same path with count = 1:
+ * *satisfied_out = 1 exactly when the status byte is 0.
+ * The check runs the prover's own front half -- the same upload, the same three sparse mat-vecs -- and then one pass over A z, B z, C z
+ * (k_r1cs_verdict: one field product per row), so what it approves is word for word what the prover consumes.  Any count: the witnesses
+ * go through the device in pieces of at most 64, the batch prover's limit.  Workspace bound per piece: 64 x (num_vars + 1) x 32 bytes of
+ * z and 64 x 3 m x 32 bytes of A z, B z, C z (m = vsp_r1cs_domain_size) -- the workspaces of vsp_groth16_prove_batch, nothing beyond them
+ * whatever count is -- plus 768 bytes of verdict records.  The call's copy of the witnesses is zeroed before it returns.  Stage times (HIP
+ * events, summed since vsp_stats_reset): vsp_get_stat "r1cs_check_ms" (the verdict kernels), "r1cs_check_front_ms" (upload and mat-vecs).
+ *
+ * Inside the prover: option "prove_check_witness" = 1 queues the same pass between the mat-vecs and witness_map in vsp_groth16_prove,
+ * vsp_groth16_prove_launch, vsp_groth16_prove_launch_packed, vsp_saver_encrypt and vsp_groth16_prove_batch(_launch).  The verdict
+ * travels to page-locked memory by an asynchronous copy and is read by the finish after its existing waits: no wait is added.
+ *   single proof  an unsatisfied witness makes the finish (and the blocking call) return VSP_ERR_UNSATISFIED; A_out, B_out, C_out, proof_out
+ *                 (and vsp_saver_encrypt's ct_out) are all zero, vsp_last_error names the first failing row and vsp_get_stat
+ *                 ("prove_first_bad_row") reports it (num_constraints after a satisfied witness).  The context is ready for the next proof.
+ *   batch         every satisfied member's outputs are byte-identical to the ones without the option, every unsatisfied member's are all
+ *                 zero, and the finish returns VSP_ERR_UNSATISFIED if any member failed.  vsp_groth16_prove_batch_verdicts then tells
+ *                 which: status_out[k] (count bytes) is 0 or bit 1 as above, first_bad_row_out[k] (may be NULL) the member's first failing
+ *                 row or num_constraints.  It speaks of the last batch that FINISHED on this context with the option set (the verdicts
+ *                 survive from the launch to the finish and until the next batch finishes); VSP_ERR_ARG if there is none.
+ * The GPU work of an unsatisfied witness is NOT skipped: the verdict is known only when the finish reads it, by which time every kernel
+ * is queued.  A value >= r keeps returning VSP_ERR_ARG from the finish, as without the option (the multi-exponentiations' census finds
+ * it; for a batch, for the whole batch), and takes precedence over VSP_ERR_UNSATISFIED.  With the option 0 nothing is checked: an
+ * unsatisfying witness yields VSP_OK and a well-formed proof that no verifier accepts. */
+int vsp_r1cs_check_batch(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64_t *witnesses /* host count x num_vars x 4 */, size_t count,
+                         uint8_t *status_out /* count */, uint64_t *first_bad_row_out /* count, may be NULL */,
+                         uint64_t *bad_rows_out /* count, may be NULL */);
+int vsp_r1cs_is_satisfied(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64_t *witness, int *satisfied_out, uint64_t *first_bad_row_out /* may be NULL */);
+int vsp_groth16_prove_batch_verdicts(vsp_ctx *ctx, uint8_t *status_out /* count */, uint64_t *first_bad_row_out /* count, may be NULL */);
 
 /* Proving key = { alpha_g1, beta_g1, beta_g2, delta_g1, delta_g2, A_query[num_vars+1],
  * B_query (G2 and G1 halves, num_vars+1 each), H_query[m-1], L_query[num_vars-num_inputs] }

@@ -61,6 +61,8 @@ PROTOTYPES = {
     "vsp_r1cs_free": (None, [_P, _P]),
     "vsp_r1cs_domain_size": (_SZ, [_P]),
     "vsp_r1cs_domain_kind": (_I, [_P]),
+    "vsp_r1cs_check_batch": (_I, [_P, _P, _P, _SZ, _P, _P, _P]),
+    "vsp_r1cs_is_satisfied": (_I, [_P, _P, _P, _P, _P]),
     "vsp_domain_create": (_P, [_P, _SZ]),
     "vsp_domain_free": (None, [_P, _P]),
     "vsp_domain_size": (_SZ, [_P]),
@@ -79,6 +81,7 @@ PROTOTYPES = {
     "vsp_groth16_prove_batch": (_I, [_P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P, _P]),
     "vsp_groth16_prove_batch_launch": (_I, [_P, _P, _P, _P, _SZ, _P, _P]),
     "vsp_groth16_prove_batch_finish": (_I, [_P, _P, _P, _P, _P]),
+    "vsp_groth16_prove_batch_verdicts": (_I, [_P, _P, _P]),
     "vsp_groth16_prove_launch": (_I, [_P] * 8),
     "vsp_groth16_prove_finish": (_I, [_P] * 5),
     "vsp_witness_pack_words": (_SZ, [_SZ]),

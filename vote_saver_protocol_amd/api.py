@@ -21,6 +21,16 @@ class VspError(RuntimeError):
     pass
 
 
+class Unsatisfied(VspError):
+    """VSP_ERR_UNSATISFIED (option "prove_check_witness"): a witness does not satisfy the constraint system.  code = -5; first_bad_row: the
+    first failing constraint of a single proof; after a batch: status [K] (bit 1 = unsatisfied), first_bad_row [K] and results = the
+    batch's (A, B, C, proofs), where the satisfied members' proofs are valid and the others' outputs all zero."""
+    code = -5
+    first_bad_row = None
+    status = None
+    results = None
+
+
 def _ptr(a):
     if a is None:
         return None
@@ -78,6 +88,8 @@ class Context:
             pass
 
     def check(self, rc):
+        if rc == Unsatisfied.code:
+            raise Unsatisfied(f"vsp error {rc}: {self.lib.vsp_last_error(self.h).decode()}")
         if rc != 0:
             raise VspError(f"vsp error {rc}: {self.lib.vsp_last_error(self.h).decode()}")
 
@@ -389,6 +401,30 @@ class R1CS:
         self.m = ctx.lib.vsp_r1cs_domain_size(self.h)              # make_evaluation_domain(num_constraints + num_inputs + 1)
         self.domain_kind = ("basic_radix2", "step_radix2")[ctx.lib.vsp_r1cs_domain_kind(self.h)]
 
+    def check(self, ctx, witnesses):
+        """bp.is_satisfied() for many witnesses (vsp_r1cs_check_batch): witnesses [count, num_vars, 4], any count.
+        -> (status u8 [count]: 0 satisfied, bit 0 a value >= r, bit 1 some constraint fails; first_bad_row u64 [count]: num_constraints
+        when none fails; bad_rows u64 [count])"""
+        witnesses = np.ascontiguousarray(witnesses, dtype=np.uint64)
+        if witnesses.ndim != 3 or witnesses.shape[1:] != (self.num_vars, 4):
+            raise ValueError("R1CS.check: witnesses must be [count, num_vars, 4]")
+        n = witnesses.shape[0]
+        status = np.zeros(n, np.uint8); first = np.zeros(n, np.uint64); bad = np.zeros(n, np.uint64)
+        # sized at least one element, so that count = 0 still passes non-null pointers
+        wp = witnesses if witnesses.size else np.zeros(4, np.uint64)
+        ctx.check(ctx.lib.vsp_r1cs_check_batch(ctx.h, self.h, _ptr(wp), n, _ptr(status if n else np.zeros(1, np.uint8)), _ptr(first if n else np.zeros(1, np.uint64)),
+                                               _ptr(bad if n else np.zeros(1, np.uint64))))
+        return status, first, bad
+
+    def is_satisfied(self, ctx, witness):
+        """bp.is_satisfied() (common.hpp:1109-1128) on the GPU: True exactly when every constraint holds and every value is canonical"""
+        witness = _u64(witness, 4)
+        if witness.shape[0] != self.num_vars:
+            raise ValueError("R1CS.is_satisfied: witness must have num_vars entries (primary || auxiliary)")
+        ok = C.c_int(0)
+        ctx.check(ctx.lib.vsp_r1cs_is_satisfied(ctx.h, self.h, _ptr(witness if witness.size else np.zeros(4, np.uint64)), C.byref(ok), None))
+        return bool(ok.value)
+
     def free(self):
         if self.h and self.ctx.h:
             self.ctx.lib.vsp_r1cs_free(self.ctx.h, self.h)
@@ -484,9 +520,38 @@ def groth16_prove(ctx, cs, pk, witness, r, s, saver_P1=None, saver_r_enc=None):
     proof = np.zeros(192, np.uint8)
     p1 = None if saver_P1 is None else _u64(saver_P1)
     re = None if saver_r_enc is None else _u64(saver_r_enc)
-    ctx.check(ctx.lib.vsp_groth16_prove(ctx.h, cs.h, pk.h, _ptr(witness), _ptr(_u64(r)), _ptr(_u64(s)), _ptr(p1), _ptr(re),
-                                        _ptr(A), _ptr(B), _ptr(Cc), _ptr(proof)))
+    _check_single(ctx, ctx.lib.vsp_groth16_prove(ctx.h, cs.h, pk.h, _ptr(witness), _ptr(_u64(r)), _ptr(_u64(s)), _ptr(p1), _ptr(re),
+                                                 _ptr(A), _ptr(B), _ptr(Cc), _ptr(proof)))
     return A, B, Cc, proof.tobytes()
+
+
+def _check_single(ctx, rc):
+    """ctx.check for the single-proof calls: an Unsatisfied carries the first failing constraint"""
+    try:
+        ctx.check(rc)
+    except Unsatisfied as e:
+        e.first_bad_row = int(ctx.stat("prove_first_bad_row"))
+        raise
+
+
+def _check_batch(ctx, rc, results):
+    """ctx.check for the batch calls: an Unsatisfied carries the members' verdicts and the batch's outputs"""
+    try:
+        ctx.check(rc)
+    except Unsatisfied as e:
+        e.status, e.first_bad_row = groth16_prove_batch_verdicts(ctx, len(results[3]))
+        e.results = results
+        raise
+    return results
+
+
+def groth16_prove_batch_verdicts(ctx, count=None):
+    """the verdicts of the last batch that finished on this context with option prove_check_witness = 1
+    -> (status u8 [K]: 0 or bit 1 = unsatisfied, first_bad_row u64 [K]); count: K when the batch was not proved through this module"""
+    K = count if count is not None else getattr(ctx, "_prove_batch_last", 0)
+    status = np.zeros(max(K, 1), np.uint8); first = np.zeros(max(K, 1), np.uint64)
+    ctx.check(ctx.lib.vsp_groth16_prove_batch_verdicts(ctx.h, _ptr(status), _ptr(first)))
+    return status[:K], first[:K]
 
 
 def _batch_inputs(cs, witnesses, r, s):
@@ -506,8 +571,9 @@ def groth16_prove_batch(ctx, cs, pk, witnesses, r, s):
     witnesses, r, s, K = _batch_inputs(cs, witnesses, r, s)
     A = np.zeros((K, 12), np.uint64); B = np.zeros((K, 24), np.uint64); Cc = np.zeros((K, 12), np.uint64)
     proofs = np.zeros((K, 192), np.uint8)
-    ctx.check(ctx.lib.vsp_groth16_prove_batch(ctx.h, cs.h, pk.h, _ptr(witnesses), K, _ptr(r), _ptr(s), _ptr(A), _ptr(B), _ptr(Cc), _ptr(proofs)))
-    return A, B, Cc, [proofs[k].tobytes() for k in range(K)]
+    ctx._prove_batch_last = K
+    rc = ctx.lib.vsp_groth16_prove_batch(ctx.h, cs.h, pk.h, _ptr(witnesses), K, _ptr(r), _ptr(s), _ptr(A), _ptr(B), _ptr(Cc), _ptr(proofs))
+    return _check_batch(ctx, rc, (A, B, Cc, [proofs[k].tobytes() for k in range(K)]))
 
 
 def groth16_prove_batch_launch(ctx, cs, pk, witnesses, r, s):
@@ -526,8 +592,9 @@ def groth16_prove_batch_finish(ctx):
     ctx._prove_batch_count = 0
     A = np.zeros((K, 12), np.uint64); B = np.zeros((K, 24), np.uint64); Cc = np.zeros((K, 12), np.uint64)
     proofs = np.zeros((K, 192), np.uint8)
-    ctx.check(ctx.lib.vsp_groth16_prove_batch_finish(ctx.h, _ptr(A), _ptr(B), _ptr(Cc), _ptr(proofs)))
-    return A, B, Cc, [proofs[k].tobytes() for k in range(K)]
+    ctx._prove_batch_last = K
+    rc = ctx.lib.vsp_groth16_prove_batch_finish(ctx.h, _ptr(A), _ptr(B), _ptr(Cc), _ptr(proofs))
+    return _check_batch(ctx, rc, (A, B, Cc, [proofs[k].tobytes() for k in range(K)]))
 
 
 class PackedWitness:
@@ -574,7 +641,7 @@ def groth16_prove_finish(ctx):
     """second half: host-side assembly work, the wait, the proof.  -> (A[12], B[24], C[12], proof_bytes[192])"""
     A = np.zeros(12, np.uint64); B = np.zeros(24, np.uint64); Cc = np.zeros(12, np.uint64)
     proof = np.zeros(192, np.uint8)
-    ctx.check(ctx.lib.vsp_groth16_prove_finish(ctx.h, _ptr(A), _ptr(B), _ptr(Cc), _ptr(proof)))
+    _check_single(ctx, ctx.lib.vsp_groth16_prove_finish(ctx.h, _ptr(A), _ptr(B), _ptr(Cc), _ptr(proof)))
     return A, B, Cc, proof.tobytes()
 
 
@@ -624,8 +691,8 @@ def saver_encrypt(ctx, spk, cs, pk, msg, witness, r_enc, r, s):
         raise ValueError("encrypt: witness must have num_vars entries and the message msg_size blocks")
     ct = np.zeros((spk.n + 2, 12), np.uint64)
     A = np.zeros(12, np.uint64); B = np.zeros(24, np.uint64); Cc = np.zeros(12, np.uint64); proof = np.zeros(192, np.uint8)
-    ctx.check(ctx.lib.vsp_saver_encrypt(ctx.h, spk.h, cs.h, pk.h, _ptr(msg), _ptr(witness), _ptr(_u64(r_enc)), _ptr(_u64(r)), _ptr(_u64(s)),
-                                        _ptr(ct), _ptr(A), _ptr(B), _ptr(Cc), _ptr(proof)))
+    _check_single(ctx, ctx.lib.vsp_saver_encrypt(ctx.h, spk.h, cs.h, pk.h, _ptr(msg), _ptr(witness), _ptr(_u64(r_enc)), _ptr(_u64(r)), _ptr(_u64(s)),
+                                                 _ptr(ct), _ptr(A), _ptr(B), _ptr(Cc), _ptr(proof)))
     return ct, (A, B, Cc), proof.tobytes()
 
 

@@ -219,12 +219,22 @@ struct vsp_ctx {
     hipEvent_t g2_ev[3] = {nullptr, nullptr, nullptr};
     // prover workspaces for K witnesses (a single proof: K = 1): z [K][num_vars + 1], A z, B z, C z [K][3][m], H [K][m], the packed witness
     vsp::DevBuf pr_z, pr_abc, pr_h, pr_pack;
+    // the witness check (prover.hip k_r1cs_verdict): per member of a piece of at most VERDICT_MEMBERS witnesses three 32-bit words --
+    // first_bad_row [64] | bad_rows [64] | a value >= r [64] -- on the device and in the pinned buffer the asynchronous copy lands in
+    static constexpr size_t VERDICT_MEMBERS = 64, VERDICT_BYTES = 3 * VERDICT_MEMBERS * sizeof(uint32_t);
+    vsp::DevBuf pr_verdict;
+    void *h_verdict = nullptr;
+    hipEvent_t check_ev[3] = {nullptr, nullptr, nullptr};      // vsp_r1cs_check_batch: around its front half and around its verdict kernels
     // the proof or the batch of K proofs in flight between a launch and its finish (one per context): the key, r and s (K x 4 words), the
     // SAVER term (single proofs only), the bytes of z the launch wrote
     struct {
         bool active = false, batch = false; const vsp_pk *pk = nullptr; size_t count = 0, z_bytes = 0; std::vector<uint64_t> r, s;
         bool has_saver = false; uint64_t P1[12], r_enc[4];
+        bool check = false;      // option "prove_check_witness": the verdict records are on their way to h_verdict
     } prove;
+    // vsp_groth16_prove_batch_verdicts: status byte and first failing row of every member of the last finished batch that was checked
+    std::vector<uint8_t> batch_status;
+    std::vector<uint64_t> batch_first_bad;
 };
 
 struct vsp_bases {
@@ -464,6 +474,21 @@ __device__ __forceinline__ bool canon_below_p(const Fp &a) {
     for (int i = Fp::N - 1; i >= 0; i--) {
         lt = lt || (!gt && a.l[i] < FpP32::MOD[i]);
         gt = gt || (!lt && a.l[i] > FpP32::MOD[i]);
+    }
+    return lt;
+}
+
+// a canonical scalar (two 16-byte halves of its eight 32-bit words) below r: the multi-exponentiations' census (msm_sort.hip k_classify) and
+// the witness check (prover.hip k_witness_canonical) refuse the same values
+__device__ __forceinline__ bool scalar_below_r(const uint4 &lo, const uint4 &hi) {
+    // r = 0x73eda753299d7d48 3339d80809a1d805 53bda402fffe5bfe ffffffff00000001, compared from the top 32-bit word down
+    const uint32_t k[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    const uint32_t r[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
+    bool lt = false, gt = false;
+#pragma unroll
+    for (int i = 7; i >= 0; i--) {
+        lt = lt || (!gt && k[i] < r[i]);
+        gt = gt || (!lt && k[i] > r[i]);
     }
     return lt;
 }

@@ -197,18 +197,6 @@ __global__ void k_scatter(const Fr *scalars, MsmGeom g, uint32_t *cursor, uint32
 // (multiexp_with_mixed_addition's case): the window size is chosen from this count, not from n.
 // counters[3] != 0: some scalar is not canonical (>= r) -- the digits of such a value would silently give another point
 // (include/vsp.h promises VSP_ERR_ARG for it; the reference's field type cannot even hold such a value).
-__device__ __forceinline__ bool scalar_below_r(const uint4 &lo, const uint4 &hi) {
-    // r = 0x73eda753299d7d48 3339d80809a1d805 53bda402fffe5bfe ffffffff00000001, compared from the top 32-bit word down
-    const uint32_t k[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    const uint32_t r[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
-    bool lt = false, gt = false;
-#pragma unroll
-    for (int i = 7; i >= 0; i--) {
-        lt = lt || (!gt && k[i] < r[i]);
-        gt = gt || (!lt && k[i] > r[i]);
-    }
-    return lt;
-}
 __global__ __launch_bounds__(256) void k_classify(const Fr *scalars, size_t n, uint32_t *counters, size_t kstride) {
     __shared__ uint32_t blk, bad;
     scalars += (size_t)blockIdx.y * kstride;                 // grid.y: the vectors of a batch, counted together

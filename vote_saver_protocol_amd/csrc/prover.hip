@@ -25,6 +25,39 @@ __global__ __launch_bounds__(256) void k_csr_matvec(const uint32_t *rp, const ui
     for (uint32_t e = rp[i]; e < rp[i + 1]; e++) acc = add(acc, mul(z[ci[e]], co[e]));
     out[i] = acc;
 }
+// ---- the witness check: does member k's z satisfy (A z)[i] (B z)[i] = (C z)[i] on the rows i < rows of the constraint system?
+// abc: member k's A z, B z, C z at abc + k stride, m values each, canonical as k_csr_matvec leaves them (rows .. m - 1 -- the
+// "input_i * 0 = 0" rows, the padding, a step domain's tail -- belong to the domain, not to the system, and are not read).  One thread per
+// (row, member): one conversion to Montgomery form and one product give the canonical a b, compared word for word with c.  The failing
+// lanes of a wave are counted by a ballot, and the lowest of them -- the wave's lowest failing row -- issues one atomicMin into
+// first_bad[k] (preset to `rows`) and one atomicAdd into bad_rows[k] (preset to 0): both results are independent of the order in which
+// waves arrive, and a satisfied witness issues no atomic at all.
+__global__ __launch_bounds__(256) void k_r1cs_verdict(const Fr *abc, size_t rows, size_t m, size_t stride, uint32_t *first_bad, uint32_t *bad_rows) {
+    const Fr *a = abc + (size_t)blockIdx.y * stride, *b = a + m, *c = b + m;      // grid.y: the witnesses of a batch, as in k_csr_matvec
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool bad = false;
+    if (i < rows) bad = !eq(mul(to_mont(a[i]), b[i]), c[i]);
+    const unsigned long long failing = __ballot(bad);
+    if (failing == 0) return;
+    if ((threadIdx.x & 63u) == (unsigned)__ffsll(failing) - 1u) {
+        atomicMin(&first_bad[blockIdx.y], (uint32_t)i);
+        atomicAdd(&bad_rows[blockIdx.y], (uint32_t)__popcll(failing));
+    }
+}
+// flag[k] != 0: member k's z = (1, witness) holds a value that is not canonical (>= r), in a wire of a constraint or not -- the mat-vec
+// reduces such a value, so the rows alone would not show it.  The comparison is the census' (common.h scalar_below_r).
+__global__ __launch_bounds__(256) void k_witness_canonical(const Fr *z, size_t n, size_t z_stride, uint32_t *flag) {
+    z += (size_t)blockIdx.y * z_stride;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool bad = false;
+    if (i < n) {
+        const uint4 *w = (const uint4 *)z[i].l;
+        const uint4 lo = w[0], hi = w[1];
+        bad = hi.w >= 0x73eda753u && !scalar_below_r(lo, hi);
+    }
+    const unsigned long long failing = __ballot(bad);
+    if (failing != 0 && (threadIdx.x & 63u) == (unsigned)__ffsll(failing) - 1u) atomicOr(&flag[blockIdx.y], 1u);
+}
 __global__ __launch_bounds__(256) void k_fr_to_mont(Fr *a, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) a[i] = to_mont(a[i]);
@@ -340,43 +373,105 @@ __global__ __launch_bounds__(256) void k_witness_expand(const uint64_t *class_wo
     z[2 * i] = lo; z[2 * i + 1] = hi;
 }
 
+// ---- the front half of every proof, and the whole device side of the stand-alone witness check (vsp_r1cs_check_batch): z_k = (1, witness_k)
+// canonical into pr_z for the K members, then A z, B z, C z of each into pr_abc (member k at pr_abc + k 3 m: A z | B z | C z, m values each,
+// zero beyond the constraint rows) and the rows "input_i * 0 = 0" of A.  There is one copy of it, so what the check approves is, word for
+// word, what witness_map_device consumes.  strided: the batch form -- K plain witnesses one after the other, copied from pageable memory
+// and waited for; else K = 1, plain or packed, nothing waited for.
+static int prove_front_half(vsp_ctx *ctx, const vsp_r1cs *cs, const WitnessSrc &wsrc, size_t K, bool strided) {
+    const size_t nv = cs->num_vars, ni = cs->num_inputs, nc = cs->num_constraints, m = cs->dom.m, zs = nv + 1;
+    hipStream_t st = ctx->stream;
+    VSP_TRY(ensure(ctx, ctx->pr_z, K * zs * sizeof(Fr)));
+    VSP_TRY(ensure(ctx, ctx->pr_abc, K * 3 * m * sizeof(Fr)));
+    Fr *dz = (Fr *)ctx->pr_z.p, *abc = (Fr *)ctx->pr_abc.p;
+    std::vector<uint64_t> ones;
+    const uint64_t one4[4] = {1, 0, 0, 0};
+    if (strided) {
+        // the K ones from a small host array, the witnesses by one strided copy
+        ones.assign(K * 4, 0); for (size_t k = 0; k < K; k++) ones[4 * k] = 1;
+        VSP_HIP(hipMemcpy2DAsync(dz, zs * 32, ones.data(), 32, 32, K, hipMemcpyHostToDevice, st));
+        if (nv) VSP_HIP(hipMemcpy2DAsync(dz + 1, zs * 32, wsrc.plain, nv * 32, nv * 32, K, hipMemcpyHostToDevice, st));
+    } else {
+        VSP_HIP(hipMemcpyAsync(dz, one4, 32, hipMemcpyHostToDevice, st));
+        if (wsrc.plain) VSP_HIP(hipMemcpyAsync(dz + 1, wsrc.plain, nv * 32, hipMemcpyHostToDevice, st));
+        else {
+            // packed witness: class map, per-word offsets and the dense values cross PCIe (a tenth of the plain witness for a 90 % boolean one); a kernel expands
+            const size_t words = (nv + 31) / 32;
+            VSP_TRY(ensure(ctx, ctx->pr_pack, words * 12 + wsrc.n_dense * 32 + 64));
+            uint64_t *d_cw = (uint64_t *)ctx->pr_pack.p; uint32_t *d_off = (uint32_t *)(d_cw + words);
+            uint4 *d_dense = (uint4 *)(((uintptr_t)(d_off + words) + 15) & ~(uintptr_t)15);
+            VSP_HIP(hipMemcpyAsync(d_cw, wsrc.class_words, words * 8, hipMemcpyHostToDevice, st));
+            VSP_HIP(hipMemcpyAsync(d_off, wsrc.word_offsets, words * 4, hipMemcpyHostToDevice, st));
+            if (wsrc.n_dense) VSP_HIP(hipMemcpyAsync(d_dense, wsrc.dense, wsrc.n_dense * 32, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, (const uint64_t *)d_cw, (const uint32_t *)d_off, (const uint4 *)d_dense, nv, (uint4 *)(dz + 1));
+            VSP_LAUNCH_CHECK();
+        }
+    }
+    // evaluation vectors (witness_map part 1): A z, B z, C z, plus the rows "input_i * 0 = 0" in A
+    VSP_HIP(hipMemsetAsync(abc, 0, K * 3 * m * sizeof(Fr), st));
+    if (nc) for (int j = 0; j < 3; j++) {
+        hipLaunchKernelGGL(k_csr_matvec, dim3((unsigned)((nc + 255) / 256), (unsigned)K), dim3(256), 0, st, (const uint32_t *)cs->rp[j], (const uint32_t *)cs->ci[j],
+                           (const Fr *)cs->co[j], (const Fr *)dz, nc, abc + (size_t)j * m, zs, 3 * m);
+        VSP_LAUNCH_CHECK();
+    }
+    if (strided) {
+        VSP_HIP(hipMemcpy2DAsync(abc + nc, 3 * m * sizeof(Fr), dz, zs * sizeof(Fr), (ni + 1) * sizeof(Fr), K, hipMemcpyDeviceToDevice, st));
+        VSP_HIP(hipStreamSynchronize(st));                   // `ones` goes out of scope; the copies above are queued from pageable memory anyway
+    } else VSP_HIP(hipMemcpyAsync(abc + nc, dz, (ni + 1) * sizeof(Fr), hipMemcpyDeviceToDevice, st));
+    return VSP_OK;
+}
+// ---- the verdict pass over the K members the front half left in pr_z / pr_abc, queued behind it on the context's stream and before
+// witness_map_device overwrites pr_abc: the records are preset (first_bad_row = num_constraints, the rest 0), k_r1cs_verdict fills
+// first_bad_row and bad_rows, with_canonical also raises the flag of a value >= r (inside the prover the multi-exponentiations' census
+// makes that check, as before); an asynchronous copy takes the records to the context's pinned buffer.  t0 / t1 (or null): events
+// around the kernels.  ctx->h_verdict is valid once everything queued here has run.
+static int verdict_queue(vsp_ctx *ctx, const vsp_r1cs *cs, size_t K, bool with_canonical, hipEvent_t t0, hipEvent_t t1) {
+    constexpr size_t M = vsp_ctx::VERDICT_MEMBERS;
+    const size_t nc = cs->num_constraints, m = cs->dom.m, zs = cs->num_vars + 1;
+    hipStream_t st = ctx->stream;
+    if (K > M) return set_error(ctx, VSP_ERR_ARG, "r1cs_check: more members than the verdict records hold");
+    VSP_TRY(ensure(ctx, ctx->pr_verdict, vsp_ctx::VERDICT_BYTES));
+    if (!ctx->h_verdict) VSP_HIP(hipHostMalloc(&ctx->h_verdict, vsp_ctx::VERDICT_BYTES, hipHostMallocDefault));
+    uint32_t *first_bad = (uint32_t *)ctx->pr_verdict.p, *bad_rows = first_bad + M, *flag = first_bad + 2 * M;
+    if (t0) VSP_HIP(hipEventRecord(t0, st));
+    VSP_HIP(hipMemsetD32Async((hipDeviceptr_t)first_bad, (int)(uint32_t)nc, M, st));
+    VSP_HIP(hipMemsetAsync(bad_rows, 0, 2 * M * sizeof(uint32_t), st));
+    if (nc) {
+        hipLaunchKernelGGL(k_r1cs_verdict, dim3((unsigned)((nc + 255) / 256), (unsigned)K), dim3(256), 0, st, (const Fr *)ctx->pr_abc.p, nc, m, 3 * m, first_bad, bad_rows);
+        VSP_LAUNCH_CHECK();
+    }
+    if (with_canonical) {
+        hipLaunchKernelGGL(k_witness_canonical, dim3((unsigned)((zs + 255) / 256), (unsigned)K), dim3(256), 0, st, (const Fr *)ctx->pr_z.p, zs, zs, flag);
+        VSP_LAUNCH_CHECK();
+    }
+    if (t1) VSP_HIP(hipEventRecord(t1, st));
+    VSP_HIP(hipMemcpyAsync(ctx->h_verdict, first_bad, vsp_ctx::VERDICT_BYTES, hipMemcpyDeviceToHost, st));
+    return VSP_OK;
+}
+// option "prove_check_witness" (default 0): every prover entry point queues the verdict pass between its front half and witness_map_device;
+// the finish reads the records after its own waits -- the copy sits on the context's stream in front of the H chain the finish waits for
+static int prove_queue_check(vsp_ctx *ctx, const vsp_r1cs *cs, size_t K) {
+    ctx->prove.check = opt(ctx, "prove_check_witness", 0) != 0;
+    return ctx->prove.check ? verdict_queue(ctx, cs, K, false, nullptr, nullptr) : VSP_OK;
+}
+// member k's record in the pinned buffer
+struct Verdict { uint32_t first_bad_row, bad_rows, not_canonical; };
+static Verdict verdict_of(const vsp_ctx *ctx, size_t k) {
+    const volatile uint32_t *h = (const volatile uint32_t *)ctx->h_verdict;
+    return Verdict{h[k], h[vsp_ctx::VERDICT_MEMBERS + k], h[2 * vsp_ctx::VERDICT_MEMBERS + k]};
+}
+
 static int prove_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const WitnessSrc &wsrc) {
-    const size_t nv = cs->num_vars, ni = cs->num_inputs, nc = cs->num_constraints;
+    const size_t nv = cs->num_vars, ni = cs->num_inputs;
     const size_t m = cs->dom.m;
     VSP_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     HostLap lap{ctx};
     // z = (1, witness) canonical on device; the workspace of a batch of one: A z, B z, C z one after the other in pr_abc
-    VSP_TRY(ensure(ctx, ctx->pr_z, (nv + 1) * sizeof(Fr)));
-    VSP_TRY(ensure(ctx, ctx->pr_abc, 3 * m * sizeof(Fr)));
+    VSP_TRY(prove_front_half(ctx, cs, wsrc, 1, false));
     VSP_TRY(ensure(ctx, ctx->pr_h, m * sizeof(Fr)));
     Fr *dz = (Fr *)ctx->pr_z.p, *dA = (Fr *)ctx->pr_abc.p, *dB = dA + m, *dC = dA + 2 * m, *dH = (Fr *)ctx->pr_h.p;
-    const uint64_t one4[4] = {1, 0, 0, 0};
-    VSP_HIP(hipMemcpyAsync(dz, one4, 32, hipMemcpyHostToDevice, st));
-    if (wsrc.plain) VSP_HIP(hipMemcpyAsync(dz + 1, wsrc.plain, nv * 32, hipMemcpyHostToDevice, st));
-    else {
-        // packed witness: class map, per-word offsets and the dense values cross PCIe (a tenth of the plain witness for a 90 % boolean one); a kernel expands
-        const size_t words = (nv + 31) / 32;
-        VSP_TRY(ensure(ctx, ctx->pr_pack, words * 12 + wsrc.n_dense * 32 + 64));
-        uint64_t *d_cw = (uint64_t *)ctx->pr_pack.p; uint32_t *d_off = (uint32_t *)(d_cw + words);
-        uint4 *d_dense = (uint4 *)(((uintptr_t)(d_off + words) + 15) & ~(uintptr_t)15);
-        VSP_HIP(hipMemcpyAsync(d_cw, wsrc.class_words, words * 8, hipMemcpyHostToDevice, st));
-        VSP_HIP(hipMemcpyAsync(d_off, wsrc.word_offsets, words * 4, hipMemcpyHostToDevice, st));
-        if (wsrc.n_dense) VSP_HIP(hipMemcpyAsync(d_dense, wsrc.dense, wsrc.n_dense * 32, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_witness_expand, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, (const uint64_t *)d_cw, (const uint32_t *)d_off, (const uint4 *)d_dense, nv, (uint4 *)(dz + 1));
-        VSP_LAUNCH_CHECK();
-    }
-    // evaluation vectors (witness_map part 1): A z, B z, C z, plus the rows "input_i * 0 = 0" in A
-    VSP_HIP(hipMemsetAsync(dA, 0, m * sizeof(Fr), st));
-    VSP_HIP(hipMemsetAsync(dB, 0, m * sizeof(Fr), st));
-    VSP_HIP(hipMemsetAsync(dC, 0, m * sizeof(Fr), st));
-    Fr *outs[3] = {dA, dB, dC};
-    if (nc) for (int k = 0; k < 3; k++) {
-        hipLaunchKernelGGL(k_csr_matvec, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, st, (const uint32_t *)cs->rp[k], (const uint32_t *)cs->ci[k],
-                           (const Fr *)cs->co[k], (const Fr *)dz, nc, outs[k]);
-        VSP_LAUNCH_CHECK();
-    }
-    VSP_HIP(hipMemcpyAsync(dA + nc, dz, (ni + 1) * sizeof(Fr), hipMemcpyDeviceToDevice, st));
+    VSP_TRY(prove_queue_check(ctx, cs, 1));
     // Order of queueing: (1) the two scalar censuses, tiny, on the context's stream; (2) witness_map (7 NTTs) and the H
     // multi-exponentiation, the longest dependent chain, on the context's stream; (3) the four multi-exponentiations over the
     // witness -- independent of witness_map -- on the low-priority slots 1-4, filling the GPU around (2).  A_query, B_query(G1)
@@ -474,6 +569,20 @@ static int prove_finish_impl(vsp_ctx *ctx, uint64_t A_out[12], uint64_t B_out[24
     for (auto &w : workers) w.join();
     if (rc != VSP_OK) return rc;
     lap("prove_wait_ms");
+    if (ctx->prove.check) {
+        // the records' copy was queued on the context's stream in front of the H chain, whose end the last wait above saw
+        const Verdict v = verdict_of(ctx, 0);
+        ctx->stats["prove_first_bad_row"] = (double)v.first_bad_row;
+        if (v.bad_rows) {
+            if (A_out) memset(A_out, 0, 12 * 8);
+            if (B_out) memset(B_out, 0, 24 * 8);
+            if (C_out) memset(C_out, 0, 12 * 8);
+            if (proof_out) memset(proof_out, 0, 192);
+            char msg[160];
+            snprintf(msg, sizeof msg, "prove: the witness does not satisfy the constraint system: constraint %u is the first of %u that fail", v.first_bad_row, v.bad_rows);
+            return set_error(ctx, VSP_ERR_UNSATISFIED, msg);
+        }
+    }
     store_proof(0, gA, gB2, proof_c(eH, eL, s_gA, r_gB1, neg_rs_delta, saver), A_out, B_out, C_out, proof_out);      // a handful of group operations
     lap("prove_assembly_ms");
     ctx->stats["prove_calls"] += 1;
@@ -490,26 +599,14 @@ static int prove_finish_impl(vsp_ctx *ctx, uint64_t A_out[12], uint64_t B_out[24
 // most 16 bits (pre_c <= 16: one bucket set per witness and query -- worth it where the tables are small, i.e. at the real circuit's size);
 // other tables, or any table with option "msm_batch_tables" = 0, are refused with VSP_ERR_UNSUPPORTED.
 static int prove_batch_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witnesses, size_t K) {
-    const size_t nv = cs->num_vars, ni = cs->num_inputs, nc = cs->num_constraints, m = cs->dom.m, zs = nv + 1;
+    const size_t nv = cs->num_vars, ni = cs->num_inputs, m = cs->dom.m, zs = nv + 1;
     VSP_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
     HostLap lap{ctx};                                         // vsp_get_stat "prove_batch_*_ms": where a batch's time goes on the host
-    VSP_TRY(ensure(ctx, ctx->pr_z, K * zs * sizeof(Fr)));
-    VSP_TRY(ensure(ctx, ctx->pr_abc, K * 3 * m * sizeof(Fr)));
+    const WitnessSrc w{witnesses, nullptr, nullptr, nullptr, 0};
+    VSP_TRY(prove_front_half(ctx, cs, w, K, true));          // z_k = (1, witness_k) and A z, B z, C z of the K members
     VSP_TRY(ensure(ctx, ctx->pr_h, K * m * sizeof(Fr)));
     Fr *dz = (Fr *)ctx->pr_z.p, *abc = (Fr *)ctx->pr_abc.p, *dH = (Fr *)ctx->pr_h.p;
-    // z_k = (1, witness_k), canonical: the K ones from a small host array, the witnesses by one strided copy
-    std::vector<uint64_t> ones(K * 4, 0); for (size_t k = 0; k < K; k++) ones[4 * k] = 1;
-    VSP_HIP(hipMemcpy2DAsync(dz, zs * 32, ones.data(), 32, 32, K, hipMemcpyHostToDevice, st));
-    VSP_HIP(hipMemcpy2DAsync(dz + 1, zs * 32, witnesses, nv * 32, nv * 32, K, hipMemcpyHostToDevice, st));
-    VSP_HIP(hipMemsetAsync(abc, 0, K * 3 * m * sizeof(Fr), st));
-    if (nc) for (int j = 0; j < 3; j++) {
-        hipLaunchKernelGGL(k_csr_matvec, dim3((unsigned)((nc + 255) / 256), (unsigned)K), dim3(256), 0, st, (const uint32_t *)cs->rp[j], (const uint32_t *)cs->ci[j],
-                           (const Fr *)cs->co[j], (const Fr *)dz, nc, abc + (size_t)j * m, zs, 3 * m);
-        VSP_LAUNCH_CHECK();
-    }
-    VSP_HIP(hipMemcpy2DAsync(abc + nc, 3 * m * sizeof(Fr), dz, zs * sizeof(Fr), (ni + 1) * sizeof(Fr), K, hipMemcpyDeviceToDevice, st));      // the rows "input_i * 0 = 0" of A
-    VSP_HIP(hipStreamSynchronize(st));                       // `ones` goes out of scope; the copies above are queued from pageable memory anyway
+    VSP_TRY(prove_queue_check(ctx, cs, K));
     VSP_TRY(prove_use_streams(ctx));                         // the H chain on the context's stream (prove_launch_impl)
     VSP_TRY(witness_map_device(ctx, &cs->dom, abc, abc + m, abc + 2 * m, 3 * m, (unsigned)K, dH, m));
     MsmRequest h(dH, m - 1), a(dz, nv + 1), l(dz + ni + 1, nv - ni);      // as in prove_launch_impl, K vectors each
@@ -531,6 +628,7 @@ static int prove_batch_finish_impl(vsp_ctx *ctx, uint64_t *A_out, uint64_t *B_ou
     const vsp_pk *pk = ctx->prove.pk;
     const size_t K = ctx->prove.count;
     const uint64_t *r = ctx->prove.r.data(), *s = ctx->prove.s.data();
+    ctx->batch_status.clear(); ctx->batch_first_bad.clear();      // vsp_groth16_prove_batch_verdicts speaks of THIS batch, once it has finished with the check on
     HostLap lap{ctx};
     VSP_HIP(hipSetDevice(ctx->device));
     // host work that needs no result: the delta multiples of every proof
@@ -562,13 +660,37 @@ static int prove_batch_finish_impl(vsp_ctx *ctx, uint64_t *A_out, uint64_t *B_ou
     lap("prove_batch_sA_rB1_ms");
     VSP_TRY(msm_slot_finish<G1>(ctx, 0, eH.data(), (unsigned)K));
     lap("prove_batch_h_finish_ms");
+    // the members' verdicts (option "prove_check_witness"; the records' copy sits in front of the H chain the finish above waited for):
+    // an unsatisfied member gets all-zero outputs -- its GPU work above was not skipped -- and every other member its proof as without the check
+    size_t unsatisfied = 0, first_member = 0;
+    if (ctx->prove.check) {
+        ctx->batch_status.assign(K, 0); ctx->batch_first_bad.assign(K, 0);
+        for (size_t k = K; k-- > 0;) {
+            const Verdict v = verdict_of(ctx, k);
+            ctx->batch_first_bad[k] = v.first_bad_row;
+            if (v.bad_rows) { ctx->batch_status[k] = 2; unsatisfied++; first_member = k; }
+        }
+    }
     host_parallel_for(K, [&](size_t k) {
+        if (ctx->prove.check && ctx->batch_status[k]) {
+            if (A_out) memset(A_out + 12 * k, 0, 12 * 8);
+            if (B_out) memset(B_out + 24 * k, 0, 24 * 8);
+            if (C_out) memset(C_out + 12 * k, 0, 12 * 8);
+            if (proofs_out) memset(proofs_out + 192 * k, 0, 192);
+            return;
+        }
         store_proof(k, gA[k], proof_b2(pk, eB2[k], s_delta2[k]), proof_c(eH[k], eL[k], s_gA[k], r_gB1[k], neg_rs_delta[k], XYZZ<HFp>::inf()),
                     A_out, B_out, C_out, proofs_out);
     });
     lap("prove_batch_assembly_ms");
     ctx->stats["prove_calls"] += (double)K;
     ctx->stats["prove_batches"] += 1;
+    if (unsatisfied) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "prove_batch: %zu of %zu witnesses do not satisfy the constraint system (the first is member %zu, at constraint %llu); their outputs are zero",
+                 unsatisfied, K, first_member, (unsigned long long)ctx->batch_first_bad[first_member]);
+        return set_error(ctx, VSP_ERR_UNSATISFIED, msg);
+    }
     return VSP_OK;
 }
 int vsp_groth16_prove_batch_launch(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witnesses, size_t count, const uint64_t *r, const uint64_t *s) {
@@ -589,6 +711,62 @@ int vsp_groth16_prove_batch(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, 
     int rc = vsp_groth16_prove_batch_launch(ctx, cs, pk, witnesses, count, r, s);
     if (rc != VSP_OK) return rc;
     return vsp_groth16_prove_batch_finish(ctx, A_out, B_out, C_out, proofs_out);
+}
+int vsp_groth16_prove_batch_verdicts(vsp_ctx *ctx, uint8_t *status_out, uint64_t *first_bad_row_out) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!status_out) return set_error(ctx, VSP_ERR_ARG, "prove_batch_verdicts: null argument");
+    if (ctx->batch_status.empty()) return set_error(ctx, VSP_ERR_ARG, "prove_batch_verdicts: no batch has finished on this context with option prove_check_witness = 1");
+    memcpy(status_out, ctx->batch_status.data(), ctx->batch_status.size());
+    if (first_bad_row_out) memcpy(first_bad_row_out, ctx->batch_first_bad.data(), ctx->batch_first_bad.size() * sizeof(uint64_t));
+    return VSP_OK;
+}
+
+// ---- the stand-alone witness check: bp.is_satisfied() (common.hpp:1109-1128).  The prover's front half and the verdict pass, in pieces
+// of at most 64 witnesses -- the batch prover's limit, so its workspaces pr_z / pr_abc serve and nothing new is allocated
+int vsp_r1cs_check_batch(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64_t *witnesses, size_t count, uint8_t *status_out, uint64_t *first_bad_row_out,
+                         uint64_t *bad_rows_out) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!cs || !witnesses || !status_out) return set_error(ctx, VSP_ERR_ARG, "r1cs_check: null argument");
+    if (ctx->prove.active) return set_error(ctx, VSP_ERR_ARG, "r1cs_check: a proof is in flight on this context and owns the workspace (finish it first)");
+    VSP_HIP(hipSetDevice(ctx->device));
+    const size_t nv = cs->num_vars;
+    size_t z_bytes = 0;
+    int rc = VSP_OK;
+    for (size_t first = 0; first < count && rc == VSP_OK; first += vsp_ctx::VERDICT_MEMBERS) {
+        const size_t K = count - first < vsp_ctx::VERDICT_MEMBERS ? count - first : vsp_ctx::VERDICT_MEMBERS;
+        const WitnessSrc w{witnesses + first * nv * 4, nullptr, nullptr, nullptr, 0};
+        rc = [&]() -> int {
+            for (hipEvent_t &e : ctx->check_ev) if (!e) VSP_HIP(hipEventCreate(&e));      // the stage timers, created on first use
+            VSP_HIP(hipEventRecord(ctx->check_ev[0], ctx->stream));
+            VSP_TRY(prove_front_half(ctx, cs, w, K, true));
+            VSP_TRY(verdict_queue(ctx, cs, K, true, ctx->check_ev[1], ctx->check_ev[2]));
+            VSP_HIP(hipStreamSynchronize(ctx->stream));
+            return VSP_OK;
+        }();
+        if (K * (nv + 1) * sizeof(Fr) > z_bytes) z_bytes = K * (nv + 1) * sizeof(Fr);
+        if (rc != VSP_OK) break;
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ctx->check_ev[0], ctx->check_ev[1]) == hipSuccess) ctx->stats["r1cs_check_front_ms"] += ms;
+        if (hipEventElapsedTime(&ms, ctx->check_ev[1], ctx->check_ev[2]) == hipSuccess) ctx->stats["r1cs_check_ms"] += ms;
+        for (size_t k = 0; k < K; k++) {
+            const Verdict v = verdict_of(ctx, k);
+            status_out[first + k] = (uint8_t)((v.not_canonical ? 1 : 0) | (v.bad_rows ? 2 : 0));
+            if (first_bad_row_out) first_bad_row_out[first + k] = v.first_bad_row;
+            if (bad_rows_out) bad_rows_out[first + k] = v.bad_rows;
+        }
+    }
+    // the call's copy of the witnesses is zeroed, as after a proof (prove_cleanup)
+    if (ctx->pr_z.p && z_bytes) hipMemsetAsync(ctx->pr_z.p, 0, z_bytes < ctx->pr_z.cap ? z_bytes : ctx->pr_z.cap, ctx->stream);
+    if (rc == VSP_OK) ctx->stats["r1cs_check_witnesses"] += (double)count;
+    return rc;
+}
+int vsp_r1cs_is_satisfied(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64_t *witness, int *satisfied_out, uint64_t *first_bad_row_out) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!satisfied_out) return set_error(ctx, VSP_ERR_ARG, "r1cs_is_satisfied: null argument");
+    uint8_t status = 0;
+    VSP_TRY(vsp_r1cs_check_batch(ctx, cs, witness, 1, &status, first_bad_row_out, nullptr));
+    *satisfied_out = status == 0;
+    return VSP_OK;
 }
 
 }  // extern "C"

@@ -175,7 +175,10 @@ int vsp_saver_encrypt(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1cs *cs,
         host_store_affine(ct_out + 12 * (n + 1), xyzz_to_affine(psi));
     };
     const uint64_t *p_ginv = spk->words.data() + 12 + 12 * n + 12 * n + 24 * (n + 1) + 12;
-    return prove_with_overlap(ctx, cs, pk, witness, r, s, p_ginv, r_enc, A_out, B_out, C_out, proof_out, &overlap);
+    const int rc = prove_with_overlap(ctx, cs, pk, witness, r, s, p_ginv, r_enc, A_out, B_out, C_out, proof_out, &overlap);
+    // option "prove_check_witness": no ciphertext leaves for a statement that has no proof
+    if (rc == VSP_ERR_UNSATISFIED) memset(ct_out, 0, (n + 2) * 12 * sizeof(uint64_t));
+    return rc;
 }
 
 int vsp_saver_rerandomize(vsp_ctx *ctx, const vsp_saver_pk *spk, const uint64_t delta_g2[24], const uint64_t rnd[12],
