@@ -510,6 +510,46 @@ int vsp_tally_add_blobs(vsp_ctx *ctx, vsp_tally *t, const uint8_t *blobs /* host
 int vsp_tally_result(vsp_ctx *ctx, const vsp_tally *t, uint64_t *ct_out /* host ct_len x 12 */, uint64_t *ballots_out /* may be NULL */);
 int vsp_tally_reset(vsp_ctx *ctx, vsp_tally *t);
 
+/* ---- pairings and Groth16 verdicts on the GPU ------------------------------------------------------
+ * e(P, Q) is the optimal ate pairing of BLS12-381 as oracle/pairing.py defines it: f_{|x|,Q}(P)^((p^12 - 1) / r) with
+ * |x| = 0xd201000000010000 and NO conjugation for the negative curve parameter (csrc/pairing.h "CONVENTION": the inverse of the value of
+ * libraries that conjugate; products-equal-one tests do not depend on it).  A GT element is 576 bytes: 12 little-endian Fp, the
+ * coefficient of u^i v^j w^k at index (k * 3 + j) * 2 + i -- the encoding vsp_vk_to_blob takes and data.bin[196:772) pins.
+ * vsp_multi_pairing_batch computes n products of m pairings each: product i is prod_j e(g1[i m + j], g2[i m + j]); m = 1 is a plain
+ * batch of pairings.  Points are canonical affine limbs, all zero = infinity (its pairing is one).  gt_out (n x 576) and is_one_out
+ * (n bytes: 1 when the product is one) may each be NULL.  One lane per pair for the Miller loop (about 6 700 field products), one lane
+ * per product for the final exponentiation (about 9 000, the exact exponent): csrc/pairing.h.
+ * SUBGROUP.  The points are ASSUMED to lie in the order-r subgroups: decode with check_subgroup (vsp_proof_from_blob_batch,
+ * vsp_g1/g2_decompress_batch).  For other curve points the result is unspecified (the call still terminates without a fault).
+ * A coordinate >= p or a point off its curve, found by a check kernel on the device: VSP_ERR_ARG (outputs unspecified; the context
+ * stays usable).  VSP_ERR_ARG also for a null g1 / g2 (also with n = 0) and for m = 0 or m > 2^16 (a product is never split over
+ * pieces, so its m bounds the workspace); VSP_ERR_HIP as elsewhere.
+ * A verification key handle validates its points on the host (canonical, on the curve; VSP_ERR_ARG and NULL otherwise), computes
+ * e(alpha_g1, beta_g2) once on the GPU -- vsp_vk_alpha_beta returns its 576 bytes, the gt argument of vsp_vk_to_blob -- and keeps
+ * -gamma_g2, -delta_g2 and the multiples 0..15 of every gamma_ABC point (16 entries, the first infinity) resident (n_abc >= 1 points:
+ * one more than public inputs).
+ * vsp_groth16_verify_batch gives one verdict byte per proof: 1 exactly when
+ *     fexp(ml(A, B) ml(acc, -gamma_g2) ml(C, -delta_g2)) = e(alpha_g1, beta_g2),   acc = gamma_ABC[0] + sum_i inputs[i] gamma_ABC[i + 1]
+ * which is when oracle/pairing.py groth16_verify accepts; acc is computed on the GPU, one lane per proof.  A coordinate >= p, a point
+ * off its curve or a scalar >= r gives verdict 0 for that proof alone.  VSP_OK whatever the verdicts are; VSP_ERR_ARG for a null
+ * pointer, also with n = 0 (inputs may be NULL when n_abc = 1); VSP_ERR_HIP as elsewhere.  No random linear combination: every verdict
+ * is exact and independent of the other proofs of the batch.
+ * Any n: the work runs in pieces of at most "pairing_chunk" products (default and maximum 2^14) and at most 2^16 pairs, at least one
+ * product.  Workspace bound per piece: 288 canonical + 288 Montgomery + 576 Miller bytes + 1 status byte per pair and 2 x 576 + 2
+ * bytes per product -- below 100 MiB of the context's grow-only workspaces whatever n and m are (m <= 2^16).  Stage times (HIP events,
+ * summed since vsp_stats_reset): vsp_get_stat "pairing_miller_ms" (Miller loops and their products), "pairing_finalexp_ms". */
+int vsp_multi_pairing_batch(vsp_ctx *ctx, const uint64_t *g1 /* host n*m x 12, canonical affine */, const uint64_t *g2 /* host n*m x 24 */,
+                            size_t m /* pairs per product, 1..2^16 */, size_t n /* products */, uint8_t *gt_out /* n x 576, may be NULL */,
+                            uint8_t *is_one_out /* n, may be NULL */);
+typedef struct vsp_vk vsp_vk;
+vsp_vk *vsp_vk_create(vsp_ctx *ctx, const uint64_t alpha_g1[12], const uint64_t beta_g2[24], const uint64_t gamma_g2[24],
+                      const uint64_t delta_g2[24], const uint64_t *gamma_abc_g1 /* n_abc x 12 */, size_t n_abc);
+int vsp_vk_alpha_beta(const vsp_vk *vk, uint8_t gt_out[576]);
+void vsp_vk_free(vsp_ctx *ctx, vsp_vk *vk);
+int vsp_groth16_verify_batch(vsp_ctx *ctx, const vsp_vk *vk, const uint64_t *inputs /* host n x (n_abc - 1) x 4, canonical Fr */,
+                             const uint64_t *A /* n x 12 */, const uint64_t *B /* n x 24 */, const uint64_t *C /* n x 12 */, size_t n,
+                             uint8_t *verdict_out /* n: 1 accepted, 0 rejected */);
+
 /* ---- wire formats of the reference's marshaling_policy (common.hpp:168-203 option::big_endian) --------------------
  * PROVISIONAL where marked: the marshalling sources are absent submodules, and only the proof bytes, the scalar vectors and the head of
  * the verification key (4 bytes, the GT element, three points) are pinned by files of the reference.  The tail of the verification key

@@ -130,6 +130,11 @@ PROTOTYPES = {
     "vsp_tally_add_blobs": (_I, [_P, _P, _P, _SZ, _I, _P, _P]),
     "vsp_tally_result": (_I, [_P, _P, _P, _P]),
     "vsp_tally_reset": (_I, [_P, _P]),
+    "vsp_multi_pairing_batch": (_I, [_P, _P, _P, _SZ, _SZ, _P, _P]),
+    "vsp_vk_create": (_P, [_P, _P, _P, _P, _P, _P, _SZ]),
+    "vsp_vk_alpha_beta": (_I, [_P, _P]),
+    "vsp_vk_free": (None, [_P, _P]),
+    "vsp_groth16_verify_batch": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _P]),
 }
 
 _lib = None

@@ -825,6 +825,65 @@ class Tally:
         self.ctx.check(self.ctx.lib.vsp_tally_reset(self.ctx.h, self.h))
 
 
+def multi_pairing_batch(ctx, g1, g2, m=1, want_gt=True):
+    """n products of m pairings each on the GPU: g1 [n*m,12], g2 [n*m,24] canonical affine limbs (all zero = infinity), product i over
+    pairs i*m .. i*m + m - 1.  Returns (gt [n,576] uint8 or None, is_one [n] uint8).  The pairing is the test oracle's (pairing.py: no
+    conjugation for the negative curve parameter); points are assumed to be in the order-r subgroups.  VspError for a coordinate >= p
+    or a point off its curve."""
+    g1 = _u64(g1, 12); g2 = _u64(g2, 24); m = int(m)
+    if m < 1 or g1.shape[0] != g2.shape[0] or g1.shape[0] % m:
+        raise ValueError("multi_pairing_batch: as many G1 as G2 points, a whole number of products of m >= 1 pairs")
+    n = g1.shape[0] // m
+    gt = np.zeros((n, 576), np.uint8) if want_gt else None
+    is_one = np.zeros(n, np.uint8)
+    ctx.check(ctx.lib.vsp_multi_pairing_batch(ctx.h, _ptr(g1), _ptr(g2), m, n, _ptr(gt), _ptr(is_one)))
+    return gt, is_one
+
+
+def pairing_batch(ctx, g1, g2):
+    """e(g1[i], g2[i]) for every i: [n,576] uint8"""
+    return multi_pairing_batch(ctx, g1, g2, 1)[0]
+
+
+class VerifyingKey:
+    """A Groth16 verification key resident on the GPU (vsp_vk): e(alpha_g1, beta_g2), -gamma_g2, -delta_g2 and the multiples of the
+    gamma_ABC points."""
+
+    def __init__(self, ctx, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1):
+        self.ctx = ctx
+        gabc = _u64(gamma_abc_g1, 12)
+        self.n_abc = gabc.shape[0]
+        a = _u64(alpha_g1).reshape(12); b = _u64(beta_g2).reshape(24); g = _u64(gamma_g2).reshape(24); d = _u64(delta_g2).reshape(24)
+        self.h = ctx.lib.vsp_vk_create(ctx.h, _ptr(a), _ptr(b), _ptr(g), _ptr(d), _ptr(gabc), self.n_abc)
+        if not self.h:
+            raise VspError("vsp_vk_create failed: " + ctx.last_error())
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.vsp_vk_free(self.ctx.h, self.h)
+            self.h = None
+
+    def alpha_beta(self):
+        """e(alpha_g1, beta_g2) as the 576 bytes vk_to_blob takes"""
+        gt = np.zeros(576, np.uint8)
+        self.ctx.check(self.ctx.lib.vsp_vk_alpha_beta(self.h, _ptr(gt)))
+        return gt.tobytes()
+
+
+def groth16_verify_batch(ctx, vk, inputs, A, B, Cc):
+    """Exact verdicts of n proofs: inputs [n, n_abc - 1, 4] canonical scalars, A [n,12], B [n,24], C [n,12] -> [n] uint8, 1 = accepted.
+    A proof with a coordinate >= p, a point off its curve or a scalar >= r is rejected; the points are assumed to be in the subgroups
+    (decode with check_subgroup)."""
+    A = _u64(A, 12); B = _u64(B, 24); Cc = _u64(Cc, 12)
+    n = A.shape[0]
+    inputs = _u64(inputs).reshape(n, -1) if vk.n_abc > 1 else np.zeros((n, 4), np.uint64)
+    if B.shape[0] != n or Cc.shape[0] != n or (vk.n_abc > 1 and inputs.shape[1] != 4 * (vk.n_abc - 1)):
+        raise ValueError("groth16_verify_batch: n proofs (A[12], B[24], C[12]) and n x (n_abc - 1) public inputs expected")
+    verdict = np.zeros(n, np.uint8)
+    ctx.check(ctx.lib.vsp_groth16_verify_batch(ctx.h, vk.h, _ptr(inputs), _ptr(A), _ptr(B), _ptr(Cc), n, _ptr(verdict)))
+    return verdict
+
+
 # ---- wire formats (f.2): the big-endian blobs of the reference's marshaling_policy (common.hpp:168-203, 462-485, 749-799) ---------
 def fr_vector_to_blob(vals):
     """serialize a scalar vector (primary input, eid, sn, rt, voting result): 8-byte count + 32-byte big-endian elements"""

@@ -204,7 +204,8 @@ void vsp_destroy(vsp_ctx *ctx) {
                       &ctx->msm_scalars, &ctx->val_flag, &ctx->fb_table[0], &ctx->fb_table[1], &ctx->fb_tmp, &ctx->fb_pre,
                       &ctx->pr_z, &ctx->pr_abc, &ctx->pr_h, &ctx->pr_pack, &ctx->pr_verdict,
                       &ctx->tally_raw, &ctx->tally_pts, &ctx->tally_pstatus, &ctx->tally_bstatus, &ctx->tally_partials,
-                      &ctx->g2_pts, &ctx->g2_pstatus};
+                      &ctx->g2_pts, &ctx->g2_pstatus,
+                      &ctx->pair_raw, &ctx->pair_g1, &ctx->pair_g2, &ctx->pair_status, &ctx->pair_ml, &ctx->pair_prod, &ctx->pair_gt};
     for (DevBuf *b : bufs) free_buf(*b);
     msm_free_slots(ctx);
     if (ctx->h_fold) hipHostFree(ctx->h_fold);
@@ -213,6 +214,7 @@ void vsp_destroy(vsp_ctx *ctx) {
     for (hipEvent_t e : ctx->tally_ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : ctx->g2_ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : ctx->check_ev) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : ctx->pair_ev) if (e) hipEventDestroy(e);
     for (hipStream_t ps : ctx->prove_streams) if (ps) hipStreamDestroy(ps);
     hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -252,6 +254,32 @@ int vsp_set_option(vsp_ctx *ctx, const char *name, long value) {
     if (!ctx || !name) return VSP_ERR_ARG;
     ctx->opts[name] = value;
     return VSP_OK;
+}
+
+// ---- pairings and Groth16 verdicts (pairing.hip)
+int vsp_multi_pairing_batch(vsp_ctx *ctx, const uint64_t *g1, const uint64_t *g2, size_t m, size_t n, uint8_t *gt_out, uint8_t *is_one_out) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!g1 || !g2) return set_error(ctx, VSP_ERR_ARG, "multi_pairing_batch: null argument");
+    if (m == 0 || m > ((size_t)1 << 16)) return set_error(ctx, VSP_ERR_ARG, "multi_pairing_batch: m outside 1..2^16");
+    return pairing_multi_batch(ctx, g1, g2, m, n, gt_out, is_one_out);
+}
+vsp_vk *vsp_vk_create(vsp_ctx *ctx, const uint64_t alpha_g1[12], const uint64_t beta_g2[24], const uint64_t gamma_g2[24], const uint64_t delta_g2[24],
+                      const uint64_t *gamma_abc_g1, size_t n_abc) {
+    if (!ctx) return nullptr;
+    if (!alpha_g1 || !beta_g2 || !gamma_g2 || !delta_g2 || !gamma_abc_g1 || n_abc == 0) { set_error(ctx, VSP_ERR_ARG, "vk_create: null argument or n_abc = 0"); return nullptr; }
+    return pairing_vk_create(ctx, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, n_abc);
+}
+int vsp_vk_alpha_beta(const vsp_vk *vk, uint8_t gt_out[576]) {
+    if (!vk || !gt_out) return VSP_ERR_ARG;
+    memcpy(gt_out, pairing_vk_alpha_beta(vk), 576);
+    return VSP_OK;
+}
+void vsp_vk_free(vsp_ctx *ctx, vsp_vk *vk) { pairing_vk_free(ctx, vk); }
+int vsp_groth16_verify_batch(vsp_ctx *ctx, const vsp_vk *vk, const uint64_t *inputs, const uint64_t *A, const uint64_t *B, const uint64_t *C, size_t n,
+                             uint8_t *verdict_out) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!vk || !A || !B || !C || !verdict_out || (!inputs && pairing_vk_n_abc(vk) > 1)) return set_error(ctx, VSP_ERR_ARG, "groth16_verify_batch: null argument");
+    return pairing_verify_batch(ctx, vk, inputs, A, B, C, n, verdict_out);
 }
 
 void *vsp_dmalloc(vsp_ctx *ctx, size_t bytes) {

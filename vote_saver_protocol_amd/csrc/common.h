@@ -217,6 +217,10 @@ struct vsp_ctx {
     // the G2 points of a chunk of proofs or of vsp_g2_decompress_batch (tally.hip) with their status bytes, and the two stages' timers
     vsp::DevBuf g2_pts, g2_pstatus;
     hipEvent_t g2_ev[3] = {nullptr, nullptr, nullptr};
+    // the pairings' piece (pairing.hip): canonical inputs, Montgomery pairs, status bytes (pairs | products | results), Miller values, their
+    // products, GT values; the timers around the Miller stage and the final exponentiation, created on first use
+    vsp::DevBuf pair_raw, pair_g1, pair_g2, pair_status, pair_ml, pair_prod, pair_gt;
+    hipEvent_t pair_ev[3] = {nullptr, nullptr, nullptr};
     // prover workspaces for K witnesses (a single proof: K = 1): z [K][num_vars + 1], A z, B z, C z [K][3][m], H [K][m], the packed witness
     vsp::DevBuf pr_z, pr_abc, pr_h, pr_pack;
     // the witness check (prover.hip k_r1cs_verdict): per member of a piece of at most VERDICT_MEMBERS witnesses three 32-bit words --
@@ -406,6 +410,14 @@ enum { BASES_CALLER = 0, BASES_OWN = 1, BASES_TRANSIENT = 2 };
 int bases_create(vsp_ctx *ctx, int group, const void *src, bool src_on_device, size_t n, int trust, vsp_bases **out);
 // out[i] = scalars[i] * the group's generator, canonical affine (fixedbase_impl.inc, instantiated by fixedbase_g1.hip / fixedbase_g2.hip)
 template <class G> int fixed_base_mul(vsp_ctx *ctx, const Fr *d_scalars, size_t n, void *d_out);
+// pairings and Groth16 verdicts (pairing.hip); the arguments are checked by the exports in capi.hip
+int pairing_multi_batch(vsp_ctx *ctx, const uint64_t *g1, const uint64_t *g2, size_t m, size_t n, uint8_t *gt_out, uint8_t *is_one_out);
+vsp_vk *pairing_vk_create(vsp_ctx *ctx, const uint64_t *alpha_g1, const uint64_t *beta_g2, const uint64_t *gamma_g2, const uint64_t *delta_g2, const uint64_t *gamma_abc_g1,
+                          size_t n_abc);
+const uint8_t *pairing_vk_alpha_beta(const vsp_vk *vk);
+size_t pairing_vk_n_abc(const vsp_vk *vk);
+void pairing_vk_free(vsp_ctx *ctx, vsp_vk *vk);
+int pairing_verify_batch(vsp_ctx *ctx, const vsp_vk *vk, const uint64_t *inputs, const uint64_t *A, const uint64_t *B, const uint64_t *C, size_t n, uint8_t *verdict_out);
 int upload_power_tables(vsp_ctx *ctx, const HFr &base, size_t hi_count, DevBuf &lo, DevBuf &hi);
 HFr host_omega(unsigned log_m);
 

@@ -1,0 +1,299 @@
+// Batched BLS12-381 pairings and exact per-proof Groth16 verdicts on the GPU (include/vsp.h "pairings").
+//
+// The verifying side of the reference (zk::verify, tvm.vergrth16) is a product of pairings per proof; the pairs of a batch are
+// independent, so the work has the shape of the decoding kernels of tally.hip: one lane per item, straight-line field arithmetic from
+// the headers fp12.h / pairing.h, which the CPU test build checks against the test oracle.  Stages per piece of a call, all on the
+// context's stream:
+//   0. k_pair_check        one lane per pair: coordinates below p, Montgomery form, on the curve (or all zero: infinity); status byte
+//      k_verify_prepare    (proofs) one lane per proof: the same checks on A, B, C, scalars below r, acc = G_0 + sum x_i G_i over the
+//                          key's table of 4-bit multiples, and the three pairs (A, B), (acc, -gamma), (C, -delta)
+//   1. k_miller            one lane per pair: the Miller value f_{|x|,Q}(P), one where a point is infinity (or was rejected)
+//   2. k_gt_product        one lane per product: the m Miller values of a product multiplied, their status bytes ORed (m > 1 only)
+//   3. k_final_exp         one lane per product: the final exponentiation; 576 canonical bytes, and a byte: equal to one -- or, for
+//                          proofs, equal to the key's e(alpha, beta) and no member rejected
+// An Fp12 value is 144 registers: the kernels keep their tower values in scratch and call the out-of-line products of fp12.h.
+#include "common.h"
+#include "pairing.h"
+
+struct vsp_vk {
+    size_t n_abc = 0;
+    uint8_t alpha_beta[576];            // e(alpha, beta), canonical tower order
+    void *d_expect = nullptr;           // the same value, Fp12 in Montgomery form
+    void *d_neg = nullptr;              // two G2Affine, Montgomery: -gamma_g2, -delta_g2
+    void *d_tab = nullptr;              // n_abc rows of 16 G1Affine, Montgomery: d * gamma_ABC[i], d = 0..15 (d = 0: infinity)
+};
+
+namespace vsp {
+
+static constexpr size_t PAIRING_CHUNK = (size_t)1 << 14;       // products of one piece (option "pairing_chunk")
+static constexpr size_t PAIRING_MAX_PAIRS = (size_t)1 << 16;   // pairs of one piece, whatever m is (a piece holds at least one product)
+static constexpr unsigned PAIRING_THREADS = 64;                // one wave per block: 2^14 lanes spread over every compute unit
+
+// the tower work as real calls on memory temporaries (see tally.hip tally_g2_y): one copy of each loop in a kernel
+__device__ __noinline__ void pr_miller(Fp12 *f, const G1Affine *P, const G2Affine *Q) { *f = miller_loop(*P, *Q); }
+__device__ __noinline__ void pr_final_exp(Fp12 *f) { const Fp12 t = final_exp(*f); *f = t; }
+__device__ __noinline__ void pr_mul(Fp12 *f, const Fp12 *g) { const Fp12 t = mul(*f, *g); *f = t; }
+__device__ __noinline__ void pr_dbl(G1XYZZ *a) { *a = xyzz_dbl(*a); }
+__device__ __noinline__ void pr_madd(G1XYZZ *a, const G1Affine *p) { G1XYZZ t = *a; xyzz_madd(t, *p); *a = t; }
+
+// canonical words -> Montgomery affine point; 0 accepted (infinity included), 1 a coordinate >= p, 2 off the curve.  A rejected point
+// comes out as infinity
+__device__ __noinline__ uint32_t pr_load_g1(const uint64_t *src, G1Affine *out) {
+    G1Affine c = *(const G1Affine *)src;
+    uint32_t st = (canon_below_p(c.x) && canon_below_p(c.y)) ? 0u : 1u;
+    G1Affine p; p.x = to_mont(c.x); p.y = to_mont(c.y);
+    const Fp four = dbl(dbl(Fp::one()));
+    if (!st && !is_inf(c) && !eq(sqr(p.y), add(mul(sqr(p.x), p.x), four))) st = 2u;
+    if (st) { p.x = Fp::zero(); p.y = Fp::zero(); }
+    *out = p;
+    return st;
+}
+__device__ __noinline__ uint32_t pr_load_g2(const uint64_t *src, G2Affine *out) {
+    G2Affine c = *(const G2Affine *)src;
+    uint32_t st = (canon_below_p(c.x.c0) && canon_below_p(c.x.c1) && canon_below_p(c.y.c0) && canon_below_p(c.y.c1)) ? 0u : 1u;
+    G2Affine p; p.x = to_mont(c.x); p.y = to_mont(c.y);
+    Fp2 b; b.c0 = dbl(dbl(Fp::one())); b.c1 = b.c0;
+    if (!st && !is_inf(c) && !eq(f2sqr(p.y), add(f2mul(f2sqr(p.x), p.x), b))) st = 2u;
+    if (st) { p.x = Fp2::zero(); p.y = Fp2::zero(); }
+    *out = p;
+    return st;
+}
+
+__global__ __launch_bounds__(PAIRING_THREADS) void k_pair_check(const uint64_t *__restrict__ g1, const uint64_t *__restrict__ g2, size_t n, G1Affine *__restrict__ p_out,
+                                                                G2Affine *__restrict__ q_out, uint8_t *__restrict__ status, uint32_t *__restrict__ flag) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    G1Affine P; G2Affine Q;
+    const uint32_t st = pr_load_g1(g1 + 12 * i, &P) | pr_load_g2(g2 + 24 * i, &Q);
+    p_out[i] = P; q_out[i] = Q;
+    status[i] = (uint8_t)st;
+    if (st) atomicOr(flag, st);
+}
+
+// proof k of a piece: pairs 3k .. 3k + 2.  inputs: n x (n_abc - 1) canonical scalars; tab: the key's multiples, neg: -gamma, -delta
+__global__ __launch_bounds__(PAIRING_THREADS) void k_verify_prepare(const uint64_t *__restrict__ A, const uint64_t *__restrict__ B, const uint64_t *__restrict__ C,
+                                                                    const uint32_t *__restrict__ inputs, size_t n, size_t n_abc, const G1Affine *__restrict__ tab,
+                                                                    const G2Affine *__restrict__ neg_gd, G1Affine *__restrict__ p_out, G2Affine *__restrict__ q_out,
+                                                                    uint8_t *__restrict__ status) {
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    G1Affine P; G2Affine Q;
+    uint32_t st = pr_load_g1(A + 12 * k, &P) | pr_load_g2(B + 24 * k, &Q);
+    p_out[3 * k] = P; q_out[3 * k] = Q;
+    status[3 * k] = (uint8_t)st;
+    st = pr_load_g1(C + 12 * k, &P);
+    p_out[3 * k + 2] = P; q_out[3 * k + 2] = neg_gd[1];
+    status[3 * k + 2] = (uint8_t)st;
+    // the public-input combination, 4 bits of every scalar at a time from the top: 4 doublings, then one table row per input
+    const size_t L = n_abc - 1;
+    const uint32_t *s = inputs + k * L * 8;
+    st = 0;
+    for (size_t i = 0; i < L; i++) {
+        const uint4 lo = *(const uint4 *)(s + 8 * i), hi = *(const uint4 *)(s + 8 * i + 4);
+        if (!scalar_below_r(lo, hi)) st = 1u;
+    }
+    G1XYZZ acc = G1XYZZ::inf();
+#pragma unroll 1
+    for (int w = 63; w >= 0; w--) {
+        if (w != 63) { pr_dbl(&acc); pr_dbl(&acc); pr_dbl(&acc); pr_dbl(&acc); }
+#pragma unroll 1
+        for (size_t i = 0; i < L; i++) {
+            const uint32_t d = (s[8 * i + (w >> 3)] >> ((w & 7) * 4)) & 15u;
+            G1Affine t = tab[(i + 1) * 16 + d];
+            pr_madd(&acc, &t);
+        }
+    }
+    { G1Affine g0 = tab[1]; pr_madd(&acc, &g0); }
+    // affine through one inversion: 1 / (ZZ ZZZ); infinity (ZZ = 0) comes out as x = y = 0
+    const Fp t = fp_inv_chain(mul(acc.ZZ, acc.ZZZ));
+    P.x = mul(acc.X, mul(t, acc.ZZZ));
+    P.y = mul(acc.Y, mul(t, acc.ZZ));
+    if (st) { P.x = Fp::zero(); P.y = Fp::zero(); }
+    p_out[3 * k + 1] = P; q_out[3 * k + 1] = neg_gd[0];
+    status[3 * k + 1] = (uint8_t)st;
+}
+
+__global__ __launch_bounds__(PAIRING_THREADS) void k_miller(const G1Affine *__restrict__ g1, const G2Affine *__restrict__ g2, size_t n, Fp12 *__restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    G1Affine P = g1[i]; G2Affine Q = g2[i];
+    Fp12 f;
+    pr_miller(&f, &P, &Q);
+    out[i] = f;
+}
+
+__global__ __launch_bounds__(PAIRING_THREADS) void k_gt_product(const Fp12 *__restrict__ ml, const uint8_t *__restrict__ status, size_t m, size_t n, Fp12 *__restrict__ out,
+                                                                uint8_t *__restrict__ pstatus) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Fp12 f = ml[i * m];
+    uint32_t st = status[i * m];
+#pragma unroll 1
+    for (size_t j = 1; j < m; j++) { Fp12 g = ml[i * m + j]; pr_mul(&f, &g); st |= status[i * m + j]; }
+    out[i] = f;
+    pstatus[i] = (uint8_t)st;
+}
+
+// expect: null (the byte says "is one") or one Fp12 in Montgomery form (the byte says "equals it, and no member was rejected")
+__global__ __launch_bounds__(PAIRING_THREADS) void k_final_exp(const Fp12 *__restrict__ in, const uint8_t *__restrict__ pstatus, size_t n, const Fp12 *__restrict__ expect,
+                                                               Fp12 *__restrict__ gt_out, uint8_t *__restrict__ flag_out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Fp12 f = in[i];
+    pr_final_exp(&f);
+    bool ok;
+    if (expect) { const Fp12 e = *expect; ok = eq(f, e) && pstatus[i] == 0; }
+    else ok = is_one(f);
+    flag_out[i] = ok ? 1 : 0;
+    if (gt_out) gt_out[i] = from_mont(f);
+}
+
+static int pairing_events(vsp_ctx *ctx) {
+    for (hipEvent_t &e : ctx->pair_ev) if (!e) VSP_HIP(hipEventCreate(&e));
+    return VSP_OK;
+}
+// products of one piece: option "pairing_chunk" (a test hook as well), 1 .. 2^14, and at most 2^16 pairs (m <= 2^16: the export refuses more)
+static size_t pairing_piece(const vsp_ctx *ctx, size_t m) {
+    const long v = opt(ctx, "pairing_chunk", (long)PAIRING_CHUNK);
+    size_t piece = v < 1 ? 1 : ((size_t)v > PAIRING_CHUNK ? PAIRING_CHUNK : (size_t)v);
+    if (piece * m > PAIRING_MAX_PAIRS) piece = PAIRING_MAX_PAIRS / m ? PAIRING_MAX_PAIRS / m : 1;
+    return piece;
+}
+static int pairing_workspace(vsp_ctx *ctx, size_t m, size_t n) {
+    VSP_TRY(ensure(ctx, ctx->pair_g1, n * m * sizeof(G1Affine)));
+    VSP_TRY(ensure(ctx, ctx->pair_g2, n * m * sizeof(G2Affine)));
+    VSP_TRY(ensure(ctx, ctx->pair_status, n * m + n + n));          // pairs | products | result bytes
+    VSP_TRY(ensure(ctx, ctx->pair_ml, n * m * sizeof(Fp12)));
+    VSP_TRY(ensure(ctx, ctx->pair_prod, n * sizeof(Fp12)));
+    VSP_TRY(ensure(ctx, ctx->pair_gt, n * sizeof(Fp12)));
+    return VSP_OK;
+}
+// stages 1 to 3 over the n products of m pairs in ctx->pair_g1 / pair_g2 / pair_status; the result bytes land at pair_status + n m + n,
+// the GT values (when want_gt) in ctx->pair_gt
+static int pairing_stages(vsp_ctx *ctx, size_t m, size_t n, const Fp12 *d_expect, bool want_gt) {
+    hipStream_t st = ctx->stream;
+    const size_t pairs = n * m;
+    uint8_t *status = (uint8_t *)ctx->pair_status.p, *pstatus = status + pairs, *result = pstatus + n;
+    VSP_HIP(hipEventRecord(ctx->pair_ev[0], st));
+    hipLaunchKernelGGL(k_miller, dim3((unsigned)((pairs + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, (const G1Affine *)ctx->pair_g1.p,
+                       (const G2Affine *)ctx->pair_g2.p, pairs, (Fp12 *)ctx->pair_ml.p);
+    VSP_LAUNCH_CHECK();
+    const Fp12 *prod = (const Fp12 *)ctx->pair_ml.p;
+    const uint8_t *ps = status;
+    const unsigned blocks = (unsigned)((n + PAIRING_THREADS - 1) / PAIRING_THREADS);
+    if (m > 1) {
+        hipLaunchKernelGGL(k_gt_product, dim3(blocks), dim3(PAIRING_THREADS), 0, st, prod, (const uint8_t *)status, m, n, (Fp12 *)ctx->pair_prod.p, pstatus);
+        VSP_LAUNCH_CHECK();
+        prod = (const Fp12 *)ctx->pair_prod.p; ps = pstatus;
+    }
+    VSP_HIP(hipEventRecord(ctx->pair_ev[1], st));
+    hipLaunchKernelGGL(k_final_exp, dim3(blocks), dim3(PAIRING_THREADS), 0, st, prod, ps, n, d_expect, want_gt ? (Fp12 *)ctx->pair_gt.p : (Fp12 *)nullptr, result);
+    VSP_LAUNCH_CHECK();
+    VSP_HIP(hipEventRecord(ctx->pair_ev[2], st));
+    return VSP_OK;
+}
+static void pairing_add_times(vsp_ctx *ctx) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ctx->pair_ev[0], ctx->pair_ev[1]) == hipSuccess) ctx->stats["pairing_miller_ms"] += ms;
+    if (hipEventElapsedTime(&ms, ctx->pair_ev[1], ctx->pair_ev[2]) == hipSuccess) ctx->stats["pairing_finalexp_ms"] += ms;
+}
+
+int pairing_multi_batch(vsp_ctx *ctx, const uint64_t *g1, const uint64_t *g2, size_t m, size_t n, uint8_t *gt_out, uint8_t *is_one_out) {
+    VSP_HIP(hipSetDevice(ctx->device));
+    VSP_TRY(pairing_events(ctx));
+    hipStream_t st = ctx->stream;
+    const size_t piece = pairing_piece(ctx, m);
+    for (size_t at = 0; at < n; at += piece) {
+        const size_t c = n - at < piece ? n - at : piece, pairs = c * m;
+        VSP_TRY(pairing_workspace(ctx, m, c));
+        VSP_TRY(ensure(ctx, ctx->pair_raw, pairs * 36 * sizeof(uint64_t) + 16));
+        uint64_t *raw1 = (uint64_t *)ctx->pair_raw.p, *raw2 = raw1 + pairs * 12;
+        uint32_t *flag = (uint32_t *)(raw2 + pairs * 24);
+        VSP_HIP(hipMemcpyAsync(raw1, g1 + at * m * 12, pairs * 12 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        VSP_HIP(hipMemcpyAsync(raw2, g2 + at * m * 24, pairs * 24 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        VSP_HIP(hipMemsetAsync(flag, 0, sizeof(uint32_t), st));
+        hipLaunchKernelGGL(k_pair_check, dim3((unsigned)((pairs + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, raw1, raw2, pairs,
+                           (G1Affine *)ctx->pair_g1.p, (G2Affine *)ctx->pair_g2.p, (uint8_t *)ctx->pair_status.p, flag);
+        VSP_LAUNCH_CHECK();
+        uint32_t h_flag = 0;
+        VSP_HIP(hipMemcpyAsync(&h_flag, flag, sizeof h_flag, hipMemcpyDeviceToHost, st));
+        VSP_HIP(hipStreamSynchronize(st));
+        if (h_flag) return set_error(ctx, VSP_ERR_ARG, h_flag & 1u ? "multi_pairing_batch: a coordinate is not below p" : "multi_pairing_batch: a point is not on its curve");
+        VSP_TRY(pairing_stages(ctx, m, c, nullptr, gt_out != nullptr));
+        if (gt_out) VSP_HIP(hipMemcpyAsync(gt_out + at * 576, ctx->pair_gt.p, c * 576, hipMemcpyDeviceToHost, st));
+        if (is_one_out) VSP_HIP(hipMemcpyAsync(is_one_out + at, (const uint8_t *)ctx->pair_status.p + pairs + c, c, hipMemcpyDeviceToHost, st));
+        VSP_HIP(hipStreamSynchronize(st));
+        pairing_add_times(ctx);
+    }
+    return VSP_OK;
+}
+
+void pairing_vk_free(vsp_ctx *ctx, vsp_vk *vk) {
+    if (!vk) return;
+    if (ctx) { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
+    if (vk->d_expect) hipFree(vk->d_expect);
+    if (vk->d_neg) hipFree(vk->d_neg);
+    if (vk->d_tab) hipFree(vk->d_tab);
+    delete vk;
+}
+
+vsp_vk *pairing_vk_create(vsp_ctx *ctx, const uint64_t *alpha_g1, const uint64_t *beta_g2, const uint64_t *gamma_g2, const uint64_t *delta_g2, const uint64_t *gamma_abc_g1,
+                          size_t n_abc) {
+    if (!affine_valid<G1>(alpha_g1) || !affine_valid<G2>(beta_g2) || !affine_valid<G2>(gamma_g2) || !affine_valid<G2>(delta_g2)) {
+        set_error(ctx, VSP_ERR_ARG, "vk_create: a point is not canonical or not on its curve"); return nullptr;
+    }
+    for (size_t i = 0; i < n_abc; i++)
+        if (!affine_valid<G1>(gamma_abc_g1 + 12 * i)) { set_error(ctx, VSP_ERR_ARG, "vk_create: a gamma_ABC point is not canonical or not on the curve"); return nullptr; }
+    vsp_vk *vk = new vsp_vk();
+    vk->n_abc = n_abc;
+    auto fail = [&](const char *msg) { if (msg) set_error(ctx, VSP_ERR_HIP, msg); pairing_vk_free(ctx, vk); return (vsp_vk *)nullptr; };
+    if (pairing_multi_batch(ctx, alpha_g1, beta_g2, 1, 1, vk->alpha_beta, nullptr) != VSP_OK) return fail(nullptr);
+    HFp12 e; memcpy(&e, vk->alpha_beta, sizeof e); e = to_mont(e);                       // HFp12 and Fp12: the same bytes
+    Affine<HFp2> ng[2] = {host_load_affine<HFp2>(gamma_g2), host_load_affine<HFp2>(delta_g2)};
+    for (auto &q : ng) q.y = neg(q.y);                                                   // infinity stays x = y = 0
+    // d * G_i for d = 0 .. 15
+    std::vector<Affine<HFp>> tab(n_abc * 16);
+    host_parallel_for(n_abc, [&](size_t i) {
+        const Affine<HFp> g = host_load_affine<HFp>(gamma_abc_g1 + 12 * i);
+        XYZZ<HFp> acc = XYZZ<HFp>::inf();
+        tab[i * 16].x = HFp::zero(); tab[i * 16].y = HFp::zero();
+        for (int d = 1; d < 16; d++) { xyzz_madd(acc, g); tab[i * 16 + d] = xyzz_to_affine(acc); }
+    });
+    if (hipMalloc(&vk->d_expect, sizeof e) != hipSuccess || hipMalloc(&vk->d_neg, sizeof ng) != hipSuccess ||
+        hipMalloc(&vk->d_tab, tab.size() * sizeof(Affine<HFp>)) != hipSuccess) return fail("vk_create: hipMalloc failed");
+    if (hipMemcpyAsync(vk->d_expect, &e, sizeof e, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(vk->d_neg, ng, sizeof ng, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(vk->d_tab, tab.data(), tab.size() * sizeof(Affine<HFp>), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess) return fail("vk_create: upload failed");
+    return vk;
+}
+const uint8_t *pairing_vk_alpha_beta(const vsp_vk *vk) { return vk->alpha_beta; }
+size_t pairing_vk_n_abc(const vsp_vk *vk) { return vk->n_abc; }
+
+int pairing_verify_batch(vsp_ctx *ctx, const vsp_vk *vk, const uint64_t *inputs, const uint64_t *A, const uint64_t *B, const uint64_t *C, size_t n, uint8_t *verdict_out) {
+    VSP_HIP(hipSetDevice(ctx->device));
+    VSP_TRY(pairing_events(ctx));
+    hipStream_t st = ctx->stream;
+    const size_t L = vk->n_abc - 1, piece = pairing_piece(ctx, 3);
+    for (size_t at = 0; at < n; at += piece) {
+        const size_t c = n - at < piece ? n - at : piece;
+        VSP_TRY(pairing_workspace(ctx, 3, c));
+        VSP_TRY(ensure(ctx, ctx->pair_raw, c * (48 + 4 * L) * sizeof(uint64_t)));
+        uint64_t *dA = (uint64_t *)ctx->pair_raw.p, *dB = dA + c * 12, *dC = dB + c * 24, *dS = dC + c * 12;
+        VSP_HIP(hipMemcpyAsync(dA, A + at * 12, c * 12 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        VSP_HIP(hipMemcpyAsync(dB, B + at * 24, c * 24 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        VSP_HIP(hipMemcpyAsync(dC, C + at * 12, c * 12 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        if (L) VSP_HIP(hipMemcpyAsync(dS, inputs + at * L * 4, c * L * 4 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_verify_prepare, dim3((unsigned)((c + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, dA, dB, dC, (const uint32_t *)dS, c,
+                           vk->n_abc, (const G1Affine *)vk->d_tab, (const G2Affine *)vk->d_neg, (G1Affine *)ctx->pair_g1.p, (G2Affine *)ctx->pair_g2.p,
+                           (uint8_t *)ctx->pair_status.p);
+        VSP_LAUNCH_CHECK();
+        VSP_TRY(pairing_stages(ctx, 3, c, (const Fp12 *)vk->d_expect, false));
+        VSP_HIP(hipMemcpyAsync(verdict_out + at, (const uint8_t *)ctx->pair_status.p + 3 * c + c, c, hipMemcpyDeviceToHost, st));
+        VSP_HIP(hipStreamSynchronize(st));
+        pairing_add_times(ctx);
+    }
+    return VSP_OK;
+}
+
+}  // namespace vsp
