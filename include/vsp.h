@@ -392,7 +392,8 @@ void vsp_keypair_free(vsp_ctx *ctx, vsp_keypair *kp);
  *   ciphertext             c_0 = r delta_g1 | c_i = r delta_s_g1[i] + m_i G_i | psi = r delta_sum_s_g1 + sum m_i t_g1[i]     ((n + 2) x 12)
  * The random values upstream draws from algebraic_random_device (common.hpp:923, 1131, 1139) are explicit inputs here.
  * gamma_abc_g1 points at the first n + 1 entries of the verification key's accumulation vector (constant term, then the n
- * message inputs).  Decryption and the two verifications are pairing work on the tally / verifier side, outside this path.
+ * message inputs).  verify_encryption is vsp_saver_verify_batch below ("SAVER ballot verdicts"); decryption and its verification
+ * are pairing work on the one aggregated ciphertext, outside this path.
  * vsp_saver_keygen, vsp_saver_pk_load and vsp_saver_rerandomize are host-only and accept ctx = NULL. */
 typedef struct vsp_saver_pk vsp_saver_pk;
 size_t vsp_saver_pk_words(size_t msg_size);     /* uint64 words of the flat public key */
@@ -549,6 +550,45 @@ void vsp_vk_free(vsp_ctx *ctx, vsp_vk *vk);
 int vsp_groth16_verify_batch(vsp_ctx *ctx, const vsp_vk *vk, const uint64_t *inputs /* host n x (n_abc - 1) x 4, canonical Fr */,
                              const uint64_t *A /* n x 12 */, const uint64_t *B /* n x 24 */, const uint64_t *C /* n x 12 */, size_t n,
                              uint8_t *verdict_out /* n: 1 accepted, 0 rejected */);
+
+/* ---- SAVER ballot verdicts on the GPU: verify_encryption<elgamal_verifiable> (common.hpp:1164-1169) ------------------------------
+ * The check every ballot passes before it may enter the tally.  A ballot is a ciphertext ct = c_0 | c_1 .. c_n | psi (n = msg_size)
+ * with a proof (A, B, C); the ciphertext stands in for the message inputs of the Groth16 statement:
+ *     equation 1:  prod_{j=0..n} e(c_j, t_g2[j]) * e(psi, -H) = 1                                   (H the generator of G2)
+ *     equation 2:  fexp(ml(A, B) ml(acc, -gamma_g2) ml(C, -delta_g2)) = e(alpha_g1, beta_g2),
+ *                  acc = gamma_ABC[0] + c_0 + .. + c_n + sum_k inputs_rest[k] gamma_ABC[n + 1 + k]
+ * verdict_out[k] is 1 exactly when oracle/saver.py verify_encryption accepts ballot k.  reason_out[k] (may be NULL) is 0 for an accepted
+ * ballot; exactly 1 for a malformed one (a coordinate >= p, a point off its curve, a scalar >= r: no pairing verdict for it, the rest
+ * of the batch is unaffected); otherwise bit 1 (value 2) is set when equation 1 fails and bit 2 (value 4) when equation 2 fails.
+ * Equal, opposite and infinity ciphertext members are legal (the additions of acc are generic); an infinity member pairs to one.
+ * A verifier handle holds a verification key as vsp_vk_create makes it, and the PREPARED LINES of the 29 fixed G2 arguments at
+ * msg_size 25 -- t_g2[0..n], -H, -gamma_g2, -delta_g2: the 68 line-coefficient triples of the Miller loop, 19 584 bytes each
+ * (csrc/pairing.h) -- so a ballot's Miller loops do no G2 point arithmetic but for B, and the pairs of an equation share their Fp12
+ * squarings in groups of "saver_verify_group" pairs (option, default 9; one lane per ballot and group).  saver_pk_words is the flat
+ * public key of vsp_saver_keygen (only t_g2 is read).  Creation validates the key points on the host (canonical, on the curve): NULL
+ * and the last error otherwise.
+ * SUBGROUP.  As for the pairings above, the points of a ballot are ASSUMED to lie in the order-r subgroups: decode with check_subgroup
+ * (vsp_tally_add_blobs, vsp_proof_from_blob_batch).
+ * vsp_saver_verify_batch returns VSP_OK whatever the verdicts are; VSP_ERR_ARG for a null pointer, also with n = 0 (inputs_rest may be
+ * NULL when n_abc = msg_size + 1), and for a verifier made on another device; VSP_ERR_HIP as elsewhere.  No random linear combination:
+ * every verdict is exact and independent of the other ballots.
+ * Any n: the work runs in pieces of at most "pairing_chunk" ballots (default and maximum 2^14) and at most 2^19 G1 arguments (a ballot
+ * has msg_size + 5 and is never split).  Workspace bound per piece: 96 canonical + 96 Montgomery bytes per G1 argument (192 MiB at
+ * 2^19), 576 bytes per ballot and group (groups: ceil((msg_size + 2) / saver_verify_group) + 1), 2 x 576 + 384 + 3 bytes and 32 per
+ * rest input per ballot -- 149 MiB at msg_size 25 with 2^14 ballots and the default grouping -- of the context's grow-only workspaces
+ * whatever n is.  Stage times (HIP events, summed since vsp_stats_reset): vsp_get_stat "saver_verify_prepare_ms",
+ * "saver_verify_miller_ms" (Miller loops and their products), "saver_verify_finalexp_ms". */
+typedef struct vsp_saver_verifier vsp_saver_verifier;
+vsp_saver_verifier *vsp_saver_verifier_create(vsp_ctx *ctx, size_t msg_size, const uint64_t *saver_pk_words /* vsp_saver_pk_words(msg_size) */,
+                                              const uint64_t alpha_g1[12], const uint64_t beta_g2[24], const uint64_t gamma_g2[24],
+                                              const uint64_t delta_g2[24], const uint64_t *gamma_abc_g1 /* n_abc x 12 */,
+                                              size_t n_abc /* >= msg_size + 1 */);
+void vsp_saver_verifier_free(vsp_ctx *ctx, vsp_saver_verifier *ver);
+size_t vsp_saver_verifier_msg_size(const vsp_saver_verifier *ver);
+int vsp_saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct /* host n x (msg_size + 2) x 12 */,
+                           const uint64_t *inputs_rest /* n x (n_abc - 1 - msg_size) x 4; may be NULL when that is 0 */,
+                           const uint64_t *A /* n x 12 */, const uint64_t *B /* n x 24 */, const uint64_t *C /* n x 12 */, size_t n,
+                           uint8_t *verdict_out /* n: 1 accepted, 0 rejected */, uint8_t *reason_out /* n, may be NULL */);
 
 /* ---- wire formats of the reference's marshaling_policy (common.hpp:168-203 option::big_endian) --------------------
  * PROVISIONAL where marked: the marshalling sources are absent submodules, and only the proof bytes, the scalar vectors and the head of

@@ -135,6 +135,10 @@ PROTOTYPES = {
     "vsp_vk_alpha_beta": (_I, [_P, _P]),
     "vsp_vk_free": (None, [_P, _P]),
     "vsp_groth16_verify_batch": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "vsp_saver_verifier_create": (_P, [_P, _SZ, _P, _P, _P, _P, _P, _P, _SZ]),
+    "vsp_saver_verifier_free": (None, [_P, _P]),
+    "vsp_saver_verifier_msg_size": (_SZ, [_P]),
+    "vsp_saver_verify_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
 }
 
 _lib = None

@@ -884,6 +884,47 @@ def groth16_verify_batch(ctx, vk, inputs, A, B, Cc):
     return verdict
 
 
+class SaverVerifier:
+    """The verifying side of a SAVER election resident on the GPU (vsp_saver_verifier): the Groth16 verification key as VerifyingKey
+    holds it, and the prepared Miller-loop lines of the fixed G2 arguments t_g2[0..msg_size], -H, -gamma_g2, -delta_g2.  pk_words is
+    the flat public key of saver_generate_keypair."""
+
+    def __init__(self, ctx, pk_words, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, msg_size):
+        self.ctx = ctx
+        self.msg_size = int(msg_size)
+        gabc = _u64(gamma_abc_g1, 12)
+        self.n_abc = gabc.shape[0]
+        words = _u64(pk_words).reshape(-1)
+        if self.msg_size < 1 or words.shape[0] != ctx.lib.vsp_saver_pk_words(self.msg_size):
+            raise ValueError("SaverVerifier: pk_words is not a public key of this msg_size")
+        a = _u64(alpha_g1).reshape(12); b = _u64(beta_g2).reshape(24); g = _u64(gamma_g2).reshape(24); d = _u64(delta_g2).reshape(24)
+        self.h = ctx.lib.vsp_saver_verifier_create(ctx.h, self.msg_size, _ptr(words), _ptr(a), _ptr(b), _ptr(g), _ptr(d), _ptr(gabc), self.n_abc)
+        if not self.h:
+            raise VspError("vsp_saver_verifier_create failed: " + ctx.last_error())
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.vsp_saver_verifier_free(self.ctx.h, self.h)
+            self.h = None
+
+
+def saver_verify_batch(ctx, ver, ct, inputs_rest, A, B, Cc):
+    """verify_encryption of n ballots: ct [n, msg_size + 2, 12], inputs_rest [n, n_abc - 1 - msg_size, 4] canonical scalars (ignored
+    when there are none), A [n,12], B [n,24], C [n,12] -> (verdict [n] uint8, 1 = accepted; reason [n] uint8: 0 accepted, 1 malformed,
+    else 2 = the ciphertext equation fails | 4 = the Groth16 equation fails).  Exact per-ballot verdicts; the points are assumed to
+    be in the subgroups (decode with check_subgroup)."""
+    A = _u64(A, 12); B = _u64(B, 24); Cc = _u64(Cc, 12)
+    n = A.shape[0]
+    n_rest = ver.n_abc - 1 - ver.msg_size
+    ct = _u64(ct).reshape(n, -1)
+    rest = _u64(inputs_rest).reshape(n, -1) if n_rest else np.zeros((n, 4), np.uint64)
+    if B.shape[0] != n or Cc.shape[0] != n or ct.shape[1] != 12 * (ver.msg_size + 2) or (n_rest and rest.shape[1] != 4 * n_rest):
+        raise ValueError("saver_verify_batch: n ballots (ct[msg_size + 2, 12], A[12], B[24], C[12]) and n x (n_abc - 1 - msg_size) rest inputs expected")
+    verdict = np.zeros(n, np.uint8); reason = np.zeros(n, np.uint8)
+    ctx.check(ctx.lib.vsp_saver_verify_batch(ctx.h, ver.h, _ptr(ct), _ptr(rest), _ptr(A), _ptr(B), _ptr(Cc), n, _ptr(verdict), _ptr(reason)))
+    return verdict, reason
+
+
 # ---- wire formats (f.2): the big-endian blobs of the reference's marshaling_policy (common.hpp:168-203, 462-485, 749-799) ---------
 def fr_vector_to_blob(vals):
     """serialize a scalar vector (primary input, eid, sn, rt, voting result): 8-byte count + 32-byte big-endian elements"""

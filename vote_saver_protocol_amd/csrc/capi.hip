@@ -215,6 +215,7 @@ void vsp_destroy(vsp_ctx *ctx) {
     for (hipEvent_t e : ctx->g2_ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : ctx->check_ev) if (e) hipEventDestroy(e);
     for (hipEvent_t e : ctx->pair_ev) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : ctx->sv_ev) if (e) hipEventDestroy(e);
     for (hipStream_t ps : ctx->prove_streams) if (ps) hipStreamDestroy(ps);
     hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -280,6 +281,23 @@ int vsp_groth16_verify_batch(vsp_ctx *ctx, const vsp_vk *vk, const uint64_t *inp
     if (!ctx) return VSP_ERR_ARG;
     if (!vk || !A || !B || !C || !verdict_out || (!inputs && pairing_vk_n_abc(vk) > 1)) return set_error(ctx, VSP_ERR_ARG, "groth16_verify_batch: null argument");
     return pairing_verify_batch(ctx, vk, inputs, A, B, C, n, verdict_out);
+}
+
+// ---- SAVER ballot verdicts (pairing.hip)
+vsp_saver_verifier *vsp_saver_verifier_create(vsp_ctx *ctx, size_t msg_size, const uint64_t *saver_pk_words, const uint64_t alpha_g1[12], const uint64_t beta_g2[24],
+                                              const uint64_t gamma_g2[24], const uint64_t delta_g2[24], const uint64_t *gamma_abc_g1, size_t n_abc) {
+    if (!ctx) return nullptr;
+    if (!saver_pk_words || !alpha_g1 || !beta_g2 || !gamma_g2 || !delta_g2 || !gamma_abc_g1) { set_error(ctx, VSP_ERR_ARG, "saver_verifier_create: null argument"); return nullptr; }
+    if (msg_size == 0 || msg_size > 1022 || n_abc < msg_size + 1) { set_error(ctx, VSP_ERR_ARG, "saver_verifier_create: msg_size outside 1..1022 or n_abc < msg_size + 1"); return nullptr; }
+    return saver_verifier_create(ctx, msg_size, saver_pk_words, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, n_abc);
+}
+void vsp_saver_verifier_free(vsp_ctx *ctx, vsp_saver_verifier *ver) { saver_verifier_free(ctx, ver); }
+size_t vsp_saver_verifier_msg_size(const vsp_saver_verifier *ver) { return ver ? saver_verifier_msg_size(ver) : 0; }
+int vsp_saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *inputs_rest, const uint64_t *A, const uint64_t *B,
+                           const uint64_t *C, size_t n, uint8_t *verdict_out, uint8_t *reason_out) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!ver || !ct || !A || !B || !C || !verdict_out || (!inputs_rest && saver_verifier_n_rest(ver) > 0)) return set_error(ctx, VSP_ERR_ARG, "saver_verify_batch: null argument");
+    return saver_verify_batch(ctx, ver, ct, inputs_rest, A, B, C, n, verdict_out, reason_out);
 }
 
 void *vsp_dmalloc(vsp_ctx *ctx, size_t bytes) {

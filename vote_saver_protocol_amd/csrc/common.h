@@ -221,6 +221,7 @@ struct vsp_ctx {
     // products, GT values; the timers around the Miller stage and the final exponentiation, created on first use
     vsp::DevBuf pair_raw, pair_g1, pair_g2, pair_status, pair_ml, pair_prod, pair_gt;
     hipEvent_t pair_ev[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t sv_ev[4] = {nullptr, nullptr, nullptr, nullptr};       // vsp_saver_verify_batch: around its prepare, Miller and final-exponentiation stages
     // prover workspaces for K witnesses (a single proof: K = 1): z [K][num_vars + 1], A z, B z, C z [K][3][m], H [K][m], the packed witness
     vsp::DevBuf pr_z, pr_abc, pr_h, pr_pack;
     // the witness check (prover.hip k_r1cs_verdict): per member of a piece of at most VERDICT_MEMBERS witnesses three 32-bit words --
@@ -418,6 +419,14 @@ const uint8_t *pairing_vk_alpha_beta(const vsp_vk *vk);
 size_t pairing_vk_n_abc(const vsp_vk *vk);
 void pairing_vk_free(vsp_ctx *ctx, vsp_vk *vk);
 int pairing_verify_batch(vsp_ctx *ctx, const vsp_vk *vk, const uint64_t *inputs, const uint64_t *A, const uint64_t *B, const uint64_t *C, size_t n, uint8_t *verdict_out);
+// SAVER ballot verdicts (pairing.hip): a verification key with the prepared lines of the election key's G2 members
+vsp_saver_verifier *saver_verifier_create(vsp_ctx *ctx, size_t msg_size, const uint64_t *saver_pk_words, const uint64_t *alpha_g1, const uint64_t *beta_g2,
+                                          const uint64_t *gamma_g2, const uint64_t *delta_g2, const uint64_t *gamma_abc_g1, size_t n_abc);
+void saver_verifier_free(vsp_ctx *ctx, vsp_saver_verifier *ver);
+size_t saver_verifier_msg_size(const vsp_saver_verifier *ver);
+size_t saver_verifier_n_rest(const vsp_saver_verifier *ver);
+int saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *inputs_rest, const uint64_t *A, const uint64_t *B,
+                       const uint64_t *C, size_t n, uint8_t *verdict_out, uint8_t *reason_out);
 int upload_power_tables(vsp_ctx *ctx, const HFr &base, size_t hi_count, DevBuf &lo, DevBuf &hi);
 HFr host_omega(unsigned log_m);
 

@@ -45,8 +45,13 @@ static constexpr uint64_t BLS_X_ABS_PLUS_1_OVER_3 = 0x460055555555aaabULL;
 
 template <class F> struct alignas(16) G2Proj { Fp2T<F> X, Y, Z; };
 
-// T = 2 T; f = f^2 l_{T,T}(P)
-template <class F> VSP_HD_CALL void miller_double(Fp12T<F> &f, G2Proj<F> &T, const F &xP, const F &yP) {
+// The three Fp2 values of a line before xP and yP are multiplied in.  Doubling: a = E - B, b = 3 J, c = H, the line is
+// a + b xP v - c yP v w.  Addition: a = j, b = th, c = la, the line is a - b xP v + c yP v w.  They depend on Q alone.
+template <class F> struct alignas(16) LineCoeffs { Fp2T<F> a, b, c; };
+static constexpr int MILLER_LINES = 68;                               // 63 doublings + 5 additions, in loop order
+
+// T = 2 T and the coefficients of l_{T,T}
+template <class F> VSP_HD_CALL void line_double(G2Proj<F> &T, LineCoeffs<F> &l) {
     const Fp2T<F> A = f2half(f2mul(T.X, T.Y)), B = f2sqr(T.Y), C = f2sqr(T.Z);
     const Fp2T<F> C4 = dbl(dbl(C)), bC = mul_xi(C4);                 // b' C = 4 (1 + u) C
     const Fp2T<F> E = add(dbl(bC), bC), Fv = add(dbl(E), E);
@@ -55,19 +60,35 @@ template <class F> VSP_HD_CALL void miller_double(Fp12T<F> &f, G2Proj<F> &T, con
     T.X = f2mul(A, sub(B, Fv));
     T.Y = sub(f2sqr(G), add(dbl(E2), E2));
     T.Z = f2mul(B, H);
-    f = sqr(f);
-    f = mul_by_014(f, sub(E, B), mul_fp(add(dbl(J), J), xP), neg(mul_fp(H, yP)));
+    l.a = sub(E, B); l.b = add(dbl(J), J); l.c = H;
 }
-// f = f l_{T,Q}(P); T = T + Q.  T = +-Q does not occur for points of order r (the multiples of Q met are below |x| < r)
-template <class F> VSP_HD_CALL void miller_add(Fp12T<F> &f, G2Proj<F> &T, const Affine<Fp2T<F>> &Q, const F &xP, const F &yP) {
+// the coefficients of l_{T,Q} and T = T + Q.  T = +-Q does not occur for points of order r (the multiples of Q met are below |x| < r)
+template <class F> VSP_HD_CALL void line_add(G2Proj<F> &T, const Affine<Fp2T<F>> &Q, LineCoeffs<F> &l) {
     const Fp2T<F> th = sub(T.Y, f2mul(Q.y, T.Z)), la = sub(T.X, f2mul(Q.x, T.Z));
     const Fp2T<F> c = f2sqr(th), d = f2sqr(la), e = f2mul(la, d), ff = f2mul(T.Z, c), g = f2mul(T.X, d);
     const Fp2T<F> h = sub(add(e, ff), dbl(g));
-    const Fp2T<F> j = sub(f2mul(th, Q.x), f2mul(la, Q.y));
+    l.a = sub(f2mul(th, Q.x), f2mul(la, Q.y));
     T.X = f2mul(la, h);
     T.Y = sub(f2mul(th, sub(g, h)), f2mul(e, T.Y));
     T.Z = f2mul(T.Z, e);
-    f = mul_by_014(f, j, neg(mul_fp(th, xP)), mul_fp(la, yP));
+    l.b = th; l.c = la;
+}
+// f = f l for the line of a doubling / of an addition, evaluated at P = (xP, yP)
+template <class F> VSP_HD void mul_line_double(Fp12T<F> &f, const LineCoeffs<F> &l, const F &xP, const F &yP) { f = mul_by_014(f, l.a, mul_fp(l.b, xP), neg(mul_fp(l.c, yP))); }
+template <class F> VSP_HD void mul_line_add(Fp12T<F> &f, const LineCoeffs<F> &l, const F &xP, const F &yP) { f = mul_by_014(f, l.a, neg(mul_fp(l.b, xP)), mul_fp(l.c, yP)); }
+
+// T = 2 T; f = f^2 l_{T,T}(P)
+template <class F> VSP_HD_CALL void miller_double(Fp12T<F> &f, G2Proj<F> &T, const F &xP, const F &yP) {
+    LineCoeffs<F> l;
+    line_double(T, l);
+    f = sqr(f);
+    mul_line_double(f, l, xP, yP);
+}
+// f = f l_{T,Q}(P); T = T + Q
+template <class F> VSP_HD_CALL void miller_add(Fp12T<F> &f, G2Proj<F> &T, const Affine<Fp2T<F>> &Q, const F &xP, const F &yP) {
+    LineCoeffs<F> l;
+    line_add(T, Q, l);
+    mul_line_add(f, l, xP, yP);
 }
 // f_{|x|,Q}(P), P and Q affine in Montgomery form; one when either is infinity (x = y = 0).  No conjugation: see CONVENTION
 template <class F> VSP_HD Fp12T<F> miller_loop(const Affine<F> &P, const Affine<Fp2T<F>> &Q) {
@@ -80,6 +101,60 @@ template <class F> VSP_HD Fp12T<F> miller_loop(const Affine<F> &P, const Affine<
     for (int i = 62; i >= 0; i--) {
         miller_double(f, T, P.x, P.y);
         if ((BLS_X_ABS >> i) & 1) miller_add(f, T, Q, P.x, P.y);
+    }
+    return f;
+}
+
+// PREPARED ARGUMENTS.  The point arithmetic of the loop depends on Q alone: for a Q that is fixed (a key member) the 68 coefficient
+// triples are computed once -- 68 x 3 x 96 = 19 584 bytes in Montgomery form -- and a pair with such a Q costs per step only the two
+// products by xP, yP and the line product: 63 (4 + 39) + 5 (4 + 39) = 2 924 field products plus its share of the squarings.
+// Q = infinity prepares to lines that are one (a = 1, b = c = 0): the pair contributes one.
+template <class F> VSP_HD void prepare_g2(const Affine<Fp2T<F>> &Q, LineCoeffs<F> *out /* MILLER_LINES */) {
+    if (is_inf(Q)) {
+        for (int s = 0; s < MILLER_LINES; s++) { out[s].a = Fp2T<F>::one(); out[s].b = Fp2T<F>::zero(); out[s].c = Fp2T<F>::zero(); }
+        return;
+    }
+    G2Proj<F> T; T.X = Q.x; T.Y = Q.y; T.Z = Fp2T<F>::one();
+    int s = 0;
+    for (int i = 62; i >= 0; i--) {
+        line_double(T, out[s++]);
+        if ((BLS_X_ABS >> i) & 1) line_add(T, Q, out[s++]);
+    }
+}
+// The Miller value of a product of pairs with ONE squaring per step: (f1 f2)^2 l1 l2 = f1^2 l1 f2^2 l2, so the result is the product of
+// the miller_loop values of the pairs, coefficient for coefficient.  g pairs with prepared arguments: pair j is P[j * p_stride] with the
+// lines at lines[j * MILLER_LINES]; and, when Qv is not null, one more pair (*Pv, *Qv) whose point arithmetic runs here (more than one
+// variable argument would want their T in an array: no caller has two).  A pair whose P is infinity contributes nothing, as does a
+// variable pair whose Q is.
+template <class F> VSP_HD Fp12T<F> miller_multi(const Affine<F> *P, size_t p_stride, const LineCoeffs<F> *lines, size_t g, const Affine<F> *Pv,
+                                                const Affine<Fp2T<F>> *Qv) {
+    Fp12T<F> f = Fp12T<F>::one();
+    const bool var = Qv && !is_inf(*Pv) && !is_inf(*Qv);
+    G2Proj<F> T;
+    if (var) { T.X = Qv->x; T.Y = Qv->y; T.Z = Fp2T<F>::one(); }
+    int s = 0;
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+    for (int i = 62; i >= 0; i--) {
+        const bool bit = (BLS_X_ABS >> i) & 1;
+        f = sqr(f);
+#if defined(__HIPCC__)
+#pragma unroll 1
+#endif
+        for (size_t j = 0; j < g; j++) {
+            const Affine<F> Pj = P[j * p_stride];
+            if (is_inf(Pj)) continue;
+            mul_line_double(f, lines[j * MILLER_LINES + s], Pj.x, Pj.y);
+            if (bit) mul_line_add(f, lines[j * MILLER_LINES + s + 1], Pj.x, Pj.y);
+        }
+        if (var) {
+            LineCoeffs<F> l;
+            line_double(T, l);
+            mul_line_double(f, l, Pv->x, Pv->y);
+            if (bit) { line_add(T, *Qv, l); mul_line_add(f, l, Pv->x, Pv->y); }
+        }
+        s += bit ? 2 : 1;
     }
     return f;
 }

@@ -23,10 +23,20 @@ struct vsp_vk {
     void *d_tab = nullptr;              // n_abc rows of 16 G1Affine, Montgomery: d * gamma_ABC[i], d = 0..15 (d = 0: infinity)
 };
 
+// A SAVER verifier: the Groth16 key as above, and the prepared lines (pairing.h) of the election key's G2 members in the order of the
+// pairs of a ballot: t_g2[0..n] | -H | -gamma_g2 | -delta_g2
+struct vsp_saver_verifier {
+    int device = 0;
+    size_t n = 0;                       // msg_size
+    vsp_vk *vk = nullptr;
+    void *d_lines = nullptr;            // (n + 4) x MILLER_LINES LineCoeffs, Montgomery
+};
+
 namespace vsp {
 
 static constexpr size_t PAIRING_CHUNK = (size_t)1 << 14;       // products of one piece (option "pairing_chunk")
 static constexpr size_t PAIRING_MAX_PAIRS = (size_t)1 << 16;   // pairs of one piece, whatever m is (a piece holds at least one product)
+static constexpr size_t SAVER_MAX_ARGS = (size_t)1 << 19;      // G1 arguments of one piece of ballots (msg_size <= 1022: at least 510 ballots)
 static constexpr unsigned PAIRING_THREADS = 64;                // one wave per block: 2^14 lanes spread over every compute unit
 
 // the tower work as real calls on memory temporaries (see tally.hip tally_g2_y): one copy of each loop in a kernel
@@ -146,6 +156,104 @@ __global__ __launch_bounds__(PAIRING_THREADS) void k_final_exp(const Fp12 *__res
     else ok = is_one(f);
     flag_out[i] = ok ? 1 : 0;
     if (gt_out) gt_out[i] = from_mont(f);
+}
+
+// ---- SAVER ballots (include/vsp.h "SAVER ballot verdicts").  A ballot of a piece of c has n + 4 G1 arguments whose G2
+// partner is a key member with prepared lines -- c_0 .. c_n, psi, acc, C: argument j of ballot k at pts[j c + k], its lines at
+// lines[j MILLER_LINES] -- and the pair (A, B)
+__device__ __noinline__ void pr_miller_multi(Fp12 *f, const G1Affine *P, size_t stride, const LineCoeffs<Fp> *lines, size_t g, const G1Affine *Pv, const G2Affine *Qv) {
+    *f = miller_multi<Fp>(P, stride, lines, g, Pv, Qv);
+}
+
+// ballot k of a piece: every limb vector checked and in Montgomery form, acc = G_0 + c_0 + .. + c_n + sum x_i G_{n+1+i} (the additions
+// generic: equal, opposite and infinity summands are legal ciphertexts; the scalar part over the key's 4-bit multiples as in
+// k_verify_prepare).  status[k]: not zero = malformed.  rest: c x n_rest canonical scalars, n_rest = n_abc - 1 - n
+__global__ __launch_bounds__(PAIRING_THREADS) void k_ballot_prepare(const uint64_t *__restrict__ ct, const uint32_t *__restrict__ rest, const uint64_t *__restrict__ A,
+                                                                    const uint64_t *__restrict__ B, const uint64_t *__restrict__ C, size_t c, size_t n, size_t n_abc,
+                                                                    const G1Affine *__restrict__ tab, G1Affine *__restrict__ pts, G1Affine *__restrict__ a_out,
+                                                                    G2Affine *__restrict__ b_out, uint8_t *__restrict__ status) {
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= c) return;
+    G1Affine P; G2Affine Q;
+    uint32_t st = pr_load_g1(A + 12 * k, &P) | pr_load_g2(B + 24 * k, &Q);
+    a_out[k] = P; b_out[k] = Q;
+    st |= pr_load_g1(C + 12 * k, &P);
+    pts[(n + 3) * c + k] = P;
+    const size_t L = n_abc - 1 - n;
+    const uint32_t *s = rest + k * L * 8;
+    for (size_t i = 0; i < L; i++) {
+        const uint4 lo = *(const uint4 *)(s + 8 * i), hi = *(const uint4 *)(s + 8 * i + 4);
+        if (!scalar_below_r(lo, hi)) st |= 1u;
+    }
+    G1XYZZ acc = G1XYZZ::inf();
+    if (L) {
+#pragma unroll 1
+        for (int w = 63; w >= 0; w--) {
+            if (w != 63) { pr_dbl(&acc); pr_dbl(&acc); pr_dbl(&acc); pr_dbl(&acc); }
+#pragma unroll 1
+            for (size_t i = 0; i < L; i++) {
+                const uint32_t d = (s[8 * i + (w >> 3)] >> ((w & 7) * 4)) & 15u;
+                G1Affine t = tab[(n + 1 + i) * 16 + d];
+                pr_madd(&acc, &t);
+            }
+        }
+    }
+    { G1Affine g0 = tab[1]; pr_madd(&acc, &g0); }
+#pragma unroll 1
+    for (size_t j = 0; j < n + 2; j++) {
+        st |= pr_load_g1(ct + (k * (n + 2) + j) * 12, &P);
+        pts[j * c + k] = P;
+        if (j <= n) pr_madd(&acc, &P);                              // psi (j = n + 1) is no summand
+    }
+    // affine through one inversion: 1 / (ZZ ZZZ); infinity (ZZ = 0) comes out as x = y = 0
+    const Fp t = fp_inv_chain(mul(acc.ZZ, acc.ZZZ));
+    P.x = mul(acc.X, mul(t, acc.ZZZ));
+    P.y = mul(acc.Y, mul(t, acc.ZZ));
+    pts[(n + 2) * c + k] = P;
+    status[k] = (uint8_t)st;
+}
+
+// lane = ballot, blockIdx.y = group: every lane of a wave reads the same line coefficients.  Groups 0 .. ng - 1 cut the n + 2 pairs of
+// the ciphertext equation into runs of G (the last may be shorter); group ng is the Groth16 side (acc, -gamma) (C, -delta) (A, B).
+// out[group c + k]
+__global__ __launch_bounds__(PAIRING_THREADS) void k_miller_ballot(const G1Affine *__restrict__ pts, const G1Affine *__restrict__ a_in, const G2Affine *__restrict__ b_in,
+                                                                   const LineCoeffs<Fp> *__restrict__ lines, size_t c, size_t n, size_t G, size_t ng, Fp12 *__restrict__ out) {
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= c) return;
+    const size_t grp = blockIdx.y;
+    Fp12 f;
+    if (grp < ng) {
+        const size_t first = grp * G, g = first + G <= n + 2 ? G : n + 2 - first;
+        pr_miller_multi(&f, pts + first * c + k, c, lines + first * MILLER_LINES, g, nullptr, nullptr);
+    } else {
+        G1Affine Pa = a_in[k]; G2Affine Qb = b_in[k];
+        pr_miller_multi(&f, pts + (n + 2) * c + k, c, lines + (n + 2) * MILLER_LINES, 2, &Pa, &Qb);
+    }
+    out[grp * c + k] = f;
+}
+
+// the two Miller values of ballot k: out[k] = the product of groups 0 .. ng - 1, out[c + k] = group ng
+__global__ __launch_bounds__(PAIRING_THREADS) void k_ballot_product(const Fp12 *__restrict__ ml, size_t c, size_t ng, Fp12 *__restrict__ out) {
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= c) return;
+    Fp12 f = ml[k];
+#pragma unroll 1
+    for (size_t j = 1; j < ng; j++) { Fp12 g = ml[j * c + k]; pr_mul(&f, &g); }
+    out[k] = f;
+    out[c + k] = ml[ng * c + k];
+}
+
+// both final exponentiations of a piece in one launch: flag[i] for i < c says "equation 1 of ballot i holds" (the value is one), for
+// i >= c "equation 2 of ballot i - c holds" (the value is the key's e(alpha, beta))
+__global__ __launch_bounds__(PAIRING_THREADS) void k_ballot_final_exp(const Fp12 *__restrict__ in, size_t c, const Fp12 *__restrict__ expect, uint8_t *__restrict__ flag) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2 * c) return;
+    Fp12 f = in[i];
+    pr_final_exp(&f);
+    bool ok;
+    if (i < c) ok = is_one(f);
+    else { const Fp12 e = *expect; ok = eq(f, e); }
+    flag[i] = ok ? 1 : 0;
 }
 
 static int pairing_events(vsp_ctx *ctx) {
@@ -292,6 +400,105 @@ int pairing_verify_batch(vsp_ctx *ctx, const vsp_vk *vk, const uint64_t *inputs,
         VSP_HIP(hipMemcpyAsync(verdict_out + at, (const uint8_t *)ctx->pair_status.p + 3 * c + c, c, hipMemcpyDeviceToHost, st));
         VSP_HIP(hipStreamSynchronize(st));
         pairing_add_times(ctx);
+    }
+    return VSP_OK;
+}
+
+// ---- SAVER ballot verdicts
+void saver_verifier_free(vsp_ctx *ctx, vsp_saver_verifier *ver) {
+    if (!ver) return;
+    pairing_vk_free(ctx, ver->vk);                                   // waits for the stream
+    if (ver->d_lines) hipFree(ver->d_lines);
+    delete ver;
+}
+size_t saver_verifier_msg_size(const vsp_saver_verifier *ver) { return ver->n; }
+size_t saver_verifier_n_rest(const vsp_saver_verifier *ver) { return ver->vk->n_abc - 1 - ver->n; }
+
+vsp_saver_verifier *saver_verifier_create(vsp_ctx *ctx, size_t n, const uint64_t *pk_words, const uint64_t *alpha_g1, const uint64_t *beta_g2, const uint64_t *gamma_g2,
+                                          const uint64_t *delta_g2, const uint64_t *gamma_abc_g1, size_t n_abc) {
+    const uint64_t *t_g2 = pk_words + 12 + 24 * n;                   // delta_g1 | delta_s_g1 [n] | t_g1 [n] | t_g2 [n + 1] | two sums (saver.hip)
+    for (size_t j = 0; j <= n; j++)
+        if (!affine_valid<G2>(t_g2 + 24 * j)) { set_error(ctx, VSP_ERR_ARG, "saver_verifier_create: a t_g2 point is not canonical or not on its curve"); return nullptr; }
+    vsp_vk *vk = pairing_vk_create(ctx, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, n_abc);      // validates the Groth16 key
+    if (!vk) return nullptr;
+    vsp_saver_verifier *ver = new vsp_saver_verifier();
+    ver->device = ctx->device; ver->n = n; ver->vk = vk;
+    std::vector<Affine<HFp2>> q(n + 4);
+    for (size_t j = 0; j <= n; j++) q[j] = host_load_affine<HFp2>(t_g2 + 24 * j);
+    q[n + 1] = host_load_affine<HFp2>(G2::GEN);
+    q[n + 2] = host_load_affine<HFp2>(gamma_g2);
+    q[n + 3] = host_load_affine<HFp2>(delta_g2);
+    for (size_t j = n + 1; j < n + 4; j++) q[j].y = neg(q[j].y);                                        // infinity stays x = y = 0
+    std::vector<LineCoeffs<HFp>> lines(q.size() * MILLER_LINES);                                        // LineCoeffs<HFp> and <Fp>: the same bytes
+    host_parallel_for(q.size(), [&](size_t j) { prepare_g2(q[j], lines.data() + j * MILLER_LINES); });
+    const size_t bytes = lines.size() * sizeof(LineCoeffs<HFp>);
+    if (hipMalloc(&ver->d_lines, bytes) != hipSuccess || hipMemcpyAsync(ver->d_lines, lines.data(), bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        set_error(ctx, VSP_ERR_HIP, "saver_verifier_create: the prepared lines could not be uploaded");
+        saver_verifier_free(ctx, ver);
+        return nullptr;
+    }
+    return ver;
+}
+
+int saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *rest, const uint64_t *A, const uint64_t *B, const uint64_t *C, size_t count,
+                       uint8_t *verdict_out, uint8_t *reason_out) {
+    if (ver->device != ctx->device) return set_error(ctx, VSP_ERR_ARG, "saver_verify_batch: the verifier belongs to another device");
+    VSP_HIP(hipSetDevice(ctx->device));
+    for (hipEvent_t &e : ctx->sv_ev) if (!e) VSP_HIP(hipEventCreate(&e));
+    hipStream_t st = ctx->stream;
+    const size_t n = ver->n, L = ver->vk->n_abc - 1 - n;
+    // ballots of one piece: "pairing_chunk" as for the pairings, and at most 2^19 G1 arguments (a ballot has n + 5; never split)
+    size_t piece = pairing_piece(ctx, 1);
+    if (piece * (n + 5) > SAVER_MAX_ARGS) piece = SAVER_MAX_ARGS / (n + 5);
+    // groups of the ciphertext equation: option "saver_verify_group" pairs each
+    const long gv = opt(ctx, "saver_verify_group", 9);
+    const size_t G = gv < 1 ? 1 : ((size_t)gv > n + 2 ? n + 2 : (size_t)gv), ng = (n + 2 + G - 1) / G;
+    std::vector<uint8_t> flags;
+    for (size_t at = 0; at < count; at += piece) {
+        const size_t c = count - at < piece ? count - at : piece;
+        const size_t ct_words = c * (n + 2) * 12;
+        VSP_TRY(ensure(ctx, ctx->pair_raw, (ct_words + c * (48 + 4 * L)) * sizeof(uint64_t)));
+        VSP_TRY(ensure(ctx, ctx->pair_g1, (n + 5) * c * sizeof(G1Affine)));                              // n + 4 prepared-side arguments, then A
+        VSP_TRY(ensure(ctx, ctx->pair_g2, c * sizeof(G2Affine)));
+        VSP_TRY(ensure(ctx, ctx->pair_status, 3 * c));                                                   // malformed | equation 1 | equation 2
+        VSP_TRY(ensure(ctx, ctx->pair_ml, (ng + 1) * c * sizeof(Fp12)));
+        VSP_TRY(ensure(ctx, ctx->pair_prod, 2 * c * sizeof(Fp12)));
+        uint64_t *d_ct = (uint64_t *)ctx->pair_raw.p, *dA = d_ct + ct_words, *dB = dA + c * 12, *dC = dB + c * 24, *dS = dC + c * 12;
+        G1Affine *pts = (G1Affine *)ctx->pair_g1.p, *a_pts = pts + (n + 4) * c;
+        uint8_t *status = (uint8_t *)ctx->pair_status.p;
+        VSP_HIP(hipMemcpyAsync(d_ct, ct + at * (n + 2) * 12, ct_words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        VSP_HIP(hipMemcpyAsync(dA, A + at * 12, c * 12 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        VSP_HIP(hipMemcpyAsync(dB, B + at * 24, c * 24 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        VSP_HIP(hipMemcpyAsync(dC, C + at * 12, c * 12 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        if (L) VSP_HIP(hipMemcpyAsync(dS, rest + at * L * 4, c * L * 4 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        const unsigned blocks = (unsigned)((c + PAIRING_THREADS - 1) / PAIRING_THREADS);
+        VSP_HIP(hipEventRecord(ctx->sv_ev[0], st));
+        hipLaunchKernelGGL(k_ballot_prepare, dim3(blocks), dim3(PAIRING_THREADS), 0, st, d_ct, (const uint32_t *)dS, dA, dB, dC, c, n, ver->vk->n_abc,
+                           (const G1Affine *)ver->vk->d_tab, pts, a_pts, (G2Affine *)ctx->pair_g2.p, status);
+        VSP_LAUNCH_CHECK();
+        VSP_HIP(hipEventRecord(ctx->sv_ev[1], st));
+        hipLaunchKernelGGL(k_miller_ballot, dim3(blocks, (unsigned)(ng + 1)), dim3(PAIRING_THREADS), 0, st, (const G1Affine *)pts, (const G1Affine *)a_pts,
+                           (const G2Affine *)ctx->pair_g2.p, (const LineCoeffs<Fp> *)ver->d_lines, c, n, G, ng, (Fp12 *)ctx->pair_ml.p);
+        VSP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_ballot_product, dim3(blocks), dim3(PAIRING_THREADS), 0, st, (const Fp12 *)ctx->pair_ml.p, c, ng, (Fp12 *)ctx->pair_prod.p);
+        VSP_LAUNCH_CHECK();
+        VSP_HIP(hipEventRecord(ctx->sv_ev[2], st));
+        hipLaunchKernelGGL(k_ballot_final_exp, dim3((unsigned)((2 * c + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, (const Fp12 *)ctx->pair_prod.p, c,
+                           (const Fp12 *)ver->vk->d_expect, status + c);
+        VSP_LAUNCH_CHECK();
+        VSP_HIP(hipEventRecord(ctx->sv_ev[3], st));
+        flags.resize(3 * c);
+        VSP_HIP(hipMemcpyAsync(flags.data(), status, 3 * c, hipMemcpyDeviceToHost, st));
+        VSP_HIP(hipStreamSynchronize(st));
+        for (size_t k = 0; k < c; k++) {
+            const uint8_t reason = flags[k] ? 1 : (uint8_t)((flags[c + k] ? 0 : 2) | (flags[2 * c + k] ? 0 : 4));
+            verdict_out[at + k] = reason == 0;
+            if (reason_out) reason_out[at + k] = reason;
+        }
+        float ms = 0;
+        static const char *const names[3] = {"saver_verify_prepare_ms", "saver_verify_miller_ms", "saver_verify_finalexp_ms"};
+        for (int i = 0; i < 3; i++) if (hipEventElapsedTime(&ms, ctx->sv_ev[i], ctx->sv_ev[i + 1]) == hipSuccess) ctx->stats[names[i]] += ms;
     }
     return VSP_OK;
 }
