@@ -123,3 +123,74 @@ def test_sign_selection_matches_the_oracle_codec(sc, fn):
     for x in ((0, 0), (1, 0)):
         assert o.fp2_sqrt(F2.add(F2.mul(F2.sqr(x), x), B2)) is None
         assert not y_of(sc, fn, x, False)[1] and not y_of(sc, fn, x, True)[1]
+
+
+# ---- the decoding rules around the root: point_decode.h decode_record on 96-byte records, as the decoding kernel runs it
+@pytest.fixture(scope="module")
+def dc(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("cpu_build") / "libdecodechk.so")
+    flags = os.environ.get("VSP_MATHCHK_FLAGS", "-O2").split()
+    subprocess.check_call(["g++"] + flags + ["-std=c++17", "-shared", "-fPIC", "-o", so,
+                           os.path.join(ROOT, "tests", "cpu_build", "decode_check.cpp")])
+    return C.CDLL(so)
+
+
+ZERO2 = ((0, 0), (0, 0))
+
+
+def decode2(lib, rec):
+    out = np.zeros(24, np.uint64)
+    st = lib.chk_decode_g2(bytes(rec), out.ctypes.data_as(C.c_void_p))
+    return st, ((I(out[:6]), I(out[6:12])), (I(out[12:18]), I(out[18:])))
+
+
+def want2(rec):
+    """status and point by the oracle codec.  What it refuses (an assertion) is status 2 when the record is well formed -- compressed,
+    finite, both coefficients < p -- and only the curve has no such point, status 1 otherwise"""
+    try:
+        pt = o.g2_decompress(bytes(rec))
+    except AssertionError:
+        x = (int.from_bytes(rec[48:96], "big"), int.from_bytes(bytes([rec[0] & 0x1F]) + bytes(rec[1:48]), "big"))
+        well_formed = (rec[0] & 0xC0) == 0x80 and x[0] < P and x[1] < P
+        assert not well_formed or not is_square(F2.add(F2.mul(F2.sqr(x), x), B2))
+        return (2 if well_formed else 1), ZERO2
+    return 0, (pt if pt is not None else ZERO2)
+
+
+def rec2(x, flags=0x80):
+    b = bytearray(x[1].to_bytes(48, "big") + x[0].to_bytes(48, "big"))
+    b[0] |= flags
+    return bytes(b)
+
+
+def test_decode_record_accepts_what_the_oracle_codec_writes(dc):
+    gen = o.splitmix64(11)
+    signs = set()
+    for k in [1, 2, o.R - 1] + [o.rand_fr(gen) for _ in range(12)]:
+        Pt = o.G2.mul(o.G2.gen, k)
+        for Q in (Pt, o.G2.neg(Pt)):
+            enc = o.g2_compress(Q)
+            signs.add(enc[0] & 0x20)
+            assert decode2(dc, enc) == (0, Q) == want2(enc)
+    assert signs == {0, 0x20}
+    inf = o.g2_compress(None)
+    assert inf == bytes([0xC0]) + bytes(95) and decode2(dc, inf) == (0, ZERO2) == want2(inf)
+
+
+def test_decode_record_rejections(dc):
+    gx = o.G2.mul(o.G2.gen, 5)[0]
+    good = o.g2_compress(o.G2.mul(o.G2.gen, 5))
+    malformed = [bytes([0xE0]) + bytes(95), bytes([0xC0]) + bytes(94) + b"\x01", bytes([0xC0]) + bytes(46) + b"\x01" + bytes(48),
+                 bytes([good[0] & 0x7F]) + good[1:], rec2((P, P)), rec2((gx[0], P)), rec2((P, gx[1])), rec2((gx[0], P), 0xA0)]
+    for rec in malformed:
+        assert decode2(dc, rec) == (1, ZERO2) == want2(rec), rec.hex()
+    # p - 1 is canonical in either coefficient: the verdict is the curve's
+    for x in ((P - 1, 0), (0, P - 1), (P - 1, P - 1)):
+        has_point = o.fp2_sqrt(F2.add(F2.mul(F2.sqr(x), x), B2)) is not None
+        for flags in (0x80, 0xA0):
+            st, pt = decode2(dc, rec2(x, flags))
+            assert (st, pt) == want2(rec2(x, flags)) and st == (0 if has_point else 2)
+    # abscissas with no point
+    for x in ((0, 0), (1, 0)):
+        for flags in (0x80, 0xA0):
+            assert decode2(dc, rec2(x, flags)) == (2, ZERO2) == want2(rec2(x, flags))

@@ -99,6 +99,19 @@ def test_stage_times_are_reported(ctx, pool):
     assert ctx.stat("g2_decode_ms") > first and ctx.stat("g2_subgroup_ms") > 0          # summed since the reset
 
 
+def test_proof_path_counts_each_group_into_its_own_stage_stats(ctx, pool):
+    """A and C of a proof count into the G1 stages, B into the G2 stages, nothing into the tally's sum; a G1 call afterwards moves
+    the G1 decoding time alone"""
+    stages = ("tally_decode_ms", "tally_subgroup_ms", "g2_decode_ms", "g2_subgroup_ms")
+    ctx.stats_reset()
+    v.proofs_from_blob_batch(ctx, b"".join(pool.blobs[:65]), check_subgroup=True)
+    after_proofs = [ctx.stat(s) for s in stages]
+    assert all(t > 0 for t in after_proofs) and ctx.stat("tally_sum_ms") == 0
+    v.g1_decompress_batch(ctx, b"".join(pool.enc1[:65]), check_subgroup=False)
+    assert ctx.stat("tally_decode_ms") > after_proofs[0]
+    assert [ctx.stat(s) for s in stages[1:]] == after_proofs[1:] and ctx.stat("tally_sum_ms") == 0
+
+
 # ---------------------------------------------------------------------------------------------- 2. rejections
 def flagged(value_bytes):
     b = bytearray(value_bytes); b[0] |= 0x80

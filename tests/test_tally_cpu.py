@@ -92,3 +92,80 @@ def test_sign_selection_matches_the_oracle_codec(sc, fn):
     # an abscissa with no point: the verdict is false for either flag
     x = next(x for x in range(2, 100) if pow((x ** 3 + 4) % P, (P - 1) // 2, P) != 1)
     assert not y_of(sc, fn, x, False)[1] and not y_of(sc, fn, x, True)[1]
+
+
+# ---- the decoding rules around the root: point_decode.h decode_record, as the decoding kernel runs it
+DECODE_SRC = os.path.join(ROOT, "tests", "cpu_build", "decode_check.cpp")
+
+
+@pytest.fixture(scope="module")
+def dc(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("cpu_build") / "libdecodechk.so")
+    flags = os.environ.get("VSP_MATHCHK_FLAGS", "-O2").split()
+    subprocess.check_call(["g++"] + flags + ["-std=c++17", "-shared", "-fPIC", "-o", so, DECODE_SRC])
+    return C.CDLL(so)
+
+
+def decode1(lib, rec):
+    out = np.zeros(12, np.uint64)
+    st = lib.chk_decode_g1(bytes(rec), out.ctypes.data_as(C.c_void_p))
+    return st, (I(out[:6]), I(out[6:]))
+
+
+def want1(rec):
+    """status and point by the oracle codec.  What it refuses (an assertion) is status 2 when the record is well formed -- compressed,
+    finite, x < p -- and only the curve has no such point, status 1 otherwise"""
+    try:
+        pt = o.g1_decompress(bytes(rec))
+    except AssertionError:
+        x = int.from_bytes(bytes([rec[0] & 0x1F]) + bytes(rec[1:]), "big")
+        well_formed = (rec[0] & 0xC0) == 0x80 and x < P
+        assert not well_formed or pow((x ** 3 + 4) % P, (P - 1) // 2, P) == P - 1
+        return (2 if well_formed else 1), (0, 0)
+    return 0, (pt if pt is not None else (0, 0))
+
+
+def rec1(x, flags=0x80):
+    b = bytearray(x.to_bytes(48, "big"))
+    b[0] |= flags
+    return bytes(b)
+
+
+def test_decode_record_accepts_what_the_oracle_codec_writes(dc):
+    gen = o.splitmix64(11)
+    signs = set()
+    for k in [1, 2, o.R - 1] + [o.rand_fr(gen) for _ in range(12)]:
+        Pt = o.G1.mul(o.G1.gen, k)
+        for Q in (Pt, o.G1.neg(Pt)):
+            enc = o.g1_compress(Q)
+            signs.add(enc[0] & 0x20)
+            assert decode1(dc, enc) == (0, Q) == want1(enc)
+    assert signs == {0, 0x20}
+    inf = o.g1_compress(None)
+    assert inf == bytes([0xC0]) + bytes(47) and decode1(dc, inf) == (0, (0, 0)) == want1(inf)
+
+
+def test_decode_record_rejections(dc):
+    good = o.g1_compress(o.G1.mul(o.G1.gen, 5))
+    malformed = [bytes([0xE0]) + bytes(47), bytes([0xC0]) + bytes(46) + b"\x01", bytes([good[0] & 0x7F]) + good[1:], rec1(P), rec1(P, 0xA0)]
+    for rec in malformed:
+        assert decode1(dc, rec) == (1, (0, 0)) == want1(rec), rec.hex()
+    # x = p - 1 is canonical: the verdict is the curve's
+    for flags in (0x80, 0xA0):
+        rec = rec1(P - 1, flags)
+        has_point = pow(((P - 1) ** 3 + 4) % P, (P - 1) // 2, P) == 1
+        st, pt = decode1(dc, rec)
+        assert (st, pt) == want1(rec) and st == (0 if has_point else 2)
+    # the first small x with no point
+    x = next(x for x in range(2, 100) if pow((x ** 3 + 4) % P, (P - 1) // 2, P) != 1)
+    for flags in (0x80, 0xA0):
+        assert decode1(dc, rec1(x, flags)) == (2, (0, 0)) == want1(rec1(x, flags))
+
+
+def test_decode_check_stand_alone_under_sanitizers(tmp_path):
+    """decode_check.cpp with its own main under AddressSanitizer and UBSan: both groups, no code loaded into python"""
+    exe = str(tmp_path / "decode_check_san")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-DDECODE_CHECK_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-static-libubsan", "-o", exe, DECODE_SRC])
+    p = subprocess.run([exe], capture_output=True, text=True)
+    assert p.returncode == 0 and "decode_check: ok" in p.stdout, p.stdout + p.stderr

@@ -1,6 +1,6 @@
 """Batched pairings and Groth16 verdicts on the GPU (vsp_multi_pairing_batch, vsp_groth16_verify_batch): pairings/s at 2^10 and 2^14
 pairs, proofs/s at 2^12 proofs, wall time of the blocking call and the two stage times, and field products/s from the operation count
-of DESIGN.md 3.6c (csrc/pairing.h): 6 700 per Miller loop, 9 196 per final exponentiation -- to set beside k_tally_decode's 56 G field
+of DESIGN.md 3.6c (csrc/pairing.h): 6 700 per Miller loop, 9 196 per final exponentiation -- to set beside k_point_decode<G1>'s 56 G field
 products/s, a kernel of the same kind.
 The points are multiples of the generators by vsp_fixed_base_mul.  The "proofs" are random subgroup points, not valid proofs: the work of
 a verdict does not depend on the data, and every verdict must come out 0.  The pairings are checked on the first 256 pairs:

@@ -747,29 +747,29 @@ def g2_decompress(data, check_subgroup=True):
     return out
 
 
+def _decompress_batch(ctx, data, group, check_subgroup):
+    """the body of g1_decompress_batch / g2_decompress_batch: records of 48 * group bytes, points of 12 * group limbs"""
+    name, size = "g%d_decompress_batch" % group, 48 * group
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    if buf.shape[0] % size:
+        raise ValueError("%s: the input is not a whole number of %d-byte points" % (name, size))
+    n = buf.shape[0] // size
+    out = np.zeros((n, 12 * group), np.uint64); status = np.zeros(n, np.uint8)
+    ctx.check(getattr(ctx.lib, "vsp_" + name)(ctx.h, _ptr(buf), n, int(check_subgroup), _ptr(out), _ptr(status)))
+    return out, status
+
+
 def g1_decompress_batch(ctx, data, check_subgroup=True):
     """n x 48 ZCash-compressed bytes -> (points [n,12], status [n]) on the GPU.  status 0 = accepted; bit 0 malformed encoding, bit 1
     no curve point has this x, bit 2 outside the order-r subgroup (only with check_subgroup).  Rejected points and infinity are all zero."""
-    buf = np.frombuffer(bytes(data), dtype=np.uint8)
-    if buf.shape[0] % 48:
-        raise ValueError("g1_decompress_batch: the input is not a whole number of 48-byte points")
-    n = buf.shape[0] // 48
-    out = np.zeros((n, 12), np.uint64); status = np.zeros(n, np.uint8)
-    ctx.check(ctx.lib.vsp_g1_decompress_batch(ctx.h, _ptr(buf), n, int(check_subgroup), _ptr(out), _ptr(status)))
-    return out, status
+    return _decompress_batch(ctx, data, 1, check_subgroup)
 
 
 def g2_decompress_batch(ctx, data, check_subgroup=True):
     """n x 96 ZCash-compressed bytes -> (points [n,24], status [n]) on the GPU.  status 0 = accepted; bit 0 malformed encoding, bit 1
     no point of the twist has this x, bit 2 outside the order-r subgroup (only with check_subgroup).  Rejected points and infinity are
     all zero."""
-    buf = np.frombuffer(bytes(data), dtype=np.uint8)
-    if buf.shape[0] % 96:
-        raise ValueError("g2_decompress_batch: the input is not a whole number of 96-byte points")
-    n = buf.shape[0] // 96
-    out = np.zeros((n, 24), np.uint64); status = np.zeros(n, np.uint8)
-    ctx.check(ctx.lib.vsp_g2_decompress_batch(ctx.h, _ptr(buf), n, int(check_subgroup), _ptr(out), _ptr(status)))
-    return out, status
+    return _decompress_batch(ctx, data, 2, check_subgroup)
 
 
 def proofs_from_blob_batch(ctx, data, check_subgroup=True):

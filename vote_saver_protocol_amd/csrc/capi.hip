@@ -203,19 +203,15 @@ void vsp_destroy(vsp_ctx *ctx) {
                       &ctx->ntt.fwd29, &ctx->ntt.inv29, &ctx->ntt.pw29[0], &ctx->ntt.pw29[1], &ctx->ntt.pw29[2], &ctx->ntt.pw29[3],
                       &ctx->msm_scalars, &ctx->val_flag, &ctx->fb_table[0], &ctx->fb_table[1], &ctx->fb_tmp, &ctx->fb_pre,
                       &ctx->pr_z, &ctx->pr_abc, &ctx->pr_h, &ctx->pr_pack, &ctx->pr_verdict,
-                      &ctx->tally_raw, &ctx->tally_pts, &ctx->tally_pstatus, &ctx->tally_bstatus, &ctx->tally_partials,
-                      &ctx->g2_pts, &ctx->g2_pstatus,
+                      &ctx->tally_raw, &ctx->tally_bstatus, &ctx->tally_partials,
+                      &ctx->decode[0].pts, &ctx->decode[0].pstatus, &ctx->decode[1].pts, &ctx->decode[1].pstatus,
                       &ctx->pair_raw, &ctx->pair_g1, &ctx->pair_g2, &ctx->pair_status, &ctx->pair_ml, &ctx->pair_prod, &ctx->pair_gt};
     for (DevBuf *b : bufs) free_buf(*b);
     msm_free_slots(ctx);
     if (ctx->h_fold) hipHostFree(ctx->h_fold);
     if (ctx->h_verdict) hipHostFree(ctx->h_verdict);
     hipEventDestroy(ctx->ev0); hipEventDestroy(ctx->ev1); hipEventDestroy(ctx->ev_aux);
-    for (hipEvent_t e : ctx->tally_ev) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : ctx->g2_ev) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : ctx->check_ev) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : ctx->pair_ev) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : ctx->sv_ev) if (e) hipEventDestroy(e);
+    for (StageTimer *t : {&ctx->decode[0].timer, &ctx->decode[1].timer, &ctx->check_timer, &ctx->pair_timer, &ctx->saver_timer}) t->destroy();
     for (hipStream_t ps : ctx->prove_streams) if (ps) hipStreamDestroy(ps);
     hipStreamDestroy(ctx->own_stream);
     delete ctx;

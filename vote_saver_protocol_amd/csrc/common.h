@@ -15,7 +15,9 @@
 #include <mutex>
 #include <thread>
 #include "curve.h"
+#include "point_decode.h"
 
+struct vsp_ctx;
 namespace vsp {
 
 // ---- the two groups: G1 over Fp, G2 over Fp2 (y^2 = x^3 + b, curve_b below) ----
@@ -50,6 +52,20 @@ inline size_t point_bytes(int group) { return with_group(group, [](auto g) { ret
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+};
+// the timers around the device stages of one kind of call: up to four events, created on first use
+struct StageTimer {
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    int event(vsp_ctx *ctx, int i, hipEvent_t *out);                // event i, created on first use
+    int mark(vsp_ctx *ctx, int i, hipStream_t st);                  // record event i on st
+    void add(vsp_ctx *ctx, int i, const char *name) const;          // ctx->stats[name] += the time from event i to event i + 1; an error is ignored
+    void destroy() { for (hipEvent_t &e : ev) if (e) { hipEventDestroy(e); e = nullptr; } }
+};
+// the decoded points of one piece of a group (decode.hip): Montgomery affine points, a status byte per point, and the timer around
+// the decoding and the subgroup check (G1: event 3 closes the tally's sum)
+struct DecodeWork {
+    DevBuf pts, pstatus;
+    StageTimer timer;
 };
 
 // stage [s0, s1) split of one NTT (see ntt.hip)
@@ -210,18 +226,15 @@ struct vsp_ctx {
     int fp28_checked[2] = {0, 0};       // known-answer check of the 28-bit-limb accumulation kernels, per group: 0 not yet, 1 passed, -1 failed (kernel disabled)
     // fixed-base tables of the generators (fb_table[group - 1]), built lazily, and the scratch of the batch exponentiation
     vsp::DevBuf fb_table[2], fb_tmp, fb_pre;
-    // the tally's chunk (tally.hip): raw blobs, decoded points, a status byte per point and per ballot, the blocks' partial sums; the
-    // stage timers, created on first use
-    vsp::DevBuf tally_raw, tally_pts, tally_pstatus, tally_bstatus, tally_partials;
-    hipEvent_t tally_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    // the G2 points of a chunk of proofs or of vsp_g2_decompress_batch (tally.hip) with their status bytes, and the two stages' timers
-    vsp::DevBuf g2_pts, g2_pstatus;
-    hipEvent_t g2_ev[3] = {nullptr, nullptr, nullptr};
+    // the receiving side's piece: raw blobs (decode.hip, tally.hip), the decoded points of either group (decode[G::ID - 1]), a status
+    // byte per ballot or proof, the tally's partial sums
+    vsp::DevBuf tally_raw, tally_bstatus, tally_partials;
+    vsp::DecodeWork decode[2];
     // the pairings' piece (pairing.hip): canonical inputs, Montgomery pairs, status bytes (pairs | products | results), Miller values, their
-    // products, GT values; the timers around the Miller stage and the final exponentiation, created on first use
+    // products, GT values; the timers around the Miller stage and the final exponentiation, and around the three stages of
+    // vsp_saver_verify_batch (prepare, Miller, final exponentiation)
     vsp::DevBuf pair_raw, pair_g1, pair_g2, pair_status, pair_ml, pair_prod, pair_gt;
-    hipEvent_t pair_ev[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t sv_ev[4] = {nullptr, nullptr, nullptr, nullptr};       // vsp_saver_verify_batch: around its prepare, Miller and final-exponentiation stages
+    vsp::StageTimer pair_timer, saver_timer;
     // prover workspaces for K witnesses (a single proof: K = 1): z [K][num_vars + 1], A z, B z, C z [K][3][m], H [K][m], the packed witness
     vsp::DevBuf pr_z, pr_abc, pr_h, pr_pack;
     // the witness check (prover.hip k_r1cs_verdict): per member of a piece of at most VERDICT_MEMBERS witnesses three 32-bit words --
@@ -229,7 +242,7 @@ struct vsp_ctx {
     static constexpr size_t VERDICT_MEMBERS = 64, VERDICT_BYTES = 3 * VERDICT_MEMBERS * sizeof(uint32_t);
     vsp::DevBuf pr_verdict;
     void *h_verdict = nullptr;
-    hipEvent_t check_ev[3] = {nullptr, nullptr, nullptr};      // vsp_r1cs_check_batch: around its front half and around its verdict kernels
+    vsp::StageTimer check_timer;          // vsp_r1cs_check_batch: around its front half and around its verdict kernels
     // the proof or the batch of K proofs in flight between a launch and its finish (one per context): the key, r and s (K x 4 words), the
     // SAVER term (single proofs only), the bytes of z the launch wrote
     struct {
@@ -347,6 +360,22 @@ int ensure(vsp_ctx *ctx, DevBuf &b, size_t bytes);
     } while (0)
 #define VSP_LAUNCH_CHECK() VSP_HIP(hipGetLastError())
 
+inline int StageTimer::event(vsp_ctx *ctx, int i, hipEvent_t *out) {
+    if (!ev[i]) VSP_HIP(hipEventCreate(&ev[i]));
+    *out = ev[i];
+    return VSP_OK;
+}
+inline int StageTimer::mark(vsp_ctx *ctx, int i, hipStream_t st) {
+    hipEvent_t e;
+    VSP_TRY(event(ctx, i, &e));
+    VSP_HIP(hipEventRecord(e, st));
+    return VSP_OK;
+}
+inline void StageTimer::add(vsp_ctx *ctx, int i, const char *name) const {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) ctx->stats[name] += ms;
+}
+
 // ---- internal entry points (each implemented in its own .hip) ----
 int ntt_launch(vsp_ctx *ctx, const NttRequest &rq);
 bool ntt29_in_use(vsp_ctx *ctx);                                // runs the 29-bit butterflies' known-answer check first: before any table set-up
@@ -411,6 +440,12 @@ enum { BASES_CALLER = 0, BASES_OWN = 1, BASES_TRANSIENT = 2 };
 int bases_create(vsp_ctx *ctx, int group, const void *src, bool src_on_device, size_t n, int trust, vsp_bases **out);
 // out[i] = scalars[i] * the group's generator, canonical affine (fixedbase_impl.inc, instantiated by fixedbase_g1.hip / fixedbase_g2.hip)
 template <class G> int fixed_base_mul(vsp_ctx *ctx, const Fr *d_scalars, size_t n, void *d_out);
+// point decoding (decode.hip).  Stages 1 and 2 over the points of group G already in ctx->tally_raw: `sets` sets of n points each, set k
+// at heads[k] of the same (per, stride) addressing, decoded one after the other into ctx->decode[G::ID - 1]; events 0, 1, 2 of its
+// timer around the stages, which decode_add_times adds to the stats ("tally_*" for G1, "g2_*" for G2; the subgroup stage on request)
+template <class G> int decode_points(vsp_ctx *ctx, size_t n, size_t per, size_t stride, const size_t *heads, size_t sets, int check_subgroup);
+template <class G> void decode_add_times(vsp_ctx *ctx, bool subgroup);
+size_t decode_chunk_points(const vsp_ctx *ctx);                 // points of one piece: option "tally_chunk_points"
 // pairings and Groth16 verdicts (pairing.hip); the arguments are checked by the exports in capi.hip
 int pairing_multi_batch(vsp_ctx *ctx, const uint64_t *g1, const uint64_t *g2, size_t m, size_t n, uint8_t *gt_out, uint8_t *is_one_out);
 vsp_vk *pairing_vk_create(vsp_ctx *ctx, const uint64_t *alpha_g1, const uint64_t *beta_g2, const uint64_t *gamma_g2, const uint64_t *delta_g2, const uint64_t *gamma_abc_g1,
@@ -477,26 +512,6 @@ template <class G> inline bool affine_valid(const uint64_t *p) {
     if (!coords_below_p(p, G::AFFINE_WORDS)) return false;
     const Affine<typename G::HF> a = host_load_affine<typename G::HF>(p);
     return is_inf(a) || eq(sqr(a.y), add(mul(sqr(a.x), a.x), curve_b<typename G::HF>()));
-}
-
-// ---- device codec helpers (wire.hip, tally.hip, msm_impl.inc)
-// 48 big-endian bytes (12 words) -> 12 little-endian 32-bit limbs; the three flag bits of the first byte are cleared
-__device__ __forceinline__ Fp fp_from_be(const uint32_t *w, bool first) {
-    Fp r;
-#pragma unroll
-    for (int j = 0; j < 12; j++) r.l[j] = __builtin_bswap32(w[11 - j]);
-    if (first) r.l[11] &= 0x1FFFFFFFu;
-    return r;
-}
-// a canonical value below p
-__device__ __forceinline__ bool canon_below_p(const Fp &a) {
-    bool lt = false, gt = false;
-#pragma unroll
-    for (int i = Fp::N - 1; i >= 0; i--) {
-        lt = lt || (!gt && a.l[i] < FpP32::MOD[i]);
-        gt = gt || (!lt && a.l[i] > FpP32::MOD[i]);
-    }
-    return lt;
 }
 
 // a canonical scalar (two 16-byte halves of its eight 32-bit words) below r: the multi-exponentiations' census (msm_sort.hip k_classify) and

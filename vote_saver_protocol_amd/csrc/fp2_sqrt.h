@@ -1,5 +1,5 @@
 // Square root in BLS12-381 Fp2 = Fp[u]/(u^2 + 1) and the y coordinate of a ZCash-compressed G2 point, shared by the gfx950 decoding
-// kernel (tally.hip, 32-bit limbs) and, through g++, by the CPU test build (tests/cpu_build/sqrt2_check.cpp).
+// kernel (decode.hip through point_decode.h, 32-bit limbs) and, through g++, by the CPU test build (tests/cpu_build/sqrt2_check.cpp).
 //
 // a = a0 + a1 u is a square in Fp2 exactly when its norm n = a0^2 + a1^2 is a square in Fp.  With s a root of n, one of
 // d = (a0 + s) / 2 and d' = (a0 - s) / 2 is a square in Fp (d d' = -a1^2 / 4 and -1 is not a square: p = 3 mod 4), d + d' = a0, and

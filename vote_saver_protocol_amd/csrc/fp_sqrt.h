@@ -1,5 +1,5 @@
 // Square root in BLS12-381 Fp and the y coordinate of a ZCash-compressed G1 point, shared by the gfx950 decoding kernel
-// (tally.hip, 32-bit limbs) and, through g++, by the CPU test build (tests/cpu_build/sqrt_check.cpp).
+// (decode.hip through point_decode.h, 32-bit limbs) and, through g++, by the CPU test build (tests/cpu_build/sqrt_check.cpp).
 //
 // p = 3 (mod 4), so a^((p+1)/4) is a square root of a whenever a is a square; whether it is one is read off the result:
 // y^2 = a.  The exponent is a constant of 379 bits and is walked in 4-bit windows from the top: 14 products for the table

@@ -712,7 +712,6 @@ __global__ __launch_bounds__(64, AccumWaves<F>::W) void k_dimbits(const XYZZ<F> 
 //   flag bit 0: a coordinate is not canonical (>= p);  bit 1 (check_curve): a point is not on y^2 = x^3 + b
 // (b = 4 for G1, 4 (1 + u) for G2; all-zero = infinity is accepted).  Subgroup membership is NOT checked here -- a scalar
 // multiplication by r per point; vsp_g1_decompress / vsp_g2_decompress offer it for points that arrive as wire bytes.
-__device__ __forceinline__ bool canon_below_p(const Fp2 &a) { return canon_below_p(a.c0) && canon_below_p(a.c1); }
 __device__ __forceinline__ Fp curve_b_mont(const Fp &) { Fp four = Fp::one(); four = dbl(dbl(four)); return four; }
 __device__ __forceinline__ Fp2 curve_b_mont(const Fp2 &) { Fp2 b; b.c0 = dbl(dbl(Fp::one())); b.c1 = b.c0; return b; }
 template <class F> __global__ __launch_bounds__(256) void k_bases_to_mont(const Affine<F> *in, Affine<F> *out, size_t n, int check_curve, uint32_t *flag) {
@@ -767,7 +766,7 @@ __global__ __launch_bounds__(MSM_THREADS, AccumWaves<F>::W) void k_subgroup_chec
     const bool ex = is_zero(sub(lx, t2.X));
     const bool ey = is_zero(sub(ly, t2.Y));
     if (inf2 || !ex || !ey) {
-        if (status) status[i] |= 4u;                        // a verdict per point (tally.hip); the lanes of a pair write the same byte
+        if (status) status[i] |= 4u;                        // a verdict per point (decode.hip); the lanes of a pair write the same byte
         else atomicOr(flag, 4u);
     }
 }

@@ -1,7 +1,7 @@
 // Batched BLS12-381 pairings and exact per-proof Groth16 verdicts on the GPU (include/vsp.h "pairings").
 //
 // The verifying side of the reference (zk::verify, tvm.vergrth16) is a product of pairings per proof; the pairs of a batch are
-// independent, so the work has the shape of the decoding kernels of tally.hip: one lane per item, straight-line field arithmetic from
+// independent, so the work has the shape of the decoding kernel of decode.hip: one lane per item, straight-line field arithmetic from
 // the headers fp12.h / pairing.h, which the CPU test build checks against the test oracle.  Stages per piece of a call, all on the
 // context's stream:
 //   0. k_pair_check        one lane per pair: coordinates below p, Montgomery form, on the curve (or all zero: infinity); status byte
@@ -39,7 +39,7 @@ static constexpr size_t PAIRING_MAX_PAIRS = (size_t)1 << 16;   // pairs of one p
 static constexpr size_t SAVER_MAX_ARGS = (size_t)1 << 19;      // G1 arguments of one piece of ballots (msg_size <= 1022: at least 510 ballots)
 static constexpr unsigned PAIRING_THREADS = 64;                // one wave per block: 2^14 lanes spread over every compute unit
 
-// the tower work as real calls on memory temporaries (see tally.hip tally_g2_y): one copy of each loop in a kernel
+// the tower work as real calls on memory temporaries (see point_decode.h record_y): one copy of each loop in a kernel
 __device__ __noinline__ void pr_miller(Fp12 *f, const G1Affine *P, const G2Affine *Q) { *f = miller_loop(*P, *Q); }
 __device__ __noinline__ void pr_final_exp(Fp12 *f) { const Fp12 t = final_exp(*f); *f = t; }
 __device__ __noinline__ void pr_mul(Fp12 *f, const Fp12 *g) { const Fp12 t = mul(*f, *g); *f = t; }
@@ -68,6 +68,39 @@ __device__ __noinline__ uint32_t pr_load_g2(const uint64_t *src, G2Affine *out) 
     *out = p;
     return st;
 }
+// the L canonical scalars at s (8 words each) all below r
+__device__ __forceinline__ bool pr_scalars_below_r(const uint32_t *s, size_t L) {
+    bool ok = true;
+    for (size_t i = 0; i < L; i++) {
+        const uint4 lo = *(const uint4 *)(s + 8 * i), hi = *(const uint4 *)(s + 8 * i + 4);
+        if (!scalar_below_r(lo, hi)) ok = false;
+    }
+    return ok;
+}
+// acc = sum s_i G_i over the key's table of multiples, rows[i * 16 + d] = d G_i: 4 bits of every scalar at a time from the top, 4
+// doublings, then one table row per input
+__device__ __forceinline__ void pr_input_sum(G1XYZZ &acc, const uint32_t *s, size_t L, const G1Affine *__restrict__ rows) {
+    acc = G1XYZZ::inf();
+    if (!L) return;
+#pragma unroll 1
+    for (int w = 63; w >= 0; w--) {
+        if (w != 63) { pr_dbl(&acc); pr_dbl(&acc); pr_dbl(&acc); pr_dbl(&acc); }
+#pragma unroll 1
+        for (size_t i = 0; i < L; i++) {
+            const uint32_t d = (s[8 * i + (w >> 3)] >> ((w & 7) * 4)) & 15u;
+            G1Affine t = rows[i * 16 + d];
+            pr_madd(&acc, &t);
+        }
+    }
+}
+// affine through one inversion: 1 / (ZZ ZZZ); infinity (ZZ = 0) comes out as x = y = 0
+__device__ __forceinline__ G1Affine pr_to_affine(const G1XYZZ &acc) {
+    const Fp t = fp_inv_chain(mul(acc.ZZ, acc.ZZZ));
+    G1Affine P;
+    P.x = mul(acc.X, mul(t, acc.ZZZ));
+    P.y = mul(acc.Y, mul(t, acc.ZZ));
+    return P;
+}
 
 __global__ __launch_bounds__(PAIRING_THREADS) void k_pair_check(const uint64_t *__restrict__ g1, const uint64_t *__restrict__ g2, size_t n, G1Affine *__restrict__ p_out,
                                                                 G2Affine *__restrict__ q_out, uint8_t *__restrict__ status, uint32_t *__restrict__ flag) {
@@ -94,30 +127,14 @@ __global__ __launch_bounds__(PAIRING_THREADS) void k_verify_prepare(const uint64
     st = pr_load_g1(C + 12 * k, &P);
     p_out[3 * k + 2] = P; q_out[3 * k + 2] = neg_gd[1];
     status[3 * k + 2] = (uint8_t)st;
-    // the public-input combination, 4 bits of every scalar at a time from the top: 4 doublings, then one table row per input
+    // the public-input combination G_0 + sum x_i G_i
     const size_t L = n_abc - 1;
     const uint32_t *s = inputs + k * L * 8;
-    st = 0;
-    for (size_t i = 0; i < L; i++) {
-        const uint4 lo = *(const uint4 *)(s + 8 * i), hi = *(const uint4 *)(s + 8 * i + 4);
-        if (!scalar_below_r(lo, hi)) st = 1u;
-    }
-    G1XYZZ acc = G1XYZZ::inf();
-#pragma unroll 1
-    for (int w = 63; w >= 0; w--) {
-        if (w != 63) { pr_dbl(&acc); pr_dbl(&acc); pr_dbl(&acc); pr_dbl(&acc); }
-#pragma unroll 1
-        for (size_t i = 0; i < L; i++) {
-            const uint32_t d = (s[8 * i + (w >> 3)] >> ((w & 7) * 4)) & 15u;
-            G1Affine t = tab[(i + 1) * 16 + d];
-            pr_madd(&acc, &t);
-        }
-    }
+    st = pr_scalars_below_r(s, L) ? 0u : 1u;
+    G1XYZZ acc;
+    pr_input_sum(acc, s, L, tab + 16);
     { G1Affine g0 = tab[1]; pr_madd(&acc, &g0); }
-    // affine through one inversion: 1 / (ZZ ZZZ); infinity (ZZ = 0) comes out as x = y = 0
-    const Fp t = fp_inv_chain(mul(acc.ZZ, acc.ZZZ));
-    P.x = mul(acc.X, mul(t, acc.ZZZ));
-    P.y = mul(acc.Y, mul(t, acc.ZZ));
+    P = pr_to_affine(acc);
     if (st) { P.x = Fp::zero(); P.y = Fp::zero(); }
     p_out[3 * k + 1] = P; q_out[3 * k + 1] = neg_gd[0];
     status[3 * k + 1] = (uint8_t)st;
@@ -144,16 +161,17 @@ __global__ __launch_bounds__(PAIRING_THREADS) void k_gt_product(const Fp12 *__re
     pstatus[i] = (uint8_t)st;
 }
 
-// expect: null (the byte says "is one") or one Fp12 in Montgomery form (the byte says "equals it, and no member was rejected")
-__global__ __launch_bounds__(PAIRING_THREADS) void k_final_exp(const Fp12 *__restrict__ in, const uint8_t *__restrict__ pstatus, size_t n, const Fp12 *__restrict__ expect,
-                                                               Fp12 *__restrict__ gt_out, uint8_t *__restrict__ flag_out) {
+// the byte of item i < n_one says "is one"; that of the others "equals *expect (one Fp12 in Montgomery form)" and, where pstatus is
+// given, "no member was rejected".  gt_out: the canonical values, or null
+__global__ __launch_bounds__(PAIRING_THREADS) void k_final_exp(const Fp12 *__restrict__ in, const uint8_t *__restrict__ pstatus, size_t n, size_t n_one,
+                                                               const Fp12 *__restrict__ expect, Fp12 *__restrict__ gt_out, uint8_t *__restrict__ flag_out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Fp12 f = in[i];
     pr_final_exp(&f);
     bool ok;
-    if (expect) { const Fp12 e = *expect; ok = eq(f, e) && pstatus[i] == 0; }
-    else ok = is_one(f);
+    if (i < n_one) ok = is_one(f);
+    else { const Fp12 e = *expect; ok = eq(f, e) && (!pstatus || pstatus[i] == 0); }
     flag_out[i] = ok ? 1 : 0;
     if (gt_out) gt_out[i] = from_mont(f);
 }
@@ -166,8 +184,8 @@ __device__ __noinline__ void pr_miller_multi(Fp12 *f, const G1Affine *P, size_t 
 }
 
 // ballot k of a piece: every limb vector checked and in Montgomery form, acc = G_0 + c_0 + .. + c_n + sum x_i G_{n+1+i} (the additions
-// generic: equal, opposite and infinity summands are legal ciphertexts; the scalar part over the key's 4-bit multiples as in
-// k_verify_prepare).  status[k]: not zero = malformed.  rest: c x n_rest canonical scalars, n_rest = n_abc - 1 - n
+// generic: equal, opposite and infinity summands are legal ciphertexts; the scalar part by pr_input_sum as in k_verify_prepare).
+// status[k]: not zero = malformed.  rest: c x n_rest canonical scalars, n_rest = n_abc - 1 - n
 __global__ __launch_bounds__(PAIRING_THREADS) void k_ballot_prepare(const uint64_t *__restrict__ ct, const uint32_t *__restrict__ rest, const uint64_t *__restrict__ A,
                                                                     const uint64_t *__restrict__ B, const uint64_t *__restrict__ C, size_t c, size_t n, size_t n_abc,
                                                                     const G1Affine *__restrict__ tab, G1Affine *__restrict__ pts, G1Affine *__restrict__ a_out,
@@ -181,23 +199,9 @@ __global__ __launch_bounds__(PAIRING_THREADS) void k_ballot_prepare(const uint64
     pts[(n + 3) * c + k] = P;
     const size_t L = n_abc - 1 - n;
     const uint32_t *s = rest + k * L * 8;
-    for (size_t i = 0; i < L; i++) {
-        const uint4 lo = *(const uint4 *)(s + 8 * i), hi = *(const uint4 *)(s + 8 * i + 4);
-        if (!scalar_below_r(lo, hi)) st |= 1u;
-    }
-    G1XYZZ acc = G1XYZZ::inf();
-    if (L) {
-#pragma unroll 1
-        for (int w = 63; w >= 0; w--) {
-            if (w != 63) { pr_dbl(&acc); pr_dbl(&acc); pr_dbl(&acc); pr_dbl(&acc); }
-#pragma unroll 1
-            for (size_t i = 0; i < L; i++) {
-                const uint32_t d = (s[8 * i + (w >> 3)] >> ((w & 7) * 4)) & 15u;
-                G1Affine t = tab[(n + 1 + i) * 16 + d];
-                pr_madd(&acc, &t);
-            }
-        }
-    }
+    if (!pr_scalars_below_r(s, L)) st |= 1u;
+    G1XYZZ acc;
+    pr_input_sum(acc, s, L, tab + (n + 1) * 16);
     { G1Affine g0 = tab[1]; pr_madd(&acc, &g0); }
 #pragma unroll 1
     for (size_t j = 0; j < n + 2; j++) {
@@ -205,11 +209,7 @@ __global__ __launch_bounds__(PAIRING_THREADS) void k_ballot_prepare(const uint64
         pts[j * c + k] = P;
         if (j <= n) pr_madd(&acc, &P);                              // psi (j = n + 1) is no summand
     }
-    // affine through one inversion: 1 / (ZZ ZZZ); infinity (ZZ = 0) comes out as x = y = 0
-    const Fp t = fp_inv_chain(mul(acc.ZZ, acc.ZZZ));
-    P.x = mul(acc.X, mul(t, acc.ZZZ));
-    P.y = mul(acc.Y, mul(t, acc.ZZ));
-    pts[(n + 2) * c + k] = P;
+    pts[(n + 2) * c + k] = pr_to_affine(acc);
     status[k] = (uint8_t)st;
 }
 
@@ -243,23 +243,6 @@ __global__ __launch_bounds__(PAIRING_THREADS) void k_ballot_product(const Fp12 *
     out[c + k] = ml[ng * c + k];
 }
 
-// both final exponentiations of a piece in one launch: flag[i] for i < c says "equation 1 of ballot i holds" (the value is one), for
-// i >= c "equation 2 of ballot i - c holds" (the value is the key's e(alpha, beta))
-__global__ __launch_bounds__(PAIRING_THREADS) void k_ballot_final_exp(const Fp12 *__restrict__ in, size_t c, const Fp12 *__restrict__ expect, uint8_t *__restrict__ flag) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= 2 * c) return;
-    Fp12 f = in[i];
-    pr_final_exp(&f);
-    bool ok;
-    if (i < c) ok = is_one(f);
-    else { const Fp12 e = *expect; ok = eq(f, e); }
-    flag[i] = ok ? 1 : 0;
-}
-
-static int pairing_events(vsp_ctx *ctx) {
-    for (hipEvent_t &e : ctx->pair_ev) if (!e) VSP_HIP(hipEventCreate(&e));
-    return VSP_OK;
-}
 // products of one piece: option "pairing_chunk" (a test hook as well), 1 .. 2^14, and at most 2^16 pairs (m <= 2^16: the export refuses more)
 static size_t pairing_piece(const vsp_ctx *ctx, size_t m) {
     const long v = opt(ctx, "pairing_chunk", (long)PAIRING_CHUNK);
@@ -282,7 +265,7 @@ static int pairing_stages(vsp_ctx *ctx, size_t m, size_t n, const Fp12 *d_expect
     hipStream_t st = ctx->stream;
     const size_t pairs = n * m;
     uint8_t *status = (uint8_t *)ctx->pair_status.p, *pstatus = status + pairs, *result = pstatus + n;
-    VSP_HIP(hipEventRecord(ctx->pair_ev[0], st));
+    VSP_TRY(ctx->pair_timer.mark(ctx, 0, st));
     hipLaunchKernelGGL(k_miller, dim3((unsigned)((pairs + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, (const G1Affine *)ctx->pair_g1.p,
                        (const G2Affine *)ctx->pair_g2.p, pairs, (Fp12 *)ctx->pair_ml.p);
     VSP_LAUNCH_CHECK();
@@ -294,21 +277,32 @@ static int pairing_stages(vsp_ctx *ctx, size_t m, size_t n, const Fp12 *d_expect
         VSP_LAUNCH_CHECK();
         prod = (const Fp12 *)ctx->pair_prod.p; ps = pstatus;
     }
-    VSP_HIP(hipEventRecord(ctx->pair_ev[1], st));
-    hipLaunchKernelGGL(k_final_exp, dim3(blocks), dim3(PAIRING_THREADS), 0, st, prod, ps, n, d_expect, want_gt ? (Fp12 *)ctx->pair_gt.p : (Fp12 *)nullptr, result);
+    VSP_TRY(ctx->pair_timer.mark(ctx, 1, st));
+    hipLaunchKernelGGL(k_final_exp, dim3(blocks), dim3(PAIRING_THREADS), 0, st, prod, ps, n, d_expect ? (size_t)0 : n, d_expect, want_gt ? (Fp12 *)ctx->pair_gt.p : (Fp12 *)nullptr, result);
     VSP_LAUNCH_CHECK();
-    VSP_HIP(hipEventRecord(ctx->pair_ev[2], st));
+    VSP_TRY(ctx->pair_timer.mark(ctx, 2, st));
     return VSP_OK;
 }
 static void pairing_add_times(vsp_ctx *ctx) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ctx->pair_ev[0], ctx->pair_ev[1]) == hipSuccess) ctx->stats["pairing_miller_ms"] += ms;
-    if (hipEventElapsedTime(&ms, ctx->pair_ev[1], ctx->pair_ev[2]) == hipSuccess) ctx->stats["pairing_finalexp_ms"] += ms;
+    ctx->pair_timer.add(ctx, 0, "pairing_miller_ms");
+    ctx->pair_timer.add(ctx, 1, "pairing_finalexp_ms");
+}
+// the proof members of a piece: c proofs from proof `at` on, with L scalars each, laid out A | B | C | scalars at dst (device words)
+struct ProofArgs { uint64_t *A, *B, *C; uint32_t *scalars; };
+static size_t proof_words(size_t c, size_t L) { return c * (48 + 4 * L); }
+static int upload_proofs(vsp_ctx *ctx, uint64_t *dst, const uint64_t *A, const uint64_t *B, const uint64_t *C, const uint64_t *scalars, size_t at, size_t c, size_t L,
+                         ProofArgs &d) {
+    hipStream_t st = ctx->stream;
+    d.A = dst; d.B = d.A + c * 12; d.C = d.B + c * 24; d.scalars = (uint32_t *)(d.C + c * 12);
+    VSP_HIP(hipMemcpyAsync(d.A, A + at * 12, c * 12 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    VSP_HIP(hipMemcpyAsync(d.B, B + at * 24, c * 24 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    VSP_HIP(hipMemcpyAsync(d.C, C + at * 12, c * 12 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (L) VSP_HIP(hipMemcpyAsync(d.scalars, scalars + at * L * 4, c * L * 4 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    return VSP_OK;
 }
 
 int pairing_multi_batch(vsp_ctx *ctx, const uint64_t *g1, const uint64_t *g2, size_t m, size_t n, uint8_t *gt_out, uint8_t *is_one_out) {
     VSP_HIP(hipSetDevice(ctx->device));
-    VSP_TRY(pairing_events(ctx));
     hipStream_t st = ctx->stream;
     const size_t piece = pairing_piece(ctx, m);
     for (size_t at = 0; at < n; at += piece) {
@@ -380,19 +374,15 @@ size_t pairing_vk_n_abc(const vsp_vk *vk) { return vk->n_abc; }
 
 int pairing_verify_batch(vsp_ctx *ctx, const vsp_vk *vk, const uint64_t *inputs, const uint64_t *A, const uint64_t *B, const uint64_t *C, size_t n, uint8_t *verdict_out) {
     VSP_HIP(hipSetDevice(ctx->device));
-    VSP_TRY(pairing_events(ctx));
     hipStream_t st = ctx->stream;
     const size_t L = vk->n_abc - 1, piece = pairing_piece(ctx, 3);
     for (size_t at = 0; at < n; at += piece) {
         const size_t c = n - at < piece ? n - at : piece;
         VSP_TRY(pairing_workspace(ctx, 3, c));
-        VSP_TRY(ensure(ctx, ctx->pair_raw, c * (48 + 4 * L) * sizeof(uint64_t)));
-        uint64_t *dA = (uint64_t *)ctx->pair_raw.p, *dB = dA + c * 12, *dC = dB + c * 24, *dS = dC + c * 12;
-        VSP_HIP(hipMemcpyAsync(dA, A + at * 12, c * 12 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        VSP_HIP(hipMemcpyAsync(dB, B + at * 24, c * 24 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        VSP_HIP(hipMemcpyAsync(dC, C + at * 12, c * 12 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        if (L) VSP_HIP(hipMemcpyAsync(dS, inputs + at * L * 4, c * L * 4 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_verify_prepare, dim3((unsigned)((c + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, dA, dB, dC, (const uint32_t *)dS, c,
+        VSP_TRY(ensure(ctx, ctx->pair_raw, proof_words(c, L) * sizeof(uint64_t)));
+        ProofArgs d;
+        VSP_TRY(upload_proofs(ctx, (uint64_t *)ctx->pair_raw.p, A, B, C, inputs, at, c, L, d));
+        hipLaunchKernelGGL(k_verify_prepare, dim3((unsigned)((c + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, d.A, d.B, d.C, d.scalars, c,
                            vk->n_abc, (const G1Affine *)vk->d_tab, (const G2Affine *)vk->d_neg, (G1Affine *)ctx->pair_g1.p, (G2Affine *)ctx->pair_g2.p,
                            (uint8_t *)ctx->pair_status.p);
         VSP_LAUNCH_CHECK();
@@ -445,7 +435,6 @@ int saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64
                        uint8_t *verdict_out, uint8_t *reason_out) {
     if (ver->device != ctx->device) return set_error(ctx, VSP_ERR_ARG, "saver_verify_batch: the verifier belongs to another device");
     VSP_HIP(hipSetDevice(ctx->device));
-    for (hipEvent_t &e : ctx->sv_ev) if (!e) VSP_HIP(hipEventCreate(&e));
     hipStream_t st = ctx->stream;
     const size_t n = ver->n, L = ver->vk->n_abc - 1 - n;
     // ballots of one piece: "pairing_chunk" as for the pairings, and at most 2^19 G1 arguments (a ballot has n + 5; never split)
@@ -458,36 +447,36 @@ int saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64
     for (size_t at = 0; at < count; at += piece) {
         const size_t c = count - at < piece ? count - at : piece;
         const size_t ct_words = c * (n + 2) * 12;
-        VSP_TRY(ensure(ctx, ctx->pair_raw, (ct_words + c * (48 + 4 * L)) * sizeof(uint64_t)));
+        VSP_TRY(ensure(ctx, ctx->pair_raw, (ct_words + proof_words(c, L)) * sizeof(uint64_t)));
         VSP_TRY(ensure(ctx, ctx->pair_g1, (n + 5) * c * sizeof(G1Affine)));                              // n + 4 prepared-side arguments, then A
         VSP_TRY(ensure(ctx, ctx->pair_g2, c * sizeof(G2Affine)));
         VSP_TRY(ensure(ctx, ctx->pair_status, 3 * c));                                                   // malformed | equation 1 | equation 2
         VSP_TRY(ensure(ctx, ctx->pair_ml, (ng + 1) * c * sizeof(Fp12)));
         VSP_TRY(ensure(ctx, ctx->pair_prod, 2 * c * sizeof(Fp12)));
-        uint64_t *d_ct = (uint64_t *)ctx->pair_raw.p, *dA = d_ct + ct_words, *dB = dA + c * 12, *dC = dB + c * 24, *dS = dC + c * 12;
+        uint64_t *d_ct = (uint64_t *)ctx->pair_raw.p;
         G1Affine *pts = (G1Affine *)ctx->pair_g1.p, *a_pts = pts + (n + 4) * c;
         uint8_t *status = (uint8_t *)ctx->pair_status.p;
         VSP_HIP(hipMemcpyAsync(d_ct, ct + at * (n + 2) * 12, ct_words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        VSP_HIP(hipMemcpyAsync(dA, A + at * 12, c * 12 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        VSP_HIP(hipMemcpyAsync(dB, B + at * 24, c * 24 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        VSP_HIP(hipMemcpyAsync(dC, C + at * 12, c * 12 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        if (L) VSP_HIP(hipMemcpyAsync(dS, rest + at * L * 4, c * L * 4 * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        ProofArgs d;
+        VSP_TRY(upload_proofs(ctx, d_ct + ct_words, A, B, C, rest, at, c, L, d));
         const unsigned blocks = (unsigned)((c + PAIRING_THREADS - 1) / PAIRING_THREADS);
-        VSP_HIP(hipEventRecord(ctx->sv_ev[0], st));
-        hipLaunchKernelGGL(k_ballot_prepare, dim3(blocks), dim3(PAIRING_THREADS), 0, st, d_ct, (const uint32_t *)dS, dA, dB, dC, c, n, ver->vk->n_abc,
+        VSP_TRY(ctx->saver_timer.mark(ctx, 0, st));
+        hipLaunchKernelGGL(k_ballot_prepare, dim3(blocks), dim3(PAIRING_THREADS), 0, st, d_ct, d.scalars, d.A, d.B, d.C, c, n, ver->vk->n_abc,
                            (const G1Affine *)ver->vk->d_tab, pts, a_pts, (G2Affine *)ctx->pair_g2.p, status);
         VSP_LAUNCH_CHECK();
-        VSP_HIP(hipEventRecord(ctx->sv_ev[1], st));
+        VSP_TRY(ctx->saver_timer.mark(ctx, 1, st));
         hipLaunchKernelGGL(k_miller_ballot, dim3(blocks, (unsigned)(ng + 1)), dim3(PAIRING_THREADS), 0, st, (const G1Affine *)pts, (const G1Affine *)a_pts,
                            (const G2Affine *)ctx->pair_g2.p, (const LineCoeffs<Fp> *)ver->d_lines, c, n, G, ng, (Fp12 *)ctx->pair_ml.p);
         VSP_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_ballot_product, dim3(blocks), dim3(PAIRING_THREADS), 0, st, (const Fp12 *)ctx->pair_ml.p, c, ng, (Fp12 *)ctx->pair_prod.p);
         VSP_LAUNCH_CHECK();
-        VSP_HIP(hipEventRecord(ctx->sv_ev[2], st));
-        hipLaunchKernelGGL(k_ballot_final_exp, dim3((unsigned)((2 * c + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, (const Fp12 *)ctx->pair_prod.p, c,
-                           (const Fp12 *)ver->vk->d_expect, status + c);
+        VSP_TRY(ctx->saver_timer.mark(ctx, 2, st));
+        // both final exponentiations of a piece in one launch: flag[i] for i < c says "equation 1 of ballot i holds" (the value is one),
+        // for i >= c "equation 2 of ballot i - c holds" (the value is the key's e(alpha, beta))
+        hipLaunchKernelGGL(k_final_exp, dim3((unsigned)((2 * c + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, (const Fp12 *)ctx->pair_prod.p,
+                           (const uint8_t *)nullptr, 2 * c, c, (const Fp12 *)ver->vk->d_expect, (Fp12 *)nullptr, status + c);
         VSP_LAUNCH_CHECK();
-        VSP_HIP(hipEventRecord(ctx->sv_ev[3], st));
+        VSP_TRY(ctx->saver_timer.mark(ctx, 3, st));
         flags.resize(3 * c);
         VSP_HIP(hipMemcpyAsync(flags.data(), status, 3 * c, hipMemcpyDeviceToHost, st));
         VSP_HIP(hipStreamSynchronize(st));
@@ -496,9 +485,8 @@ int saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64
             verdict_out[at + k] = reason == 0;
             if (reason_out) reason_out[at + k] = reason;
         }
-        float ms = 0;
         static const char *const names[3] = {"saver_verify_prepare_ms", "saver_verify_miller_ms", "saver_verify_finalexp_ms"};
-        for (int i = 0; i < 3; i++) if (hipEventElapsedTime(&ms, ctx->sv_ev[i], ctx->sv_ev[i + 1]) == hipSuccess) ctx->stats[names[i]] += ms;
+        for (int i = 0; i < 3; i++) ctx->saver_timer.add(ctx, i, names[i]);
     }
     return VSP_OK;
 }

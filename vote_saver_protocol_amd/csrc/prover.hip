@@ -736,18 +736,19 @@ int vsp_r1cs_check_batch(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64_t *witne
         const size_t K = count - first < vsp_ctx::VERDICT_MEMBERS ? count - first : vsp_ctx::VERDICT_MEMBERS;
         const WitnessSrc w{witnesses + first * nv * 4, nullptr, nullptr, nullptr, 0};
         rc = [&]() -> int {
-            for (hipEvent_t &e : ctx->check_ev) if (!e) VSP_HIP(hipEventCreate(&e));      // the stage timers, created on first use
-            VSP_HIP(hipEventRecord(ctx->check_ev[0], ctx->stream));
+            hipEvent_t t0, t1;                                                            // around the verdict kernels
+            VSP_TRY(ctx->check_timer.event(ctx, 1, &t0));
+            VSP_TRY(ctx->check_timer.event(ctx, 2, &t1));
+            VSP_TRY(ctx->check_timer.mark(ctx, 0, ctx->stream));
             VSP_TRY(prove_front_half(ctx, cs, w, K, true));
-            VSP_TRY(verdict_queue(ctx, cs, K, true, ctx->check_ev[1], ctx->check_ev[2]));
+            VSP_TRY(verdict_queue(ctx, cs, K, true, t0, t1));
             VSP_HIP(hipStreamSynchronize(ctx->stream));
             return VSP_OK;
         }();
         if (K * (nv + 1) * sizeof(Fr) > z_bytes) z_bytes = K * (nv + 1) * sizeof(Fr);
         if (rc != VSP_OK) break;
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ctx->check_ev[0], ctx->check_ev[1]) == hipSuccess) ctx->stats["r1cs_check_front_ms"] += ms;
-        if (hipEventElapsedTime(&ms, ctx->check_ev[1], ctx->check_ev[2]) == hipSuccess) ctx->stats["r1cs_check_ms"] += ms;
+        ctx->check_timer.add(ctx, 0, "r1cs_check_front_ms");
+        ctx->check_timer.add(ctx, 1, "r1cs_check_ms");
         for (size_t k = 0; k < K; k++) {
             const Verdict v = verdict_of(ctx, k);
             status_out[first + k] = (uint8_t)((v.not_canonical ? 1 : 0) | (v.bad_rows ? 2 : 0));
