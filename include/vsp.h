@@ -392,8 +392,9 @@ void vsp_keypair_free(vsp_ctx *ctx, vsp_keypair *kp);
  *   ciphertext             c_0 = r delta_g1 | c_i = r delta_s_g1[i] + m_i G_i | psi = r delta_sum_s_g1 + sum m_i t_g1[i]     ((n + 2) x 12)
  * The random values upstream draws from algebraic_random_device (common.hpp:923, 1131, 1139) are explicit inputs here.
  * gamma_abc_g1 points at the first n + 1 entries of the verification key's accumulation vector (constant term, then the n
- * message inputs).  verify_encryption is vsp_saver_verify_batch below ("SAVER ballot verdicts"); decryption and its verification
- * are pairing work on the one aggregated ciphertext, outside this path.
+ * message inputs).  verify_encryption is vsp_saver_verify_batch below ("SAVER ballot verdicts"); decryption and its verification,
+ * pairing work and a discrete logarithm on the one aggregated ciphertext, are vsp_saver_decrypt_batch and
+ * vsp_saver_verify_decryption_batch ("SAVER decryption").
  * vsp_saver_keygen, vsp_saver_pk_load and vsp_saver_rerandomize are host-only and accept ctx = NULL. */
 typedef struct vsp_saver_pk vsp_saver_pk;
 size_t vsp_saver_pk_words(size_t msg_size);     /* uint64 words of the flat public key */
@@ -589,6 +590,74 @@ int vsp_saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const ui
                            const uint64_t *inputs_rest /* n x (n_abc - 1 - msg_size) x 4; may be NULL when that is 0 */,
                            const uint64_t *A /* n x 12 */, const uint64_t *B /* n x 24 */, const uint64_t *C /* n x 12 */, size_t n,
                            uint8_t *verdict_out /* n: 1 accepted, 0 rejected */, uint8_t *reason_out /* n, may be NULL */);
+
+/* ---- SAVER decryption on the GPU: decrypt / verify_decryption<elgamal_verifiable> (common.hpp:1220-1223, 1282-1283) -----------------
+ * The last step of the election: opening the aggregated ciphertext that vsp_tally_result returns, and checking a published result.
+ * With n = msg_size, G_i = gamma_abc_g1[i], H the generator of G2, V_i = rho_sv_g2[i-1], W_i = rho_rhov_g2[i-1] (the verification key of
+ * vsp_saver_keygen) and a ciphertext c_0 | c_1 .. c_n | psi:
+ *     nu      = rho c_0                                                   (the decryption proof)
+ *     value_i = fexp(ml(c_i, W_i) ml(-nu, V_i)),   base_i = e(G_i, W_i)   i = 1..n
+ *     m_i     = the m in [0, max_value] with base_i^m = value_i
+ *     verify_decryption:   equation 0   e(nu, H) e(c_0, -rho_g2) = 1        equation i   value_i = base_i^(m_i)
+ * Equation i is e(c_i, W_i) e(-nu, V_i) e(-m_i G_i, W_i) = 1 of oracle/saver.py verify_decryption by bilinearity.
+ * SUBGROUP.  As for the pairings above, key and ciphertext points are ASSUMED to lie in the order-r subgroups (decode with
+ * check_subgroup: vsp_tally_add_blobs checks every ballot); that is also what makes equation i the oracle's.  psi takes no part.
+ * A decryptor handle is made of PUBLIC data only -- the secret rho is an argument of vsp_saver_decrypt_batch alone, so a voter who
+ * only verifies builds the same object.  Creation validates the key points on the host (canonical, on the curve), prepares the
+ * Miller-loop lines of the 2 n + 2 fixed G2 arguments V_i, W_i, H, -rho_g2 (19 584 bytes each, csrc/pairing.h), computes every base_i
+ * on the GPU (vsp_saver_decryptor_base returns its 576 bytes: those of vsp_multi_pairing_batch for (G_i, W_i)) and builds the baby-step
+ * tables of the discrete logarithm (csrc/gt_dlog.h): per slot B = 2^b entries (fingerprint(base_i^j), j), j < B, sorted by fingerprint
+ * on the host once, 12 bytes per entry on the device -- 20 MB at msg_size 25 and b = 16.  The fingerprint of a GT value is the low
+ * "saver_decrypt_fp_bits" bits (option, 1..64, default 64, read at creation; small values are a test hook for the collision path)
+ * of the low 64 bits of its first coefficient in Montgomery form.  b is option "saver_decrypt_baby_bits" (1..20; 0, the default:
+ * ceil(log2(max_value + 1) / 2), kept within 1..20), read at creation; the search then takes ceil((max_value + 1) / B) giant steps,
+ * at most 2^24.  NULL and VSP_ERR_ARG in the last error for a null pointer, msg_size outside 1..1022, an option outside its range, more
+ * than 2^24 giant steps, a point that is not canonical or not on its curve, and a DEGENERATE key: a G_i, V_i or W_i at infinity or a
+ * base_i equal to one.
+ * vsp_saver_decrypt_batch opens `count` ciphertexts.  msgs_out[k n + i] is slot i + 1 of ciphertext k, status_out[k n + i]:
+ *     0  found
+ *     1  no m in [0, max_value] (msgs_out is UINT64_MAX); an m that the last giant step reaches beyond max_value is not a result
+ *     2  malformed ciphertext: a coordinate >= p or a point off the curve among c_0 .. c_n.  Every slot of that ciphertext gets 2
+ *        (msgs_out UINT64_MAX, nu_out all zero); the others of the batch are unaffected
+ * nu_out (count x 12, may be NULL) receives rho c_0 as canonical affine limbs, infinity all zero.  Members at infinity are legal and
+ * answer by the equations (an empty tally decrypts to zeros).  The search walks x = value g^k, g = base^(-B), one lane per run of 64
+ * giant steps, looks every x up by its fingerprint and CONFIRMS every candidate m = k B + j <= max_value by computing base^m in
+ * full: no false positive whatever the fingerprint width, no false negative.  The giant range is launched in pieces until every slot
+ * has its result, so a small tally in a large range stops early.  VSP_OK whatever the statuses are.
+ * vsp_saver_verify_decryption_batch judges `count` stated results (msgs: canonical scalars, the full width of Fr; nu).  verdict_out[k]
+ * is 1 exactly when oracle/saver.py verify_decryption accepts.  reason_out[k] (may be NULL) is 0 for an accepted result; exactly 1 for a
+ * malformed one (a coordinate >= p or a point off the curve among c_0 .. c_n and nu, an m_i >= r: no pairing verdict, the rest of the
+ * batch unaffected); otherwise bit 1 (value 2) is set when equation 0 fails and bit 2 (value 4) when some slot equation fails.
+ * first_bad_slot_out[k] (may be NULL) is the lowest failing slot, 0-based, or UINT32_MAX when none fails (also for a malformed result).
+ * No random linear combination: every verdict is exact and independent of the rest of the batch.  It needs no baby table, only the
+ * lines and the bases.
+ * Both: VSP_ERR_ARG for a null pointer, also with count = 0 (nu_out, reason_out, first_bad_slot_out may be NULL), for a decryptor made
+ * on another device and for rho >= r; count = 0 with valid pointers is VSP_OK; VSP_ERR_HIP as elsewhere.
+ * Any count: the work runs in pieces of at most "pairing_chunk" ciphertexts (default and maximum 2^14) and at most 65 535 (ciphertext,
+ * slot) items (msg_size + 1 per ciphertext, never split).  Workspace bound per piece: 96 canonical + 96 Montgomery bytes per ciphertext
+ * member, and 576 Miller + 576 GT + 8 result + 2 status bytes per item -- below 100 MiB of the context's grow-only workspaces whatever
+ * count is.  Stage times (HIP events, summed since vsp_stats_reset): vsp_get_stat "saver_decrypt_prepare_ms", "saver_decrypt_values_ms"
+ * (Miller loops and final exponentiations), "saver_decrypt_dlog_ms" (the giant search, its waits between launches included),
+ * "saver_decrypt_power_ms" (verification: the powers), and of creation "saver_decrypt_table_ms" (the baby-step kernel) and
+ * "saver_decrypt_sort_ms" (the host sort, wall time); "saver_decrypt_dlog_launches" counts the launches of the giant search.
+ * Three names are CONSTANTS of the search (csrc/gt_dlog.h), not statistics -- vsp_stats_reset does not touch them:
+ * "saver_decrypt_run_steps" (giant steps of one lane, 64), "saver_decrypt_block_lanes" (64) and "saver_decrypt_launch_lanes" (2^16:
+ * a launch gives every item max(64, floor(2^16 / items / 64) 64) lanes, at most what its range takes). */
+typedef struct vsp_saver_decryptor vsp_saver_decryptor;
+vsp_saver_decryptor *vsp_saver_decryptor_create(vsp_ctx *ctx, size_t msg_size, const uint64_t *saver_vk_words /* vsp_saver_vk_words(msg_size) */,
+                                                const uint64_t *gamma_abc_g1 /* (msg_size + 1) x 12 */, uint64_t max_value);
+void vsp_saver_decryptor_free(vsp_ctx *ctx, vsp_saver_decryptor *dec);
+size_t vsp_saver_decryptor_msg_size(const vsp_saver_decryptor *dec);
+uint64_t vsp_saver_decryptor_max_value(const vsp_saver_decryptor *dec);
+unsigned vsp_saver_decryptor_baby_bits(const vsp_saver_decryptor *dec);
+int vsp_saver_decryptor_base(const vsp_saver_decryptor *dec, size_t slot /* 0 .. msg_size - 1 */, uint8_t gt_out[576]);
+int vsp_saver_decrypt_batch(vsp_ctx *ctx, const vsp_saver_decryptor *dec, const uint64_t rho[4], const uint64_t *ct /* host count x (msg_size + 2) x 12 */,
+                            size_t count, uint64_t *msgs_out /* count x msg_size */, uint64_t *nu_out /* count x 12, may be NULL */,
+                            uint8_t *status_out /* count x msg_size */);
+int vsp_saver_verify_decryption_batch(vsp_ctx *ctx, const vsp_saver_decryptor *dec, const uint64_t *ct /* count x (msg_size + 2) x 12 */,
+                                      const uint64_t *msgs /* count x msg_size x 4, canonical Fr */, const uint64_t *nu /* count x 12 */, size_t count,
+                                      uint8_t *verdict_out /* count */, uint8_t *reason_out /* count, may be NULL */,
+                                      uint32_t *first_bad_slot_out /* count, may be NULL */);
 
 /* ---- wire formats of the reference's marshaling_policy (common.hpp:168-203 option::big_endian) --------------------
  * PROVISIONAL where marked: the marshalling sources are absent submodules, and only the proof bytes, the scalar vectors and the head of

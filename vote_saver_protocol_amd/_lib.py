@@ -139,6 +139,14 @@ PROTOTYPES = {
     "vsp_saver_verifier_free": (None, [_P, _P]),
     "vsp_saver_verifier_msg_size": (_SZ, [_P]),
     "vsp_saver_verify_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
+    "vsp_saver_decryptor_create": (_P, [_P, _SZ, _P, _P, C.c_uint64]),
+    "vsp_saver_decryptor_free": (None, [_P, _P]),
+    "vsp_saver_decryptor_msg_size": (_SZ, [_P]),
+    "vsp_saver_decryptor_max_value": (C.c_uint64, [_P]),
+    "vsp_saver_decryptor_baby_bits": (_U, [_P]),
+    "vsp_saver_decryptor_base": (_I, [_P, _SZ, _P]),
+    "vsp_saver_decrypt_batch": (_I, [_P, _P, _P, _P, _SZ, _P, _P, _P]),
+    "vsp_saver_verify_decryption_batch": (_I, [_P, _P, _P, _P, _P, _SZ, _P, _P, _P]),
 }
 
 _lib = None

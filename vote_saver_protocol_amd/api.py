@@ -69,6 +69,7 @@ class Context:
         if not self.h:
             raise VspError(f"vsp_create({device}) failed: no such HIP device (this path has no CPU fallback)")
         self.device = device
+        self.options = {}                   # what set_option has set (the library has no getter): lets a caller put a value back
 
     def close(self):
         if self.h:
@@ -110,6 +111,7 @@ class Context:
 
     def set_option(self, name, value):
         self.check(self.lib.vsp_set_option(self.h, name.encode(), int(value)))
+        self.options[name] = int(value)
 
     # ---- raw device memory
     def dmalloc(self, nbytes):
@@ -923,6 +925,92 @@ def saver_verify_batch(ctx, ver, ct, inputs_rest, A, B, Cc):
     verdict = np.zeros(n, np.uint8); reason = np.zeros(n, np.uint8)
     ctx.check(ctx.lib.vsp_saver_verify_batch(ctx.h, ver.h, _ptr(ct), _ptr(rest), _ptr(A), _ptr(B), _ptr(Cc), n, _ptr(verdict), _ptr(reason)))
     return verdict, reason
+
+
+class SaverDecryptor:
+    """The opening side of a SAVER election resident on the GPU (vsp_saver_decryptor), made of public data only: the prepared
+    Miller-loop lines of rho_sv_g2, rho_rhov_g2, H and -rho_g2, the bases e(G_i, rho_rhov_g2[i]) and their baby-step tables for
+    messages in [0, max_value].  vk_words is the flat verification key of saver_generate_keypair, gamma_abc_g1 the first
+    msg_size + 1 points of the accumulation vector.  baby_bits / fp_bits set the options "saver_decrypt_baby_bits" /
+    "saver_decrypt_fp_bits" for this creation alone (None: the context's values); afterwards the options are what they were.  A context
+    manager: the handle is freed on exit."""
+
+    def __init__(self, ctx, vk_words, gamma_abc_g1, msg_size, max_value, baby_bits=None, fp_bits=None):
+        self.ctx = ctx
+        self.msg_size = int(msg_size)
+        self.h = None
+        words = _u64(vk_words).reshape(-1)
+        gabc = _u64(gamma_abc_g1, 12)
+        if self.msg_size < 1 or words.shape[0] != ctx.lib.vsp_saver_vk_words(self.msg_size) or gabc.shape[0] < self.msg_size + 1:
+            raise ValueError("SaverDecryptor: vk_words / gamma_abc_g1 are not a verification key of this msg_size")
+        if not 0 <= int(max_value) < 1 << 64:
+            raise ValueError("SaverDecryptor: max_value outside 0 .. 2^64 - 1")
+        # the two options are read at creation only: set for this creation, then put back to what they were (or their defaults)
+        forced = {k: x for k, x in (("saver_decrypt_baby_bits", baby_bits), ("saver_decrypt_fp_bits", fp_bits)) if x is not None}
+        before = {k: ctx.options.get(k, {"saver_decrypt_baby_bits": 0, "saver_decrypt_fp_bits": 64}[k]) for k in forced}
+        try:
+            for k, x in forced.items():
+                ctx.set_option(k, x)
+            self.h = ctx.lib.vsp_saver_decryptor_create(ctx.h, self.msg_size, _ptr(words), _ptr(gabc), int(max_value))
+            err = ctx.last_error()
+        finally:
+            for k, x in before.items():
+                ctx.set_option(k, x)
+        if not self.h:
+            raise VspError("vsp_saver_decryptor_create failed: " + err)
+        self.max_value = ctx.lib.vsp_saver_decryptor_max_value(self.h)
+        self.baby_bits = ctx.lib.vsp_saver_decryptor_baby_bits(self.h)
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.vsp_saver_decryptor_free(self.ctx.h, self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def base(self, slot):
+        """e(G_{slot+1}, rho_rhov_g2[slot]) as 576 bytes"""
+        gt = np.zeros(576, np.uint8)
+        self.ctx.check(self.ctx.lib.vsp_saver_decryptor_base(self.h, int(slot), _ptr(gt)))
+        return gt.tobytes()
+
+
+def saver_decrypt_batch(ctx, dec, rho, ct):
+    """decrypt of n ciphertexts (usually the one Tally.result()): rho [4] the secret key, ct [n, msg_size + 2, 12] ->
+    (msgs [n, msg_size] uint64, nu [n, 12] the decryption proofs rho c_0, status [n, msg_size] uint8: 0 found, 1 no message in
+    [0, max_value] (msgs is 2^64 - 1), 2 malformed ciphertext).  The points are assumed to be in the subgroup."""
+    rho = _u64(rho).reshape(4)
+    ct = _u64(ct).reshape(-1, 12 * (dec.msg_size + 2))
+    n = ct.shape[0]
+    msgs = np.zeros((n, dec.msg_size), np.uint64); nu = np.zeros((n, 12), np.uint64); status = np.zeros((n, dec.msg_size), np.uint8)
+    if n:
+        ctx.check(ctx.lib.vsp_saver_decrypt_batch(ctx.h, dec.h, _ptr(rho), _ptr(ct), n, _ptr(msgs), _ptr(nu), _ptr(status)))
+    return msgs, nu, status
+
+
+def saver_verify_decryption_batch(ctx, dec, ct, msgs, nu):
+    """verify_decryption of n stated results: ct [n, msg_size + 2, 12], msgs [n, msg_size] python ints or uint64, or
+    [n, msg_size, 4] canonical scalars, nu [n, 12] -> (verdict [n] uint8, 1 = accepted; reason [n] uint8: 0 accepted, 1 malformed,
+    else 2 = the equation of nu fails | 4 = a slot equation fails; first_bad_slot [n] uint32, 2^32 - 1 when no slot fails)."""
+    ct = _u64(ct).reshape(-1, 12 * (dec.msg_size + 2))
+    n = ct.shape[0]
+    m = np.asarray(msgs, dtype=object)      # Python objects first: no numeric coercion may touch an integer of up to 256 bits
+    if m.size == n * dec.msg_size:
+        m = np.array([[(int(x) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)] for x in m.reshape(-1)], dtype=np.uint64)
+    else:
+        m = np.array([int(x) for x in m.reshape(-1)], dtype=np.uint64)
+    m = m.reshape(n, -1)
+    nu = _u64(nu).reshape(-1, 12)
+    if m.shape[1] != 4 * dec.msg_size or nu.shape[0] != n:
+        raise ValueError("saver_verify_decryption_batch: n results (ct[msg_size + 2, 12], msgs[msg_size], nu[12]) expected")
+    verdict = np.zeros(n, np.uint8); reason = np.zeros(n, np.uint8); first = np.full(n, 0xFFFFFFFF, np.uint32)
+    if n:
+        ctx.check(ctx.lib.vsp_saver_verify_decryption_batch(ctx.h, dec.h, _ptr(ct), _ptr(m), _ptr(nu), n, _ptr(verdict), _ptr(reason), _ptr(first)))
+    return verdict, reason, first
 
 
 # ---- wire formats (f.2): the big-endian blobs of the reference's marshaling_policy (common.hpp:168-203, 462-485, 749-799) ---------

@@ -3,6 +3,7 @@
 #include "common.h"
 #include "fp28.h"
 #include "fr29.h"
+#include "gt_dlog.h"
 #include "lane_view.h"
 
 namespace vsp {
@@ -205,13 +206,13 @@ void vsp_destroy(vsp_ctx *ctx) {
                       &ctx->pr_z, &ctx->pr_abc, &ctx->pr_h, &ctx->pr_pack, &ctx->pr_verdict,
                       &ctx->tally_raw, &ctx->tally_bstatus, &ctx->tally_partials,
                       &ctx->decode[0].pts, &ctx->decode[0].pstatus, &ctx->decode[1].pts, &ctx->decode[1].pstatus,
-                      &ctx->pair_raw, &ctx->pair_g1, &ctx->pair_g2, &ctx->pair_status, &ctx->pair_ml, &ctx->pair_prod, &ctx->pair_gt};
+                      &ctx->pair_raw, &ctx->pair_g1, &ctx->pair_g2, &ctx->pair_status, &ctx->pair_ml, &ctx->pair_prod, &ctx->pair_gt, &ctx->dec_out};
     for (DevBuf *b : bufs) free_buf(*b);
     msm_free_slots(ctx);
     if (ctx->h_fold) hipHostFree(ctx->h_fold);
     if (ctx->h_verdict) hipHostFree(ctx->h_verdict);
     hipEventDestroy(ctx->ev0); hipEventDestroy(ctx->ev1); hipEventDestroy(ctx->ev_aux);
-    for (StageTimer *t : {&ctx->decode[0].timer, &ctx->decode[1].timer, &ctx->check_timer, &ctx->pair_timer, &ctx->saver_timer}) t->destroy();
+    for (StageTimer *t : {&ctx->decode[0].timer, &ctx->decode[1].timer, &ctx->check_timer, &ctx->pair_timer, &ctx->saver_timer, &ctx->dec_timer}) t->destroy();
     for (hipStream_t ps : ctx->prove_streams) if (ps) hipStreamDestroy(ps);
     hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -232,6 +233,9 @@ int vsp_synchronize(vsp_ctx *ctx) {
 }
 double vsp_get_stat(vsp_ctx *ctx, const char *name) {
     if (!ctx || !name) return 0.0;
+    if (!strcmp(name, "saver_decrypt_run_steps")) return (double)DLOG_RUN_STEPS;          // constants of the giant search (csrc/gt_dlog.h)
+    if (!strcmp(name, "saver_decrypt_block_lanes")) return (double)DLOG_BLOCK_LANES;
+    if (!strcmp(name, "saver_decrypt_launch_lanes")) return (double)DLOG_LAUNCH_LANES;
     if (!strcmp(name, "runtime_hw_queues_env")) { const char *q = getenv("GPU_MAX_HW_QUEUES"); return q ? atof(q) : 0.0; }      // include/vsp.h "Runtime environment"
     auto it = ctx->stats.find(name);
     return it == ctx->stats.end() ? 0.0 : it->second;
@@ -294,6 +298,36 @@ int vsp_saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const ui
     if (!ctx) return VSP_ERR_ARG;
     if (!ver || !ct || !A || !B || !C || !verdict_out || (!inputs_rest && saver_verifier_n_rest(ver) > 0)) return set_error(ctx, VSP_ERR_ARG, "saver_verify_batch: null argument");
     return saver_verify_batch(ctx, ver, ct, inputs_rest, A, B, C, n, verdict_out, reason_out);
+}
+
+// ---- SAVER decryption and its verification (decrypt.hip)
+vsp_saver_decryptor *vsp_saver_decryptor_create(vsp_ctx *ctx, size_t msg_size, const uint64_t *saver_vk_words, const uint64_t *gamma_abc_g1, uint64_t max_value) {
+    if (!ctx) return nullptr;
+    if (!saver_vk_words || !gamma_abc_g1) { set_error(ctx, VSP_ERR_ARG, "saver_decryptor_create: null argument"); return nullptr; }
+    if (msg_size == 0 || msg_size > 1022) { set_error(ctx, VSP_ERR_ARG, "saver_decryptor_create: msg_size outside 1..1022"); return nullptr; }
+    return saver_decryptor_create(ctx, msg_size, saver_vk_words, gamma_abc_g1, max_value);
+}
+void vsp_saver_decryptor_free(vsp_ctx *ctx, vsp_saver_decryptor *dec) { saver_decryptor_free(ctx, dec); }
+size_t vsp_saver_decryptor_msg_size(const vsp_saver_decryptor *dec) { return dec ? saver_decryptor_msg_size(dec) : 0; }
+uint64_t vsp_saver_decryptor_max_value(const vsp_saver_decryptor *dec) { return dec ? saver_decryptor_max_value(dec) : 0; }
+unsigned vsp_saver_decryptor_baby_bits(const vsp_saver_decryptor *dec) { return dec ? saver_decryptor_baby_bits(dec) : 0; }
+int vsp_saver_decryptor_base(const vsp_saver_decryptor *dec, size_t slot, uint8_t gt_out[576]) {
+    const uint8_t *b = dec && gt_out ? saver_decryptor_base(dec, slot) : nullptr;
+    if (!b) return VSP_ERR_ARG;
+    memcpy(gt_out, b, 576);
+    return VSP_OK;
+}
+int vsp_saver_decrypt_batch(vsp_ctx *ctx, const vsp_saver_decryptor *dec, const uint64_t rho[4], const uint64_t *ct, size_t count, uint64_t *msgs_out, uint64_t *nu_out,
+                            uint8_t *status_out) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!dec || !rho || !ct || !msgs_out || !status_out) return set_error(ctx, VSP_ERR_ARG, "saver_decrypt_batch: null argument");
+    return saver_decrypt_batch(ctx, dec, rho, ct, count, msgs_out, nu_out, status_out);
+}
+int vsp_saver_verify_decryption_batch(vsp_ctx *ctx, const vsp_saver_decryptor *dec, const uint64_t *ct, const uint64_t *msgs, const uint64_t *nu, size_t count,
+                                      uint8_t *verdict_out, uint8_t *reason_out, uint32_t *first_bad_slot_out) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!dec || !ct || !msgs || !nu || !verdict_out) return set_error(ctx, VSP_ERR_ARG, "saver_verify_decryption_batch: null argument");
+    return saver_verify_decryption_batch(ctx, dec, ct, msgs, nu, count, verdict_out, reason_out, first_bad_slot_out);
 }
 
 void *vsp_dmalloc(vsp_ctx *ctx, size_t bytes) {

@@ -235,6 +235,10 @@ struct vsp_ctx {
     // vsp_saver_verify_batch (prepare, Miller, final exponentiation)
     vsp::DevBuf pair_raw, pair_g1, pair_g2, pair_status, pair_ml, pair_prod, pair_gt;
     vsp::StageTimer pair_timer, saver_timer;
+    // SAVER decryption (decrypt.hip): a result word per (ciphertext, slot) item and the pending count of the giant search; the timer around
+    // the stages of vsp_saver_decrypt_batch / vsp_saver_verify_decryption_batch (prepare, values, search or powers) and around the table build
+    vsp::DevBuf dec_out;
+    vsp::StageTimer dec_timer;
     // prover workspaces for K witnesses (a single proof: K = 1): z [K][num_vars + 1], A z, B z, C z [K][3][m], H [K][m], the packed witness
     vsp::DevBuf pr_z, pr_abc, pr_h, pr_pack;
     // the witness check (prover.hip k_r1cs_verdict): per member of a piece of at most VERDICT_MEMBERS witnesses three 32-bit words --
@@ -462,6 +466,19 @@ size_t saver_verifier_msg_size(const vsp_saver_verifier *ver);
 size_t saver_verifier_n_rest(const vsp_saver_verifier *ver);
 int saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *inputs_rest, const uint64_t *A, const uint64_t *B,
                        const uint64_t *C, size_t n, uint8_t *verdict_out, uint8_t *reason_out);
+// the final exponentiation of n Miller values on the device (stage 3 of pairing.hip on its own): canonical GT values and is-one bytes
+int pairing_final_exp(vsp_ctx *ctx, const void *d_miller, size_t n, void *d_gt_out, uint8_t *d_is_one_out);
+// SAVER decryption and its verification (decrypt.hip): the baby-step tables of a key, resident
+vsp_saver_decryptor *saver_decryptor_create(vsp_ctx *ctx, size_t msg_size, const uint64_t *saver_vk_words, const uint64_t *gamma_abc_g1, uint64_t max_value);
+void saver_decryptor_free(vsp_ctx *ctx, vsp_saver_decryptor *dec);
+size_t saver_decryptor_msg_size(const vsp_saver_decryptor *dec);
+uint64_t saver_decryptor_max_value(const vsp_saver_decryptor *dec);
+unsigned saver_decryptor_baby_bits(const vsp_saver_decryptor *dec);
+const uint8_t *saver_decryptor_base(const vsp_saver_decryptor *dec, size_t slot);
+int saver_decrypt_batch(vsp_ctx *ctx, const vsp_saver_decryptor *dec, const uint64_t rho[4], const uint64_t *ct, size_t count, uint64_t *msgs_out, uint64_t *nu_out,
+                        uint8_t *status_out);
+int saver_verify_decryption_batch(vsp_ctx *ctx, const vsp_saver_decryptor *dec, const uint64_t *ct, const uint64_t *msgs, const uint64_t *nu, size_t count,
+                                  uint8_t *verdict_out, uint8_t *reason_out, uint32_t *first_bad_slot_out);
 int upload_power_tables(vsp_ctx *ctx, const HFr &base, size_t hi_count, DevBuf &lo, DevBuf &hi);
 HFr host_omega(unsigned log_m);
 

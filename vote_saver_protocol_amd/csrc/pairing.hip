@@ -14,6 +14,7 @@
 // An Fp12 value is 144 registers: the kernels keep their tower values in scratch and call the out-of-line products of fp12.h.
 #include "common.h"
 #include "pairing.h"
+#include "pairing_g1.h"
 
 struct vsp_vk {
     size_t n_abc = 0;
@@ -43,21 +44,8 @@ static constexpr unsigned PAIRING_THREADS = 64;                // one wave per b
 __device__ __noinline__ void pr_miller(Fp12 *f, const G1Affine *P, const G2Affine *Q) { *f = miller_loop(*P, *Q); }
 __device__ __noinline__ void pr_final_exp(Fp12 *f) { const Fp12 t = final_exp(*f); *f = t; }
 __device__ __noinline__ void pr_mul(Fp12 *f, const Fp12 *g) { const Fp12 t = mul(*f, *g); *f = t; }
-__device__ __noinline__ void pr_dbl(G1XYZZ *a) { *a = xyzz_dbl(*a); }
-__device__ __noinline__ void pr_madd(G1XYZZ *a, const G1Affine *p) { G1XYZZ t = *a; xyzz_madd(t, *p); *a = t; }
 
-// canonical words -> Montgomery affine point; 0 accepted (infinity included), 1 a coordinate >= p, 2 off the curve.  A rejected point
-// comes out as infinity
-__device__ __noinline__ uint32_t pr_load_g1(const uint64_t *src, G1Affine *out) {
-    G1Affine c = *(const G1Affine *)src;
-    uint32_t st = (canon_below_p(c.x) && canon_below_p(c.y)) ? 0u : 1u;
-    G1Affine p; p.x = to_mont(c.x); p.y = to_mont(c.y);
-    const Fp four = dbl(dbl(Fp::one()));
-    if (!st && !is_inf(c) && !eq(sqr(p.y), add(mul(sqr(p.x), p.x), four))) st = 2u;
-    if (st) { p.x = Fp::zero(); p.y = Fp::zero(); }
-    *out = p;
-    return st;
-}
+// pr_load_g1, pr_dbl, pr_madd, pr_to_affine: pairing_g1.h
 __device__ __noinline__ uint32_t pr_load_g2(const uint64_t *src, G2Affine *out) {
     G2Affine c = *(const G2Affine *)src;
     uint32_t st = (canon_below_p(c.x.c0) && canon_below_p(c.x.c1) && canon_below_p(c.y.c0) && canon_below_p(c.y.c1)) ? 0u : 1u;
@@ -92,14 +80,6 @@ __device__ __forceinline__ void pr_input_sum(G1XYZZ &acc, const uint32_t *s, siz
             pr_madd(&acc, &t);
         }
     }
-}
-// affine through one inversion: 1 / (ZZ ZZZ); infinity (ZZ = 0) comes out as x = y = 0
-__device__ __forceinline__ G1Affine pr_to_affine(const G1XYZZ &acc) {
-    const Fp t = fp_inv_chain(mul(acc.ZZ, acc.ZZZ));
-    G1Affine P;
-    P.x = mul(acc.X, mul(t, acc.ZZZ));
-    P.y = mul(acc.Y, mul(t, acc.ZZ));
-    return P;
 }
 
 __global__ __launch_bounds__(PAIRING_THREADS) void k_pair_check(const uint64_t *__restrict__ g1, const uint64_t *__restrict__ g2, size_t n, G1Affine *__restrict__ p_out,
@@ -286,6 +266,12 @@ static int pairing_stages(vsp_ctx *ctx, size_t m, size_t n, const Fp12 *d_expect
 static void pairing_add_times(vsp_ctx *ctx) {
     ctx->pair_timer.add(ctx, 0, "pairing_miller_ms");
     ctx->pair_timer.add(ctx, 1, "pairing_finalexp_ms");
+}
+int pairing_final_exp(vsp_ctx *ctx, const void *d_miller, size_t n, void *d_gt_out, uint8_t *d_is_one_out) {
+    hipLaunchKernelGGL(k_final_exp, dim3((unsigned)((n + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, ctx->stream, (const Fp12 *)d_miller,
+                       (const uint8_t *)nullptr, n, n, (const Fp12 *)nullptr, (Fp12 *)d_gt_out, d_is_one_out);
+    VSP_LAUNCH_CHECK();
+    return VSP_OK;
 }
 // the proof members of a piece: c proofs from proof `at` on, with L scalars each, laid out A | B | C | scalars at dst (device words)
 struct ProofArgs { uint64_t *A, *B, *C; uint32_t *scalars; };
