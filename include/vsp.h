@@ -591,6 +591,45 @@ int vsp_saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const ui
                            const uint64_t *A /* n x 12 */, const uint64_t *B /* n x 24 */, const uint64_t *C /* n x 12 */, size_t n,
                            uint8_t *verdict_out /* n: 1 accepted, 0 rejected */, uint8_t *reason_out /* n, may be NULL */);
 
+/* ---- SAVER ballots screened in bulk: one random linear combination per range, exact on failure -------------------------------------
+ * vsp_saver_verify_batch confirms every honest ballot on its own.  With caller-supplied coefficients z_i in [1, 2^128) the WELL-FORMED
+ * ballots of a range R are accepted together when two pairing-product equations hold (n = msg_size):
+ *     S_j = sum_{i in R} z_i c_{i,j} (j = 0..n),  S_psi = sum z_i psi_i,  ACC = sum z_i acc_i,  Csum = sum z_i C_i,  Z = sum z_i mod r
+ *     equation 1:  fexp( prod_{j=0..n} ml(S_j, t_g2[j]) * ml(S_psi, -H) ) = 1
+ *     equation 2:  fexp( prod_{i in R} ml(z_i A_i, B_i) * ml(ACC, -gamma_g2) * ml(Csum, -delta_g2) * ml(-Z alpha_g1, beta_g2) ) = 1
+ * Arguments, layouts, return codes and the SUBGROUP assumption are those of vsp_saver_verify_batch.  coeff (host, n x 2 words, the
+ * little-endian 128-bit z_i) must not be NULL, and a zero coefficient is VSP_ERR_ARG before any GPU work; VSP_ERR_ARG as well while a
+ * proof is in flight on the context (the call uses the multi-exponentiation work slots: finish the proof first).
+ * VERDICTS.  A verdict of 0 and its reason always come from the exact path: they equal what vsp_saver_verify_batch gives for that
+ * ballot, reason 1 for a malformed ballot included.  A verdict of 1 means that the exact path accepted the ballot, or that the ballot is
+ * well formed and lies in a range whose two equations held.  No valid ballot is ever rejected: if every ballot of a range satisfies an
+ * equation, the combined equation holds with certainty.  Malformed ballots are taken out of every sum and product (their coefficient
+ * counts as absent, their Miller value as one) and do not make a range fail.
+ * SOUNDNESS.  If a ballot of the range fails an equation, the points are in their subgroups, and the z_i are uniform in [1, 2^128) and
+ * chosen AFTER the ballots are fixed, the combined equation holds with probability at most 1 / (2^128 - 1).  The coefficients must be
+ * fresh for every call, uniform, and drawn after the ballots are fixed: a sender who knows them can make invalid ballots cancel (two
+ * ballots whose defects are z_2 and -z_1 pass under (z_1, z_2)).  For points OUTSIDE the order-r subgroups the screened and the exact
+ * verdict may differ (a small-order component can vanish under a coefficient): decode with check_subgroup.
+ * PROCEDURE.  Pieces of at most "saver_screen_chunk" ballots (option, default and maximum 2^16).  A piece is prepared by the exact
+ * path's own kernel, A_i is multiplied by z_i (one lane per ballot), one Miller loop per ballot gives ml(z_i A_i, B_i), a product tree
+ * multiplies them, the n + 4 sums are multi-exponentiations over one shared digit sort of the z_i (plain bases, generic additions:
+ * exact for equal, opposite and infinity points), and n + 5 Miller loops over prepared lines and two final exponentiations judge the
+ * piece.  A piece that fails is cut into "saver_screen_split" equal sub-ranges (option, default 4, at most 1024; 0 or 1: no second
+ * level) that are judged the same way in one pass, the per-ballot Miller values reused; the sub-ranges that fail go to
+ * vsp_saver_verify_batch's code as contiguous runs.  There is no deeper level.
+ * Workspace bound per piece, beside that of the exact path for the runs handed to it: 96 canonical + 96 Montgomery bytes per G1
+ * argument (msg_size + 5 per ballot), 576 + 384 + 3 + 48 bytes and 32 per rest input per ballot, 2 x 576 / 16 bytes per ballot for the
+ * tree, 672 (msg_size + 5) + 1 154 bytes per sub-range, and the work slots' sort of one 255-bit scalar per ballot -- 438 MiB at msg_size
+ * 25 with 2^16 ballots.  Statistics (vsp_get_stat, summed since vsp_stats_reset): "saver_screen_checks" ranges judged,
+ * "saver_screen_failed" ranges that failed, "saver_screen_exact_ballots" ballots handed to the exact path; stage times by HIP events
+ * "saver_screen_prepare_ms", "saver_screen_scale_ms", "saver_screen_miller_ms" (per-ballot and fixed-argument Miller loops and their
+ * products), "saver_screen_msm_ms" (the column sums, their host folds included), "saver_screen_finalexp_ms". */
+int vsp_saver_verify_batch_screened(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct /* host n x (msg_size + 2) x 12 */,
+                                    const uint64_t *inputs_rest /* n x (n_abc - 1 - msg_size) x 4; may be NULL when that is 0 */,
+                                    const uint64_t *A /* n x 12 */, const uint64_t *B /* n x 24 */, const uint64_t *C /* n x 12 */, size_t n,
+                                    const uint64_t *coeff /* host n x 2, little-endian 128-bit, not zero */,
+                                    uint8_t *verdict_out /* n: 1 accepted, 0 rejected */, uint8_t *reason_out /* n, may be NULL */);
+
 /* ---- SAVER decryption on the GPU: decrypt / verify_decryption<elgamal_verifiable> (common.hpp:1220-1223, 1282-1283) -----------------
  * The last step of the election: opening the aggregated ciphertext that vsp_tally_result returns, and checking a published result.
  * With n = msg_size, G_i = gamma_abc_g1[i], H the generator of G2, V_i = rho_sv_g2[i-1], W_i = rho_rhov_g2[i-1] (the verification key of

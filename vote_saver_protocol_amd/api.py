@@ -11,6 +11,7 @@ through libvsp_hip.so; nothing here computes field or curve arithmetic on the CP
 """
 import collections
 import ctypes as C
+import secrets
 
 import numpy as np
 
@@ -888,7 +889,8 @@ def groth16_verify_batch(ctx, vk, inputs, A, B, Cc):
 
 class SaverVerifier:
     """The verifying side of a SAVER election resident on the GPU (vsp_saver_verifier): the Groth16 verification key as VerifyingKey
-    holds it, and the prepared Miller-loop lines of the fixed G2 arguments t_g2[0..msg_size], -H, -gamma_g2, -delta_g2.  pk_words is
+    holds it, and the prepared Miller-loop lines of the fixed G2 arguments t_g2[0..msg_size], -H, -gamma_g2, -delta_g2 (and beta_g2, for
+    saver_verify_batch_screened).  pk_words is
     the flat public key of saver_generate_keypair."""
 
     def __init__(self, ctx, pk_words, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, msg_size):
@@ -924,6 +926,27 @@ def saver_verify_batch(ctx, ver, ct, inputs_rest, A, B, Cc):
         raise ValueError("saver_verify_batch: n ballots (ct[msg_size + 2, 12], A[12], B[24], C[12]) and n x (n_abc - 1 - msg_size) rest inputs expected")
     verdict = np.zeros(n, np.uint8); reason = np.zeros(n, np.uint8)
     ctx.check(ctx.lib.vsp_saver_verify_batch(ctx.h, ver.h, _ptr(ct), _ptr(rest), _ptr(A), _ptr(B), _ptr(Cc), n, _ptr(verdict), _ptr(reason)))
+    return verdict, reason
+
+
+def saver_verify_batch_screened(ctx, ver, ct, inputs_rest, A, B, Cc, coeff=None):
+    """saver_verify_batch with the well-formed ballots of a range accepted together under one random linear combination
+    (vsp_saver_verify_batch_screened): the same arguments and results; a verdict of 0 and its reason always come from the exact path.
+    coeff [n, 2]: the little-endian 128-bit coefficients, none zero; None draws them from `secrets`.  They must be fresh, uniform and
+    drawn after the ballots are fixed: then an invalid ballot of subgroup points is accepted with probability at most 1 / (2^128 - 1)."""
+    A = _u64(A, 12); B = _u64(B, 24); Cc = _u64(Cc, 12)
+    n = A.shape[0]
+    n_rest = ver.n_abc - 1 - ver.msg_size
+    ct = _u64(ct).reshape(n, -1)
+    rest = _u64(inputs_rest).reshape(n, -1) if n_rest else np.zeros((n, 4), np.uint64)
+    if coeff is None:
+        zs = [secrets.randbelow((1 << 128) - 1) + 1 for _ in range(n)]
+        coeff = np.array([[z & 0xFFFFFFFFFFFFFFFF, z >> 64] for z in zs], np.uint64).reshape(n, 2)
+    coeff = _u64(coeff).reshape(-1, 2)
+    if B.shape[0] != n or Cc.shape[0] != n or coeff.shape[0] != n or ct.shape[1] != 12 * (ver.msg_size + 2) or (n_rest and rest.shape[1] != 4 * n_rest):
+        raise ValueError("saver_verify_batch_screened: n ballots (ct[msg_size + 2, 12], A[12], B[24], C[12]), n x (n_abc - 1 - msg_size) rest inputs and n x 2 coefficient words expected")
+    verdict = np.zeros(n, np.uint8); reason = np.zeros(n, np.uint8)
+    ctx.check(ctx.lib.vsp_saver_verify_batch_screened(ctx.h, ver.h, _ptr(ct), _ptr(rest), _ptr(A), _ptr(B), _ptr(Cc), n, _ptr(coeff), _ptr(verdict), _ptr(reason)))
     return verdict, reason
 
 

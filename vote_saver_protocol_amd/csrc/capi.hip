@@ -206,13 +206,13 @@ void vsp_destroy(vsp_ctx *ctx) {
                       &ctx->pr_z, &ctx->pr_abc, &ctx->pr_h, &ctx->pr_pack, &ctx->pr_verdict,
                       &ctx->tally_raw, &ctx->tally_bstatus, &ctx->tally_partials,
                       &ctx->decode[0].pts, &ctx->decode[0].pstatus, &ctx->decode[1].pts, &ctx->decode[1].pstatus,
-                      &ctx->pair_raw, &ctx->pair_g1, &ctx->pair_g2, &ctx->pair_status, &ctx->pair_ml, &ctx->pair_prod, &ctx->pair_gt, &ctx->dec_out};
+                      &ctx->pair_raw, &ctx->pair_g1, &ctx->pair_g2, &ctx->pair_status, &ctx->pair_ml, &ctx->pair_prod, &ctx->pair_gt, &ctx->dec_out, &ctx->screen_ws};
     for (DevBuf *b : bufs) free_buf(*b);
     msm_free_slots(ctx);
     if (ctx->h_fold) hipHostFree(ctx->h_fold);
     if (ctx->h_verdict) hipHostFree(ctx->h_verdict);
     hipEventDestroy(ctx->ev0); hipEventDestroy(ctx->ev1); hipEventDestroy(ctx->ev_aux);
-    for (StageTimer *t : {&ctx->decode[0].timer, &ctx->decode[1].timer, &ctx->check_timer, &ctx->pair_timer, &ctx->saver_timer, &ctx->dec_timer}) t->destroy();
+    for (StageTimer *t : {&ctx->decode[0].timer, &ctx->decode[1].timer, &ctx->check_timer, &ctx->pair_timer, &ctx->saver_timer, &ctx->dec_timer, &ctx->screen_timer[0], &ctx->screen_timer[1]}) t->destroy();
     for (hipStream_t ps : ctx->prove_streams) if (ps) hipStreamDestroy(ps);
     hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -298,6 +298,16 @@ int vsp_saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const ui
     if (!ctx) return VSP_ERR_ARG;
     if (!ver || !ct || !A || !B || !C || !verdict_out || (!inputs_rest && saver_verifier_n_rest(ver) > 0)) return set_error(ctx, VSP_ERR_ARG, "saver_verify_batch: null argument");
     return saver_verify_batch(ctx, ver, ct, inputs_rest, A, B, C, n, verdict_out, reason_out);
+}
+// the screened check (screen.hip)
+int vsp_saver_verify_batch_screened(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *inputs_rest, const uint64_t *A, const uint64_t *B,
+                                    const uint64_t *C, size_t n, const uint64_t *coeff, uint8_t *verdict_out, uint8_t *reason_out) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!ver || !ct || !A || !B || !C || !coeff || !verdict_out || (!inputs_rest && saver_verifier_n_rest(ver) > 0))
+        return set_error(ctx, VSP_ERR_ARG, "saver_verify_batch_screened: null argument");
+    for (size_t k = 0; k < n; k++)
+        if (!(coeff[2 * k] | coeff[2 * k + 1])) return set_error(ctx, VSP_ERR_ARG, "saver_verify_batch_screened: a coefficient is zero");
+    return saver_verify_batch_screened(ctx, ver, ct, inputs_rest, A, B, C, n, coeff, verdict_out, reason_out);
 }
 
 // ---- SAVER decryption and its verification (decrypt.hip)

@@ -235,6 +235,10 @@ struct vsp_ctx {
     // vsp_saver_verify_batch (prepare, Miller, final exponentiation)
     vsp::DevBuf pair_raw, pair_g1, pair_g2, pair_status, pair_ml, pair_prod, pair_gt;
     vsp::StageTimer pair_timer, saver_timer;
+    // the screened ballot check (screen.hip): coefficients, range arguments, their Miller values and the product tree's levels in one
+    // workspace; the timers around prepare | scale | Miller and tree, and around column sums | fixed-argument Miller | final exponentiation
+    vsp::DevBuf screen_ws;
+    vsp::StageTimer screen_timer[2];
     // SAVER decryption (decrypt.hip): a result word per (ciphertext, slot) item and the pending count of the giant search; the timer around
     // the stages of vsp_saver_decrypt_batch / vsp_saver_verify_decryption_batch (prepare, values, search or powers) and around the table build
     vsp::DevBuf dec_out;
@@ -315,6 +319,24 @@ struct vsp_pk {
     mutable std::atomic<bool> tab_ready{false};
     mutable std::vector<vsp::XYZZ<vsp::HFp>> tab1;
     mutable std::vector<vsp::XYZZ<vsp::HFp2>> tab2;
+};
+
+// a Groth16 verification key resident on the device (pairing.hip)
+struct vsp_vk {
+    size_t n_abc = 0;
+    uint8_t alpha_beta[576];            // e(alpha, beta), canonical tower order
+    void *d_expect = nullptr;           // the same value, Fp12 in Montgomery form
+    void *d_neg = nullptr;              // two G2Affine, Montgomery: -gamma_g2, -delta_g2
+    void *d_tab = nullptr;              // n_abc rows of 16 G1Affine, Montgomery: d * gamma_ABC[i], d = 0..15 (d = 0: infinity)
+};
+// A SAVER verifier: the Groth16 key as above, and the prepared lines (pairing.h) of the election key's G2 members in the order of the
+// pairs of a ballot: t_g2[0..n] | -H | -gamma_g2 | -delta_g2, then beta_g2 and alpha_g1 for the screened check's e(alpha, beta)^Z (screen.hip)
+struct vsp_saver_verifier {
+    int device = 0;
+    size_t n = 0;                       // msg_size
+    vsp_vk *vk = nullptr;
+    void *d_lines = nullptr;            // (n + 5) x MILLER_LINES LineCoeffs, Montgomery
+    vsp::Affine<vsp::HFp> alpha_g1;     // host, Montgomery
 };
 
 namespace vsp {
@@ -466,6 +488,16 @@ size_t saver_verifier_msg_size(const vsp_saver_verifier *ver);
 size_t saver_verifier_n_rest(const vsp_saver_verifier *ver);
 int saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *inputs_rest, const uint64_t *A, const uint64_t *B,
                        const uint64_t *C, size_t n, uint8_t *verdict_out, uint8_t *reason_out);
+// one piece of ballots (pairing.hip): c ballots from ballot `at` on uploaded and k_ballot_prepare run between events 0 and 1 of `timer`.
+// Leaves the arguments c_0 .. c_n | psi | acc | C column by column and A in ctx->pair_g1 ((n + 5) c points), B in ctx->pair_g2, the
+// status bytes in ctx->pair_status (room for 3 c)
+int saver_piece_prepare(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *inputs_rest, const uint64_t *A, const uint64_t *B,
+                        const uint64_t *C, size_t at, size_t c, StageTimer &timer);
+// the screened check (screen.hip); coeff: count x 2 words, none zero (capi.hip checks)
+int saver_verify_batch_screened(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *inputs_rest, const uint64_t *A, const uint64_t *B,
+                                const uint64_t *C, size_t n, const uint64_t *coeff, uint8_t *verdict_out, uint8_t *reason_out);
+// stage 1 of pairing.hip on its own: the Miller values of n device pairs (Montgomery affine points; infinity gives one)
+int pairing_miller(vsp_ctx *ctx, const void *d_g1, const void *d_g2, size_t n, void *d_out);
 // the final exponentiation of n Miller values on the device (stage 3 of pairing.hip on its own): canonical GT values and is-one bytes
 int pairing_final_exp(vsp_ctx *ctx, const void *d_miller, size_t n, void *d_gt_out, uint8_t *d_is_one_out);
 // SAVER decryption and its verification (decrypt.hip): the baby-step tables of a key, resident

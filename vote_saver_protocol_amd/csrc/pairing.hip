@@ -16,23 +16,7 @@
 #include "pairing.h"
 #include "pairing_g1.h"
 
-struct vsp_vk {
-    size_t n_abc = 0;
-    uint8_t alpha_beta[576];            // e(alpha, beta), canonical tower order
-    void *d_expect = nullptr;           // the same value, Fp12 in Montgomery form
-    void *d_neg = nullptr;              // two G2Affine, Montgomery: -gamma_g2, -delta_g2
-    void *d_tab = nullptr;              // n_abc rows of 16 G1Affine, Montgomery: d * gamma_ABC[i], d = 0..15 (d = 0: infinity)
-};
-
-// A SAVER verifier: the Groth16 key as above, and the prepared lines (pairing.h) of the election key's G2 members in the order of the
-// pairs of a ballot: t_g2[0..n] | -H | -gamma_g2 | -delta_g2
-struct vsp_saver_verifier {
-    int device = 0;
-    size_t n = 0;                       // msg_size
-    vsp_vk *vk = nullptr;
-    void *d_lines = nullptr;            // (n + 4) x MILLER_LINES LineCoeffs, Montgomery
-};
-
+// vsp_vk, vsp_saver_verifier: common.h
 namespace vsp {
 
 static constexpr size_t PAIRING_CHUNK = (size_t)1 << 14;       // products of one piece (option "pairing_chunk")
@@ -267,6 +251,12 @@ static void pairing_add_times(vsp_ctx *ctx) {
     ctx->pair_timer.add(ctx, 0, "pairing_miller_ms");
     ctx->pair_timer.add(ctx, 1, "pairing_finalexp_ms");
 }
+int pairing_miller(vsp_ctx *ctx, const void *d_g1, const void *d_g2, size_t n, void *d_out) {
+    hipLaunchKernelGGL(k_miller, dim3((unsigned)((n + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, ctx->stream, (const G1Affine *)d_g1,
+                       (const G2Affine *)d_g2, n, (Fp12 *)d_out);
+    VSP_LAUNCH_CHECK();
+    return VSP_OK;
+}
 int pairing_final_exp(vsp_ctx *ctx, const void *d_miller, size_t n, void *d_gt_out, uint8_t *d_is_one_out) {
     hipLaunchKernelGGL(k_final_exp, dim3((unsigned)((n + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, ctx->stream, (const Fp12 *)d_miller,
                        (const uint8_t *)nullptr, n, n, (const Fp12 *)nullptr, (Fp12 *)d_gt_out, d_is_one_out);
@@ -399,11 +389,13 @@ vsp_saver_verifier *saver_verifier_create(vsp_ctx *ctx, size_t n, const uint64_t
     if (!vk) return nullptr;
     vsp_saver_verifier *ver = new vsp_saver_verifier();
     ver->device = ctx->device; ver->n = n; ver->vk = vk;
-    std::vector<Affine<HFp2>> q(n + 4);
+    ver->alpha_g1 = host_load_affine<HFp>(alpha_g1);
+    std::vector<Affine<HFp2>> q(n + 5);
     for (size_t j = 0; j <= n; j++) q[j] = host_load_affine<HFp2>(t_g2 + 24 * j);
     q[n + 1] = host_load_affine<HFp2>(G2::GEN);
     q[n + 2] = host_load_affine<HFp2>(gamma_g2);
     q[n + 3] = host_load_affine<HFp2>(delta_g2);
+    q[n + 4] = host_load_affine<HFp2>(beta_g2);
     for (size_t j = n + 1; j < n + 4; j++) q[j].y = neg(q[j].y);                                        // infinity stays x = y = 0
     std::vector<LineCoeffs<HFp>> lines(q.size() * MILLER_LINES);                                        // LineCoeffs<HFp> and <Fp>: the same bytes
     host_parallel_for(q.size(), [&](size_t j) { prepare_g2(q[j], lines.data() + j * MILLER_LINES); });
@@ -417,12 +409,34 @@ vsp_saver_verifier *saver_verifier_create(vsp_ctx *ctx, size_t n, const uint64_t
     return ver;
 }
 
+int saver_piece_prepare(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *rest, const uint64_t *A, const uint64_t *B, const uint64_t *C,
+                        size_t at, size_t c, StageTimer &timer) {
+    hipStream_t st = ctx->stream;
+    const size_t n = ver->n, L = ver->vk->n_abc - 1 - n;
+    const size_t ct_words = c * (n + 2) * 12;
+    VSP_TRY(ensure(ctx, ctx->pair_raw, (ct_words + proof_words(c, L)) * sizeof(uint64_t)));
+    VSP_TRY(ensure(ctx, ctx->pair_g1, (n + 5) * c * sizeof(G1Affine)));                              // n + 4 prepared-side arguments, then A
+    VSP_TRY(ensure(ctx, ctx->pair_g2, c * sizeof(G2Affine)));
+    VSP_TRY(ensure(ctx, ctx->pair_status, 3 * c));                                                   // malformed | equation 1 | equation 2
+    uint64_t *d_ct = (uint64_t *)ctx->pair_raw.p;
+    G1Affine *pts = (G1Affine *)ctx->pair_g1.p, *a_pts = pts + (n + 4) * c;
+    VSP_HIP(hipMemcpyAsync(d_ct, ct + at * (n + 2) * 12, ct_words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    ProofArgs d;
+    VSP_TRY(upload_proofs(ctx, d_ct + ct_words, A, B, C, rest, at, c, L, d));
+    VSP_TRY(timer.mark(ctx, 0, st));
+    hipLaunchKernelGGL(k_ballot_prepare, dim3((unsigned)((c + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, d_ct, d.scalars, d.A, d.B, d.C, c, n,
+                       ver->vk->n_abc, (const G1Affine *)ver->vk->d_tab, pts, a_pts, (G2Affine *)ctx->pair_g2.p, (uint8_t *)ctx->pair_status.p);
+    VSP_LAUNCH_CHECK();
+    VSP_TRY(timer.mark(ctx, 1, st));
+    return VSP_OK;
+}
+
 int saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *rest, const uint64_t *A, const uint64_t *B, const uint64_t *C, size_t count,
                        uint8_t *verdict_out, uint8_t *reason_out) {
     if (ver->device != ctx->device) return set_error(ctx, VSP_ERR_ARG, "saver_verify_batch: the verifier belongs to another device");
     VSP_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const size_t n = ver->n, L = ver->vk->n_abc - 1 - n;
+    const size_t n = ver->n;
     // ballots of one piece: "pairing_chunk" as for the pairings, and at most 2^19 G1 arguments (a ballot has n + 5; never split)
     size_t piece = pairing_piece(ctx, 1);
     if (piece * (n + 5) > SAVER_MAX_ARGS) piece = SAVER_MAX_ARGS / (n + 5);
@@ -432,25 +446,12 @@ int saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64
     std::vector<uint8_t> flags;
     for (size_t at = 0; at < count; at += piece) {
         const size_t c = count - at < piece ? count - at : piece;
-        const size_t ct_words = c * (n + 2) * 12;
-        VSP_TRY(ensure(ctx, ctx->pair_raw, (ct_words + proof_words(c, L)) * sizeof(uint64_t)));
-        VSP_TRY(ensure(ctx, ctx->pair_g1, (n + 5) * c * sizeof(G1Affine)));                              // n + 4 prepared-side arguments, then A
-        VSP_TRY(ensure(ctx, ctx->pair_g2, c * sizeof(G2Affine)));
-        VSP_TRY(ensure(ctx, ctx->pair_status, 3 * c));                                                   // malformed | equation 1 | equation 2
+        VSP_TRY(saver_piece_prepare(ctx, ver, ct, rest, A, B, C, at, c, ctx->saver_timer));
         VSP_TRY(ensure(ctx, ctx->pair_ml, (ng + 1) * c * sizeof(Fp12)));
         VSP_TRY(ensure(ctx, ctx->pair_prod, 2 * c * sizeof(Fp12)));
-        uint64_t *d_ct = (uint64_t *)ctx->pair_raw.p;
         G1Affine *pts = (G1Affine *)ctx->pair_g1.p, *a_pts = pts + (n + 4) * c;
         uint8_t *status = (uint8_t *)ctx->pair_status.p;
-        VSP_HIP(hipMemcpyAsync(d_ct, ct + at * (n + 2) * 12, ct_words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        ProofArgs d;
-        VSP_TRY(upload_proofs(ctx, d_ct + ct_words, A, B, C, rest, at, c, L, d));
         const unsigned blocks = (unsigned)((c + PAIRING_THREADS - 1) / PAIRING_THREADS);
-        VSP_TRY(ctx->saver_timer.mark(ctx, 0, st));
-        hipLaunchKernelGGL(k_ballot_prepare, dim3(blocks), dim3(PAIRING_THREADS), 0, st, d_ct, d.scalars, d.A, d.B, d.C, c, n, ver->vk->n_abc,
-                           (const G1Affine *)ver->vk->d_tab, pts, a_pts, (G2Affine *)ctx->pair_g2.p, status);
-        VSP_LAUNCH_CHECK();
-        VSP_TRY(ctx->saver_timer.mark(ctx, 1, st));
         hipLaunchKernelGGL(k_miller_ballot, dim3(blocks, (unsigned)(ng + 1)), dim3(PAIRING_THREADS), 0, st, (const G1Affine *)pts, (const G1Affine *)a_pts,
                            (const G2Affine *)ctx->pair_g2.p, (const LineCoeffs<Fp> *)ver->d_lines, c, n, G, ng, (Fp12 *)ctx->pair_ml.p);
         VSP_LAUNCH_CHECK();
