@@ -327,7 +327,7 @@ int vsp_groth16_prove(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const 
  * bucket set; over a key with tables of window multiples (windows of at most 16 bits) every witness has ONE per query, which is ~12 %
  * faster where the tables are small -- 2^16 constraints, precompute = 17 (all five queries), option "generate_precompute_window" = 14:
  * 1.7 GB -- and no use at 2^20 (19 GB).  Option "msm_batch_tables" = 0 refuses table keys (VSP_ERR_UNSUPPORTED), as the first version did.
- * No SAVER addend (vsp_saver_encrypt proves one vote). */
+ * Ballots in batches -- these proofs with the SAVER addend, beside their ciphertexts -- are vsp_saver_encrypt_batch ("SAVER ballots in batches"). */
 int vsp_groth16_prove_batch(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witnesses, size_t count,
                             const uint64_t *r, const uint64_t *s, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out);
 /* The batch in two halves, as vsp_groth16_prove_launch / _finish below: launch copies the witnesses, r and s, queues every kernel of the
@@ -415,6 +415,59 @@ int vsp_saver_encrypt(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1cs *cs,
  * C' = C + (z1 z2) A + r' gamma_inverse_sum_s_g1;  proof_out (may be NULL) receives the 192 compressed bytes of the new proof */
 int vsp_saver_rerandomize(vsp_ctx *ctx, const vsp_saver_pk *spk, const uint64_t delta_g2[24], const uint64_t rnd[12],
                           uint64_t *ct, uint64_t A[12], uint64_t B[24], uint64_t C[12], uint8_t proof_out[192]);
+
+/* ---- SAVER ballots in batches: the ciphertexts on the GPU beside vsp_groth16_prove_batch's proofs --------------------
+ * THE TABLES.  Every element of a ciphertext is a sum of scalar multiples of FIXED points of the election key, 3 msg_size + 3 of them:
+ * X_0 .. X_{n+1} = delta_g1 | delta_s_g1[i] | delta_sum_s_g1, P2 = gamma_inverse_sum_s_g1, the message bases G_1 .. G_n and
+ * Y_1 .. Y_n = t_g1[i].  vsp_saver_pk_upload builds the table of each (64 four-bit windows x 15 affine entries d 16^w P in Montgomery
+ * form: 92 160 bytes a base, 7.2 MB at msg_size 25) on the host -- those of G and Y exist nowhere else -- and uploads them to the
+ * context's device; it does nothing the second time, and the batch calls below make it themselves.  The tables belong to the KEY:
+ * contexts of one device share them (another device: VSP_ERR_UNSUPPORTED), vsp_saver_pk_device_bytes is their device size (0 before the
+ * upload) and vsp_saver_pk_free releases them.  A base at infinity is legal: its table is flagged and its terms are skipped.
+ * vsp_saver_pk_load stays host-only and accepts ctx = NULL.  PRECONDITION, as for the tables vsp_saver_pk_load builds: the key's points
+ * are in the order-r subgroup.  The load checks curve membership only, and a curve point of small order has multiples at infinity
+ * among its table entries, which the tables' shared inversion does not survive: such a key gives wrong ciphertexts without a message.
+ *
+ * vsp_saver_ciphertext_batch: `count` ciphertexts and nothing else.  msgs: count x msg_size x 4 words, r_enc: count x 4, all
+ * canonical (< r).  ct_out[k] = c_0 | c_1 .. c_n | psi of ballot k as canonical affine words (infinity: all zero) -- bit for bit
+ * oracle/saver.py encrypt_ct --, addend_out[k] = r_enc_k gamma_inverse_sum_s_g1 (the term the proof's C carries), ct_blobs_out = each
+ * ciphertext as vsp_g1_vector_to_blob writes it (8 + 48 (msg_size + 2) bytes a ballot), ready for vsp_tally_add_blobs.  Any count:
+ * pieces of at most "saver_ct_chunk" ballots (option, default and maximum 1024) bound the workspace, the context's own and grow-only, at
+ * 320 msg_size + 896 device bytes and 128 msg_size + 320 pinned bytes per ballot of a piece (9.1 MB + 3.6 MB at msg_size 25).
+ * VSP_ERR_ARG before any GPU work for a null pointer or a scalar >= r; vsp_last_error names the member.
+ * How it is computed (csrc/saver_ct.h, csrc/saver_batch.hip): every output column is a sum of window terms (table of base b, window
+ * w, digit w of scalar s) -- 64 for c_0 and for the addend, 128 for c_i, 64 (msg_size + 1) for psi -- described as data; a group of 8 to 64
+ * lanes per (ballot, column) adds up a share of the terms each by mixed additions, zero digits skipped, and folds the partial sums
+ * through LDS, so no chain of dependent additions is longer than 32 at msg_size 25; a second kernel makes the sums canonical affine
+ * points.  Every addition is complete (equal operands double, opposite ones give infinity, infinity on either side).
+ *
+ * vsp_saver_encrypt_batch: `count` (1..64) ballots of one election, each byte-identical -- ciphertext, A, B, C and the 192 proof
+ * bytes -- to vsp_saver_encrypt on the same (msg_k, witness_k, r_enc_k, r_k, s_k).  msgs: count x msg_size x 4, witnesses: count x
+ * num_vars x 4, r_enc, r, s: count x 4; outputs count x (msg_size + 2) x 12 | 12 | 24 | 12 words, count x 192 bytes and count blobs as
+ * above; any output may be NULL.  _launch makes vsp_saver_encrypt's checks for every member before anything is queued (message
+ * canonical and equal to the first msg_size public inputs of the witness, r_enc < r: VSP_ERR_ARG, vsp_last_error names the member),
+ * launches the batch prover as vsp_groth16_prove_batch_launch does, and queues the ciphertext kernels on a stream of the context's
+ * own, where they fill the gaps between the prover's kernels; the results land in pinned memory behind an event.  _finish waits for that
+ * event, hands the members' addends to the batch assembly and finishes the proofs.  One batch (of ballots or of proofs) in flight per
+ * context; a finish without a launch is VSP_ERR_ARG.  With option "prove_check_witness" an unsatisfied member's outputs are all zero,
+ * ciphertext and blob included, the call returns VSP_ERR_UNSATISFIED, vsp_groth16_prove_batch_verdicts names the members and the other
+ * members are as without the check.
+ * Option "saver_encrypt_gpu" (default 1): 0 computes the ciphertexts and addends on the host instead -- the same columns over the same
+ * tables, a ballot per host thread, in the finish's wait for the proofs -- as the other leg of a measurement and a second
+ * implementation for the tests.  Nothing switches to it on its own.
+ * Statistics (vsp_get_stat, summed since vsp_stats_reset): "saver_ct_ms" HIP events around the ciphertext kernels, "saver_ct_table_ms"
+ * the tables' build and upload (once per key, wall time), "saver_encrypt_batches" batches finished. */
+int vsp_saver_pk_upload(vsp_ctx *ctx, vsp_saver_pk *spk);
+size_t vsp_saver_pk_device_bytes(const vsp_saver_pk *spk);
+int vsp_saver_ciphertext_batch(vsp_ctx *ctx, const vsp_saver_pk *spk, const uint64_t *msgs /* count x msg_size x 4 */, const uint64_t *r_enc /* count x 4 */,
+                               size_t count, uint64_t *ct_out /* count x (msg_size + 2) x 12 */, uint64_t *addend_out /* count x 12, may be NULL */,
+                               uint8_t *ct_blobs_out /* count x (8 + 48 (msg_size + 2)), may be NULL */);
+int vsp_saver_encrypt_batch_launch(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *msgs, const uint64_t *witnesses,
+                                   size_t count /* 1..64 */, const uint64_t *r_enc, const uint64_t *r, const uint64_t *s);
+int vsp_saver_encrypt_batch_finish(vsp_ctx *ctx, uint64_t *ct_out, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out, uint8_t *ct_blobs_out);
+int vsp_saver_encrypt_batch(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *msgs, const uint64_t *witnesses,
+                            size_t count /* 1..64 */, const uint64_t *r_enc, const uint64_t *r, const uint64_t *s, uint64_t *ct_out, uint64_t *A_out, uint64_t *B_out,
+                            uint64_t *C_out, uint8_t *proofs_out, uint8_t *ct_blobs_out);
 
 /* ---- generator-side batch exponentiation (section 8(f).1; also builds synthetic benchmark bases) ---
  * out[i] = scalars[i] * generator, written to DEVICE memory as canonical affine points. */

@@ -680,6 +680,16 @@ class SaverPublicKey:
         if not self.h:
             raise VspError("saver_pk_load failed: " + ctx.last_error())
 
+    def upload(self, ctx=None):
+        """build the tables of all 3 msg_size + 3 fixed points and put them on the context's device (vsp_saver_pk_upload); the batch
+        calls do it themselves, and a second call does nothing"""
+        ctx = ctx or self.ctx
+        ctx.check(ctx.lib.vsp_saver_pk_upload(ctx.h, self.h))
+
+    @property
+    def device_bytes(self):
+        return int(self.ctx.lib.vsp_saver_pk_device_bytes(self.h))
+
     def free(self):
         if self.h and self.ctx.h:
             self.ctx.lib.vsp_saver_pk_free(self.ctx.h, self.h)
@@ -697,6 +707,60 @@ def saver_encrypt(ctx, spk, cs, pk, msg, witness, r_enc, r, s):
     _check_single(ctx, ctx.lib.vsp_saver_encrypt(ctx.h, spk.h, cs.h, pk.h, _ptr(msg), _ptr(witness), _ptr(_u64(r_enc)), _ptr(_u64(r)), _ptr(_u64(s)),
                                                  _ptr(ct), _ptr(A), _ptr(B), _ptr(Cc), _ptr(proof)))
     return ct, (A, B, Cc), proof.tobytes()
+
+
+def saver_ciphertext_batch(ctx, spk, msgs, r_enc, addends=True, blobs=True):
+    """the ciphertexts of K ballots on the GPU (vsp_saver_ciphertext_batch): msgs [K, msg_size, 4], r_enc [K, 4]
+    -> (ct [K, msg_size + 2, 12], addends [K, 12] = r_enc_k gamma_inverse_sum_s_g1 or None, [blob bytes] * K or None)"""
+    msgs = np.ascontiguousarray(msgs, dtype=np.uint64).reshape(-1, spk.n, 4)
+    K = msgs.shape[0]
+    r_enc = np.ascontiguousarray(r_enc, dtype=np.uint64).reshape(K, 4)
+    ct = np.zeros((K, spk.n + 2, 12), np.uint64)
+    add = np.zeros((K, 12), np.uint64) if addends else None
+    bl = np.zeros((K, ctx.lib.vsp_g1_vector_blob_size(spk.n + 2)), np.uint8) if blobs else None
+    ctx.check(ctx.lib.vsp_saver_ciphertext_batch(ctx.h, spk.h, _ptr(msgs), _ptr(r_enc), K, _ptr(ct), _ptr(add), _ptr(bl)))
+    return ct, add, None if bl is None else [bl[k].tobytes() for k in range(K)]
+
+
+def saver_encrypt_batch_launch(ctx, spk, cs, pk, msgs, witnesses, r_enc, r, s):
+    """first half of saver_encrypt_batch: every member checked, the K proofs and the ciphertext kernels queued; returns K"""
+    witnesses, r, s, K = _batch_inputs(cs, witnesses, r, s)
+    msgs = np.ascontiguousarray(msgs, dtype=np.uint64)
+    if msgs.shape != (K, spk.n, 4):
+        raise ValueError("encrypt_batch: msgs must be [K, msg_size, 4]")
+    r_enc = np.ascontiguousarray(r_enc, dtype=np.uint64).reshape(K, 4)
+    ctx.check(ctx.lib.vsp_saver_encrypt_batch_launch(ctx.h, spk.h, cs.h, pk.h, _ptr(msgs), _ptr(witnesses), K, _ptr(r_enc), _ptr(r), _ptr(s)))
+    ctx._saver_batch = (K, spk.n)
+    return K
+
+
+def saver_encrypt_batch_finish(ctx):
+    """second half: -> (ct [K, msg_size + 2, 12], (A [K, 12], B [K, 24], C [K, 12]), [proof bytes] * K, [ciphertext blob bytes] * K).
+    With option prove_check_witness an Unsatisfied carries .status, .first_bad_row and .results = these outputs (zero for its members)."""
+    K, n = getattr(ctx, "_saver_batch", None) or (0, 0)
+    ctx._saver_batch = None
+    if not K:
+        ctx.check(ctx.lib.vsp_saver_encrypt_batch_finish(ctx.h, None, None, None, None, None, None))      # the library's refusal
+    ct = np.zeros((K, n + 2, 12), np.uint64)
+    A = np.zeros((K, 12), np.uint64); B = np.zeros((K, 24), np.uint64); Cc = np.zeros((K, 12), np.uint64)
+    proofs = np.zeros((K, 192), np.uint8); bl = np.zeros((K, ctx.lib.vsp_g1_vector_blob_size(n + 2)), np.uint8)
+    ctx._prove_batch_last = K
+    rc = ctx.lib.vsp_saver_encrypt_batch_finish(ctx.h, _ptr(ct), _ptr(A), _ptr(B), _ptr(Cc), _ptr(proofs), _ptr(bl))
+    results = (ct, (A, B, Cc), [proofs[k].tobytes() for k in range(K)], [bl[k].tobytes() for k in range(K)])
+    try:
+        ctx.check(rc)
+    except Unsatisfied as e:
+        e.status, e.first_bad_row = groth16_prove_batch_verdicts(ctx, K)
+        e.results = results
+        raise
+    return results
+
+
+def saver_encrypt_batch(ctx, spk, cs, pk, msgs, witnesses, r_enc, r, s):
+    """K ballots of one election in one pass (vsp_saver_encrypt_batch): member k is byte-identical to saver_encrypt(msgs[k], witnesses[k],
+    r_enc[k], r[k], s[k]).  -> as saver_encrypt_batch_finish"""
+    saver_encrypt_batch_launch(ctx, spk, cs, pk, msgs, witnesses, r_enc, r, s)
+    return saver_encrypt_batch_finish(ctx)
 
 
 def saver_rerandomize(ctx, spk, delta_g2, rnd3, ct, proof_abc):

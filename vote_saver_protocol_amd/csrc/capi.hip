@@ -209,6 +209,7 @@ void vsp_destroy(vsp_ctx *ctx) {
                       &ctx->pair_raw, &ctx->pair_g1, &ctx->pair_g2, &ctx->pair_status, &ctx->pair_ml, &ctx->pair_prod, &ctx->pair_gt, &ctx->dec_out, &ctx->screen_ws};
     for (DevBuf *b : bufs) free_buf(*b);
     msm_free_slots(ctx);
+    saver_ct_release(ctx);
     if (ctx->h_fold) hipHostFree(ctx->h_fold);
     if (ctx->h_verdict) hipHostFree(ctx->h_verdict);
     hipEventDestroy(ctx->ev0); hipEventDestroy(ctx->ev1); hipEventDestroy(ctx->ev_aux);

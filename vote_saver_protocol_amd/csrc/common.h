@@ -16,6 +16,7 @@
 #include <thread>
 #include "curve.h"
 #include "point_decode.h"
+#include "saver_ct.h"
 
 struct vsp_ctx;
 namespace vsp {
@@ -256,8 +257,20 @@ struct vsp_ctx {
     struct {
         bool active = false, batch = false; const vsp_pk *pk = nullptr; size_t count = 0, z_bytes = 0; std::vector<uint64_t> r, s;
         bool has_saver = false; uint64_t P1[12], r_enc[4];
+        std::vector<uint64_t> addend;      // a batch's SAVER terms, K canonical affine points added to C (saver_batch.hip sets them before the finish); empty: none
         bool check = false;      // option "prove_check_witness": the verdict records are on their way to h_verdict
     } prove;
+    // ballots in batches (saver_batch.hip): the ciphertext kernels' stream, their device workspace (a piece's scalars, column sums and
+    // canonical points), the pinned staging of the scalars and of the points with the event behind the copy back, the timer around the
+    // kernels; and the batch between vsp_saver_encrypt_batch_launch and its finish
+    struct {
+        hipStream_t stream = nullptr;
+        vsp::DevBuf scalars, sums, points;
+        void *h_scalars = nullptr, *h_points = nullptr; size_t h_scalars_cap = 0, h_points_cap = 0;
+        hipEvent_t done = nullptr;
+        vsp::StageTimer timer;
+        bool active = false, gpu = false; const vsp_saver_pk *spk = nullptr; size_t count = 0;
+    } saver_ct;
     // vsp_groth16_prove_batch_verdicts: status byte and first failing row of every member of the last finished batch that was checked
     std::vector<uint8_t> batch_status;
     std::vector<uint64_t> batch_first_bad;
@@ -319,6 +332,63 @@ struct vsp_pk {
     mutable std::atomic<bool> tab_ready{false};
     mutable std::vector<vsp::XYZZ<vsp::HFp>> tab1;
     mutable std::vector<vsp::XYZZ<vsp::HFp2>> tab2;
+};
+
+// k * P for a fixed P: table[w][d - 1] = d * 16^w * P (affine), 64 windows x 15 entries; a product is <= 64 mixed additions
+namespace vsp {
+struct FixedBase {
+    std::vector<Affine<HFp>> tab;
+    bool inf = false;
+    void build(const Affine<HFp> &p) {
+        inf = is_inf(p);
+        if (inf) return;
+        std::vector<XYZZ<HFp>> pts(64 * 15);
+        XYZZ<HFp> base = xyzz_from_affine(p);
+        for (int w = 0; w < 64; w++) {
+            XYZZ<HFp> acc = base;
+            for (int d = 1; d <= 15; d++) { pts[w * 15 + d - 1] = acc; xyzz_add(acc, base); }
+            base = acc;                                            // 16 * base
+        }
+        // batch normalisation (one inversion): prefix products of ZZZ
+        std::vector<HFp> pre(pts.size());
+        HFp run = HFp::one();
+        for (size_t i = 0; i < pts.size(); i++) { pre[i] = run; run = mul(run, pts[i].ZZZ); }
+        HFp ri = inv(run);
+        tab.resize(pts.size());
+        for (size_t i = pts.size(); i-- > 0;) {
+            HFp zi3 = mul(ri, pre[i]);                               // 1 / ZZZ_i
+            ri = mul(ri, pts[i].ZZZ);
+            HFp zi = mul(zi3, pts[i].ZZ), zi2 = sqr(zi);
+            tab[i].x = mul(pts[i].X, zi2); tab[i].y = mul(pts[i].Y, zi3);
+        }
+    }
+    XYZZ<HFp> mul_scalar(const uint64_t k[4]) const {
+        XYZZ<HFp> acc = XYZZ<HFp>::inf();
+        if (inf) return acc;
+        for (int w = 0; w < 64; w++) {
+            unsigned d = (unsigned)(k[w >> 4] >> ((w & 15) * 4)) & 15u;
+            if (d) xyzz_madd(acc, tab[w * 15 + d - 1]);
+        }
+        return acc;
+    }
+};
+}  // namespace vsp
+// the SAVER public key (saver.hip); saver_batch.hip adds the tables of ALL its 3 n + 3 fixed points in the order of saver_ct.h, on the
+// host (`flat`) and on one device, built once by the first vsp_saver_pk_upload under the mutex (contexts on several threads share a key)
+struct vsp_saver_pk {
+    size_t n = 0;
+    std::vector<uint64_t> words;                   // the flat public key
+    std::vector<uint64_t> gabc;                    // G_0 .. G_n (canonical)
+    std::vector<vsp::FixedBase> X;                 // delta_g1, delta_s_g1[0..n), delta_sum_s_g1   (n + 2 tables: the bases of the ciphertext)
+    vsp::FixedBase P2;                             // gamma_inverse_sum_s_g1
+    std::vector<vsp::Affine<vsp::HFp>> G, Y;       // message bases G_i (i = 1..n) and t_g1[i]
+    mutable std::mutex up_mu;
+    mutable std::atomic<bool> uploaded{false};
+    mutable int device = -1;
+    mutable std::vector<vsp::Affine<vsp::HFp>> flat;      // (3 n + 3) x 960 points; the table of a base at infinity is all zero
+    mutable vsp::SaverPlan plan;                          // which scalars meet which bases in which column, and the lanes of a ballot
+    mutable void *d_tab = nullptr, *d_desc = nullptr;     // the table and the plan (columns | pairs | lane_col) on the device
+    mutable size_t device_bytes = 0;
 };
 
 // a Groth16 verification key resident on the device (pairing.hip)
@@ -423,6 +493,10 @@ int witness_map_device(vsp_ctx *ctx, const vsp_domain *d, Fr *dA, Fr *dB, Fr *dC
 int prove_with_overlap(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witness, const uint64_t r[4], const uint64_t s[4],
                        const uint64_t *saver_P1, const uint64_t *saver_r_enc, uint64_t A_out[12], uint64_t B_out[24], uint64_t C_out[12],
                        uint8_t proof_out[192], const std::function<void()> *overlap);
+
+// ballots in batches (saver_batch.hip): what vsp_destroy and vsp_saver_pk_free release
+void saver_ct_release(vsp_ctx *ctx);
+void saver_pk_release_device(vsp_saver_pk *spk);
 
 // MSM on device-resident Montgomery bases; result as host XYZZ (Montgomery, 64-bit limbs).  The templates over the group: msm_impl.inc,
 // instantiated by msm_g1.hip / msm_g2.hip.  Everything without a template parameter is group-independent and defined once, in

@@ -229,6 +229,8 @@ static int prove_begin(vsp_ctx *ctx, bool batch, bool args_present, const vsp_r1
     p.batch = batch; p.pk = pk; p.count = K; p.z_bytes = K * (nv + 1) * sizeof(Fr);
     p.r.assign(r, r + 4 * K); p.s.assign(s, s + 4 * K);
     p.has_saver = saver_P1 && saver_r_enc;
+    p.addend.clear();                      // a batch of ballots sets its members' terms before its finish (saver_batch.hip)
+    ctx->saver_ct.active = false;          // and marks itself after this launch: a ballot batch finished as a plain one does not outlive it
     if (p.has_saver) { memcpy(p.P1, saver_P1, 96); memcpy(p.r_enc, saver_r_enc, 32); }
     return VSP_OK;
 }
@@ -679,8 +681,8 @@ static int prove_batch_finish_impl(vsp_ctx *ctx, uint64_t *A_out, uint64_t *B_ou
             if (proofs_out) memset(proofs_out + 192 * k, 0, 192);
             return;
         }
-        store_proof(k, gA[k], proof_b2(pk, eB2[k], s_delta2[k]), proof_c(eH[k], eL[k], s_gA[k], r_gB1[k], neg_rs_delta[k], XYZZ<HFp>::inf()),
-                    A_out, B_out, C_out, proofs_out);
+        const XYZZ<HFp> saver = ctx->prove.addend.empty() ? XYZZ<HFp>::inf() : xyzz_from_affine(host_load_affine<HFp>(ctx->prove.addend.data() + 12 * k));
+        store_proof(k, gA[k], proof_b2(pk, eB2[k], s_delta2[k]), proof_c(eH[k], eL[k], s_gA[k], r_gB1[k], neg_rs_delta[k], saver), A_out, B_out, C_out, proofs_out);
     });
     lap("prove_batch_assembly_ms");
     ctx->stats["prove_calls"] += (double)K;

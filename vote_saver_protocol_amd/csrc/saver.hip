@@ -19,44 +19,6 @@
 
 namespace vsp {
 
-// k * P for a fixed P: table[w][d - 1] = d * 16^w * P (affine), 64 windows x 15 entries; a product is <= 64 mixed additions
-struct FixedBase {
-    std::vector<Affine<HFp>> tab;
-    bool inf = false;
-    void build(const Affine<HFp> &p) {
-        inf = is_inf(p);
-        if (inf) return;
-        std::vector<XYZZ<HFp>> pts(64 * 15);
-        XYZZ<HFp> base = xyzz_from_affine(p);
-        for (int w = 0; w < 64; w++) {
-            XYZZ<HFp> acc = base;
-            for (int d = 1; d <= 15; d++) { pts[w * 15 + d - 1] = acc; xyzz_add(acc, base); }
-            base = acc;                                            // 16 * base
-        }
-        // batch normalisation (one inversion): prefix products of ZZZ
-        std::vector<HFp> pre(pts.size());
-        HFp run = HFp::one();
-        for (size_t i = 0; i < pts.size(); i++) { pre[i] = run; run = mul(run, pts[i].ZZZ); }
-        HFp ri = inv(run);
-        tab.resize(pts.size());
-        for (size_t i = pts.size(); i-- > 0;) {
-            HFp zi3 = mul(ri, pre[i]);                               // 1 / ZZZ_i
-            ri = mul(ri, pts[i].ZZZ);
-            HFp zi = mul(zi3, pts[i].ZZ), zi2 = sqr(zi);
-            tab[i].x = mul(pts[i].X, zi2); tab[i].y = mul(pts[i].Y, zi3);
-        }
-    }
-    XYZZ<HFp> mul_scalar(const uint64_t k[4]) const {
-        XYZZ<HFp> acc = XYZZ<HFp>::inf();
-        if (inf) return acc;
-        for (int w = 0; w < 64; w++) {
-            unsigned d = (unsigned)(k[w >> 4] >> ((w & 15) * 4)) & 15u;
-            if (d) xyzz_madd(acc, tab[w * 15 + d - 1]);
-        }
-        return acc;
-    }
-};
-
 static int bit_length(const uint64_t k[4]) {
     for (int i = 3; i >= 0; i--) if (k[i]) return 64 * i + 64 - __builtin_clzll(k[i]);
     return 0;
@@ -64,15 +26,6 @@ static int bit_length(const uint64_t k[4]) {
 }  // namespace vsp
 
 using namespace vsp;
-
-struct vsp_saver_pk {
-    size_t n = 0;
-    std::vector<uint64_t> words;                   // the flat public key
-    std::vector<uint64_t> gabc;                    // G_0 .. G_n (canonical)
-    std::vector<FixedBase> X;                      // delta_g1, delta_s_g1[0..n), delta_sum_s_g1   (n + 2 tables: the bases of the ciphertext)
-    FixedBase P2;                                  // gamma_inverse_sum_s_g1
-    std::vector<Affine<HFp>> G, Y;                 // message bases G_i (i = 1..n) and t_g1[i]
-};
 
 static size_t pk_words(size_t n) { return 12 + 12 * n + 12 * n + 24 * (n + 1) + 12 + 12; }
 static size_t vk_words(size_t n) { return 24 + 24 * n + 24 * n; }
@@ -146,7 +99,7 @@ vsp_saver_pk *vsp_saver_pk_load(vsp_ctx *ctx, size_t n, const uint64_t *pk_in, c
     for (size_t i = 0; i < n; i++) { k->G[i] = host_load_affine<HFp>(gamma_abc_g1 + 12 * (i + 1)); k->Y[i] = host_load_affine<HFp>(p_t_g1 + 12 * i); }
     return k;
 }
-void vsp_saver_pk_free(vsp_ctx *, vsp_saver_pk *k) { delete k; }
+void vsp_saver_pk_free(vsp_ctx *, vsp_saver_pk *k) { if (k) saver_pk_release_device(k); delete k; }
 size_t vsp_saver_pk_msg_size(const vsp_saver_pk *k) { return k ? k->n : 0; }
 
 int vsp_saver_encrypt(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *msg, const uint64_t *witness,
