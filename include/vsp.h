@@ -395,7 +395,8 @@ void vsp_keypair_free(vsp_ctx *ctx, vsp_keypair *kp);
  * message inputs).  verify_encryption is vsp_saver_verify_batch below ("SAVER ballot verdicts"); decryption and its verification,
  * pairing work and a discrete logarithm on the one aggregated ciphertext, are vsp_saver_decrypt_batch and
  * vsp_saver_verify_decryption_batch ("SAVER decryption").
- * vsp_saver_keygen, vsp_saver_pk_load and vsp_saver_rerandomize are host-only and accept ctx = NULL. */
+ * vsp_saver_keygen, vsp_saver_pk_load and vsp_saver_rerandomize are host-only and accept ctx = NULL; vsp_saver_rerandomize takes one
+ * ballot a call, and the ballot box's bulk form of it on the GPU is vsp_saver_rerandomize_batch ("SAVER ballots in batches"). */
 typedef struct vsp_saver_pk vsp_saver_pk;
 size_t vsp_saver_pk_words(size_t msg_size);     /* uint64 words of the flat public key */
 size_t vsp_saver_vk_words(size_t msg_size);
@@ -468,6 +469,44 @@ int vsp_saver_encrypt_batch_finish(vsp_ctx *ctx, uint64_t *ct_out, uint64_t *A_o
 int vsp_saver_encrypt_batch(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *msgs, const uint64_t *witnesses,
                             size_t count /* 1..64 */, const uint64_t *r_enc, const uint64_t *r, const uint64_t *s, uint64_t *ct_out, uint64_t *A_out, uint64_t *B_out,
                             uint64_t *C_out, uint8_t *proofs_out, uint8_t *ct_blobs_out);
+/* RERANDOMIZATION IN BATCHES: what the ballot box does to every ballot it receives, `count` ballots a call.
+ * A vsp_saver_rerandomizer is public data of one election: the key (which must outlive it) with the device tables vsp_saver_pk_upload
+ * builds -- _new makes the upload -- and one more table of the same layout in G2, 64 four-bit windows x 15 affine entries d 16^w delta_g2
+ * in Montgomery form (184 320 bytes; vsp_saver_rerandomizer_device_bytes counts it and the two column plans, not the key's tables).
+ * _new validates delta_g2 on the curve (NULL and vsp_last_error otherwise; infinity is legal, its table is flagged).  PRECONDITION, as for
+ * vsp_saver_pk_upload: delta_g2 is in the order-r subgroup -- the table's shared inversion does not survive a multiple at infinity.
+ *
+ * vsp_saver_rerandomize_batch: for every member k the outputs are, word for word and byte for byte, what vsp_saver_rerandomize writes for
+ * (rnd_k, ct_k, A_k, B_k, C_k) under the same key and delta_g2:
+ *     ct_i' = ct_i + r' X_i  (i = 0 .. msg_size + 1)     A' = z1 A     B' = z1^-1 B + z2 delta_g2     C' = C + (z1 z2) A + r' P2
+ * as canonical affine words, infinity all zero; proofs_out[k] the 192 compressed bytes of (A', B', C'), ct_blobs_out[k] the blob of ct'
+ * as vsp_g1_vector_to_blob writes it.  rnd: count x 12 words r' | z1 | z2; ct: count x (msg_size + 2) x 12; A, C: count x 12; B: count x
+ * 24.  Any output may be NULL, and an output array may be the input array of the same name.
+ * Before any GPU work: a null input, a scalar >= r or z1 = 0 in any member is VSP_ERR_ARG, and vsp_last_error names the member.
+ * On the device: every input point has coordinates below p and is on its curve or the all-zero infinity.  A member with a point that
+ * is not gets status_out[k] = 1 and all-zero outputs, blob and proof bytes included; the other members are unaffected and the call
+ * returns VSP_OK.  With status_out = NULL such a member makes the call return VSP_ERR_ARG after the fact (the outputs are written as
+ * described), and vsp_last_error names the first one.  No subgroup check, as in the single call: every addition used is complete for
+ * any curve point.
+ * Any count: pieces of at most "saver_rerandomize_chunk" ballots (option, default and maximum 2^16) bound the workspace, the context's
+ * own and grow-only, at 384 msg_size + 2 276 device bytes and 192 msg_size + 1 316 pinned bytes per ballot of a piece (778 MB + 401 MB
+ * for 2^16 ballots at msg_size 25, a quarter of that for pieces of 2^14, which are a third slower; a smaller call takes what its count needs).  While a batch of ballots or of proofs is in flight on the context the call is refused with
+ * VSP_ERR_ARG.  Option "saver_rerandomize_w4" (default 1): the variable-base multiplications walk 4-bit windows; 0 walks single bits.
+ * How it is computed (csrc/saver_rerand.h, csrc/saver_rerand.hip): the msg_size + 3 sums r' X_i and r' P2 are columns of window terms over
+ * the key's tables as in vsp_saver_ciphertext_batch, 8 lanes each, and lane 0 adds the ballot's own ct_i or C; z2 delta_g2 is one
+ * such column over the G2 table; z1 A and (z1 z2) A take a lane each and z1^-1 B one, in kernels of their own group; 1 / z1 of a whole
+ * piece comes from one inversion on the host.
+ * Statistics: "saver_rerandomize_ms" HIP events around the kernels, split into "saver_rerandomize_check_ms", "_columns_ms", "_affine_ms",
+ * "_g1_ms" and "_g2_ms"; "saver_rerandomize_ballots" ballots through the kernels. */
+typedef struct vsp_saver_rerandomizer vsp_saver_rerandomizer;
+vsp_saver_rerandomizer *vsp_saver_rerandomizer_new(vsp_ctx *ctx, vsp_saver_pk *spk, const uint64_t delta_g2[24]);
+void   vsp_saver_rerandomizer_free(vsp_ctx *ctx, vsp_saver_rerandomizer *rr);
+size_t vsp_saver_rerandomizer_msg_size(const vsp_saver_rerandomizer *rr);
+size_t vsp_saver_rerandomizer_device_bytes(const vsp_saver_rerandomizer *rr);
+int vsp_saver_rerandomize_batch(vsp_ctx *ctx, const vsp_saver_rerandomizer *rr, const uint64_t *rnd /* count x 12: r' | z1 | z2 */,
+                                const uint64_t *ct /* count x (msg_size + 2) x 12 */, const uint64_t *A, const uint64_t *B, const uint64_t *C,
+                                size_t count, uint64_t *ct_out, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out,
+                                uint8_t *proofs_out /* count x 192 */, uint8_t *ct_blobs_out, uint8_t *status_out /* count */);
 
 /* ---- generator-side batch exponentiation (section 8(f).1; also builds synthetic benchmark bases) ---
  * out[i] = scalars[i] * generator, written to DEVICE memory as canonical affine points. */

@@ -106,6 +106,11 @@ PROTOTYPES = {
     "vsp_saver_encrypt_batch_launch": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P]),
     "vsp_saver_encrypt_batch_finish": (_I, [_P] * 7),
     "vsp_saver_encrypt_batch": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vsp_saver_rerandomizer_new": (_P, [_P, _P, _P]),
+    "vsp_saver_rerandomizer_free": (None, [_P, _P]),
+    "vsp_saver_rerandomizer_msg_size": (_SZ, [_P]),
+    "vsp_saver_rerandomizer_device_bytes": (_SZ, [_P]),
+    "vsp_saver_rerandomize_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P, _P, _P]),
     "vsp_fr_vector_blob_size": (_SZ, [_SZ]),
     "vsp_fr_vector_to_blob": (_I, [_P, _SZ, _P]),
     "vsp_fr_vector_from_blob": (_I, [_P, _SZ, _P, _SZ, _P]),

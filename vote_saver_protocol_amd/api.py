@@ -774,6 +774,58 @@ def saver_rerandomize(ctx, spk, delta_g2, rnd3, ct, proof_abc):
     return ct, (A, B, Cc), proof.tobytes()
 
 
+class SaverRerandomizer:
+    """the public data of one election that rerandomizes its ballots in batches (vsp_saver_rerandomizer): the key with its device tables
+    and the table of delta_g2.  The key must outlive it."""
+
+    def __init__(self, ctx, spk, delta_g2):
+        self.ctx, self.spk, self.n = ctx, spk, spk.n
+        d2 = _u64(delta_g2).reshape(-1)
+        if d2.size != 24:
+            raise ValueError("SaverRerandomizer: delta_g2 is one G2 point of 24 words")
+        self.h = ctx.lib.vsp_saver_rerandomizer_new(ctx.h, spk.h, _ptr(d2))
+        if not self.h:
+            raise VspError("saver_rerandomizer_new failed: " + ctx.last_error())
+
+    @property
+    def device_bytes(self):
+        return int(self.ctx.lib.vsp_saver_rerandomizer_device_bytes(self.h))
+
+    def free(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.vsp_saver_rerandomizer_free(self.ctx.h, self.h)
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+
+def saver_rerandomize_batch(ctx, rr, rnd, ct, proofs_abc, proofs=True, blobs=True, status=True, in_place=False):
+    """K ballots rerandomized on the GPU (vsp_saver_rerandomize_batch): rnd [K, 3, 4] = (r', z1, z2) of every member, ct [K, msg_size + 2, 12],
+    proofs_abc = (A [K, 12], B [K, 24], C [K, 12]); member k is byte-identical to saver_rerandomize on the same inputs.
+    -> (ct', (A', B', C'), [proof bytes] * K or None, [ciphertext blob bytes] * K or None, status [K] or None).  A member with a point
+    that is no curve point has status 1 and all-zero outputs; with status=False such a member raises instead.  in_place: the outputs
+    are written over ct and proofs_abc, which must then be contiguous uint64 arrays."""
+    n = rr.n
+    ct = np.ascontiguousarray(ct, dtype=np.uint64).reshape(-1, n + 2, 12)
+    K = ct.shape[0]
+    rnd = np.ascontiguousarray(rnd, dtype=np.uint64).reshape(K, 12)
+    A, B, Cc = (np.ascontiguousarray(x, dtype=np.uint64).reshape(K, w) for x, w in zip(proofs_abc, (12, 24, 12)))
+    if in_place:
+        ct2, A2, B2, C2 = ct, A, B, Cc
+    else:
+        ct2, A2, B2, C2 = np.zeros_like(ct), np.zeros_like(A), np.zeros_like(B), np.zeros_like(Cc)
+    pr = np.zeros((K, 192), np.uint8) if proofs else None
+    bl = np.zeros((K, ctx.lib.vsp_g1_vector_blob_size(n + 2)), np.uint8) if blobs else None
+    st = np.zeros(K, np.uint8) if status else None
+    ctx.check(ctx.lib.vsp_saver_rerandomize_batch(ctx.h, rr.h, _ptr(rnd), _ptr(ct), _ptr(A), _ptr(B), _ptr(Cc), K, _ptr(ct2), _ptr(A2), _ptr(B2), _ptr(C2),
+                                                  _ptr(pr), _ptr(bl), _ptr(st)))
+    return (ct2, (A2, B2, C2), None if pr is None else [pr[k].tobytes() for k in range(K)], None if bl is None else [bl[k].tobytes() for k in range(K)], st)
+
+
 def fixed_base_mul(ctx, d_scalars, n, group=1):
     """Generator-side batch_exp: device array out[i] = scalars[i] * generator (canonical affine).  Returns a device pointer."""
     gr = _group(group)

@@ -210,6 +210,7 @@ void vsp_destroy(vsp_ctx *ctx) {
     for (DevBuf *b : bufs) free_buf(*b);
     msm_free_slots(ctx);
     saver_ct_release(ctx);
+    saver_rr_release(ctx);
     if (ctx->h_fold) hipHostFree(ctx->h_fold);
     if (ctx->h_verdict) hipHostFree(ctx->h_verdict);
     hipEventDestroy(ctx->ev0); hipEventDestroy(ctx->ev1); hipEventDestroy(ctx->ev_aux);

@@ -17,6 +17,7 @@
 #include "curve.h"
 #include "point_decode.h"
 #include "saver_ct.h"
+#include "saver_rerand.h"
 
 struct vsp_ctx;
 namespace vsp {
@@ -271,6 +272,14 @@ struct vsp_ctx {
         vsp::StageTimer timer;
         bool active = false, gpu = false; const vsp_saver_pk *spk = nullptr; size_t count = 0;
     } saver_ct;
+    // rerandomization in batches (saver_rerand.hip): a piece's device workspace -- canonical words in and out (one buffer), scalar records,
+    // Montgomery points, column sums of both groups, a status word per ballot --, the pinned staging of both directions, the timers
+    // around check | columns | affine and around the G1 | G2 multiplications
+    struct {
+        vsp::DevBuf words, scalars, given, b_in, sums, sums2, status;
+        void *h_in = nullptr, *h_out = nullptr; size_t h_in_cap = 0, h_out_cap = 0;
+        vsp::StageTimer timer[2];
+    } saver_rr;
     // vsp_groth16_prove_batch_verdicts: status byte and first failing row of every member of the last finished batch that was checked
     std::vector<uint8_t> batch_status;
     std::vector<uint64_t> batch_first_bad;
@@ -497,6 +506,7 @@ int prove_with_overlap(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const
 // ballots in batches (saver_batch.hip): what vsp_destroy and vsp_saver_pk_free release
 void saver_ct_release(vsp_ctx *ctx);
 void saver_pk_release_device(vsp_saver_pk *spk);
+void saver_rr_release(vsp_ctx *ctx);                            // saver_rerand.hip
 
 // MSM on device-resident Montgomery bases; result as host XYZZ (Montgomery, 64-bit limbs).  The templates over the group: msm_impl.inc,
 // instantiated by msm_g1.hip / msm_g2.hip.  Everything without a template parameter is group-independent and defined once, in

@@ -28,12 +28,7 @@ __global__ __launch_bounds__(CT_BLOCK) void k_saver_ct(const G1Affine *tab, cons
         lanes = col.lanes; lane = (unsigned)(g % ballot_lanes) - col.lane0;
         saver_lane_sum(acc, tab, scalars + ballot * n_scalars * 4, col, pairs, lane, lanes, [](G1XYZZ *a, const G1Affine *q) { xyzz_madd(*a, *q); });
     }
-#pragma unroll 1
-    for (unsigned s = 32; s >= 1; s >>= 1) {
-        if (saver_fold_gives(lane, lanes, s)) part[threadIdx.x] = acc;      // a lane gives once: no slot is written twice, one barrier a level
-        __syncthreads();
-        if (saver_fold_takes(lane, lanes, s)) xyzz_add(acc, part[threadIdx.x + s]);
-    }
+    saver_fold_lds(acc, part, lane, lanes);
     if (lanes && lane == 0) sums[ballot * n_cols + c] = acc;
 }
 // canonical affine words of every sum (infinity: all zero), one inversion per point

@@ -61,6 +61,18 @@ VSP_HD void saver_lane_sum(XYZZ<F> &acc, const Affine<F> *tab, const uint64_t *s
 // l - s takes it (a full addition, complete as well); after level 1 lane 0 holds the column
 VSP_HD bool saver_fold_gives(unsigned lane, unsigned lanes, unsigned s) { return s < lanes && lane >= s && lane < 2 * s; }
 VSP_HD bool saver_fold_takes(unsigned lane, unsigned lanes, unsigned s) { return s < lanes && lane < s; }
+#if defined(__HIPCC__)
+// the fold in a kernel, through the block's LDS: part has a slot per thread (a group lies inside one wave, the barriers are the block's:
+// EVERY thread of the block calls this, an idle one with lanes = 0).  A lane gives once: no slot is written twice, one barrier a level
+template <class F> __device__ __forceinline__ void saver_fold_lds(XYZZ<F> &acc, XYZZ<F> *part, unsigned lane, unsigned lanes) {
+#pragma unroll 1
+    for (unsigned s = 32; s >= 1; s >>= 1) {
+        if (saver_fold_gives(lane, lanes, s)) part[threadIdx.x] = acc;
+        __syncthreads();
+        if (saver_fold_takes(lane, lanes, s)) xyzz_add(acc, part[threadIdx.x + s]);
+    }
+}
+#endif
 
 // the columns of a key of n message blocks, the pairs behind them, and the column of every lane of a ballot's span (SAVER_NO_COLUMN: an
 // idle lane).  Groups lie in the span by descending size, so none straddles a wave; the span is a whole number of waves.
