@@ -722,6 +722,51 @@ int vsp_saver_verify_batch_screened(vsp_ctx *ctx, const vsp_saver_verifier *ver,
                                     const uint64_t *coeff /* host n x 2, little-endian 128-bit, not zero */,
                                     uint8_t *verdict_out /* n: 1 accepted, 0 rejected */, uint8_t *reason_out /* n, may be NULL */);
 
+/* ---- ballots received from their blobs: one decode for verdicts and tally --------------------------------------------
+ * The ballot box's receiving step as one call: the wire in, verdicts and a running tally out.  A ballot arrives as three blobs -- the
+ * ciphertext vector (8 + 48 (msg_size + 2) bytes), the proof (192 bytes) and the remaining public inputs as a scalar vector exactly as
+ * vsp_fr_vector_to_blob writes it for n_rest = n_abc - 1 - msg_size scalars (8 + 32 n_rest bytes).  Every point is decoded once, on
+ * the device, and stays there for the verifier and the tally; no limb crosses PCIe.  The meaning is that of calls above:
+ * WIRE STATUS.  wire_status_out[3k] is the byte vsp_tally_add_blobs gives ciphertext blob k under the same check_subgroup (the count
+ * header against msg_size + 2 included); [3k + 1] is the byte vsp_proof_from_blob_batch gives proof k (bits 0..2 and 4..6); [3k + 2]
+ * is 0 when vsp_fr_vector_from_blob accepts input blob k with a count of exactly n_rest, else 1 (a wrong header or a scalar >= r).
+ * A ballot with any of the three set is WIRE-REJECTED: verdict 0, reason 1; for the screening it is what a malformed ballot is to
+ * vsp_saver_verify_batch_screened -- out of every sum and product, and it makes no range fail.
+ * VERDICTS.  For every other ballot verdict and reason equal what vsp_saver_verify_batch (coeff NULL: the exact path) or
+ * vsp_saver_verify_batch_screened (coeff set) gives on the limbs the decoders produce, every wire-rejected ballot replaced at its own
+ * index by a malformed one; options, coefficients and ranges go by the original indices.  All guarantees of the screened call carry
+ * over word for word: a verdict of 0 comes from the exact path, no valid ballot is ever rejected, and the SOUNDNESS conditions on the
+ * coefficients are unchanged.  SUBGROUP: with check_subgroup = 0 the caller vouches for the subgroups, as for the verify calls.
+ * TALLY.  With tally != NULL (its ct_len must be msg_size + 2) every ballot with verdict 1 is added to the handle: afterwards
+ * vsp_tally_result is what it would be had vsp_tally_add_blobs been given exactly the ciphertext blobs of those ballots.  Equal
+ * ballots, infinity members and a running sum passing through infinity are legal.  A piece is added whole, after its verdicts are
+ * known, or not at all: an error leaves the handle as it was after the last complete piece, and *accepted_out says how many ballots
+ * (verdict 1, of complete pieces) went in.
+ * RETURNS VSP_OK whatever the verdicts are; count = 0 with valid pointers is VSP_OK.  VSP_ERR_ARG before any GPU work for a null ver,
+ * ct_blobs, proof_blobs or verdict_out (also with count = 0), a null input_blobs with n_rest > 0, a tally of another ct_len, a
+ * verifier of another device, a zero coefficient and, with coeff set, a proof in flight on the context.  VSP_ERR_HIP as elsewhere;
+ * after an error nothing stays in flight on the work slots and the context is usable.
+ * PIECES of at most min("saver_screen_chunk", "tally_chunk_points" / (msg_size + 2)) ballots when screening; on the exact path
+ * "pairing_chunk" and its 2^19-argument bound take the place of "saver_screen_chunk".  A piece is at least one ballot.  Per piece:
+ * the ciphertext blobs are decoded and subgroup-checked into a workspace of their own, the proofs behind them, the input blobs by
+ * one lane per scalar; the verifier's piece is gathered from the decoded points -- the whole piece first, then the failing
+ * sub-ranges for the exact path -- and after the verdicts the accepted ballots' members are summed where they lie.
+ * Workspace bound per piece, beside the verifier's own without its canonical upload: per ballot max(8 + 48 (msg_size + 2), 192) raw
+ * bytes, 97 (msg_size + 2) bytes of decoded members and their status, 387 bytes of A, B, C and their status, 8 + 64 n_rest bytes of
+ * inputs and 5 status bytes; at most 768 KiB of partial sums -- 290 MiB at msg_size 25 with 5 rest inputs and 2^16 ballots.
+ * Statistics: the decoding, tally and verify stages feed their existing names ("tally_decode_ms", "tally_subgroup_ms",
+ * "g2_decode_ms", "g2_subgroup_ms", "tally_sum_ms", "saver_verify_*", "saver_screen_*"); "saver_receive_prepare_ms" is the time of
+ * the two kernels of this section by HIP events, "saver_receive_ballots" the ballots received, "saver_receive_wire_rejected" those
+ * wire-rejected. */
+int vsp_saver_receive_blobs(vsp_ctx *ctx, const vsp_saver_verifier *ver, vsp_tally *tally /* may be NULL */,
+                            const uint8_t *ct_blobs /* host, count x (8 + 48 (msg_size + 2)), back to back */,
+                            const uint8_t *proof_blobs /* host, count x 192 */,
+                            const uint8_t *input_blobs /* host, count x (8 + 32 n_rest); may be NULL when n_rest = 0 */,
+                            size_t count, int check_subgroup,
+                            const uint64_t *coeff /* host count x 2, little-endian 128-bit, none zero; NULL = the exact path */,
+                            uint8_t *verdict_out /* count */, uint8_t *reason_out /* count, may be NULL */,
+                            uint8_t *wire_status_out /* count x 3, may be NULL */, size_t *accepted_out /* may be NULL */);
+
 /* ---- SAVER decryption on the GPU: decrypt / verify_decryption<elgamal_verifiable> (common.hpp:1220-1223, 1282-1283) -----------------
  * The last step of the election: opening the aggregated ciphertext that vsp_tally_result returns, and checking a published result.
  * With n = msg_size, G_i = gamma_abc_g1[i], H the generator of G2, V_i = rho_sv_g2[i-1], W_i = rho_rhov_g2[i-1] (the verification key of

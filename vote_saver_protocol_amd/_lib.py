@@ -151,6 +151,7 @@ PROTOTYPES = {
     "vsp_saver_verifier_msg_size": (_SZ, [_P]),
     "vsp_saver_verify_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     "vsp_saver_verify_batch_screened": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P]),
+    "vsp_saver_receive_blobs": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P]),
     "vsp_saver_decryptor_create": (_P, [_P, _SZ, _P, _P, C.c_uint64]),
     "vsp_saver_decryptor_free": (None, [_P, _P]),
     "vsp_saver_decryptor_msg_size": (_SZ, [_P]),

@@ -1066,6 +1066,33 @@ def saver_verify_batch_screened(ctx, ver, ct, inputs_rest, A, B, Cc, coeff=None)
     return verdict, reason
 
 
+def saver_receive_blobs(ctx, ver, ct_blobs, proof_blobs, input_blobs, coeff=None, tally=None, check_subgroup=True):
+    """The ballot box's receiving step (vsp_saver_receive_blobs): n ballots as their blobs -- ct_blobs n x (8 + 48 (msg_size + 2))
+    bytes, proof_blobs n x 192, input_blobs n x (8 + 32 n_rest) scalar vectors of the remaining public inputs (None when there are
+    none); each one bytes object or a list of per-ballot blobs.  Decodes every point once on the GPU, gives the verdicts of
+    saver_verify_batch (coeff None) or saver_verify_batch_screened (coeff [n, 2], little-endian 128-bit words, none zero, fresh and
+    drawn after the ballots are fixed) and adds exactly the accepted ballots to `tally` (a Tally of ct_len msg_size + 2, or None).
+    Returns (verdict [n] uint8, reason [n] uint8, wire_status [n, 3] uint8: the bytes of Tally.add_blobs, proofs_from_blob_batch and
+    0 / 1 for the input blob; accepted).  A ballot with a wire status byte set has verdict 0 and reason 1."""
+    def joined(b):
+        return bytes(b) if isinstance(b, (bytes, bytearray, memoryview)) else b"".join(bytes(x) for x in b)
+    n_rest = ver.n_abc - 1 - ver.msg_size
+    ct = joined(ct_blobs); pr = joined(proof_blobs); inp = None if input_blobs is None else joined(input_blobs)
+    ct_size = 8 + 48 * (ver.msg_size + 2); in_size = 8 + 32 * n_rest
+    if len(ct) % ct_size or len(pr) != len(ct) // ct_size * 192 or (inp is not None and len(inp) != len(ct) // ct_size * in_size) or (inp is None and n_rest):
+        raise ValueError(f"saver_receive_blobs: n ciphertext blobs of {ct_size} bytes, n proofs of 192 bytes and n input blobs of {in_size} bytes expected")
+    n = len(ct) // ct_size
+    if coeff is not None:
+        coeff = _u64(coeff).reshape(-1, 2)
+        if coeff.shape[0] != n:
+            raise ValueError("saver_receive_blobs: n x 2 coefficient words expected")
+    verdict = np.zeros(n, np.uint8); reason = np.zeros(n, np.uint8); wire = np.zeros((n, 3), np.uint8); accepted = C.c_size_t(0)
+    bufs = [np.frombuffer(b if b else bytes(1), dtype=np.uint8) if b is not None else None for b in (ct, pr, inp)]
+    ctx.check(ctx.lib.vsp_saver_receive_blobs(ctx.h, ver.h, tally.h if tally is not None else None, _ptr(bufs[0]), _ptr(bufs[1]), _ptr(bufs[2]), n, int(check_subgroup),
+                                              _ptr(coeff), _ptr(verdict), _ptr(reason), _ptr(wire), C.byref(accepted)))
+    return verdict, reason, wire, accepted.value
+
+
 class SaverDecryptor:
     """The opening side of a SAVER election resident on the GPU (vsp_saver_decryptor), made of public data only: the prepared
     Miller-loop lines of rho_sv_g2, rho_rhov_g2, H and -rho_g2, the bases e(G_i, rho_rhov_g2[i]) and their baby-step tables for

@@ -69,6 +69,23 @@ struct DecodeWork {
     DevBuf pts, pstatus;
     StageTimer timer;
 };
+// a piece of ballots decoded from their blobs and resident on the device until the piece is finished (receive.hip): `count` ballots
+// of which the first is ballot `base` of the call.  Montgomery affine points as the decoder leaves them: the ciphertext members
+// ballot-major, members[k (n + 2) + j]; A of ballot k at ac[k], C at ac[count + k]; B at b[k]; the rest inputs as canonical words,
+// rest[(k n_rest + i) 8 ..]; the three wire status bytes of ballot k at wire[k], wire[stride + k], wire[2 stride + k]
+struct ReceivedPiece {
+    size_t base = 0, count = 0, wire_stride = 0;
+    const void *members = nullptr, *ac = nullptr, *b = nullptr;
+    const uint32_t *rest = nullptr;
+    const uint8_t *wire = nullptr;
+};
+// where the verifiers take the ballots of a piece from (pairing.hip saver_piece_prepare): canonical limbs of the whole call in host
+// memory -- ballots [at, at + c) are uploaded and checked by k_ballot_prepare -- or, with `dev` set, a range of a decoded piece, which
+// k_receive_prepare gathers.  Ballot indices are the call's in both
+struct BallotSource {
+    const uint64_t *ct = nullptr, *rest = nullptr, *A = nullptr, *B = nullptr, *C = nullptr;
+    const ReceivedPiece *dev = nullptr;
+};
 
 // stage [s0, s1) split of one NTT (see ntt.hip)
 struct NttTables {
@@ -241,6 +258,10 @@ struct vsp_ctx {
     // workspace; the timers around prepare | scale | Miller and tree, and around column sums | fixed-argument Miller | final exponentiation
     vsp::DevBuf screen_ws;
     vsp::StageTimer screen_timer[2];
+    // ballots received from their blobs (receive.hip): the decoded ciphertext members of a piece with their status bytes, the raw input
+    // blobs, the decoded rest inputs, the wire status bytes (3 x a stride); the timer around k_receive_scalars
+    vsp::DevBuf recv_members, recv_mstatus, recv_raw, recv_rest, recv_wire;
+    vsp::StageTimer recv_timer;
     // SAVER decryption (decrypt.hip): a result word per (ciphertext, slot) item and the pending count of the giant search; the timer around
     // the stages of vsp_saver_decrypt_batch / vsp_saver_verify_decryption_batch (prepare, values, search or powers) and around the table build
     vsp::DevBuf dec_out;
@@ -553,9 +574,23 @@ template <class G> int fixed_base_mul(vsp_ctx *ctx, const Fr *d_scalars, size_t 
 // point decoding (decode.hip).  Stages 1 and 2 over the points of group G already in ctx->tally_raw: `sets` sets of n points each, set k
 // at heads[k] of the same (per, stride) addressing, decoded one after the other into ctx->decode[G::ID - 1]; events 0, 1, 2 of its
 // timer around the stages, which decode_add_times adds to the stats ("tally_*" for G1, "g2_*" for G2; the subgroup stage on request)
-template <class G> int decode_points(vsp_ctx *ctx, size_t n, size_t per, size_t stride, const size_t *heads, size_t sets, int check_subgroup);
+// With dst / dst_status the points and their status bytes go there instead (room for sets n of each): a piece that needs more than
+// one decode of a group keeps the first (receive.hip)
+template <class G> int decode_points(vsp_ctx *ctx, size_t n, size_t per, size_t stride, const size_t *heads, size_t sets, int check_subgroup,
+                                     typename G::Point *dst = nullptr, uint8_t *dst_status = nullptr);
 template <class G> void decode_add_times(vsp_ctx *ctx, bool subgroup);
 size_t decode_chunk_points(const vsp_ctx *ctx);                 // points of one piece: option "tally_chunk_points"
+// k_proof_status over the m proofs just decoded into ctx->decode (A, C: decode[0], sets of m; B: decode[1]): a byte per proof to d_out
+int decode_proof_status(vsp_ctx *ctx, size_t m, uint8_t *d_out);
+// the tally's sum stage (tally.hip) over m resident ballots of ct_len members each, ballot-major; d_skip[b] not zero: ballot b adds
+// nothing.  tally_colsum_launch queues k_tally_colsum, event 3 of *sum_end behind it, and the copy of its partial sums into h_part
+// (parts x ct_len; valid once the stream is waited for); tally_fold adds them to the handle's running sums and `accepted` to its
+// ballot count.  tally_ballots_launch: k_tally_ballots, a status byte per ballot from its count header and its points' bytes
+int tally_colsum_launch(vsp_ctx *ctx, const void *d_pts, const uint8_t *d_skip, size_t m, size_t ct_len, std::vector<XYZZ<HFp>> &h_part, size_t *parts_out,
+                        StageTimer *sum_end);
+void tally_fold(vsp_tally *t, const std::vector<XYZZ<HFp>> &h_part, size_t parts, size_t accepted);
+size_t tally_ct_len(const vsp_tally *t);
+void tally_ballots_launch(vsp_ctx *ctx, const uint8_t *d_blobs, size_t m, size_t ct_len, const uint8_t *d_pstatus, uint8_t *d_bstatus);
 // pairings and Groth16 verdicts (pairing.hip); the arguments are checked by the exports in capi.hip
 int pairing_multi_batch(vsp_ctx *ctx, const uint64_t *g1, const uint64_t *g2, size_t m, size_t n, uint8_t *gt_out, uint8_t *is_one_out);
 vsp_vk *pairing_vk_create(vsp_ctx *ctx, const uint64_t *alpha_g1, const uint64_t *beta_g2, const uint64_t *gamma_g2, const uint64_t *delta_g2, const uint64_t *gamma_abc_g1,
@@ -572,14 +607,23 @@ size_t saver_verifier_msg_size(const vsp_saver_verifier *ver);
 size_t saver_verifier_n_rest(const vsp_saver_verifier *ver);
 int saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *inputs_rest, const uint64_t *A, const uint64_t *B,
                        const uint64_t *C, size_t n, uint8_t *verdict_out, uint8_t *reason_out);
-// one piece of ballots (pairing.hip): c ballots from ballot `at` on uploaded and k_ballot_prepare run between events 0 and 1 of `timer`.
+// the same over ballots [first, first + n) of a source: verdict_out[i], reason_out[i] belong to ballot first + i
+int saver_verify_source(vsp_ctx *ctx, const vsp_saver_verifier *ver, const BallotSource &src, size_t first, size_t n, uint8_t *verdict_out, uint8_t *reason_out);
+size_t saver_exact_piece(const vsp_ctx *ctx, size_t msg_size);  // ballots of one piece of the exact path: "pairing_chunk" and the 2^19-argument bound
+// one piece of ballots (pairing.hip): the c ballots from ballot `at` of the source on, prepared between events 0 and 1 of `timer` --
+// host limbs uploaded and k_ballot_prepare run, or a range of a decoded piece gathered by k_receive_prepare (receive.hip).
 // Leaves the arguments c_0 .. c_n | psi | acc | C column by column and A in ctx->pair_g1 ((n + 5) c points), B in ctx->pair_g2, the
 // status bytes in ctx->pair_status (room for 3 c)
-int saver_piece_prepare(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *inputs_rest, const uint64_t *A, const uint64_t *B,
-                        const uint64_t *C, size_t at, size_t c, StageTimer &timer);
+int saver_piece_prepare(vsp_ctx *ctx, const vsp_saver_verifier *ver, const BallotSource &src, size_t at, size_t c, StageTimer &timer);
+// the device half of it for a decoded piece (receive.hip): ballots [lo, lo + c) of the piece
+int receive_piece_prepare(vsp_ctx *ctx, const vsp_saver_verifier *ver, const ReceivedPiece &rp, size_t lo, size_t c, void *d_pts, void *d_a, void *d_b, uint8_t *d_status);
 // the screened check (screen.hip); coeff: count x 2 words, none zero (capi.hip checks)
 int saver_verify_batch_screened(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *inputs_rest, const uint64_t *A, const uint64_t *B,
                                 const uint64_t *C, size_t n, const uint64_t *coeff, uint8_t *verdict_out, uint8_t *reason_out);
+// one piece of it: ballots [at, at + c) of the source, c at most screen_piece_ballots; coeff, verdict_out, reason_out are the call's
+// (indexed by ballot).  The caller drains the work slots after an error
+int screen_piece(vsp_ctx *ctx, const vsp_saver_verifier *ver, const BallotSource &src, size_t at, size_t c, const uint64_t *coeff, uint8_t *verdict_out, uint8_t *reason_out);
+size_t screen_piece_ballots(const vsp_ctx *ctx);                // option "saver_screen_chunk"
 // stage 1 of pairing.hip on its own: the Miller values of n device pairs (Montgomery affine points; infinity gives one)
 int pairing_miller(vsp_ctx *ctx, const void *d_g1, const void *d_g2, size_t n, void *d_out);
 // the final exponentiation of n Miller values on the device (stage 3 of pairing.hip on its own): canonical GT values and is-one bytes

@@ -52,30 +52,42 @@ size_t decode_chunk_points(const vsp_ctx *ctx) {
     const long v = opt(ctx, "tally_chunk_points", (long)DECODE_CHUNK_POINTS);
     return v < 1 ? 1 : ((size_t)v > DECODE_CHUNK_POINTS ? DECODE_CHUNK_POINTS : (size_t)v);
 }
-template <class G> int decode_points(vsp_ctx *ctx, size_t n, size_t per, size_t stride, const size_t *heads, size_t sets, int check_subgroup) {
+template <class G> int decode_points(vsp_ctx *ctx, size_t n, size_t per, size_t stride, const size_t *heads, size_t sets, int check_subgroup, typename G::Point *dst,
+                                     uint8_t *dst_status) {
     using Point = typename G::Point;
     hipStream_t st = ctx->stream;
     DecodeWork &w = ctx->decode[G::ID - 1];
-    VSP_TRY(ensure(ctx, w.pts, sets * n * sizeof(Point)));
-    VSP_TRY(ensure(ctx, w.pstatus, sets * n));
+    if (!dst) {
+        VSP_TRY(ensure(ctx, w.pts, sets * n * sizeof(Point)));
+        VSP_TRY(ensure(ctx, w.pstatus, sets * n));
+        dst = (Point *)w.pts.p; dst_status = (uint8_t *)w.pstatus.p;
+    }
     VSP_TRY(w.timer.mark(ctx, 0, st));
     for (size_t k = 0; k < sets; k++)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_decode<G>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const uint8_t *)ctx->tally_raw.p, n, per, stride,
-                           heads[k], (Point *)w.pts.p + k * n, (uint8_t *)w.pstatus.p + k * n);
+                           heads[k], dst + k * n, dst_status + k * n);
     VSP_LAUNCH_CHECK();
     VSP_TRY(w.timer.mark(ctx, 1, st));
     // rejected points are infinity by now, which the check passes over: their bytes keep the decoder's verdict
-    if (check_subgroup) VSP_TRY(subgroup_check<G>(ctx, (const Point *)w.pts.p, sets * n, nullptr, (uint8_t *)w.pstatus.p));
+    if (check_subgroup) VSP_TRY(subgroup_check<G>(ctx, (const Point *)dst, sets * n, nullptr, dst_status));
     VSP_TRY(w.timer.mark(ctx, 2, st));
     return VSP_OK;
 }
-template int decode_points<G1>(vsp_ctx *, size_t, size_t, size_t, const size_t *, size_t, int);
+template int decode_points<G1>(vsp_ctx *, size_t, size_t, size_t, const size_t *, size_t, int, G1Affine *, uint8_t *);
+template int decode_points<G2>(vsp_ctx *, size_t, size_t, size_t, const size_t *, size_t, int, G2Affine *, uint8_t *);
 template <class G> void decode_add_times(vsp_ctx *ctx, bool subgroup) {
     const StageTimer &t = ctx->decode[G::ID - 1].timer;
     t.add(ctx, 0, G::ID == 1 ? "tally_decode_ms" : "g2_decode_ms");
     if (subgroup) t.add(ctx, 1, G::ID == 1 ? "tally_subgroup_ms" : "g2_subgroup_ms");
 }
 template void decode_add_times<G1>(vsp_ctx *, bool);
+template void decode_add_times<G2>(vsp_ctx *, bool);
+int decode_proof_status(vsp_ctx *ctx, size_t m, uint8_t *d_out) {
+    hipLaunchKernelGGL(k_proof_status, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, (const uint8_t *)ctx->decode[0].pstatus.p,
+                       (const uint8_t *)ctx->decode[1].pstatus.p, m, d_out);
+    VSP_LAUNCH_CHECK();
+    return VSP_OK;
+}
 // Montgomery -> canonical (zero where `status` is set) and the copy to the host, for n points of either group
 template <class F> static int export_points(vsp_ctx *ctx, Affine<F> *pts, const uint8_t *status, size_t n, uint64_t *out) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_point_export<F>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, pts, status, n);
@@ -136,9 +148,7 @@ int vsp_proof_from_blob_batch(vsp_ctx *ctx, const uint8_t *blobs, size_t n, int 
         VSP_TRY(decode_points<G1>(ctx, m, 1, 192, heads, 2, check_subgroup));     // A: points [0, m), C: [m, 2m)
         VSP_TRY(decode_points<G2>(ctx, m, 1, 192, &head_b, 1, check_subgroup));
         const uint8_t *pstatus = (const uint8_t *)ctx->tally_bstatus.p;
-        hipLaunchKernelGGL(k_proof_status, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint8_t *)w1.pstatus.p, (const uint8_t *)w2.pstatus.p, m,
-                           (uint8_t *)ctx->tally_bstatus.p);
-        VSP_LAUNCH_CHECK();
+        VSP_TRY(decode_proof_status(ctx, m, (uint8_t *)ctx->tally_bstatus.p));
         if (A_out) VSP_TRY(export_points(ctx, (G1Affine *)w1.pts.p, pstatus, m, A_out + 12 * at));
         if (C_out) VSP_TRY(export_points(ctx, (G1Affine *)w1.pts.p + m, pstatus, m, C_out + 12 * at));
         if (B_out) VSP_TRY(export_points(ctx, (G2Affine *)w2.pts.p, pstatus, m, B_out + 24 * at));

@@ -40,31 +40,7 @@ __device__ __noinline__ uint32_t pr_load_g2(const uint64_t *src, G2Affine *out) 
     *out = p;
     return st;
 }
-// the L canonical scalars at s (8 words each) all below r
-__device__ __forceinline__ bool pr_scalars_below_r(const uint32_t *s, size_t L) {
-    bool ok = true;
-    for (size_t i = 0; i < L; i++) {
-        const uint4 lo = *(const uint4 *)(s + 8 * i), hi = *(const uint4 *)(s + 8 * i + 4);
-        if (!scalar_below_r(lo, hi)) ok = false;
-    }
-    return ok;
-}
-// acc = sum s_i G_i over the key's table of multiples, rows[i * 16 + d] = d G_i: 4 bits of every scalar at a time from the top, 4
-// doublings, then one table row per input
-__device__ __forceinline__ void pr_input_sum(G1XYZZ &acc, const uint32_t *s, size_t L, const G1Affine *__restrict__ rows) {
-    acc = G1XYZZ::inf();
-    if (!L) return;
-#pragma unroll 1
-    for (int w = 63; w >= 0; w--) {
-        if (w != 63) { pr_dbl(&acc); pr_dbl(&acc); pr_dbl(&acc); pr_dbl(&acc); }
-#pragma unroll 1
-        for (size_t i = 0; i < L; i++) {
-            const uint32_t d = (s[8 * i + (w >> 3)] >> ((w & 7) * 4)) & 15u;
-            G1Affine t = rows[i * 16 + d];
-            pr_madd(&acc, &t);
-        }
-    }
-}
+// pr_scalars_below_r, pr_input_sum, pr_ballot_acc_start: pairing_g1.h
 
 __global__ __launch_bounds__(PAIRING_THREADS) void k_pair_check(const uint64_t *__restrict__ g1, const uint64_t *__restrict__ g2, size_t n, G1Affine *__restrict__ p_out,
                                                                 G2Affine *__restrict__ q_out, uint8_t *__restrict__ status, uint32_t *__restrict__ flag) {
@@ -165,8 +141,7 @@ __global__ __launch_bounds__(PAIRING_THREADS) void k_ballot_prepare(const uint64
     const uint32_t *s = rest + k * L * 8;
     if (!pr_scalars_below_r(s, L)) st |= 1u;
     G1XYZZ acc;
-    pr_input_sum(acc, s, L, tab + (n + 1) * 16);
-    { G1Affine g0 = tab[1]; pr_madd(&acc, &g0); }
+    pr_ballot_acc_start(acc, s, L, n, tab);
 #pragma unroll 1
     for (size_t j = 0; j < n + 2; j++) {
         st |= pr_load_g1(ct + (k * (n + 2) + j) * 12, &P);
@@ -409,20 +384,26 @@ vsp_saver_verifier *saver_verifier_create(vsp_ctx *ctx, size_t n, const uint64_t
     return ver;
 }
 
-int saver_piece_prepare(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *rest, const uint64_t *A, const uint64_t *B, const uint64_t *C,
-                        size_t at, size_t c, StageTimer &timer) {
+int saver_piece_prepare(vsp_ctx *ctx, const vsp_saver_verifier *ver, const BallotSource &src, size_t at, size_t c, StageTimer &timer) {
     hipStream_t st = ctx->stream;
     const size_t n = ver->n, L = ver->vk->n_abc - 1 - n;
-    const size_t ct_words = c * (n + 2) * 12;
-    VSP_TRY(ensure(ctx, ctx->pair_raw, (ct_words + proof_words(c, L)) * sizeof(uint64_t)));
     VSP_TRY(ensure(ctx, ctx->pair_g1, (n + 5) * c * sizeof(G1Affine)));                              // n + 4 prepared-side arguments, then A
     VSP_TRY(ensure(ctx, ctx->pair_g2, c * sizeof(G2Affine)));
     VSP_TRY(ensure(ctx, ctx->pair_status, 3 * c));                                                   // malformed | equation 1 | equation 2
-    uint64_t *d_ct = (uint64_t *)ctx->pair_raw.p;
     G1Affine *pts = (G1Affine *)ctx->pair_g1.p, *a_pts = pts + (n + 4) * c;
-    VSP_HIP(hipMemcpyAsync(d_ct, ct + at * (n + 2) * 12, ct_words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (src.dev) {
+        // a range of a decoded piece: nothing to upload
+        VSP_TRY(timer.mark(ctx, 0, st));
+        VSP_TRY(receive_piece_prepare(ctx, ver, *src.dev, at - src.dev->base, c, pts, a_pts, ctx->pair_g2.p, (uint8_t *)ctx->pair_status.p));
+        VSP_TRY(timer.mark(ctx, 1, st));
+        return VSP_OK;
+    }
+    const size_t ct_words = c * (n + 2) * 12;
+    VSP_TRY(ensure(ctx, ctx->pair_raw, (ct_words + proof_words(c, L)) * sizeof(uint64_t)));
+    uint64_t *d_ct = (uint64_t *)ctx->pair_raw.p;
+    VSP_HIP(hipMemcpyAsync(d_ct, src.ct + at * (n + 2) * 12, ct_words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     ProofArgs d;
-    VSP_TRY(upload_proofs(ctx, d_ct + ct_words, A, B, C, rest, at, c, L, d));
+    VSP_TRY(upload_proofs(ctx, d_ct + ct_words, src.A, src.B, src.C, src.rest, at, c, L, d));
     VSP_TRY(timer.mark(ctx, 0, st));
     hipLaunchKernelGGL(k_ballot_prepare, dim3((unsigned)((c + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, d_ct, d.scalars, d.A, d.B, d.C, c, n,
                        ver->vk->n_abc, (const G1Affine *)ver->vk->d_tab, pts, a_pts, (G2Affine *)ctx->pair_g2.p, (uint8_t *)ctx->pair_status.p);
@@ -431,51 +412,70 @@ int saver_piece_prepare(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint6
     return VSP_OK;
 }
 
-int saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *rest, const uint64_t *A, const uint64_t *B, const uint64_t *C, size_t count,
-                       uint8_t *verdict_out, uint8_t *reason_out) {
-    if (ver->device != ctx->device) return set_error(ctx, VSP_ERR_ARG, "saver_verify_batch: the verifier belongs to another device");
-    VSP_HIP(hipSetDevice(ctx->device));
+// the exact verdicts of a prepared piece of c ballots (what saver_piece_prepare left, events 0 and 1 of ctx->saver_timer around it):
+// the Miller groups of G pairs, their products, both final exponentiations in one launch and the read-back
+static int saver_piece_judge(vsp_ctx *ctx, const vsp_saver_verifier *ver, size_t c, size_t G, size_t ng, bool from_device, std::vector<uint8_t> &flags, uint8_t *verdict_out,
+                             uint8_t *reason_out) {
     hipStream_t st = ctx->stream;
     const size_t n = ver->n;
-    // ballots of one piece: "pairing_chunk" as for the pairings, and at most 2^19 G1 arguments (a ballot has n + 5; never split)
+    VSP_TRY(ensure(ctx, ctx->pair_ml, (ng + 1) * c * sizeof(Fp12)));
+    VSP_TRY(ensure(ctx, ctx->pair_prod, 2 * c * sizeof(Fp12)));
+    G1Affine *pts = (G1Affine *)ctx->pair_g1.p, *a_pts = pts + (n + 4) * c;
+    uint8_t *status = (uint8_t *)ctx->pair_status.p;
+    const unsigned blocks = (unsigned)((c + PAIRING_THREADS - 1) / PAIRING_THREADS);
+    hipLaunchKernelGGL(k_miller_ballot, dim3(blocks, (unsigned)(ng + 1)), dim3(PAIRING_THREADS), 0, st, (const G1Affine *)pts, (const G1Affine *)a_pts,
+                       (const G2Affine *)ctx->pair_g2.p, (const LineCoeffs<Fp> *)ver->d_lines, c, n, G, ng, (Fp12 *)ctx->pair_ml.p);
+    VSP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_ballot_product, dim3(blocks), dim3(PAIRING_THREADS), 0, st, (const Fp12 *)ctx->pair_ml.p, c, ng, (Fp12 *)ctx->pair_prod.p);
+    VSP_LAUNCH_CHECK();
+    VSP_TRY(ctx->saver_timer.mark(ctx, 2, st));
+    // both final exponentiations of a piece in one launch: flag[i] for i < c says "equation 1 of ballot i holds" (the value is one),
+    // for i >= c "equation 2 of ballot i - c holds" (the value is the key's e(alpha, beta))
+    hipLaunchKernelGGL(k_final_exp, dim3((unsigned)((2 * c + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, (const Fp12 *)ctx->pair_prod.p,
+                       (const uint8_t *)nullptr, 2 * c, c, (const Fp12 *)ver->vk->d_expect, (Fp12 *)nullptr, status + c);
+    VSP_LAUNCH_CHECK();
+    VSP_TRY(ctx->saver_timer.mark(ctx, 3, st));
+    flags.resize(3 * c);
+    VSP_HIP(hipMemcpyAsync(flags.data(), status, 3 * c, hipMemcpyDeviceToHost, st));
+    VSP_HIP(hipStreamSynchronize(st));
+    for (size_t k = 0; k < c; k++) {
+        const uint8_t reason = flags[k] ? 1 : (uint8_t)((flags[c + k] ? 0 : 2) | (flags[2 * c + k] ? 0 : 4));
+        verdict_out[k] = reason == 0;
+        if (reason_out) reason_out[k] = reason;
+    }
+    static const char *const names[3] = {"saver_verify_prepare_ms", "saver_verify_miller_ms", "saver_verify_finalexp_ms"};
+    for (int i = 0; i < 3; i++) ctx->saver_timer.add(ctx, i, names[i]);
+    if (from_device) ctx->saver_timer.add(ctx, 0, "saver_receive_prepare_ms");
+    return VSP_OK;
+}
+
+// ballots of one piece: "pairing_chunk" as for the pairings, and at most 2^19 G1 arguments (a ballot has n + 5; never split)
+size_t saver_exact_piece(const vsp_ctx *ctx, size_t n) {
     size_t piece = pairing_piece(ctx, 1);
     if (piece * (n + 5) > SAVER_MAX_ARGS) piece = SAVER_MAX_ARGS / (n + 5);
+    return piece;
+}
+
+int saver_verify_source(vsp_ctx *ctx, const vsp_saver_verifier *ver, const BallotSource &src, size_t first, size_t count, uint8_t *verdict_out, uint8_t *reason_out) {
+    if (ver->device != ctx->device) return set_error(ctx, VSP_ERR_ARG, "saver_verify_batch: the verifier belongs to another device");
+    VSP_HIP(hipSetDevice(ctx->device));
+    const size_t n = ver->n, piece = saver_exact_piece(ctx, n);
     // groups of the ciphertext equation: option "saver_verify_group" pairs each
     const long gv = opt(ctx, "saver_verify_group", 9);
     const size_t G = gv < 1 ? 1 : ((size_t)gv > n + 2 ? n + 2 : (size_t)gv), ng = (n + 2 + G - 1) / G;
     std::vector<uint8_t> flags;
     for (size_t at = 0; at < count; at += piece) {
         const size_t c = count - at < piece ? count - at : piece;
-        VSP_TRY(saver_piece_prepare(ctx, ver, ct, rest, A, B, C, at, c, ctx->saver_timer));
-        VSP_TRY(ensure(ctx, ctx->pair_ml, (ng + 1) * c * sizeof(Fp12)));
-        VSP_TRY(ensure(ctx, ctx->pair_prod, 2 * c * sizeof(Fp12)));
-        G1Affine *pts = (G1Affine *)ctx->pair_g1.p, *a_pts = pts + (n + 4) * c;
-        uint8_t *status = (uint8_t *)ctx->pair_status.p;
-        const unsigned blocks = (unsigned)((c + PAIRING_THREADS - 1) / PAIRING_THREADS);
-        hipLaunchKernelGGL(k_miller_ballot, dim3(blocks, (unsigned)(ng + 1)), dim3(PAIRING_THREADS), 0, st, (const G1Affine *)pts, (const G1Affine *)a_pts,
-                           (const G2Affine *)ctx->pair_g2.p, (const LineCoeffs<Fp> *)ver->d_lines, c, n, G, ng, (Fp12 *)ctx->pair_ml.p);
-        VSP_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_ballot_product, dim3(blocks), dim3(PAIRING_THREADS), 0, st, (const Fp12 *)ctx->pair_ml.p, c, ng, (Fp12 *)ctx->pair_prod.p);
-        VSP_LAUNCH_CHECK();
-        VSP_TRY(ctx->saver_timer.mark(ctx, 2, st));
-        // both final exponentiations of a piece in one launch: flag[i] for i < c says "equation 1 of ballot i holds" (the value is one),
-        // for i >= c "equation 2 of ballot i - c holds" (the value is the key's e(alpha, beta))
-        hipLaunchKernelGGL(k_final_exp, dim3((unsigned)((2 * c + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, (const Fp12 *)ctx->pair_prod.p,
-                           (const uint8_t *)nullptr, 2 * c, c, (const Fp12 *)ver->vk->d_expect, (Fp12 *)nullptr, status + c);
-        VSP_LAUNCH_CHECK();
-        VSP_TRY(ctx->saver_timer.mark(ctx, 3, st));
-        flags.resize(3 * c);
-        VSP_HIP(hipMemcpyAsync(flags.data(), status, 3 * c, hipMemcpyDeviceToHost, st));
-        VSP_HIP(hipStreamSynchronize(st));
-        for (size_t k = 0; k < c; k++) {
-            const uint8_t reason = flags[k] ? 1 : (uint8_t)((flags[c + k] ? 0 : 2) | (flags[2 * c + k] ? 0 : 4));
-            verdict_out[at + k] = reason == 0;
-            if (reason_out) reason_out[at + k] = reason;
-        }
-        static const char *const names[3] = {"saver_verify_prepare_ms", "saver_verify_miller_ms", "saver_verify_finalexp_ms"};
-        for (int i = 0; i < 3; i++) ctx->saver_timer.add(ctx, i, names[i]);
+        VSP_TRY(saver_piece_prepare(ctx, ver, src, first + at, c, ctx->saver_timer));
+        VSP_TRY(saver_piece_judge(ctx, ver, c, G, ng, src.dev != nullptr, flags, verdict_out + at, reason_out ? reason_out + at : nullptr));
     }
     return VSP_OK;
+}
+int saver_verify_batch(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *rest, const uint64_t *A, const uint64_t *B, const uint64_t *C, size_t count,
+                       uint8_t *verdict_out, uint8_t *reason_out) {
+    BallotSource src;
+    src.ct = ct; src.rest = rest; src.A = A; src.B = B; src.C = C;
+    return saver_verify_source(ctx, ver, src, 0, count, verdict_out, reason_out);
 }
 
 }  // namespace vsp

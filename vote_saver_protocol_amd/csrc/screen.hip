@@ -3,9 +3,10 @@
 //     equation 1:  fexp( prod_{j=0..n} ml(S_j, t_g2[j]) * ml(S_psi, -H) ) = 1
 //     equation 2:  fexp( prod_{i in R} ml(z_i A_i, B_i) * ml(ACC, -gamma_g2) * ml(Csum, -delta_g2) * ml(-Z alpha_g1, beta_g2) ) = 1
 // S_j = sum z_i c_{i,j}, S_psi = sum z_i psi_i, ACC = sum z_i acc_i, Csum = sum z_i C_i, Z = sum z_i mod r.  A range that fails is cut
-// once into "saver_screen_split" sub-ranges, and the sub-ranges that fail go to the exact path (pairing.hip saver_verify_batch), which
+// once into "saver_screen_split" sub-ranges, and the sub-ranges that fail go to the exact path (pairing.hip saver_verify_source), which
 // alone gives a verdict of 0 and its reason.  Stages per piece of a call:
-//   0. k_ballot_prepare    (pairing.hip, unchanged) the arguments column by column, A, B, a status byte per ballot
+//   0. k_ballot_prepare    (pairing.hip, unchanged; k_receive_prepare of receive.hip for a decoded piece) the arguments column by column, A, B,
+//                          a status byte per ballot
 //   1. k_screen_scale      one lane per ballot: A_i <- z_i A_i, z_i widened to a canonical scalar; a malformed ballot: infinity and 0;
 //                          then the digit sort and bucket plan over the z of the piece (step 4), so that its column sums run beside step 2
 //   2. k_miller            (pairing.hip) one lane per ballot: ml(z_i A_i, B_i), kept for the second level
@@ -114,6 +115,7 @@ struct ScreenPiece {
     size_t c, n, na;                        // ballots, msg_size, arguments of a range (n + 5)
     const uint64_t *coeff;                  // the piece's coefficients (host)
     const uint8_t *status;                  // the piece's status bytes (host)
+    bool from_device;                       // prepared by k_receive_prepare: its time counts as "saver_receive_prepare_ms" too
     ScreenWork w;
 };
 
@@ -198,6 +200,7 @@ int screen_level(ScreenPiece &p, size_t len, bool first, std::vector<uint8_t> &h
     for (size_t r = 0; r < R; r++) { holds[r] = flags[2 * r] && flags[2 * r + 1]; failed += !holds[r]; }
     ctx->stats["saver_screen_checks"] += (double)R;
     ctx->stats["saver_screen_failed"] += (double)failed;
+    if (first && p.from_device) t0.add(ctx, 0, "saver_receive_prepare_ms");
     t0.add(ctx, 0, "saver_screen_prepare_ms"); t0.add(ctx, 1, "saver_screen_scale_ms"); t0.add(ctx, 2, "saver_screen_miller_ms");
     t1.add(ctx, 0, "saver_screen_msm_ms"); t1.add(ctx, 1, "saver_screen_miller_ms"); t1.add(ctx, 2, "saver_screen_finalexp_ms");
     return VSP_OK;
@@ -205,70 +208,77 @@ int screen_level(ScreenPiece &p, size_t len, bool first, std::vector<uint8_t> &h
 
 }  // anonymous namespace
 
-static int screen_pieces(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *rest, const uint64_t *A, const uint64_t *B, const uint64_t *C,
-                         size_t count, const uint64_t *coeff, uint8_t *verdict_out, uint8_t *reason_out) {
+size_t screen_piece_ballots(const vsp_ctx *ctx) {
+    const long cv = opt(ctx, "saver_screen_chunk", (long)SCREEN_CHUNK);
+    return cv < 1 ? 1 : ((size_t)cv > SCREEN_CHUNK_MAX ? SCREEN_CHUNK_MAX : (size_t)cv);
+}
+
+int screen_piece(vsp_ctx *ctx, const vsp_saver_verifier *ver, const BallotSource &src, size_t at, size_t c, const uint64_t *coeff, uint8_t *verdict_out, uint8_t *reason_out) {
+    hipStream_t st = ctx->stream;
+    const size_t n = ver->n, na = n + 5;
+    const long sv = opt(ctx, "saver_screen_split", SCREEN_SPLIT);
+    const size_t split = sv < 2 ? 1 : ((size_t)sv > SCREEN_SPLIT_MAX ? SCREEN_SPLIT_MAX : (size_t)sv);
+    std::vector<uint8_t> status, holds;
+    // 0. to 2.
+    VSP_TRY(saver_piece_prepare(ctx, ver, src, at, c, ctx->screen_timer[0]));
+    VSP_TRY(ensure(ctx, ctx->pair_ml, c * sizeof(Fp12)));
+    VSP_TRY(ensure(ctx, ctx->screen_ws, ScreenWork::bytes(c, split, na)));
+    ScreenPiece p{ctx, ver, c, n, na, coeff + 2 * at, nullptr, src.dev != nullptr, ScreenWork(ctx->screen_ws.p, c, split, na)};
+    G1Affine *a_pts = (G1Affine *)ctx->pair_g1.p + (n + 4) * c;
+    const uint8_t *d_status = (const uint8_t *)ctx->pair_status.p;
+    status.resize(c);
+    VSP_HIP(hipMemcpyAsync(status.data(), d_status, c, hipMemcpyDeviceToHost, st));
+    VSP_HIP(hipEventRecord(ctx->ev_aux, st));
+    VSP_HIP(hipMemcpyAsync(p.w.coeff, p.coeff, c * 16, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_screen_scale, dim3((unsigned)((c + SCREEN_THREADS - 1) / SCREEN_THREADS)), dim3(SCREEN_THREADS), 0, st, a_pts, d_status, (const uint64_t *)p.w.coeff, c,
+                       p.w.z);
+    VSP_LAUNCH_CHECK();
+    // the plan of the whole piece goes in front of the Miller loops: the column sums (other streams) wait for the plan alone and
+    // run beside them
+    VSP_TRY(screen_plan(ctx, p.w.z, c));
+    VSP_TRY(ctx->screen_timer[0].mark(ctx, 2, st));
+    VSP_TRY(pairing_miller(ctx, a_pts, ctx->pair_g2.p, c, ctx->pair_ml.p));
+    VSP_HIP(hipEventSynchronize(ctx->ev_aux));                   // the status bytes alone: the stream runs on
+    p.status = status.data();
+    // a malformed ballot's verdict is the exact path's own: the status byte of the same kernel
+    for (size_t k = 0; k < c; k++) {
+        verdict_out[at + k] = status[k] == 0;
+        if (reason_out) reason_out[at + k] = status[k] ? 1 : 0;
+    }
+    VSP_TRY(screen_level(p, c, true, holds));
+    if (holds[0]) return VSP_OK;
+    // the second level, then the exact path over runs of failed sub-ranges
+    size_t len = c;
+    if (split > 1 && c > 1) {
+        len = (c + split - 1) / split;
+        VSP_TRY(screen_level(p, len, false, holds));
+    }
+    const size_t R = (c + len - 1) / len;
+    for (size_t r = 0; r < R;) {
+        if (holds[r]) { r++; continue; }
+        size_t e = r + 1;
+        while (e < R && !holds[e]) e++;
+        const size_t lo = at + r * len, hi = e * len < c ? at + e * len : at + c;
+        VSP_TRY(saver_verify_source(ctx, ver, src, lo, hi - lo, verdict_out + lo, reason_out ? reason_out + lo : nullptr));
+        ctx->stats["saver_screen_exact_ballots"] += (double)(hi - lo);
+        r = e;
+    }
+    return VSP_OK;
+}
+
+static int screen_pieces(vsp_ctx *ctx, const vsp_saver_verifier *ver, const BallotSource &src, size_t count, const uint64_t *coeff, uint8_t *verdict_out, uint8_t *reason_out) {
     if (ver->device != ctx->device) return set_error(ctx, VSP_ERR_ARG, "saver_verify_batch_screened: the verifier belongs to another device");
     if (ctx->prove.active) return set_error(ctx, VSP_ERR_ARG, "saver_verify_batch_screened: a proof is in flight on this context and owns the work slots (finish it first)");
     VSP_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const size_t n = ver->n, na = n + 5, L = ver->vk->n_abc - 1 - n;
-    const long cv = opt(ctx, "saver_screen_chunk", (long)SCREEN_CHUNK), sv = opt(ctx, "saver_screen_split", SCREEN_SPLIT);
-    const size_t piece = cv < 1 ? 1 : ((size_t)cv > SCREEN_CHUNK_MAX ? SCREEN_CHUNK_MAX : (size_t)cv);
-    const size_t split = sv < 2 ? 1 : ((size_t)sv > SCREEN_SPLIT_MAX ? SCREEN_SPLIT_MAX : (size_t)sv);
-    std::vector<uint8_t> status, holds;
-    for (size_t at = 0; at < count; at += piece) {
-        const size_t c = count - at < piece ? count - at : piece;
-        // 0. to 2.
-        VSP_TRY(saver_piece_prepare(ctx, ver, ct, rest, A, B, C, at, c, ctx->screen_timer[0]));
-        VSP_TRY(ensure(ctx, ctx->pair_ml, c * sizeof(Fp12)));
-        VSP_TRY(ensure(ctx, ctx->screen_ws, ScreenWork::bytes(c, split, na)));
-        ScreenPiece p{ctx, ver, c, n, na, coeff + 2 * at, nullptr, ScreenWork(ctx->screen_ws.p, c, split, na)};
-        G1Affine *a_pts = (G1Affine *)ctx->pair_g1.p + (n + 4) * c;
-        const uint8_t *d_status = (const uint8_t *)ctx->pair_status.p;
-        status.resize(c);
-        VSP_HIP(hipMemcpyAsync(status.data(), d_status, c, hipMemcpyDeviceToHost, st));
-        VSP_HIP(hipEventRecord(ctx->ev_aux, st));
-        VSP_HIP(hipMemcpyAsync(p.w.coeff, p.coeff, c * 16, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_screen_scale, dim3((unsigned)((c + SCREEN_THREADS - 1) / SCREEN_THREADS)), dim3(SCREEN_THREADS), 0, st, a_pts, d_status, (const uint64_t *)p.w.coeff, c,
-                           p.w.z);
-        VSP_LAUNCH_CHECK();
-        // the plan of the whole piece goes in front of the Miller loops: the column sums (other streams) wait for the plan alone and
-        // run beside them
-        VSP_TRY(screen_plan(ctx, p.w.z, c));
-        VSP_TRY(ctx->screen_timer[0].mark(ctx, 2, st));
-        VSP_TRY(pairing_miller(ctx, a_pts, ctx->pair_g2.p, c, ctx->pair_ml.p));
-        VSP_HIP(hipEventSynchronize(ctx->ev_aux));                   // the status bytes alone: the stream runs on
-        p.status = status.data();
-        // a malformed ballot's verdict is the exact path's own: the status byte of the same kernel
-        for (size_t k = 0; k < c; k++) {
-            verdict_out[at + k] = status[k] == 0;
-            if (reason_out) reason_out[at + k] = status[k] ? 1 : 0;
-        }
-        VSP_TRY(screen_level(p, c, true, holds));
-        if (holds[0]) continue;
-        // the second level, then the exact path over runs of failed sub-ranges
-        size_t len = c;
-        if (split > 1 && c > 1) {
-            len = (c + split - 1) / split;
-            VSP_TRY(screen_level(p, len, false, holds));
-        }
-        const size_t R = (c + len - 1) / len;
-        for (size_t r = 0; r < R;) {
-            if (holds[r]) { r++; continue; }
-            size_t e = r + 1;
-            while (e < R && !holds[e]) e++;
-            const size_t lo = at + r * len, hi = e * len < c ? at + e * len : at + c;
-            VSP_TRY(saver_verify_batch(ctx, ver, ct + lo * (n + 2) * 12, L ? rest + lo * L * 4 : rest, A + lo * 12, B + lo * 24, C + lo * 12, hi - lo, verdict_out + lo,
-                                       reason_out ? reason_out + lo : nullptr));
-            ctx->stats["saver_screen_exact_ballots"] += (double)(hi - lo);
-            r = e;
-        }
-    }
+    const size_t piece = screen_piece_ballots(ctx);
+    for (size_t at = 0; at < count; at += piece) VSP_TRY(screen_piece(ctx, ver, src, at, count - at < piece ? count - at : piece, coeff, verdict_out, reason_out));
     return VSP_OK;
 }
 int saver_verify_batch_screened(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *rest, const uint64_t *A, const uint64_t *B, const uint64_t *C,
                                 size_t count, const uint64_t *coeff, uint8_t *verdict_out, uint8_t *reason_out) {
-    const int rc = screen_pieces(ctx, ver, ct, rest, A, B, C, count, coeff, verdict_out, reason_out);
+    BallotSource src;
+    src.ct = ct; src.rest = rest; src.A = A; src.B = B; src.C = C;
+    const int rc = screen_pieces(ctx, ver, src, count, coeff, verdict_out, reason_out);
     if (rc != VSP_OK) msm_drain_slots(ctx);                         // nothing stays in flight on the work slots after an error
     return rc;
 }

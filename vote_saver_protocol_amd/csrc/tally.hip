@@ -70,6 +70,34 @@ __global__ __launch_bounds__(TALLY_SUM_THREADS) void k_tally_colsum(const G1Affi
     if (threadIdx.x == 0) partials[j * gridDim.x + blockIdx.x] = acc;
 }
 
+size_t tally_ct_len(const vsp_tally *t) { return t->ct_len; }
+void tally_ballots_launch(vsp_ctx *ctx, const uint8_t *d_blobs, size_t m, size_t ct_len, const uint8_t *d_pstatus, uint8_t *d_bstatus) {
+    hipLaunchKernelGGL(k_tally_ballots, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, d_blobs, m, ct_len, d_pstatus, d_bstatus);
+}
+int tally_colsum_launch(vsp_ctx *ctx, const void *d_pts, const uint8_t *d_skip, size_t m, size_t ct_len, std::vector<XYZZ<HFp>> &h_part, size_t *parts_out,
+                        StageTimer *sum_end) {
+    hipStream_t st = ctx->stream;
+    const size_t L = ct_len, span = (size_t)TALLY_SUM_THREADS * TALLY_SUM_PER_LANE;
+    // parts of `span` ballots, and wider ones where that would be more partial sums than the host should fold
+    size_t parts = (m + span - 1) / span, part_span = span;
+    const size_t max_parts = TALLY_MAX_PARTIALS / L ? TALLY_MAX_PARTIALS / L : 1;
+    if (parts > max_parts) { part_span = (m + max_parts - 1) / max_parts; parts = (m + part_span - 1) / part_span; }
+    VSP_TRY(ensure(ctx, ctx->tally_partials, parts * L * sizeof(G1XYZZ)));
+    hipLaunchKernelGGL(k_tally_colsum, dim3((unsigned)parts, (unsigned)L), dim3(TALLY_SUM_THREADS), 0, st, (const G1Affine *)d_pts, d_skip, m, L, part_span,
+                       (G1XYZZ *)ctx->tally_partials.p);
+    VSP_LAUNCH_CHECK();
+    if (sum_end) VSP_TRY(sum_end->mark(ctx, 3, st));
+    h_part.resize(parts * L);
+    VSP_HIP(hipMemcpyAsync(h_part.data(), ctx->tally_partials.p, parts * L * sizeof(G1XYZZ), hipMemcpyDeviceToHost, st));   // XYZZ<Fp> and XYZZ<HFp>: the same bytes
+    *parts_out = parts;
+    return VSP_OK;
+}
+void tally_fold(vsp_tally *t, const std::vector<XYZZ<HFp>> &h_part, size_t parts, size_t accepted) {
+    for (size_t j = 0; j < t->ct_len; j++)
+        for (size_t b = 0; b < parts; b++) xyzz_add(t->sums[j], h_part[j * parts + b]);
+    t->ballots += accepted;
+}
+
 }  // namespace vsp
 
 using namespace vsp;
@@ -105,41 +133,29 @@ int vsp_tally_add_blobs(vsp_ctx *ctx, vsp_tally *t, const uint8_t *blobs, size_t
     DecodeWork &w = ctx->decode[0];
     size_t piece = decode_chunk_points(ctx) / L;                    // ballots of one piece: at least one
     if (piece < 1) piece = 1;
-    const size_t span = (size_t)TALLY_SUM_THREADS * TALLY_SUM_PER_LANE;
     std::vector<uint8_t> h_status;
     std::vector<XYZZ<HFp>> h_part;
     size_t accepted = 0;
     for (size_t at = 0; at < count; at += piece) {
         const size_t m = count - at < piece ? count - at : piece;
-        // parts of `span` ballots, and wider ones where that would be more partial sums than the host should fold
-        size_t parts = (m + span - 1) / span, part_span = span;
-        const size_t max_parts = TALLY_MAX_PARTIALS / L ? TALLY_MAX_PARTIALS / L : 1;
-        if (parts > max_parts) { part_span = (m + max_parts - 1) / max_parts; parts = (m + part_span - 1) / part_span; }
+        size_t parts = 0;
         VSP_TRY(ensure(ctx, ctx->tally_raw, m * ballot_bytes));
         VSP_TRY(ensure(ctx, ctx->tally_bstatus, m));
-        VSP_TRY(ensure(ctx, ctx->tally_partials, parts * L * sizeof(G1XYZZ)));
         VSP_HIP(hipMemcpyAsync(ctx->tally_raw.p, blobs + at * ballot_bytes, m * ballot_bytes, hipMemcpyHostToDevice, st));
         VSP_TRY(decode_points<G1>(ctx, m * L, L, ballot_bytes, &head, 1, check_subgroup));
-        hipLaunchKernelGGL(k_tally_ballots, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint8_t *)ctx->tally_raw.p, m, L,
-                           (const uint8_t *)w.pstatus.p, (uint8_t *)ctx->tally_bstatus.p);
-        hipLaunchKernelGGL(k_tally_colsum, dim3((unsigned)parts, (unsigned)L), dim3(TALLY_SUM_THREADS), 0, st, (const G1Affine *)w.pts.p,
-                           (const uint8_t *)ctx->tally_bstatus.p, m, L, part_span, (G1XYZZ *)ctx->tally_partials.p);
-        VSP_LAUNCH_CHECK();
-        VSP_TRY(w.timer.mark(ctx, 3, st));
-        h_status.resize(m); h_part.resize(parts * L);
+        tally_ballots_launch(ctx, (const uint8_t *)ctx->tally_raw.p, m, L, (const uint8_t *)w.pstatus.p, (uint8_t *)ctx->tally_bstatus.p);
+        VSP_TRY(tally_colsum_launch(ctx, w.pts.p, (const uint8_t *)ctx->tally_bstatus.p, m, L, h_part, &parts, &w.timer));
+        h_status.resize(m);
         VSP_HIP(hipMemcpyAsync(h_status.data(), ctx->tally_bstatus.p, m, hipMemcpyDeviceToHost, st));
-        VSP_HIP(hipMemcpyAsync(h_part.data(), ctx->tally_partials.p, parts * L * sizeof(G1XYZZ), hipMemcpyDeviceToHost, st));   // XYZZ<Fp> and XYZZ<HFp>: the same bytes
         VSP_HIP(hipStreamSynchronize(st));
         decode_add_times<G1>(ctx, check_subgroup != 0);
         w.timer.add(ctx, 2, "tally_sum_ms");
         // nothing of this piece has touched the handle before this point: an error above leaves the tally as it was
-        for (size_t j = 0; j < L; j++)
-            for (size_t b = 0; b < parts; b++) xyzz_add(t->sums[j], h_part[j * parts + b]);
         size_t ok = 0;
         for (size_t b = 0; b < m; b++) ok += h_status[b] == 0;
+        tally_fold(t, h_part, parts, ok);
         if (status_out) memcpy(status_out + at, h_status.data(), m);
         accepted += ok;
-        t->ballots += ok;
         if (accepted_out) *accepted_out = accepted;
     }
     return VSP_OK;
