@@ -99,8 +99,116 @@ def main():
                      "coset_fft_g7": [hx(x) for x in o.ntt(a, coset=7)],
                      "inverse_coset_fft_g7": [hx(x) for x in o.ntt(a, inverse=True, coset=7)]})
     json.dump(nttv, open(os.path.join(OUT, "ntt.json"), "w"), indent=0)
+    cofactor_points()
     print("golden fixtures written to", os.path.normpath(OUT))
 
 
+# ---- curve points OUTSIDE the order-r subgroups, of every small cofactor order (cofactor_points.json)
+# z = -BLS_X.  #E(Fp) = h1 r with h1 = (z - 1)^2 / 3 = 3 . 11^2 . 10177^2 . 859267^2 . 52437899^2;
+# #E'(Fp2) = h2 r with h2 = (z^8 - 4 z^7 + 5 z^6 - 4 z^4 + 6 z^3 - 4 z^2 - 4 z + 13) / 9 = 13^2 . 23^2 . 2713 . 11953 . 262069 . c448
+# (c448: the remaining 448-bit factor, taken as it is).  Both are the published cofactors of BLS12-381; the products are asserted below.
+G1_COFACTOR_PRIMES = (3, 11, 10177, 859267, 52437899)
+G2_COFACTOR_PRIMES = (13, 23, 2713, 11953, 262069)
+# Points of order q^2: none exist.  For every squared prime of either cofactor (G1: 11, 10177, 859267, 52437899; G2: 13, 23)
+# (#E / q^2) Q had order <= q for each of the first 12 curve points Q (point_of_order_q2): the q-part of the group is (Z/q)^2, not
+# cyclic, so the fixture holds no q^2 record.
+SUBGROUP_SCALAR = 0x5EED5EED5EED5EED5EED                  # S = SUBGROUP_SCALAR . generator, the fixed subgroup point of the S + T_q records
+
+
+def curve_points(cur):
+    """the curve points with x = 1, 2, 3, ... (G2: x = (k, 1)), both square roots' first, in that order"""
+    k = 0
+    while True:
+        k += 1
+        if cur is o.G1:
+            x = k
+            y = o.fp_sqrt((x * x * x + o.B1) % o.P)
+        else:
+            x = (k, 1)
+            y = o.fp2_sqrt(o.Fp2Ops.add(o.Fp2Ops.mul(o.Fp2Ops.sqr(x), x), o.B2))
+        if y is not None:
+            assert cur.is_on_curve((x, y))
+            yield (x, y)
+
+
+def q_part(order, q):
+    e = 0
+    while order % q ** (e + 1) == 0:
+        e += 1
+    return q ** e
+
+
+def point_of_order(cur, order, q, label):
+    """a point of order q (q prime, or the unfactored c448) from the first found curve point Q with a q-component: (#E / q^e) Q for the
+    whole q-part q^e of #E, times q while that is not yet of order q.  ((#E / q) Q itself is infinity for every Q where the q-part is
+    (Z/q)^2 and not cyclic: all of G1's squared primes.)"""
+    assert order % q == 0
+    for Q in curve_points(cur):
+        T = cur.mul(Q, order // q_part(order, q))
+        if T is None:
+            continue
+        while cur.mul(T, q) is not None:
+            T = cur.mul(T, q)
+        assert cur.is_on_curve(T) and cur.mul(T, q) is None, label
+        return T
+
+
+def point_of_order_q2(cur, order, q, tries=12):
+    """a point of order exactly q^2, or None when (#E / q^2) Q has order <= q for the first `tries` curve points Q: the q-part of the
+    group is then (Z/q)^2 and not cyclic (a cyclic q-part gives order q^2 with probability 1 - 1/q per try)"""
+    if order % (q * q):
+        return None
+    gen = curve_points(cur)
+    for _ in range(tries):
+        U = cur.mul(next(gen), order // (q * q))
+        if U is not None and cur.mul(U, q) is not None:
+            assert cur.mul(U, q * q) is None
+            return U
+    return None
+
+
+def cofactor_points():
+    z = -o.BLS_X
+    h1 = (z - 1) ** 2 // 3
+    h2 = (z ** 8 - 4 * z ** 7 + 5 * z ** 6 - 4 * z ** 4 + 6 * z ** 3 - 4 * z ** 2 - 4 * z + 13) // 9
+    prod1 = 3
+    for q in G1_COFACTOR_PRIMES[1:]:
+        prod1 *= q * q
+    assert prod1 == h1
+    c448 = h2 // (13 ** 2 * 23 ** 2 * 2713 * 11953 * 262069)
+    assert c448 * 13 ** 2 * 23 ** 2 * 2713 * 11953 * 262069 == h2 and c448.bit_length() == 448
+    out = {}
+    for name, cur, enc, h, primes in (("g1", o.G1, pt1, h1, G1_COFACTOR_PRIMES), ("g2", o.G2, pt2, h2, G2_COFACTOR_PRIMES)):
+        order = h * o.R
+        assert cur.mul(next(curve_points(cur)), order) is None
+        S = cur.mul(cur.gen, SUBGROUP_SCALAR)
+        recs = []
+
+        def rec(label, order_label, pt):
+            assert pt is not None and cur.is_on_curve(pt)
+            recs.append({"label": label, "order": order_label, "point": enc(pt), "in_subgroup": cur.in_subgroup(pt)})
+
+        orders = [(q, str(q)) for q in primes] + ([(c448, "c448")] if name == "g2" else [])
+        for q, ql in orders:
+            T = point_of_order(cur, order, q, ql)
+            if name == "g1" and q == 3:
+                assert T in ((0, 2), (0, o.P - 2))
+                T = (0, 2)                                     # the order-3 point with x = 0: phi fixes it
+            rec("T_" + ql, ql, T)
+            rec("S+T_" + ql, "r*" + ql, cur.add(S, T))
+            rec("-T_" + ql, ql, cur.neg(T))
+            if q != c448:
+                U = point_of_order_q2(cur, order, q)
+                if U is not None:
+                    rec("U_%s^2" % ql, ql + "^2", U)
+        rec("S", "r", S)
+        out[name] = recs
+    json.dump(out, open(os.path.join(OUT, "cofactor_points.json"), "w"), indent=0)
+    return out
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["cofactor_points"]:
+        cofactor_points()
+    else:
+        main()
