@@ -767,6 +767,60 @@ int vsp_saver_receive_blobs(vsp_ctx *ctx, const vsp_saver_verifier *ver, vsp_tal
                             uint8_t *verdict_out /* count */, uint8_t *reason_out /* count, may be NULL */,
                             uint8_t *wire_status_out /* count x 3, may be NULL */, size_t *accepted_out /* may be NULL */);
 
+/* ---- the ballot box: spent serial numbers, eid and rt checked on the GPU -----------------------------------------------
+ * vsp_saver_receive_blobs accepts any ballot whose proof verifies against the rest inputs the ballot itself carries.  A ballot box adds
+ * the rule that makes the tally mean something (the reference keeps it on chain: voting_admin.sol:112-129): a ballot counts once, and
+ * only for this election and this voter list.  The box is a handle over a verifier (which must outlive it, same device) that holds, on
+ * the device, the serials of every ballot it has accepted, in ORDINAL order -- a ballot's ordinal is its position among the ballots the
+ * box has accepted so far, from 0 -- and an open-addressing table over them (a power of two of slots, at most half full; the first has
+ * 2^"ballot_box_table_bits" slots, option read at creation, default 16, 2..30).
+ * ROLES.  role[i] says what rest input i is: 0 FREE (ignored), 1 FIXED (must equal expected[4 i ..], a canonical scalar below r), 2 SERIAL.
+ * A ballot's serial is its SERIAL inputs, S of them (1..8), concatenated in order.  The reference's rest inputs eid | sn | rt are the roles
+ * FIXED, SERIAL, FIXED.  vsp_ballot_box_create: NULL and VSP_ERR_ARG in the last error for a null argument, n_rest = 0 or not the
+ * verifier's n_abc - 1 - msg_size, a role above 2, no SERIAL input or more than 8, a FIXED scalar >= r, a verifier of another device.
+ * RECEIVING.  vsp_ballot_box_receive_blobs takes the arguments of vsp_saver_receive_blobs (the verifier is the box's) and is the same
+ * path.  Walk the ballots in index order, across pieces and across earlier calls on the box: a ballot is ACCEPTED exactly when it is not
+ * wire-rejected, its FIXED inputs equal the box's, vsp_saver_verify_batch accepts it (coeff set: the screened call, whose guarantees
+ * carry over as for vsp_saver_receive_blobs) and no earlier accepted ballot holds its serial.  Accepted ballots enter the tally and the
+ * box, no others do; an invalid ballot never reserves its serial.  verdict_out, the tally, the box's contents, the ordinals and
+ * holder_out do not depend on the piece sizes, on how the ballots are split over calls, on coeff being NULL or set, or on how the GPU
+ * schedules its lanes.
+ * REASONS, the first that applies: 1 wire-rejected; 8 a FIXED input differs; 16 the serial is held by a ballot accepted in an earlier
+ * piece or call (such a ballot is not verified: to the verifier it is what a wire-rejected one is -- out of every sum and product, no
+ * pairing verdict, no range fails because of it; coefficients and ranges still go by original indices; a piece in which every ballot
+ * is turned away before the verifier runs no pairing at all); 2, 4 or 6 the verifier's; 16 the serial is held by an accepted ballot of
+ * lower index in the same piece.  holder_out[k] is the holder's ordinal for reason 16 and all-ones otherwise, with one addition.  A
+ * ballot that both fails an equation and repeats the serial of an earlier accepted ballot gets 16 when that serial was committed by an
+ * earlier piece and the verifier's reason when the holder is in its own piece: reason_out of such ballots is the ONLY output that
+ * depends on the piece boundaries.  So that holder_out does not, such a ballot gets the holder's ordinal under either reason (a
+ * ballot with reason 2, 4 or 6 whose holder_out is not all-ones is one of them).
+ * ATOMICITY.  A piece enters the tally and the box whole or not at all: after an error both are as after the last complete piece (the
+ * table is rebuilt from the serials where the piece had claimed slots).  ERRORS as for vsp_saver_receive_blobs, and VSP_ERR_ARG for a
+ * null box or input_blobs and a box of another device.  A probe of the table never takes more steps than the table has slots: a full
+ * or damaged table is VSP_ERR_HIP with a message that names the ballot box, never a spin.
+ * PERSISTENCE.  vsp_ballot_box_serials exports the serials [first, first + count) in ordinal order (count x S x 4 words; VSP_ERR_ARG
+ * for a range outside the box).  vsp_ballot_box_add_serials restores them or adds serials in bulk through the same claim: the first
+ * occurrence wins and gets the next ordinal, status_out[k] = 1 says serial k was already held (by the box or by a lower index),
+ * *added_out how many went in; a scalar >= r is VSP_ERR_ARG before any GPU work.  Exporting box A into a fresh box B gives B the
+ * ordinals of A.  vsp_ballot_box_count: accepted ballots; _serial_scalars: S; _device_bytes: device memory the box holds.
+ * Statistics: "ballot_box_ms" the box's kernels by HIP events, "ballot_box_mismatched" reason 8, "ballot_box_spent" reason 16,
+ * "ballot_box_grown" rebuilds into a larger table. */
+typedef struct vsp_ballot_box vsp_ballot_box;
+vsp_ballot_box *vsp_ballot_box_create(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *expected /* n_rest x 4 */,
+                                      const uint8_t *role /* n_rest */, size_t n_rest);
+void vsp_ballot_box_free(vsp_ctx *ctx, vsp_ballot_box *box);
+uint64_t vsp_ballot_box_count(const vsp_ballot_box *box);
+size_t vsp_ballot_box_serial_scalars(const vsp_ballot_box *box);
+size_t vsp_ballot_box_device_bytes(const vsp_ballot_box *box);
+int vsp_ballot_box_serials(vsp_ctx *ctx, const vsp_ballot_box *box, uint64_t first, size_t count, uint64_t *out /* count x S x 4 */);
+int vsp_ballot_box_add_serials(vsp_ctx *ctx, vsp_ballot_box *box, const uint64_t *serials /* count x S x 4 */, size_t count,
+                               uint8_t *status_out /* count: 1 = already held; may be NULL */, size_t *added_out /* may be NULL */);
+int vsp_ballot_box_receive_blobs(vsp_ctx *ctx, vsp_ballot_box *box, vsp_tally *tally /* may be NULL */, const uint8_t *ct_blobs,
+                                 const uint8_t *proof_blobs, const uint8_t *input_blobs, size_t count, int check_subgroup,
+                                 const uint64_t *coeff /* NULL = the exact path */, uint8_t *verdict_out, uint8_t *reason_out /* may be NULL */,
+                                 uint8_t *wire_status_out /* may be NULL */, size_t *accepted_out /* may be NULL */,
+                                 uint64_t *holder_out /* count, may be NULL */);
+
 /* ---- SAVER decryption on the GPU: decrypt / verify_decryption<elgamal_verifiable> (common.hpp:1220-1223, 1282-1283) -----------------
  * The last step of the election: opening the aggregated ciphertext that vsp_tally_result returns, and checking a published result.
  * With n = msg_size, G_i = gamma_abc_g1[i], H the generator of G2, V_i = rho_sv_g2[i-1], W_i = rho_rhov_g2[i-1] (the verification key of

@@ -152,6 +152,14 @@ PROTOTYPES = {
     "vsp_saver_verify_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
     "vsp_saver_verify_batch_screened": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P]),
     "vsp_saver_receive_blobs": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P]),
+    "vsp_ballot_box_create": (_P, [_P, _P, _P, _P, _SZ]),
+    "vsp_ballot_box_free": (None, [_P, _P]),
+    "vsp_ballot_box_count": (C.c_uint64, [_P]),
+    "vsp_ballot_box_serial_scalars": (_SZ, [_P]),
+    "vsp_ballot_box_device_bytes": (_SZ, [_P]),
+    "vsp_ballot_box_serials": (_I, [_P, _P, C.c_uint64, _SZ, _P]),
+    "vsp_ballot_box_add_serials": (_I, [_P, _P, _P, _SZ, _P, _P]),
+    "vsp_ballot_box_receive_blobs": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _P]),
     "vsp_saver_decryptor_create": (_P, [_P, _SZ, _P, _P, C.c_uint64]),
     "vsp_saver_decryptor_free": (None, [_P, _P]),
     "vsp_saver_decryptor_msg_size": (_SZ, [_P]),

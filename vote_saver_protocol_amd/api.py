@@ -1093,6 +1093,82 @@ def saver_receive_blobs(ctx, ver, ct_blobs, proof_blobs, input_blobs, coeff=None
     return verdict, reason, wire, accepted.value
 
 
+FREE, FIXED, SERIAL = 0, 1, 2                                       # roles of a rest input in a BallotBox
+
+
+class BallotBox:
+    """A ballot box over a SaverVerifier (vsp_ballot_box): which serial numbers are spent, and whether a ballot's FIXED rest inputs are
+    this election's, decided on the GPU.  roles [n_rest]: FREE, FIXED or SERIAL per rest input; expected [n_rest, 4]: the canonical
+    scalars the FIXED inputs must equal (the other rows are ignored).  The reference's eid | sn | rt is (FIXED, SERIAL, FIXED).  The
+    verifier must outlive the box.  Option "ballot_box_table_bits" is read at creation."""
+
+    def __init__(self, ctx, ver, expected, roles):
+        self.ctx, self.ver = ctx, ver
+        role = np.ascontiguousarray(roles, dtype=np.uint8).reshape(-1)
+        exp = _u64(expected, 4)
+        if exp.shape[0] != role.shape[0]:
+            raise ValueError("BallotBox: one role and one expected scalar per rest input")
+        self.h = ctx.lib.vsp_ballot_box_create(ctx.h, ver.h, _ptr(exp), _ptr(role), role.shape[0])
+        if not self.h:
+            raise VspError("vsp_ballot_box_create failed: " + ctx.last_error())
+        self.serial_scalars = ctx.lib.vsp_ballot_box_serial_scalars(self.h)
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.vsp_ballot_box_free(self.ctx.h, self.h)
+            self.h = None
+
+    def count(self):
+        """ballots accepted so far: the next ordinal"""
+        return self.ctx.lib.vsp_ballot_box_count(self.h)
+
+    def device_bytes(self):
+        return self.ctx.lib.vsp_ballot_box_device_bytes(self.h)
+
+    def receive_blobs(self, ct_blobs, proof_blobs, input_blobs, coeff=None, tally=None, check_subgroup=True):
+        """saver_receive_blobs with the box's rule (vsp_ballot_box_receive_blobs): a ballot is accepted when it is not wire-rejected, its
+        FIXED inputs are the box's, the verifier accepts it and no earlier accepted ballot holds its serial.  Returns (verdict, reason,
+        wire_status, accepted, holder [n] uint64): reason 8 = a FIXED input differs, 16 = the serial is spent, and then holder is the
+        ordinal of the ballot that holds it (all-ones otherwise; a ballot the verifier refused, reason 2, 4 or 6, whose serial an earlier
+        accepted ballot holds gets that ordinal too, so that holder does not depend on the piece boundaries)."""
+        def joined(b):
+            return bytes(b) if isinstance(b, (bytes, bytearray, memoryview)) else b"".join(bytes(x) for x in b)
+        ver = self.ver
+        n_rest = ver.n_abc - 1 - ver.msg_size
+        ct = joined(ct_blobs); pr = joined(proof_blobs); inp = joined(input_blobs)
+        ct_size = 8 + 48 * (ver.msg_size + 2); in_size = 8 + 32 * n_rest
+        if len(ct) % ct_size or len(pr) != len(ct) // ct_size * 192 or len(inp) != len(ct) // ct_size * in_size:
+            raise ValueError(f"BallotBox.receive_blobs: n ciphertext blobs of {ct_size} bytes, n proofs of 192 bytes and n input blobs of {in_size} bytes expected")
+        n = len(ct) // ct_size
+        if coeff is not None:
+            coeff = _u64(coeff).reshape(-1, 2)
+            if coeff.shape[0] != n:
+                raise ValueError("BallotBox.receive_blobs: n x 2 coefficient words expected")
+        verdict = np.zeros(n, np.uint8); reason = np.zeros(n, np.uint8); wire = np.zeros((n, 3), np.uint8); accepted = C.c_size_t(0)
+        holder = np.full(n, 0xFFFFFFFFFFFFFFFF, np.uint64)
+        bufs = [np.frombuffer(b if b else bytes(1), dtype=np.uint8) for b in (ct, pr, inp)]
+        ctx = self.ctx
+        ctx.check(ctx.lib.vsp_ballot_box_receive_blobs(ctx.h, self.h, tally.h if tally is not None else None, _ptr(bufs[0]), _ptr(bufs[1]), _ptr(bufs[2]), n,
+                                                       int(check_subgroup), _ptr(coeff), _ptr(verdict), _ptr(reason), _ptr(wire), C.byref(accepted), _ptr(holder)))
+        return verdict, reason, wire, accepted.value, holder
+
+    def serials(self, first=0, count=None):
+        """the serials of ordinals [first, first + count) as [count, S, 4] canonical scalars (count None: to the end)"""
+        if count is None:
+            count = self.count() - first
+        out = np.zeros((max(count, 0), self.serial_scalars, 4), np.uint64)
+        self.ctx.check(self.ctx.lib.vsp_ballot_box_serials(self.ctx.h, self.h, int(first), int(count), _ptr(out)))
+        return out
+
+    def add_serials(self, serials):
+        """restore exported serials, or add serials in bulk: [count, S, 4]; the first occurrence wins and gets the next ordinal.  Returns
+        (status [count] uint8, 1 = already held; added)"""
+        s = _u64(serials).reshape(-1, self.serial_scalars, 4)
+        status = np.zeros(s.shape[0], np.uint8); added = C.c_size_t(0)
+        self.ctx.check(self.ctx.lib.vsp_ballot_box_add_serials(self.ctx.h, self.h, _ptr(s), s.shape[0], _ptr(status), C.byref(added)))
+        return status, added.value
+
+
 class SaverDecryptor:
     """The opening side of a SAVER election resident on the GPU (vsp_saver_decryptor), made of public data only: the prepared
     Miller-loop lines of rho_sv_g2, rho_rhov_g2, H and -rho_g2, the bases e(G_i, rho_rhov_g2[i]) and their baby-step tables for

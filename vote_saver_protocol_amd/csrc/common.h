@@ -73,11 +73,13 @@ struct DecodeWork {
 // of which the first is ballot `base` of the call.  Montgomery affine points as the decoder leaves them: the ciphertext members
 // ballot-major, members[k (n + 2) + j]; A of ballot k at ac[k], C at ac[count + k]; B at b[k]; the rest inputs as canonical words,
 // rest[(k n_rest + i) 8 ..]; the three wire status bytes of ballot k at wire[k], wire[stride + k], wire[2 stride + k]
+// With a ballot box (ballot_box.hip) a fourth status row, box_row[k]: not zero for a ballot the box has turned away before the verifier
 struct ReceivedPiece {
     size_t base = 0, count = 0, wire_stride = 0;
     const void *members = nullptr, *ac = nullptr, *b = nullptr;
     const uint32_t *rest = nullptr;
     const uint8_t *wire = nullptr;
+    const uint8_t *box_row = nullptr;
 };
 // where the verifiers take the ballots of a piece from (pairing.hip saver_piece_prepare): canonical limbs of the whole call in host
 // memory -- ballots [at, at + c) are uploaded and checked by k_ballot_prepare -- or, with `dev` set, a range of a decoded piece, which
@@ -439,6 +441,24 @@ struct vsp_saver_verifier {
     vsp::Affine<vsp::HFp> alpha_g1;     // host, Montgomery
 };
 
+// A ballot box (ballot_box.hip; the rules: ballot_box.h): the roles and the FIXED values of the rest inputs, the serials of the accepted
+// ballots in ordinal order (`store`, count x words) and the open-addressing table over them (`table`, `slots` 64-bit slots, at most half
+// full), all on the verifier's device; the workspace of one piece -- its serials (`pend`), per ballot the holder found before the
+// verifier (`hold`), the slot's value and position after the claim (`win`, `pos`), the ordinals of the winners (`ord`) -- and the
+// device-side error word.  dirty: a piece has claimed slots and is not committed; the table is rebuilt from the store before its next use
+struct vsp_ballot_box {
+    int device = 0;
+    const vsp_saver_verifier *ver = nullptr;
+    size_t L = 0, S = 0, words = 0;     // rest inputs, SERIAL inputs, 8 S
+    std::vector<uint8_t> role;
+    vsp::DevBuf d_role, d_expected, store, table, pend, hold, win, pos, ord, flag;
+    uint64_t slots = 0, count = 0;
+    bool dirty = false;
+    std::vector<uint64_t> h_hold, h_win, h_ord;
+    uint32_t h_flag[2] = {0, 0};
+    vsp::StageTimer timer[2];           // [0] 0-1 the screening; [1] 0-1 growth, claim and resolve, 2-3 the commit
+};
+
 namespace vsp {
 
 // option `name` of the context (vsp_set_option), or dflt when it was never set
@@ -617,6 +637,21 @@ size_t saver_exact_piece(const vsp_ctx *ctx, size_t msg_size);  // ballots of on
 int saver_piece_prepare(vsp_ctx *ctx, const vsp_saver_verifier *ver, const BallotSource &src, size_t at, size_t c, StageTimer &timer);
 // the device half of it for a decoded piece (receive.hip): ballots [lo, lo + c) of the piece
 int receive_piece_prepare(vsp_ctx *ctx, const vsp_saver_verifier *ver, const ReceivedPiece &rp, size_t lo, size_t c, void *d_pts, void *d_a, void *d_b, uint8_t *d_status);
+// the ballot box's share of a received piece of c ballots (ballot_box.hip).  Each queues its kernels and copies on the context's stream;
+// the host arrays they fill are valid once the stream is waited for.
+//   screen   k_box_screen over the decoded rest inputs: d_row[k] = 0, 8 (a FIXED input differs) or 16 (the serial is committed);
+//            box->h_hold[k] the holder's ordinal for 16
+//   settle   grows the table where the piece could pass half its slots; k_box_claim and k_box_resolve over the ballots with
+//            d_skip[k] = 0; a ballot whose serial a lower index of the piece holds gets d_skip[k] = 1; box->h_win, box->h_flag
+//   commit   after the wait: the losers' verdicts (0, reason 16, holder) and the winners' ordinals, k_box_commit, the wait for it;
+//            *accepted_out the ballots of the piece that remain accepted.  verdict / reason / holder: the piece's own (reason, holder
+//            may be null; for vsp_ballot_box_add_serials verdict is a status array: 1 = already held)
+//   restore  the table rebuilt from the store (after an error between settle and commit)
+int box_piece_screen(vsp_ctx *ctx, vsp_ballot_box *box, const uint32_t *d_rest, size_t c, uint8_t *d_row);
+int box_piece_settle(vsp_ctx *ctx, vsp_ballot_box *box, size_t c, uint8_t *d_skip);
+int box_piece_commit(vsp_ctx *ctx, vsp_ballot_box *box, size_t c, uint8_t *verdict, uint8_t *reason, uint64_t *holder, bool as_status, size_t *accepted_out);
+int box_restore(vsp_ctx *ctx, vsp_ballot_box *box);
+void box_add_times(vsp_ctx *ctx, vsp_ballot_box *box, bool screen, bool settle);
 // the screened check (screen.hip); coeff: count x 2 words, none zero (capi.hip checks)
 int saver_verify_batch_screened(vsp_ctx *ctx, const vsp_saver_verifier *ver, const uint64_t *ct, const uint64_t *inputs_rest, const uint64_t *A, const uint64_t *B,
                                 const uint64_t *C, size_t n, const uint64_t *coeff, uint8_t *verdict_out, uint8_t *reason_out);
