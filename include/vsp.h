@@ -821,6 +821,57 @@ int vsp_ballot_box_receive_blobs(vsp_ctx *ctx, vsp_ballot_box *box, vsp_tally *t
                                  uint8_t *wire_status_out /* may be NULL */, size_t *accepted_out /* may be NULL */,
                                  uint64_t *holder_out /* count, may be NULL */);
 
+/* ---- the voter registry: Pedersen hashes over Jubjub and the Merkle tree of the public keys ----------------------------
+ * What the election's set-up and every voter compute outside BLS12-381 (common.hpp:833 pk = hash(sk), :1047 sn = hash(eid | sk),
+ * :956-1029 the tree over the public keys, its root rt and a voter's copath): one primitive, the Pedersen hash over Jubjub, the twisted
+ * Edwards curve -u^2 + v^2 = 1 + d u^2 v^2 over Fr with d = -10240 / 10241 (order 8 s, s prime; the addition law is complete).
+ * THE HASH of a message of n >= 1 bits m_0 .. m_(n-1) under generators G_0 .. G_(g-1): zero bits pad it to whole chunks of 3; chunk c =
+ * (m_3c, m_3c+1, m_3c+2) = (s0, s1, s2) encodes (1 - 2 s2)(1 + s0 + 2 s1) and belongs to segment c / 63, window c % 63;
+ * P = sum_c enc(c) 2^(4 (c % 63)) G_(c / 63); the digest is the canonical u(P) as 255 bits in four words, bit k of weight 2^k.
+ * A message is a row of ceil(n / 64) words, bit k at word k / 64, position k % 64; bits at or above n in the last word are ignored.  A
+ * point is 8 words, canonical u | v.  This is the Sapling construction; the reference pins the curve, arity 2, 255-bit digests, the order
+ * of the nodes and the blob -- the rest, the generators above all, is the caller's (DESIGN.md 3.6i says which conventions are guesses).
+ * vsp_pedersen_create validates the generators on the host (VSP_ERR_ARG and a last error that names the generator for a coordinate >= r,
+ * a point off the curve, the identity, a point outside the subgroup of order s; equal or opposite generators are accepted: independence
+ * is the caller's business) and builds the window table on the device: per generator 63 windows x {1, 2, 3, 4} 2^(4 j) G as
+ * (v + u, v - u, 2 d u v), 24 KiB.  vsp_pedersen_hash_batch: count hashes of nbits bits each; nbits = 0 or above 189 g is VSP_ERR_ARG.
+ * A hash is summed by a group of 1, 4, 16 or 64 lanes chosen from the count (option "pedersen_lanes": 0 automatic, 1 / 4 / 16 / 64 forces).
+ * THE TREE of depth D over count <= 2^D keys of 255 bits (four words, bit 255 clear; absent keys are zero): level 0 is H(pk_i) over 255
+ * bits (hash_leaves = 1, the default of the Python layer) or pk_i itself (0); node i of level l + 1 is H(node(l, 2 i) | node(l, 2 i + 1)),
+ * 510 bits, so a registry needs g >= 3.  depth > 24 is VSP_ERR_UNSUPPORTED; count = 0 gives the tree of absent keys.  The levels are built
+ * on the device without a host round trip; the top levels run in one single-workgroup launch (option "registry_fused_levels": 0 = the
+ * levels of at most four nodes, n > 0 = the top n levels, negative = none).
+ * vsp_registry_root: the root and, where asked, rt as the circuit's two public inputs (root mod 2^254 | root >> 254).
+ * vsp_registry_nodes: nodes [first, first + count) of a level (0 = leaves).  vsp_registry_paths: for every index x < 2^D the copath
+ * node(l, (x >> l) ^ 1), l = 0 .. D - 1 (an index >= 2^D is VSP_ERR_ARG).  THE BLOB: 32 octets a node, leaves first, root last; digest
+ * bit b at octet b / 8, bit position 7 - b % 8; the 256th bit is zero.  vsp_registry_from_blob refuses a wrong length and a set 256th
+ * bit (VSP_ERR_ARG); with verify = 1 every inner node is compared with the hash of its children and *first_bad_node_out is the lowest
+ * index (in blob order) of a node that differs, all-ones when the tree is consistent -- the call returns VSP_OK whatever the verdict.
+ * ERRORS as elsewhere: a null pointer is VSP_ERR_ARG also with a count of zero (points_out, rt_scalars_out, first_bad_node_out may be
+ * NULL); a count of zero with valid pointers is VSP_OK; a handle made on another device is VSP_ERR_ARG.  Calls on one context run one
+ * after the other.  Statistics: "pedersen_ms", "registry_build_ms", "registry_paths_ms", "registry_check_ms": the kernels by HIP events. */
+typedef struct vsp_pedersen vsp_pedersen;
+int vsp_pedersen_create(vsp_ctx *ctx, const uint64_t *generators /* g x 8 */, size_t g, vsp_pedersen **out);
+void vsp_pedersen_free(vsp_ctx *ctx, vsp_pedersen *ped);
+size_t vsp_pedersen_generators(const vsp_pedersen *ped);
+size_t vsp_pedersen_max_bits(const vsp_pedersen *ped);            /* 189 g */
+size_t vsp_pedersen_device_bytes(const vsp_pedersen *ped);
+int vsp_pedersen_hash_batch(vsp_ctx *ctx, const vsp_pedersen *ped, const uint64_t *msgs /* count x ceil(nbits / 64) */, size_t nbits, size_t count,
+                            uint64_t *digests_out /* count x 4 */, uint64_t *points_out /* count x 8, may be NULL */);
+typedef struct vsp_registry vsp_registry;
+int vsp_registry_build(vsp_ctx *ctx, const vsp_pedersen *ped, const uint64_t *pks /* count x 4 */, size_t count, unsigned depth, int hash_leaves,
+                       vsp_registry **out);
+int vsp_registry_from_blob(vsp_ctx *ctx, const vsp_pedersen *ped, const uint8_t *blob, size_t len, unsigned depth, int verify, vsp_registry **out,
+                           uint64_t *first_bad_node_out /* ~0 when consistent; may be NULL */);
+void vsp_registry_free(vsp_ctx *ctx, vsp_registry *reg);
+unsigned vsp_registry_depth(const vsp_registry *reg);
+size_t vsp_registry_device_bytes(const vsp_registry *reg);
+int vsp_registry_root(vsp_ctx *ctx, const vsp_registry *reg, uint64_t digest_out[4], uint64_t rt_scalars_out[8] /* may be NULL */);
+int vsp_registry_nodes(vsp_ctx *ctx, const vsp_registry *reg, unsigned level, uint64_t first, size_t count, uint64_t *out /* count x 4 */);
+int vsp_registry_paths(vsp_ctx *ctx, const vsp_registry *reg, const uint64_t *indices, size_t n, uint64_t *siblings_out /* n x depth x 4 */);
+size_t vsp_registry_blob_size(unsigned depth);                    /* 32 (2^(depth + 1) - 1) */
+int vsp_registry_to_blob(vsp_ctx *ctx, const vsp_registry *reg, uint8_t *out);
+
 /* ---- SAVER decryption on the GPU: decrypt / verify_decryption<elgamal_verifiable> (common.hpp:1220-1223, 1282-1283) -----------------
  * The last step of the election: opening the aggregated ciphertext that vsp_tally_result returns, and checking a published result.
  * With n = msg_size, G_i = gamma_abc_g1[i], H the generator of G2, V_i = rho_sv_g2[i-1], W_i = rho_rhov_g2[i-1] (the verification key of

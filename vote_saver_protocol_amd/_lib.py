@@ -160,6 +160,22 @@ PROTOTYPES = {
     "vsp_ballot_box_serials": (_I, [_P, _P, C.c_uint64, _SZ, _P]),
     "vsp_ballot_box_add_serials": (_I, [_P, _P, _P, _SZ, _P, _P]),
     "vsp_ballot_box_receive_blobs": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _P]),
+    "vsp_pedersen_create": (_I, [_P, _P, _SZ, _P]),
+    "vsp_pedersen_free": (None, [_P, _P]),
+    "vsp_pedersen_generators": (_SZ, [_P]),
+    "vsp_pedersen_max_bits": (_SZ, [_P]),
+    "vsp_pedersen_device_bytes": (_SZ, [_P]),
+    "vsp_pedersen_hash_batch": (_I, [_P, _P, _P, _SZ, _SZ, _P, _P]),
+    "vsp_registry_build": (_I, [_P, _P, _P, _SZ, _U, _I, _P]),
+    "vsp_registry_from_blob": (_I, [_P, _P, _P, _SZ, _U, _I, _P, _P]),
+    "vsp_registry_free": (None, [_P, _P]),
+    "vsp_registry_depth": (_U, [_P]),
+    "vsp_registry_device_bytes": (_SZ, [_P]),
+    "vsp_registry_root": (_I, [_P, _P, _P, _P]),
+    "vsp_registry_nodes": (_I, [_P, _P, _U, C.c_uint64, _SZ, _P]),
+    "vsp_registry_paths": (_I, [_P, _P, _P, _SZ, _P]),
+    "vsp_registry_blob_size": (_SZ, [_U]),
+    "vsp_registry_to_blob": (_I, [_P, _P, _P]),
     "vsp_saver_decryptor_create": (_P, [_P, _SZ, _P, _P, C.c_uint64]),
     "vsp_saver_decryptor_free": (None, [_P, _P]),
     "vsp_saver_decryptor_msg_size": (_SZ, [_P]),

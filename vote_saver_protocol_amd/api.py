@@ -1169,6 +1169,134 @@ class BallotBox:
         return status, added.value
 
 
+class Pedersen:
+    """The Pedersen hash over Jubjub under the caller's generators (vsp_pedersen): generators [g, 8] canonical u | v, validated by the
+    library (on the curve, of prime order, not the identity; equal generators are accepted), their window tables resident on the GPU.
+    A message has 1 .. max_bits = 189 g bits."""
+
+    def __init__(self, ctx, generators):
+        self.ctx = ctx
+        gens = _u64(generators, 8)
+        h = C.c_void_p(None)
+        ctx.check(ctx.lib.vsp_pedersen_create(ctx.h, _ptr(gens), gens.shape[0], C.byref(h)))
+        self.h = h
+        self.generators = ctx.lib.vsp_pedersen_generators(self.h)
+        self.max_bits = ctx.lib.vsp_pedersen_max_bits(self.h)
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.vsp_pedersen_free(self.ctx.h, self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def device_bytes(self):
+        return self.ctx.lib.vsp_pedersen_device_bytes(self.h)
+
+
+def pedersen_hash_batch(ctx, ped, msgs, nbits, points=False):
+    """count hashes of nbits bits each (vsp_pedersen_hash_batch): msgs [count, ceil(nbits / 64)] words, bit k of a message at word
+    k // 64, position k % 64 (bits at or above nbits are ignored).  Returns the digests [count, 4] (the canonical u of the hash point,
+    255 bits), and with points=True also the points [count, 8] (u | v)."""
+    row = (int(nbits) + 63) // 64
+    m = _u64(msgs, max(row, 1))
+    digests = np.zeros((m.shape[0], 4), np.uint64)
+    pts = np.zeros((m.shape[0], 8), np.uint64) if points else None
+    ctx.check(ctx.lib.vsp_pedersen_hash_batch(ctx.h, ped.h, _ptr(m), int(nbits), m.shape[0], _ptr(digests), _ptr(pts)))
+    return (digests, pts) if points else digests
+
+
+def digest_scalars(digests):
+    """digests [n, 4] of 255 bits as the circuit's public inputs [n, 2, 4]: the low 254 bits and the bit above them, the packing of
+    get_multi_field_element_from_bits (common.hpp:563-574) that Registry.rt_scalars applies to the root.  Both scalars are below r, as a
+    BallotBox expects its FIXED values and compares its serials"""
+    d = _u64(digests, 4)
+    out = np.zeros((d.shape[0], 2, 4), np.uint64)
+    out[:, 0, :] = d
+    out[:, 0, 3] &= np.uint64(0x3FFFFFFFFFFFFFFF)
+    out[:, 1, 0] = (d[:, 3] >> np.uint64(62)) & np.uint64(1)
+    return out
+
+
+class Registry:
+    """The Merkle tree of the voters' public keys on the GPU (vsp_registry): arity 2, Pedersen hashes of `ped` (at least 3 generators),
+    nodes of 255 bits, leaves first and the root last.  Made by Registry.build or Registry.from_blob."""
+
+    def __init__(self, ctx, handle, first_bad_node=None):
+        self.ctx, self.h = ctx, handle
+        self.depth = ctx.lib.vsp_registry_depth(handle)
+        self.first_bad_node = first_bad_node        # from_blob(verify=True): None when the tree is consistent, else the lowest node that differs
+
+    @classmethod
+    def build(cls, ctx, ped, pks, depth, hash_leaves=True):
+        """the tree of depth `depth` over pks [count, 4] (255-bit keys, count <= 2^depth; absent keys are zero).  hash_leaves: level 0 is
+        H(pk) (the default, a guess: DESIGN.md 3.6i) or pk itself"""
+        keys = _u64(pks, 4)
+        h = C.c_void_p(None)
+        ctx.check(ctx.lib.vsp_registry_build(ctx.h, ped.h, _ptr(keys if keys.shape[0] else np.zeros((1, 4), np.uint64)), keys.shape[0], int(depth), int(bool(hash_leaves)),
+                                             C.byref(h)))
+        return cls(ctx, h)
+
+    @classmethod
+    def from_blob(cls, ctx, ped, blob, depth, verify=True):
+        """the tree of a blob of 32 (2^(depth + 1) - 1) octets; verify: every inner node is compared with the hash of its children on the
+        GPU and first_bad_node names the lowest one that differs"""
+        data = np.frombuffer(bytes(blob) if blob else bytes(1), dtype=np.uint8)
+        h = C.c_void_p(None); bad = C.c_uint64(0)
+        ctx.check(ctx.lib.vsp_registry_from_blob(ctx.h, ped.h, _ptr(data), len(blob), int(depth), int(bool(verify)), C.byref(h), C.byref(bad)))
+        return cls(ctx, h, None if bad.value == 0xFFFFFFFFFFFFFFFF else bad.value)
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.vsp_registry_free(self.ctx.h, self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def device_bytes(self):
+        return self.ctx.lib.vsp_registry_device_bytes(self.h)
+
+    def root(self):
+        out = np.zeros(4, np.uint64)
+        self.ctx.check(self.ctx.lib.vsp_registry_root(self.ctx.h, self.h, _ptr(out), None))
+        return out
+
+    def rt_scalars(self):
+        """rt as the circuit's two public inputs [2, 4]: root mod 2^254 and root >> 254"""
+        root = np.zeros(4, np.uint64); out = np.zeros((2, 4), np.uint64)
+        self.ctx.check(self.ctx.lib.vsp_registry_root(self.ctx.h, self.h, _ptr(root), _ptr(out)))
+        return out
+
+    def nodes(self, level, first=0, count=None):
+        """nodes [first, first + count) of a level (0 = the leaves, depth = the root) as [count, 4]; count None: to the level's end"""
+        if count is None:
+            count = (1 << (self.depth - level)) - first
+        out = np.zeros((max(count, 0), 4), np.uint64)
+        self.ctx.check(self.ctx.lib.vsp_registry_nodes(self.ctx.h, self.h, int(level), int(first), int(count), _ptr(out if out.shape[0] else np.zeros((1, 4), np.uint64))))
+        return out
+
+    def paths(self, indices):
+        """the copaths of leaf indices [n] as [n, depth, 4]: level l holds node(l, (x >> l) ^ 1)"""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        out = np.zeros((idx.shape[0], self.depth, 4), np.uint64)
+        dummy = np.zeros(4, np.uint64)
+        self.ctx.check(self.ctx.lib.vsp_registry_paths(self.ctx.h, self.h, _ptr(idx if idx.shape[0] else dummy), idx.shape[0], _ptr(out if out.size else dummy)))
+        return out
+
+    def to_blob(self):
+        out = np.zeros(self.ctx.lib.vsp_registry_blob_size(self.depth), np.uint8)
+        self.ctx.check(self.ctx.lib.vsp_registry_to_blob(self.ctx.h, self.h, _ptr(out)))
+        return out.tobytes()
+
+
 class SaverDecryptor:
     """The opening side of a SAVER election resident on the GPU (vsp_saver_decryptor), made of public data only: the prepared
     Miller-loop lines of rho_sv_g2, rho_rhov_g2, H and -rho_g2, the bases e(G_i, rho_rhov_g2[i]) and their baby-step tables for

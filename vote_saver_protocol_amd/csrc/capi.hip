@@ -207,7 +207,7 @@ void vsp_destroy(vsp_ctx *ctx) {
                       &ctx->tally_raw, &ctx->tally_bstatus, &ctx->tally_partials,
                       &ctx->decode[0].pts, &ctx->decode[0].pstatus, &ctx->decode[1].pts, &ctx->decode[1].pstatus,
                       &ctx->pair_raw, &ctx->pair_g1, &ctx->pair_g2, &ctx->pair_status, &ctx->pair_ml, &ctx->pair_prod, &ctx->pair_gt, &ctx->dec_out, &ctx->screen_ws,
-                      &ctx->recv_members, &ctx->recv_mstatus, &ctx->recv_raw, &ctx->recv_rest, &ctx->recv_wire};
+                      &ctx->recv_members, &ctx->recv_mstatus, &ctx->recv_raw, &ctx->recv_rest, &ctx->recv_wire, &ctx->ped_in, &ctx->ped_out, &ctx->ped_zero};
     for (DevBuf *b : bufs) free_buf(*b);
     msm_free_slots(ctx);
     saver_ct_release(ctx);
@@ -215,7 +215,7 @@ void vsp_destroy(vsp_ctx *ctx) {
     if (ctx->h_fold) hipHostFree(ctx->h_fold);
     if (ctx->h_verdict) hipHostFree(ctx->h_verdict);
     hipEventDestroy(ctx->ev0); hipEventDestroy(ctx->ev1); hipEventDestroy(ctx->ev_aux);
-    for (StageTimer *t : {&ctx->decode[0].timer, &ctx->decode[1].timer, &ctx->check_timer, &ctx->pair_timer, &ctx->saver_timer, &ctx->dec_timer, &ctx->screen_timer[0], &ctx->screen_timer[1], &ctx->recv_timer}) t->destroy();
+    for (StageTimer *t : {&ctx->decode[0].timer, &ctx->decode[1].timer, &ctx->check_timer, &ctx->pair_timer, &ctx->saver_timer, &ctx->dec_timer, &ctx->screen_timer[0], &ctx->screen_timer[1], &ctx->recv_timer, &ctx->ped_timer}) t->destroy();
     for (hipStream_t ps : ctx->prove_streams) if (ps) hipStreamDestroy(ps);
     hipStreamDestroy(ctx->own_stream);
     delete ctx;

@@ -268,6 +268,10 @@ struct vsp_ctx {
     // the stages of vsp_saver_decrypt_batch / vsp_saver_verify_decryption_batch (prepare, values, search or powers) and around the table build
     vsp::DevBuf dec_out;
     vsp::StageTimer dec_timer;
+    // Pedersen hashes and the registry (pedersen.hip): a piece's messages, keys or indices; its digests, points, copaths or blob words;
+    // the all-zero row that absent keys read; the timer around the kernels of one call
+    vsp::DevBuf ped_in, ped_out, ped_zero;
+    vsp::StageTimer ped_timer;
     // prover workspaces for K witnesses (a single proof: K = 1): z [K][num_vars + 1], A z, B z, C z [K][3][m], H [K][m], the packed witness
     vsp::DevBuf pr_z, pr_abc, pr_h, pr_pack;
     // the witness check (prover.hip k_r1cs_verdict): per member of a piece of at most VERDICT_MEMBERS witnesses three 32-bit words --
