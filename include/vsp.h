@@ -527,6 +527,37 @@ int vsp_selftest_field(vsp_ctx *ctx, int field, int op, const uint64_t *a, const
  * formulas, 1 = the 14 x 28-bit lazy form the merges and the bucket reduction run.  The result is some representation of the sum
  * (compare X / ZZ, Y / ZZZ).  Covers the exceptional cases -- doubling, cancellation, infinity on either side -- lane by lane. */
 int vsp_selftest_xyzz_add(vsp_ctx *ctx, int group, int form, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n);
+/* One operation of the tower Fp2 / Fp6 / Fp12 (csrc/fp12.h, csrc/gt_dlog.h) as the GPU compiles it, on n values: out[i] = op(a[i], b[i]).
+ * Host buffers of canonical little-endian values, an element 6 * level words (level 2, 6 or 12), coefficients in the order of the
+ * 576-byte GT encoding (u^i v^j w^k at index (k * 3 + j) * 2 + i); the kernel brings them to Montgomery form and back.  a, b and out
+ * have the same element size whatever the operation reads of b.  One lane per value, 64-lane blocks; the level 6 and 12 kernels are part
+ * of the pairing kernels' translation unit and call its out-of-line tower functions on values kept in memory.
+ *   level 2 (one lane holds the whole value):
+ *      0 mul   1 sqr(a)   2 inv(a), the generic power   3 conj(a)   4 f2inv(a), the fixed chain   5 mul_xi(a)   6 f2half(a)   7 add   8 sub
+ *      9 mul_fp(a, b.c0)   10 neg(a)   11 dbl(a)   12 fp_half of each component of a   13 fp_inv_chain of each component of a
+ *   level 6:
+ *      0 mul   1 mul_v(a)   2 inv(a)   3 mul_by_01(a, b.c0, b.c1)   4 mul_by_1(a, b.c1)   7 add   8 sub
+ *   level 12:
+ *      0 mul   1 sqr(a)   2 inv(a)   3 conj(a)   4 frobenius(a)   5 frobenius2(a)   6 cyclotomic_sqr(a)   7 add   8 sub   9 final_exp(a)
+ *      10 mul_by_014(a, l0, l1, l4), the line taken from the Fp2 coefficients 0, 1 and 4 of b, the rest of b ignored
+ *      11 is_one(a): 0 or 1 in the first word of out[i], the other words zero
+ *      12 gt_pow(a, e), e the first four words of b (256 bits), through the decryption kernels' own power function
+ * Inverses map 0 to 0; cyclotomic_sqr and gt_pow are for values of the cyclotomic subgroup only.
+ * VSP_ERR_ARG for a null pointer, another level, or an op the level does not have. */
+int vsp_selftest_tower(vsp_ctx *ctx, int level, int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n);
+/* The Fp2 arithmetic of the G2 kernels, where one value lives in a lane pair (even lane c0, odd lane c1) and products exchange halves
+ * by DPP, on n sets of canonical Fp2 operands a, b, c, d (12 words each; host buffers); results out_p and, for mul_pair, out_q (12
+ * words each; out_q is zero otherwise).  Two lanes per element.
+ *   form 0, the 12 x 32-bit Fp2L of csrc/field.h:
+ *      0 mul(a, b)   1 sqr(a)   2 mul_pair: p = a b, q = c d   3 prod_diff: a b - c d   4 mul_add2: a b + c d
+ *      5 is_zero(a): each lane's answer, 0 or 1, in the first word of its component of out_p
+ *      6 add(a, b)   7 sub(a, b)   8 neg(a)   9 dbl(a)
+ *   form 1, the 14 x 28-bit pair form of csrc/fp28.h on canonical operands (tight limbs), back through fp28_to_fp:
+ *      0 mulF2(a, b, K8_L1)   1 mulF2(a, b, K64_L4)   2 sqrF2(a, K8_L1)   3 sqrF2(a, K32_L1)   4 sqrF2(a, K64_L1)
+ *   op -1: element i runs op i mod K (K = 10, form 1: 5), so neighbouring pairs of a wave take different branches around the exchanges.
+ * VSP_ERR_ARG for a null pointer, another form, or an op the form does not have. */
+int vsp_selftest_fp2_lanes(vsp_ctx *ctx, int form, int op, const uint64_t *a, const uint64_t *b, const uint64_t *c, const uint64_t *d,
+                           uint64_t *out_p, uint64_t *out_q, size_t n);
 
 /* ---- wire format helpers (host only, tiny) ---------------------------------------------------
  * compress: VSP_ERR_ARG for a null pointer or a coordinate that is not canonical (>= p). */

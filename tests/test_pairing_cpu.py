@@ -10,8 +10,10 @@ import pytest
 
 import bls12_381 as o
 import pairing as pg
+import tower_cases as tc
 import wire
 from conftest import L, ROOT, g1_limbs, g2_limbs
+from tower_cases import rand_fp, samples
 
 P, R = o.P, o.R
 SRC = os.path.join(ROOT, "tests", "cpu_build", "pairing_check.cpp")
@@ -62,24 +64,6 @@ def product(lib, pre, pairs):
     return out.tobytes(), bool(one)
 
 
-def rand_fp(gen):
-    a = 0
-    for _ in range(6):
-        a = (a << 64) | next(gen)
-    return a % P
-
-
-def samples():
-    gen = o.splitmix64(381)
-    vals = [[rand_fp(gen) for _ in range(12)] for _ in range(16)]
-    vals += [pg.ZERO, pg.ONE, pg.W]
-    for k in range(12):
-        single = [0] * 12
-        single[k] = rand_fp(gen)
-        vals.append(single)
-    return vals
-
-
 _FROBENIUS = {}
 
 
@@ -114,6 +98,21 @@ def test_fp12_operations_match_the_oracle(pc, pre):
         f1 = op(pc, pre, 4, a)
         assert op(pc, pre, 4, f1) == op(pc, pre, 5, a)
         assert op(pc, pre, 5, op(pc, pre, 5, op(pc, pre, 5, a))) == op(pc, pre, 3, a)
+
+
+@pytest.mark.parametrize("pre", TYPES)
+def test_the_shared_case_list_level_by_level(pc, pre):
+    """every (level, op) of tower_cases.py -- the list the GPU selftests run -- through the g++ build of the same headers"""
+    fn = getattr(pc, pre + "tower_op")
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    for (level, op), (a, b, want) in sorted(tc.tower_cases().items()):
+        out = np.zeros_like(a)
+        assert fn(level, op, p(a), p(b), p(out), C.c_size_t(a.shape[0])) == 0
+        bad = np.flatnonzero((out != want).any(axis=1))
+        assert bad.size == 0, (level, op, bad[:8].tolist())
+    out = np.zeros(72, np.uint64)
+    for level, op in ((3, 0), (2, 14), (6, 5), (6, 9), (12, 13), (12, -1)):
+        assert fn(level, op, p(out), p(out), p(out), C.c_size_t(1)) == 1
 
 
 @pytest.mark.parametrize("pre", TYPES)

@@ -126,11 +126,107 @@ template <class M, class F28> __global__ __launch_bounds__(64) void k_selftest_x
 #endif
 }
 
+// The Fp2 arithmetic of the lane pairs on its own (diagnostic entry point vsp_selftest_fp2_lanes; the op tables are in include/vsp.h): a
+// record of `in` holds the canonical operands a, b, c, d where a point has X, Y, ZZ, ZZZ, a record of `out` the results p, q, 0, 0, so
+// both travel through LaneView as the points of k_selftest_xyzz_add do.  op < 0: element i runs op i mod K -- neighbouring pairs of a
+// wave branch apart around the DPP exchanges, as the cases of xyzz_add make them.  form 0: Fp2L (field.h); 1: the 28-bit pair form
+// (fp28.h) on tight canonical operands.
+__global__ __launch_bounds__(64) void k_selftest_fp2_lanes(int form, int op, const XYZZ<Fp2> *in, XYZZ<Fp2> *out, size_t n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    using LV = LaneView<Fp2>;
+    const size_t i = gid<Fp2>();
+    if (i >= n) return;                                           // both lanes of a pair leave together
+    const XYZZ<Fp2L> v = LV::load(&in[i]);
+    Fp2L a, b, c, d, p = Fp2L::zero(), q = Fp2L::zero();
+    a.v = to_mont(v.X.v); b.v = to_mont(v.Y.v); c.v = to_mont(v.ZZ.v); d.v = to_mont(v.ZZZ.v);
+    bool flag = false, answer = false;
+    if (form == 0) {
+        switch (op < 0 ? (int)(i % 10) : op) {
+            case 0: p = mul(a, b); break;
+            case 1: p = sqr(a); break;
+            case 2: mul_pair(a, b, c, d, p, q); break;
+            case 3: p = prod_diff(a, b, c, d); break;
+            case 4: p = mul_add2(a, b, c, d); break;
+            case 5: flag = true; answer = is_zero(a); break;
+            case 6: p = add(a, b); break;
+            case 7: p = sub(a, b); break;
+            case 8: p = neg(a); break;
+            default: p = dbl(a); break;                           // op 9
+        }
+    } else {
+        const Fp28 x = fp_to_fp28(a.v), y = fp_to_fp28(b.v);
+        Fp28 r;
+        switch (op < 0 ? (int)(i % 5) : op) {
+            case 0: r = mulF2(x, y, FP28_K8_L1); break;
+            case 1: r = mulF2(x, y, FP28_K64_L4); break;
+            case 2: r = sqrF2(x, FP28_K8_L1); break;
+            case 3: r = sqrF2(x, FP28_K32_L1); break;
+            default: r = sqrF2(x, FP28_K64_L1); break;             // op 4
+        }
+        p.v = fp28_to_fp(r);
+    }
+    XYZZ<Fp2L> res;
+    res.X.v = from_mont(p.v); res.Y.v = from_mont(q.v); res.ZZ = Fp2L::zero(); res.ZZZ = Fp2L::zero();
+    if (flag) { res.X.v = Fp::zero(); res.X.v.l[0] = answer ? 1u : 0u; }      // each lane's own answer, not a field value
+    LV::store(&out[i], res);
+#endif
+}
+
 }  // namespace vsp
 
 using namespace vsp;
 
 extern "C" {
+
+int vsp_selftest_tower(vsp_ctx *ctx, int level, int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n) {
+    if (!ctx) return VSP_ERR_ARG;
+    const bool known = level == 2 ? (op >= 0 && op <= 13) : level == 6 ? ((op >= 0 && op <= 4) || op == 7 || op == 8) : level == 12 ? (op >= 0 && op <= 12) : false;
+    if (!a || !b || !out || !known) return set_error(ctx, VSP_ERR_ARG, "selftest: bad argument");
+    if (n == 0) return VSP_OK;
+    VSP_HIP(hipSetDevice(ctx->device));
+    const size_t esz = (size_t)level * sizeof(Fp);
+    DevBuf da, db, dc;
+    int rc = ensure(ctx, da, n * esz); if (rc == VSP_OK) rc = ensure(ctx, db, n * esz); if (rc == VSP_OK) rc = ensure(ctx, dc, n * esz);
+    if (rc == VSP_OK) {
+        hipMemcpyAsync(da.p, a, n * esz, hipMemcpyHostToDevice, ctx->stream);
+        hipMemcpyAsync(db.p, b, n * esz, hipMemcpyHostToDevice, ctx->stream);
+        rc = level == 12 && op == 12 ? decrypt_selftest_gt_pow(ctx, da.p, db.p, dc.p, n) : pairing_selftest_tower(ctx, level, op, da.p, db.p, dc.p, n);
+        hipMemcpyAsync(out, dc.p, n * esz, hipMemcpyDeviceToHost, ctx->stream);
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = set_error(ctx, VSP_ERR_HIP, "selftest: kernel failed");
+    }
+    free_buf(da); free_buf(db); free_buf(dc);
+    return rc;
+}
+
+int vsp_selftest_fp2_lanes(vsp_ctx *ctx, int form, int op, const uint64_t *a, const uint64_t *b, const uint64_t *c, const uint64_t *d, uint64_t *out_p, uint64_t *out_q,
+                           size_t n) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!a || !b || !c || !d || !out_p || !out_q || (form != 0 && form != 1) || op < -1 || op > (form == 0 ? 9 : 4)) return set_error(ctx, VSP_ERR_ARG, "selftest: bad argument");
+    if (n == 0) return VSP_OK;
+    VSP_HIP(hipSetDevice(ctx->device));
+    using P = XYZZ<Fp2>;
+    constexpr size_t W = sizeof(Fp2) / sizeof(uint64_t);          // words of an operand: 12; a record is four of them
+    std::vector<uint64_t> rec(n * 4 * W);
+    for (size_t i = 0; i < n; i++) {
+        const uint64_t *src[4] = {a + i * W, b + i * W, c + i * W, d + i * W};
+        for (int k = 0; k < 4; k++) memcpy(&rec[(i * 4 + k) * W], src[k], W * sizeof(uint64_t));
+    }
+    DevBuf din, dout;
+    int rc = ensure(ctx, din, n * sizeof(P)); if (rc == VSP_OK) rc = ensure(ctx, dout, n * sizeof(P));
+    if (rc == VSP_OK) {
+        hipMemcpyAsync(din.p, rec.data(), n * sizeof(P), hipMemcpyHostToDevice, ctx->stream);
+        hipLaunchKernelGGL(k_selftest_fp2_lanes, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, ctx->stream, form, op, (const P *)din.p, (P *)dout.p, n);
+        hipMemcpyAsync(rec.data(), dout.p, n * sizeof(P), hipMemcpyDeviceToHost, ctx->stream);
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = set_error(ctx, VSP_ERR_HIP, "selftest: kernel failed");
+    }
+    free_buf(din); free_buf(dout);
+    if (rc == VSP_OK)
+        for (size_t i = 0; i < n; i++) {
+            memcpy(out_p + i * W, &rec[(i * 4) * W], W * sizeof(uint64_t));
+            memcpy(out_q + i * W, &rec[(i * 4 + 1) * W], W * sizeof(uint64_t));
+        }
+    return rc;
+}
 
 int vsp_selftest_field(vsp_ctx *ctx, int field, int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n) {
     if (!ctx) return VSP_ERR_ARG;

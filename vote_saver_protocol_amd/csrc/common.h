@@ -667,6 +667,10 @@ size_t screen_piece_ballots(const vsp_ctx *ctx);                // option "saver
 int pairing_miller(vsp_ctx *ctx, const void *d_g1, const void *d_g2, size_t n, void *d_out);
 // the final exponentiation of n Miller values on the device (stage 3 of pairing.hip on its own): canonical GT values and is-one bytes
 int pairing_final_exp(vsp_ctx *ctx, const void *d_miller, size_t n, void *d_gt_out, uint8_t *d_is_one_out);
+// one tower operation on n device values of 6 * level words, canonical in and out (vsp_selftest_tower; level and op already checked):
+// pairing.hip runs everything but the power of level 12, which is decrypt.hip's (e: the first four words of each b)
+int pairing_selftest_tower(vsp_ctx *ctx, int level, int op, const void *d_a, const void *d_b, void *d_out, size_t n);
+int decrypt_selftest_gt_pow(vsp_ctx *ctx, const void *d_a, const void *d_b, void *d_out, size_t n);
 // SAVER decryption and its verification (decrypt.hip): the baby-step tables of a key, resident
 vsp_saver_decryptor *saver_decryptor_create(vsp_ctx *ctx, size_t msg_size, const uint64_t *saver_vk_words, const uint64_t *gamma_abc_g1, uint64_t max_value);
 void saver_decryptor_free(vsp_ctx *ctx, vsp_saver_decryptor *dec);

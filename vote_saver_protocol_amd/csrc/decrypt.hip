@@ -172,6 +172,25 @@ __global__ __launch_bounds__(DLOG_BLOCK_LANES) void k_dec_power(const Fp12 *__re
     ok[item] = eq(pw, v) ? 1 : 0;
 }
 
+// the power on its own (include/vsp.h vsp_selftest_tower, level 12 op 12): canonical a, the exponent in the first four words of b,
+// through the dc_pow that k_dec_power calls
+__global__ __launch_bounds__(DLOG_BLOCK_LANES) void k_selftest_gt_pow(const Fp12 *__restrict__ a, const Fp12 *__restrict__ b, Fp12 *__restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t *src = (const uint64_t *)(b + i);
+    uint64_t e[4];
+    for (int w = 0; w < 4; w++) e[w] = src[w];
+    Fp12 bs = to_mont(a[i]), pw;
+    dc_pow(&pw, &bs, e, 4);
+    out[i] = from_mont(pw);
+}
+int decrypt_selftest_gt_pow(vsp_ctx *ctx, const void *d_a, const void *d_b, void *d_out, size_t n) {
+    hipLaunchKernelGGL(k_selftest_gt_pow, dim3((unsigned)((n + DLOG_BLOCK_LANES - 1) / DLOG_BLOCK_LANES)), dim3(DLOG_BLOCK_LANES), 0, ctx->stream, (const Fp12 *)d_a,
+                       (const Fp12 *)d_b, (Fp12 *)d_out, n);
+    VSP_LAUNCH_CHECK();
+    return VSP_OK;
+}
+
 void saver_decryptor_free(vsp_ctx *ctx, vsp_saver_decryptor *dec) {
     if (!dec) return;
     if (ctx) { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }

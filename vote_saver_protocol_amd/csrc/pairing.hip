@@ -182,6 +182,95 @@ __global__ __launch_bounds__(PAIRING_THREADS) void k_ballot_product(const Fp12 *
     out[c + k] = ml[ng * c + k];
 }
 
+// ---- the tower on its own (include/vsp.h vsp_selftest_tower): one operation per lane on canonical values.  Levels 6 and 12 go through
+// wrappers of the kind above on memory temporaries, so the out-of-line bodies they reach (fp12.h VSP_HD_CALL) are this translation
+// unit's copies, the ones k_miller and k_final_exp run
+__device__ __noinline__ void pr_sqr(Fp12 *f) { const Fp12 t = sqr(*f); *f = t; }
+__device__ __noinline__ void pr_inv(Fp12 *f) { const Fp12 t = inv(*f); *f = t; }
+__device__ __noinline__ void pr_frobenius(Fp12 *f) { const Fp12 t = frobenius(*f); *f = t; }
+__device__ __noinline__ void pr_frobenius2(Fp12 *f) { const Fp12 t = frobenius2(*f); *f = t; }
+__device__ __noinline__ void pr_cyclotomic_sqr(Fp12 *f) { const Fp12 t = cyclotomic_sqr(*f); *f = t; }
+__device__ __noinline__ void pr_mul_by_014(Fp12 *f, const Fp2 *l0, const Fp2 *l1, const Fp2 *l4) { const Fp12 t = mul_by_014(*f, *l0, *l1, *l4); *f = t; }
+__device__ __noinline__ void pr6_mul(Fp6 *f, const Fp6 *g) { const Fp6 t = mul(*f, *g); *f = t; }
+__device__ __noinline__ void pr6_inv(Fp6 *f) { const Fp6 t = inv(*f); *f = t; }
+__device__ __noinline__ void pr6_mul_by_01(Fp6 *f, const Fp2 *b0, const Fp2 *b1) { const Fp6 t = mul_by_01(*f, *b0, *b1); *f = t; }
+__device__ __noinline__ void pr6_mul_by_1(Fp6 *f, const Fp2 *b1) { const Fp6 t = mul_by_1(*f, *b1); *f = t; }
+__device__ __forceinline__ Fp6 to_mont(const Fp6 &a) { Fp6 r; r.c0 = to_mont(a.c0); r.c1 = to_mont(a.c1); r.c2 = to_mont(a.c2); return r; }
+__device__ __forceinline__ Fp6 from_mont(const Fp6 &a) { Fp6 r; r.c0 = from_mont(a.c0); r.c1 = from_mont(a.c1); r.c2 = from_mont(a.c2); return r; }
+
+__global__ __launch_bounds__(PAIRING_THREADS) void k_selftest_fp12(int op, const Fp12 *__restrict__ a, const Fp12 *__restrict__ b, Fp12 *__restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Fp12 x = to_mont(a[i]), y = to_mont(b[i]);
+    switch (op) {
+        case 0: pr_mul(&x, &y); break;
+        case 1: pr_sqr(&x); break;
+        case 2: pr_inv(&x); break;
+        case 3: x = conj(x); break;
+        case 4: pr_frobenius(&x); break;
+        case 5: pr_frobenius2(&x); break;
+        case 6: pr_cyclotomic_sqr(&x); break;
+        case 7: x = add(x, y); break;
+        case 8: x = sub(x, y); break;
+        case 9: pr_final_exp(&x); break;
+        case 10: pr_mul_by_014(&x, &y.c0.c0, &y.c0.c1, &y.c1.c1); break;
+        default: {                                                  // op 11: the answer in the first word, not a field value
+            Fp12 flag = Fp12::zero();
+            flag.c0.c0.c0.l[0] = is_one(x) ? 1u : 0u;
+            out[i] = flag;
+            return;
+        }
+    }
+    out[i] = from_mont(x);
+}
+__global__ __launch_bounds__(PAIRING_THREADS) void k_selftest_fp6(int op, const Fp6 *__restrict__ a, const Fp6 *__restrict__ b, Fp6 *__restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Fp6 x = to_mont(a[i]), y = to_mont(b[i]);
+    switch (op) {
+        case 0: pr6_mul(&x, &y); break;
+        case 1: x = mul_v(x); break;
+        case 2: pr6_inv(&x); break;
+        case 3: pr6_mul_by_01(&x, &y.c0, &y.c1); break;
+        case 4: pr6_mul_by_1(&x, &y.c1); break;
+        case 7: x = add(x, y); break;
+        default: x = sub(x, y); break;                              // op 8
+    }
+    out[i] = from_mont(x);
+}
+// Fp2T<Fp> with the whole value in one lane, as decoding, the pairing and decryption use it
+__global__ __launch_bounds__(PAIRING_THREADS) void k_selftest_fp2(int op, const Fp2 *__restrict__ a, const Fp2 *__restrict__ b, Fp2 *__restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Fp2 x = to_mont(a[i]), y = to_mont(b[i]);
+    Fp2 r;
+    switch (op) {
+        case 0: r = mul(x, y); break;
+        case 1: r = sqr(x); break;
+        case 2: r = inv(x); break;
+        case 3: r = conj(x); break;
+        case 4: r = f2inv(x); break;
+        case 5: r = mul_xi(x); break;
+        case 6: r = f2half(x); break;
+        case 7: r = add(x, y); break;
+        case 8: r = sub(x, y); break;
+        case 9: r = mul_fp(x, y.c0); break;
+        case 10: r = neg(x); break;
+        case 11: r = dbl(x); break;
+        case 12: r.c0 = fp_half(x.c0); r.c1 = fp_half(x.c1); break;
+        default: r.c0 = fp_inv_chain(x.c0); r.c1 = fp_inv_chain(x.c1); break;      // op 13
+    }
+    out[i] = from_mont(r);
+}
+int pairing_selftest_tower(vsp_ctx *ctx, int level, int op, const void *d_a, const void *d_b, void *d_out, size_t n) {
+    const dim3 blocks((unsigned)((n + PAIRING_THREADS - 1) / PAIRING_THREADS)), threads(PAIRING_THREADS);
+    if (level == 12) hipLaunchKernelGGL(k_selftest_fp12, blocks, threads, 0, ctx->stream, op, (const Fp12 *)d_a, (const Fp12 *)d_b, (Fp12 *)d_out, n);
+    else if (level == 6) hipLaunchKernelGGL(k_selftest_fp6, blocks, threads, 0, ctx->stream, op, (const Fp6 *)d_a, (const Fp6 *)d_b, (Fp6 *)d_out, n);
+    else hipLaunchKernelGGL(k_selftest_fp2, blocks, threads, 0, ctx->stream, op, (const Fp2 *)d_a, (const Fp2 *)d_b, (Fp2 *)d_out, n);
+    VSP_LAUNCH_CHECK();
+    return VSP_OK;
+}
+
 // products of one piece: option "pairing_chunk" (a test hook as well), 1 .. 2^14, and at most 2^16 pairs (m <= 2^16: the export refuses more)
 static size_t pairing_piece(const vsp_ctx *ctx, size_t m) {
     const long v = opt(ctx, "pairing_chunk", (long)PAIRING_CHUNK);
