@@ -89,7 +89,10 @@ void vsp_stats_reset(vsp_ctx *ctx);
  * pass and the pointwise step inside the last transform's first pass, basic domains on the 29-bit butterflies; 0: transform by transform,
  * proof by proof), "msm_dimsum_lanes" (8/16/32/64 lanes per bucket-digit sum; 0 = chosen by the library),
  * "msm_dimsum_maxw" (256..4096, default 1024: waves the per-digit lane plan of the bucket reduction may fill; 2048 = two per SIMD),
- * "msm_dimsum_prefetch" (1: the bucket reduction requests the next bucket before the current addition; default 0, it spills), "msm_dimbits" (1 / 0: the last
+ * "msm_dimsum_prefetch" (1: the bucket reduction requests the next bucket before the current addition; default 0, it spills),
+ * "msm_dimsum_dense" (default 1: one-lane fields fold the bucket-digit sums in 256-thread blocks whose tree levels are packed onto the
+ * waves that have live additions; 0: one wave per block, masked tree levels; vsp_get_stat "msm_dimsum_dense_launches" counts the launches
+ * of the packed kernel), "msm_dimbits" (1 / 0: the last
  * step of the bucket reduction as plain subset sums folded by the host's doubling chain / as weighted sums on the GPU; default by group),
  * "msm_slot_normal_priority" (1 before the first use of a work slot: its stream gets the context's priority instead of the lowest --
  * faster single proofs, slower independent multi-exponentiations in flight), "ntt_fr29" (default 1: butterflies on

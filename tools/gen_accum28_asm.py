@@ -20,7 +20,23 @@ Register map.  Field elements live in BLOCKS of 14 consecutive VGPRs:
     v157 i, v158 end (this lane's range in the sorted index), v159 entry of the current point, v160 entry of the next one,
     v161 flag (1: an equal-x pair was met, the part must be redone by the generic kernel), v[162:163] address, v164..v166 scratch
     s0..s13 p, s14 -1/p mod 2^28, s15 2^28 - 1, s16..s29 the redundant 32p (FP28_K32_L1), s[30:31] return address,
-    s[36:37] table, s[38:39] sorted index, s[40:41] EXEC at entry, s[42:43] live lanes, s[44:49] masks   (s32..s35 reserved by the ABI)
+    s[36:37] table, s[38:39] sorted index, s[40:41] EXEC at entry, s[42:43] live lanes, s[44:49] masks, s[50:51] zero   (s32..s35 reserved by the ABI)
+
+Issue slots.  With several multi-exponentiations in flight the GPU is full of these waves, and an instruction issued is time spent.
+Beside the 3 544 multiply-adds an iteration issued 1 050 other VALU instructions (the first-point block aside); 152 of them computed
+nothing the result needs:
+  * the carry passes of P = x ZZ + 32p - X and R = y ZZZ + 32p - Y (2 x 39).  Both stay loose -- limb i below 2^28 + K32_L1[i] < 1.5 * 2^29.  They
+    are read by P^2 and R^2 (against 2P, 2R: limbs < 1.5 * 2^30; a column is at most 7 * (1.5 * 2^29)(1.5 * 2^30) + (1.5 * 2^29)^2 + 14 * 2^56
+    < 2^63.2), by P PP (loose x tight) and by the dual product R (Q + 32p - X3) + (32p - Y) PPP, both of whose first operands are now loose:
+    14 * (1.5 * 2^29)^2 + 14 * 2^57 + 14 * 2^56 < 2^63.4.  A Montgomery output depends on its operands' VALUES, not on their limb split, so
+    every stored coordinate is bit-identical; the value bounds of fp28.h do not move.  The carry pass of X3 stays: X3 is stored and the
+    invariants want it tight.  tests/test_accum28_lean_cpu.py proves the column bounds with the real K32_L1 / K8_L1 / K8_L4 limbs.
+  * the full tests for a table row at infinity, an accumulator at infinity (23) and an equal-x pair (38) in every iteration.  The common path
+    tests a NECESSARY condition on limb 0 (limb 0 of x | y zero; limb 0 of ZZ zero; limb 0 of PP equal to 0 or p_0: 3 + 2 instructions); only
+    when some lane passes does the wave run the full test, in a cold block after the loop's back branch, which leaves the very masks the full
+    test left.  (The routine's subset has no unconditional branch: a cold block returns through s_cbranch_scc1 right after an s_and_b64 of the
+    non-empty EXEC with itself.)
+  * two v_mov_b32 per product to zero the column accumulator (18): the first multiply-add of a product reads the zero pair s[50:51] instead.
 The routine is entered by s_swappc_b64 from the trampoline at the end of the header (private convention, exact clobber list), exactly as
 the product routines of mont_asm_gfx950.h are.
 
@@ -72,7 +88,8 @@ S_INV, S_MASK = "s14", "s15"
 SK32 = lambda i: f"s{16 + i}"            # FP28_K32_L1 limbs
 # (s32..s35 are the stack, frame and base pointers of the function ABI: reserved, never touched)
 S_TABLE, S_SORTED, S_EXEC0, S_LIVE, S_M0, S_M1, S_M2 = "s[36:37]", "s[38:39]", "s[40:41]", "s[42:43]", "s[44:45]", "s[46:47]", "s[48:49]"
-NSGPR = 50
+S_ZERO = "s[50:51]"                      # constant 0: the addend of the first multiply-add of every product
+NSGPR = 52
 S_RESERVED = (30, 31, 32, 33, 34, 35)
 
 
@@ -89,24 +106,29 @@ class Emit:
         sqr_of = (a, a2): the square of block a given a2 = 2a (off-diagonal products once against the doubled operand)."""
         e = self
         assert all(dst not in pr for pr in pairs) and (sqr_of is None or dst not in sqr_of)
-        e(f"v_mov_b32 {ACC_LO}, 0"); e(f"v_mov_b32 {ACC_HI}, 0")
+        first = [True]                      # the first multiply-add starts the column accumulator from the zero pair
+
+        def mad(x, y):
+            assert not (first[0] and y.startswith("s")), "one SGPR operand per instruction: the first multiply-add reads the zero pair"
+            e(f"v_mad_u64_u32 {ACC}, vcc, {x}, {y}, {S_ZERO if first[0] else ACC}")
+            first[0] = False
         for k in range(2 * N - 1):
             for i in range(max(0, k - N + 1), min(k, N - 1) + 1):
                 if sqr_of is not None:
                     a, a2 = sqr_of
                     if i < k - i:
-                        e(f"v_mad_u64_u32 {ACC}, vcc, {R(a, i)}, {R(a2, k - i)}, {ACC}")
+                        mad(R(a, i), R(a2, k - i))
                     elif i == k - i:
-                        e(f"v_mad_u64_u32 {ACC}, vcc, {R(a, i)}, {R(a, i)}, {ACC}")
+                        mad(R(a, i), R(a, i))
                     continue
                 for a, b in pairs:
-                    e(f"v_mad_u64_u32 {ACC}, vcc, {R(a, i)}, {R(b, k - i)}, {ACC}")
+                    mad(R(a, i), R(b, k - i))
             for i in (range(0, k) if k < N else range(k - N + 1, N)):
-                e(f"v_mad_u64_u32 {ACC}, vcc, {R(dst, i)}, {SP(k - i)}, {ACC}")
+                mad(R(dst, i), SP(k - i))
             if k < N:
                 e(f"v_mul_lo_u32 {MK}, {ACC_LO}, {S_INV}")
                 e(f"v_and_b32 {R(dst, k)}, {S_MASK}, {MK}")
-                e(f"v_mad_u64_u32 {ACC}, vcc, {R(dst, k)}, {SP(0)}, {ACC}")
+                mad(R(dst, k), SP(0))
             else:
                 e(f"v_and_b32 {R(dst, k - N)}, {S_MASK}, {ACC_LO}")
             e(f"v_lshrrev_b64 {ACC}, {W}, {ACC}")
@@ -173,6 +195,7 @@ def gen_body():
     e(f"s_mov_b32 {S_INV}, 0x{INV28:x}"); e(f"s_mov_b32 {S_MASK}, 0x{MASK:x}")
     for i in range(N):
         e(f"s_mov_b32 {SK32(i)}, 0x{K32_L1[i]:x}")
+    e("s_mov_b32 s50, 0"); e("s_mov_b32 s51, 0")             # S_ZERO
     e(f"s_mov_b64 {S_EXEC0}, exec")
     for b in ("X", "Y", "ZZ", "ZZZ"):
         for i in range(N):
@@ -192,11 +215,16 @@ def gen_body():
     e(".Lvsp_acc28_loop:")
     # ---------------------------------------------------------------- top of the loop: EXEC = live lanes
     e("s_waitcnt vmcnt(0)")
-    # the point at infinity is the all-zero row; the accumulator at infinity has ZZ = 0
-    e.or_all(AUX1, blk_regs("x") + blk_regs("y"))
+    # the point at infinity is the all-zero row; the accumulator at infinity has ZZ = 0.  Common path: the necessary conditions on limb 0
+    # alone (limb 0 of x | y zero, limb 0 of ZZ zero); a lane that passes one sends the wave through the full tests of the cold block, which
+    # leaves M0 and M1 exact.  Where no lane passes, M0 = every live lane and M1 = none ARE the exact masks.
+    e(f"v_or_b32 {AUX1}, {R('x', 0)}, {R('y', 0)}")
     e(f"v_cmp_ne_u32 {S_M0}, 0, {AUX1}")                      # M0: a finite point
-    e.or_all(AUX2, blk_regs("ZZ"))
-    e(f"v_cmp_eq_u32 {S_M1}, 0, {AUX2}")                      # M1: accumulator at infinity
+    e(f"v_cmp_eq_u32 {S_M1}, 0, {R('ZZ', 0)}")                # M1: accumulator at infinity
+    e(f"s_andn2_b64 {S_M2}, {S_LIVE}, {S_M0}")
+    e(f"s_or_b64 {S_M2}, {S_M2}, {S_M1}")
+    e("s_cbranch_scc1 .Lvsp_acc28_cold_inf")
+    e(".Lvsp_acc28_inf_done:")
     # the digit's sign (bit 31 of the entry): y <- 8p - y
     e(f"v_cmp_gt_i32 vcc, 0, {V_E}")
     for i in range(N):
@@ -216,8 +244,11 @@ def gen_body():
     e(f"s_and_b64 {S_M0}, {S_M2}, {S_LIVE}")                  # M0 := body lanes (kept until the end of the iteration)
     e(f"s_mov_b64 exec, {S_M0}")
     e("s_cbranch_scc0 .Lvsp_acc28_advance")
-    e.mul("T1", "x", "ZZ"); e.sub("T1", "T1", "s", "X"); e.norm("T1")          # P = x ZZ + 32p - X
-    e.mul("T2", "y", "ZZZ"); e.sub("T2", "T2", "s", "Y"); e.norm("T2")         # R = y ZZZ + 32p - Y
+    # P and R stay LOOSE (limbs below 2^28 + K32_L1[i] < 1.5 * 2^29): every product and square that reads them keeps its columns below
+    # 2^64 (fp28.h madd28; tests/test_accum28_lean_cpu.py proves it with these constants), and a product's output depends on its operands'
+    # values only, so the two carry passes that stood here changed no result bit
+    e.mul("T1", "x", "ZZ"); e.sub("T1", "T1", "s", "X")                        # P = x ZZ + 32p - X
+    e.mul("T2", "y", "ZZZ"); e.sub("T2", "T2", "s", "Y")                       # R = y ZZZ + 32p - Y
     e(".Lvsp_acc28_advance:")
     # ---- x and y are dead in every live lane: step to the next point and gather it while the products below run
     e(f"s_mov_b64 exec, {S_LIVE}")
@@ -229,17 +260,13 @@ def gen_body():
     e(f"s_and_b64 {S_M2}, {S_M0}, {S_M0}")                    # SCC = any body lane
     e("s_cbranch_scc0 .Lvsp_acc28_next")
     e.sqr("T4", "T1", "T3")                                                    # PP = P^2
-    # equal x (PP = 0 mod p: PP is 0 or p): flag the lane and take it out of the live set; its accumulator is void from here on
-    e.or_all(AUX1, blk_regs("T4"))
-    e(f"v_xor_b32 {AUX2}, {SP(0)}, {R('T4', 0)}")
-    for i in range(1, N):
-        e(f"v_xor_b32 {AUX0}, {SP(i)}, {R('T4', i)}")
-        e(f"v_or_b32 {AUX2}, {AUX2}, {AUX0}")
-    e(f"v_cmp_eq_u32 {S_M1}, 0, {AUX1}")
-    e(f"v_cmp_eq_u32 {S_M2}, 0, {AUX2}")
+    # equal x (PP = 0 mod p: PP is 0 or p): flag the lane and take it out of the live set; its accumulator is void from here on.  Common
+    # path: limb 0 of PP is 0 or p_0 (necessary; 2^-27 per lane); the full test and the flagging are the cold block's
+    e(f"v_cmp_eq_u32 {S_M1}, 0, {R('T4', 0)}")
+    e(f"v_cmp_eq_u32 {S_M2}, {SP(0)}, {R('T4', 0)}")
     e(f"s_or_b64 {S_M1}, {S_M1}, {S_M2}")
-    e(f"v_cndmask_b32 {V_FLAG}, {V_FLAG}, 1, {S_M1}")
-    e(f"v_cndmask_b32 {V_END}, {V_END}, 0, {S_M1}")
+    e("s_cbranch_scc1 .Lvsp_acc28_cold_eqx")
+    e(".Lvsp_acc28_eqx_done:")
     e.mul("T3", "T1", "T4")                                                    # PPP = P PP
     e.mul("T1", "X", "T4")                                                     # Q = X PP
     e.mul("T5", "ZZ", "T4")                                                    # ZZ' = ZZ PP
@@ -259,6 +286,31 @@ def gen_body():
     e(f"s_and_b64 {S_LIVE}, {S_LIVE}, vcc")
     e(f"s_mov_b64 exec, {S_LIVE}")
     e("s_cbranch_scc1 .Lvsp_acc28_loop")
+    e("s_cbranch_scc0 .Lvsp_acc28_exit")                      # SCC = 0 here: over the cold blocks
+    # ---------------------------------------------------------------- cold blocks (a block returns by a branch on an SCC it has just set: EXEC is
+    # never empty where one is entered)
+    # the full infinity tests, EXEC = live lanes
+    e(".Lvsp_acc28_cold_inf:")
+    e.or_all(AUX1, blk_regs("x") + blk_regs("y"))
+    e(f"v_cmp_ne_u32 {S_M0}, 0, {AUX1}")
+    e.or_all(AUX2, blk_regs("ZZ"))
+    e(f"v_cmp_eq_u32 {S_M1}, 0, {AUX2}")
+    e(f"s_and_b64 {S_M2}, exec, exec")
+    e("s_cbranch_scc1 .Lvsp_acc28_inf_done")
+    # the full equal-x test, EXEC = body lanes
+    e(".Lvsp_acc28_cold_eqx:")
+    e.or_all(AUX1, blk_regs("T4"))
+    e(f"v_xor_b32 {AUX2}, {SP(0)}, {R('T4', 0)}")
+    for i in range(1, N):
+        e(f"v_xor_b32 {AUX0}, {SP(i)}, {R('T4', i)}")
+        e(f"v_or_b32 {AUX2}, {AUX2}, {AUX0}")
+    e(f"v_cmp_eq_u32 {S_M1}, 0, {AUX1}")
+    e(f"v_cmp_eq_u32 {S_M2}, 0, {AUX2}")
+    e(f"s_or_b64 {S_M1}, {S_M1}, {S_M2}")
+    e(f"v_cndmask_b32 {V_FLAG}, {V_FLAG}, 1, {S_M1}")
+    e(f"v_cndmask_b32 {V_END}, {V_END}, 0, {S_M1}")
+    e(f"s_and_b64 {S_M2}, exec, exec")
+    e("s_cbranch_scc1 .Lvsp_acc28_eqx_done")
     e(".Lvsp_acc28_exit:")
     e("s_waitcnt vmcnt(0)")                                   # the last iteration's look-ahead loads land in dead registers: let them, before the caller reuses them
     e(f"s_mov_b64 exec, {S_EXEC0}")

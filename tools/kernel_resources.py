@@ -23,7 +23,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-pass-failed", "-Wno-unused-value", "-Wno-unused-function",
          "-Wno-unused-result", "--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage", "-mllvm", "-enable-misched=0"]
 # the G1 kernels of the 28-bit bucket reduction and merges: no call, no stack
-GUARDED = re.compile(r"(k_dimsum|k_dimbits|k_dimweight|k_merge_a|k_merge2)<vsp::Fp28[,>]")
+GUARDED = re.compile(r"(k_dimsum|k_dimsum_dense|k_dimbits|k_dimweight|k_merge_a|k_merge2)<vsp::Fp28[,>]")
 EXEMPT = re.compile(r"k_dimsum_mixed")
 VGPR_CAP = int(os.environ.get("VSP_GUARD_VGPR_CAP", "256"))
 

@@ -9,7 +9,7 @@ the derived figures the roofline discussion needs:
 import collections, csv, glob, json, sys
 
 dirs, out_path = sys.argv[1:-1], sys.argv[-1]
-KEEP = ("k_accum28", "k_accum28_cxx", "k_ntt29_pass", "k_scatter_lds", "k_count_lds", "k_dimsum", "k_dimsum_mixed", "k_dimbits", "k_dimweight", "k_merge_a", "k_digits", "k_glv_digits", "k_glv_split", "k_accum_redo", "k_ms_pairs", "k_ms_hist", "k_ms_scatter", "k_ms_final")
+KEEP = ("k_accum28", "k_accum28_cxx", "k_ntt29_pass", "k_scatter_lds", "k_count_lds", "k_dimsum", "k_dimsum_mixed", "k_dimsum_dense", "k_dimbits", "k_dimweight", "k_merge_a", "k_digits", "k_glv_digits", "k_glv_split", "k_accum_redo", "k_ms_pairs", "k_ms_hist", "k_ms_scatter", "k_ms_final")
 
 
 def short(name):

@@ -17,6 +17,12 @@
 // Derivation (p / 2^392 = 1 / 2521):  P = U2 + 32p - X < 33.1p,  PP = P^2 < (33.1^2 / 2521 + 1) p = 1.44p,  PPP, Q < 1.02p,
 //   R = S2 + 32p - Y < 33.5p,  R^2 < 1.45p,  s = PPP + 2Q < 3.1p (limbs < 3 * 2^28),  X3 = R^2 + 8p - s < 9.5p,
 //   Q - X3 + 32p < 33.1p (limbs < 2^30),  32p - Y1 < 32p (limbs < 2^29),  Y3 = [R (Q - X3) + (32p - Y1) PPP] / 2^392 + p < 1.5p.
+// The generated loop (accum28_asm_gfx950.h) runs the same formulas WITHOUT the carry passes of P and R: both stay loose, limb i below
+//   2^28 + K32_L1[i] < 1.5 * 2^29 (top limb: a product output's top limb + K32_L1[13]), values as above.  Their readers' columns:
+//   P^2, R^2 against the doubled operand (limbs < 1.5 * 2^30): 7 * (1.5 * 2^29)(1.5 * 2^30) + (1.5 * 2^29)^2 + 14 * 2^56 < 2^63.2;
+//   P PP: loose x tight;  R (Q + 32p - X3) + (32p - Y1) PPP with R and the difference loose: 14 * (1.5 * 2^29)^2 + 14 * 2^57 + 14 * 2^56 < 2^63.4.
+//   A product's output depends on its operands' values only, so the results are those of madd28 below bit for bit
+//   (tests/test_accum28_lean_cpu.py: exact limb model with these constants).
 // G1: the bucket sums stay in this form through the merges and the bucket reduction (XYZZ<Fp28> below); conversion happens once per
 // table entry (at precomputation) and once per window result.  G2 converts at the store of each bucket part.
 #pragma once
@@ -199,6 +205,7 @@ __device__ __forceinline__ bool madd28(XYZZ28 &acc, const Affine28 &q, bool nega
     if (is_inf28(acc)) { acc.X = q.x; acc.Y = negate ? norm28(qy) : qy; acc.ZZ = fp28_const(FP28_ONE); acc.ZZZ = acc.ZZ; return true; }
     Fp28 U2 = mul28(q.x, acc.ZZ);
     Fp28 S2 = mul28(qy, acc.ZZZ);
+    // (the two carry passes of P and R are this twin's own: the generated loop keeps both loose, limbs < 1.5 * 2^29 -- header above; same results)
     Fp28 P = norm28(sub28(U2, FP28_K32_L1, acc.X));                      // X1 tight, < 16p  ->  P tight, < 33.1p
     Fp28 PP = sqr28(P);                                                  // P tight  ->  < 1.44p
     if (fp28_product_is_zero(PP)) return false;
@@ -210,6 +217,7 @@ __device__ __forceinline__ bool madd28(XYZZ28 &acc, const Affine28 &q, bool nega
     for (int i = 0; i < 14; i++) s.l[i] = PPP.l[i] + 2u * Q.l[i];
     Fp28 X3 = norm28(sub28(sqr28(R), FP28_K8_L4, s));                    // R tight;  X3 tight, < 9.5p
     // Y3 = R (Q - X3) - Y1 PPP = R (Q - X3) + (32p - Y1) PPP: one dual product, one reduction; limb bounds 28+30 and 29+28
+    // (generated loop, R loose: 1.5 * 2^29 times 1.5 * 2^29, and 29+28 -- columns < 2^63.4)
     acc.Y = mul28x2(R, sub28(Q, FP28_K32_L1, X3), neg28(FP28_K32_L1, acc.Y), PPP);      // tight, < 1.5p
     acc.X = X3;
     acc.ZZ = mul28(acc.ZZ, PP);

@@ -578,6 +578,67 @@ __global__ __launch_bounds__(64, AccumWaves<F>::W) void k_dimsum_mixed(const XYZ
     }
     if (live && lane == 0) LV::store(&dims[(size_t)w * per_w + base + v], acc);
 }
+// The same sums, the same lane count per digit, the same additions -- with the TREE packed onto as few waves as it has live additions
+// (one-lane fields; option "msm_dimsum_dense", default 1).  In k_dimsum_mixed a tree level leaves 1/2, 1/4, ... of a wave's lanes live, and
+// an EXEC-masked full addition takes the issue slots of a dense one: at 32 lanes per sum a wave issues 7 serial + 5 tree additions.  Here a
+// workgroup is four such waves (256 threads, the partial sums in LDS: 256 x 224 B, the footprint of k_merge_a) and a tree level is
+// renumbered: its A = (sums of the block) x s live additions sit on threads 0 .. A - 1 -- thread j folds lanes l = j % s and l + s of sum
+// j / s -- and a wave without a live addition only reaches the barrier.  4 x 7 + (2 + 1 + 1 + 1 + 1) = 34 wave-additions per block against
+// 4 x 12 at 32 lanes per sum, 4 x 7 + (2 + 1 + 1 + 1) = 33 against 4 x 11 at 16: 27 % fewer at c = 16.  The dependent chain is as long as
+// before (the serial prefix, then log2(LPS) levels, one barrier each).  Within a level the slot (sum, l) is read and written by its own
+// thread only and the slot (sum, l + s) is read only: no hazard inside a level.
+// Block b serves digit d when blk0[d] <= b < blk0[d + 1]; the sums of a digit are dealt to whole blocks (a ragged last block per digit).
+struct DimSumDensePlan { unsigned lps[3]; unsigned blk0[4]; };
+static constexpr unsigned DIMSUM_DENSE_NT = 256;
+template <class F>
+__global__ __launch_bounds__(DIMSUM_DENSE_NT, AccumWaves<F>::W) void k_dimsum_dense(const XYZZ<F> *buckets, MsmGeom g, XYZZ<F> *dims, DimSumDensePlan pl) {
+    using LV = LaneView<F>; using E = typename LV::E;
+    static_assert(LV::LANES == 1, "the lane-pair form keeps k_dimsum_mixed");
+    constexpr unsigned NT = DIMSUM_DENSE_NT;
+    __shared__ XYZZ<E> sh[NT];
+    const unsigned n0 = 1u << g.q0, n1 = 1u << g.q1, n2 = dims_n2(g);
+    const unsigned per_w = dims_per_w(g);
+    const unsigned d = blockIdx.x < pl.blk0[1] ? 0u : (blockIdx.x < pl.blk0[2] ? 1u : 2u);        // uniform over the block
+    const unsigned LPS = pl.lps[d], SPB = NT / LPS;                                               // sums per block
+    const unsigned nd = d == 0 ? n0 : (d == 1 ? n1 : n2), base = d == 0 ? 0u : (d == 1 ? n0 : n0 + n1);
+    const unsigned qd = d == 0 ? g.q0 : (d == 1 ? g.q1 : g.q2);
+    const unsigned id0 = (blockIdx.x - pl.blk0[d]) * SPB;                                         // first sum of this block: (window, value)
+    const unsigned lane = threadIdx.x % LPS;
+    {
+        const unsigned id = id0 + threadIdx.x / LPS;
+        const bool live = id < g.Wr * nd;
+        const unsigned w = live ? id / nd : 0, v = live ? id % nd : 0;
+        const unsigned items = live ? g.B >> qd : 0;
+        const XYZZ<F> *bw = buckets + (size_t)w * g.B;
+        auto index_of = [&](unsigned i) {
+            if (d == 0) return (i << g.q0) | v;
+            if (d == 1) return ((i >> g.q0) << (g.q1 + g.q0)) | (v << g.q0) | (i & (n0 - 1));
+            return (v << (g.q1 + g.q0)) | i;
+        };
+        XYZZ<E> acc = XYZZ<E>::inf();
+        for (unsigned i = lane; i < items; i += LPS) xyzz_add(acc, LV::load(&bw[index_of(i)]));
+        sh[threadIdx.x] = acc;
+    }
+    __syncthreads();
+    const unsigned wave_first = threadIdx.x & ~63u;                                              // uniform over the wave
+    for (unsigned s = LPS / 2; s >= 1; s >>= 1) {
+        const unsigned A = SPB * s;                                                               // live additions of this level
+        if (wave_first < A) {                                                                     // a wave above them only reaches the barrier
+            const unsigned j = threadIdx.x;
+            if (j < A) {
+                const unsigned slot = (j / s) * LPS + j % s;
+                XYZZ<E> acc = sh[slot];
+                xyzz_add(acc, sh[slot + s]);
+                if (s > 1) sh[slot] = acc;
+                else {                                                                            // thread j holds sum id0 + j
+                    const unsigned id = id0 + j;
+                    if (id < g.Wr * nd) LV::store(&dims[(size_t)(id / nd) * per_w + base + id % nd], acc);
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
 template <class F> static DimSumPlan dimsum_plan(const MsmGeom &g, unsigned MAXW = 1024) {      // wave0[3] == 0: no plan; MAXW 1024 = one wave per SIMD of an MI355X
     constexpr unsigned LL = 64 / LaneView<F>::LANES;
     const unsigned nd[3] = {1u << g.q0, 1u << g.q1, dims_n2(g)};
@@ -828,7 +889,23 @@ static int launch_tail(vsp_ctx *ctx, hipStream_t st, const MsmWork *pl, const Ms
         if (!forced_lanes) pl = dimsum_plan<F>(g, maxw);      // a lane count per digit (k_dimsum_mixed); "msm_dimsum_lanes" keeps one count for all
         ctx->stats["msm_dimsum_waves"] = pl.wave0[3];
         const long pf = opt(ctx, "msm_dimsum_prefetch", 0);
-        if (pl.wave0[3] && pf && LaneView<F>::LANES == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dimsum_mixed<F, true>), dim3(pl.wave0[3]), dim3(64), 0, st, (const XYZZ<F> *)buckets, g, dims, pl);
+        bool dense = false;
+        if constexpr (LaneView<F>::LANES == 1) {
+            // the plan's lane counts, its sums dealt to whole 256-thread blocks per digit ("msm_dimsum_dense" = 0: one wave per block, k_dimsum_mixed)
+            if (pl.wave0[3] && !pf && opt(ctx, "msm_dimsum_dense", 1)) {
+                const unsigned nd[3] = {1u << g.q0, 1u << g.q1, dims_n2(g)};
+                DimSumDensePlan dp; dp.blk0[0] = 0;
+                for (unsigned d = 0; d < 3; d++) {
+                    dp.lps[d] = pl.lps[d];
+                    dp.blk0[d + 1] = dp.blk0[d] + (unsigned)(((size_t)g.Wr * nd[d] * pl.lps[d] + DIMSUM_DENSE_NT - 1) / DIMSUM_DENSE_NT);
+                }
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dimsum_dense<F>), dim3(dp.blk0[3]), dim3(DIMSUM_DENSE_NT), 0, st, (const XYZZ<F> *)buckets, g, dims, dp);
+                ctx->stats["msm_dimsum_dense_launches"] += 1;
+                dense = true;
+            }
+        }
+        if (dense) {}
+        else if (pl.wave0[3] && pf && LaneView<F>::LANES == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dimsum_mixed<F, true>), dim3(pl.wave0[3]), dim3(64), 0, st, (const XYZZ<F> *)buckets, g, dims, pl);
         else if (pl.wave0[3]) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dimsum_mixed<F, false>), dim3(pl.wave0[3]), dim3(64), 0, st, (const XYZZ<F> *)buckets, g, dims, pl);
         else
         if (lps == 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dimsum<F, 8>), grid, dim3(64), 0, st, (const XYZZ<F> *)buckets, g, dims);
