@@ -906,6 +906,50 @@ int vsp_registry_paths(vsp_ctx *ctx, const vsp_registry *reg, const uint64_t *in
 size_t vsp_registry_blob_size(unsigned depth);                    /* 32 (2^(depth + 1) - 1) */
 int vsp_registry_to_blob(vsp_ctx *ctx, const vsp_registry *reg, uint8_t *out);
 
+/* ---- the voting circuit: the statement of the election's proofs, and its witnesses in batches -------------------------
+ * What process_encrypted_input_mode_vote_phase builds (common.hpp:1054-1128): "I know sk and a copath such that H(sk) is a leaf of the
+ * tree with root rt, sn = H(eid | sk), and m is my ballot".  PINNED by the reference: the public inputs and their order, m_1 .. m_n |
+ * eid_packed (ceil(eid_bits / 254) scalars) | sn_packed (2) | rt_packed (2); the packing in chunks of 254 bits (bit i of a block: scalar
+ * i / 254, weight 2^(i % 254)); m = the first n entries of the witness; the rest inputs are what a vsp_ballot_box calls FIXED, SERIAL,
+ * FIXED.  The statement's private side and every gadget are this library's (csrc/vote_circuit.h says what each row is): every m_i is 0
+ * or 1 and they sum to 1; every private bit is boolean; pk = H(sk) over 255 bits, leaf = H(pk) with hash_leaves (else pk); cur_(l+1) =
+ * H(cur_l | sib_l) or H(sib_l | cur_l) by address bit l, cur_depth = rt; sn = H(eid | sk).  H is the hash of `ped`; a digest in the
+ * circuit is the canonical 255 bits of u, held below r by a strict comparison.
+ * vsp_vote_circuit_create builds the three CSR matrices on the host from the table of `ped` (which must outlive the circuit) and uploads
+ * them with vsp_r1cs_upload: vsp_vote_circuit_r1cs is that system, for every prover, generator and checker call.  VSP_ERR_ARG: a null
+ * pointer, a handle of another device, fewer than 3 generators, msg_size = 0, eid_bits = 0 or eid_bits + 255 > 189 g; depth > 24 is
+ * VSP_ERR_UNSUPPORTED.  vsp_vote_circuit_sizes: rows, public inputs, variables and the entries of A, B, C (any output may be NULL);
+ * vsp_vote_circuit_csr copies matrix 0, 1 or 2 out (row_ptr num_constraints + 1, col and coef x 4 words by its entries; columns ascending,
+ * column 0 the constant 1).  vsp_vote_circuit_wires: the first index into a witness and the count of a named block.
+ * vsp_vote_witness_batch fills the witnesses of `count` ballots (any count, pieces of 64) on the device against a resident registry of
+ * the circuit's depth: eid_bits_words ceil(eid_bits / 64) words, sks count x 4 (255 bits), indices the voters' leaves, votes the chosen
+ * slot.  status_out[k]: 0 ok; 1 the leaf computed from sk is not the registry's leaf at the index (or a node of the path is not the hash
+ * of its children): the witness is all zero; 2 vote >= msg_size, index >= 2^depth or sk >= 2^255: all zero, no GPU work.  VSP_OK whatever
+ * the statuses.  The call's device copies of sk, of the chains and of the witnesses are zeroed before it returns.  Statistic
+ * "vote_witness_ms": the kernels by HIP events.  vsp_vote_witness_host is the header's one-core host path over the same layout functions
+ * from an explicit copath (depth x 4 words), for tests and measurements: nothing switches to it.  leaf_out may be NULL.
+ * vsp_vote_cast_batch: count (1..64) ballots = vsp_vote_witness_batch, then vsp_saver_encrypt_batch with m one-hot at the vote over the
+ * members of status 0; outputs as vsp_saver_encrypt_batch (any may be NULL) plus status_out; a member of non-zero status gets all-zero
+ * outputs.  The witnesses travel through host memory. */
+typedef struct vsp_vote_circuit vsp_vote_circuit;
+enum { VSP_VOTE_M = 0, VSP_VOTE_EID_PACKED = 1, VSP_VOTE_SN_PACKED = 2, VSP_VOTE_RT_PACKED = 3, VSP_VOTE_EID_BITS = 4, VSP_VOTE_SK_BITS = 5,
+       VSP_VOTE_ADDRESS_BITS = 6, VSP_VOTE_COPATH_BITS = 7, VSP_VOTE_SN_BITS = 8, VSP_VOTE_RT_BITS = 9 };
+int vsp_vote_circuit_create(vsp_ctx *ctx, const vsp_pedersen *ped, size_t msg_size, size_t eid_bits, unsigned depth, int hash_leaves, vsp_vote_circuit **out);
+void vsp_vote_circuit_free(vsp_ctx *ctx, vsp_vote_circuit *circ);
+const vsp_r1cs *vsp_vote_circuit_r1cs(const vsp_vote_circuit *circ);
+int vsp_vote_circuit_sizes(const vsp_vote_circuit *circ, size_t *num_constraints_out, size_t *num_inputs_out, size_t *num_vars_out, size_t nnz_out[3]);
+int vsp_vote_circuit_csr(const vsp_vote_circuit *circ, int matrix, uint32_t *row_ptr_out, uint32_t *col_out, uint64_t *coef_out);
+int vsp_vote_circuit_wires(const vsp_vote_circuit *circ, int block, size_t *first_out, size_t *count_out);
+int vsp_vote_witness_host(const vsp_vote_circuit *circ, const uint64_t *eid_bits_words, const uint64_t sk[4], uint64_t index, uint32_t vote,
+                          const uint64_t *copath /* depth x 4 */, uint64_t *witness_out /* num_vars x 4 */, uint64_t leaf_out[4] /* may be NULL */);
+int vsp_vote_witness_batch(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_registry *reg, const uint64_t *eid_bits_words, const uint64_t *sks /* count x 4 */,
+                           const uint64_t *indices /* count */, const uint32_t *votes /* count */, size_t count,
+                           uint64_t *witnesses_out /* host count x num_vars x 4, canonical */, uint8_t *status_out /* count */);
+int vsp_vote_cast_batch(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_registry *reg, const vsp_saver_pk *spk, const vsp_pk *pk, const uint64_t *eid_bits_words,
+                        const uint64_t *sks, const uint64_t *indices, const uint32_t *votes, size_t count /* 1..64 */, const uint64_t *r_enc, const uint64_t *r,
+                        const uint64_t *s, uint64_t *ct_out, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out, uint8_t *ct_blobs_out,
+                        uint8_t *status_out /* count */);
+
 /* ---- SAVER decryption on the GPU: decrypt / verify_decryption<elgamal_verifiable> (common.hpp:1220-1223, 1282-1283) -----------------
  * The last step of the election: opening the aggregated ciphertext that vsp_tally_result returns, and checking a published result.
  * With n = msg_size, G_i = gamma_abc_g1[i], H the generator of G2, V_i = rho_sv_g2[i-1], W_i = rho_rhov_g2[i-1] (the verification key of

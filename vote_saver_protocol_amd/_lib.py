@@ -178,6 +178,15 @@ PROTOTYPES = {
     "vsp_registry_paths": (_I, [_P, _P, _P, _SZ, _P]),
     "vsp_registry_blob_size": (_SZ, [_U]),
     "vsp_registry_to_blob": (_I, [_P, _P, _P]),
+    "vsp_vote_circuit_create": (_I, [_P, _P, _SZ, _SZ, _U, _I, _P]),
+    "vsp_vote_circuit_free": (None, [_P, _P]),
+    "vsp_vote_circuit_r1cs": (_P, [_P]),
+    "vsp_vote_circuit_sizes": (_I, [_P, _P, _P, _P, _P]),
+    "vsp_vote_circuit_csr": (_I, [_P, _I, _P, _P, _P]),
+    "vsp_vote_circuit_wires": (_I, [_P, _I, _P, _P]),
+    "vsp_vote_witness_host": (_I, [_P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P]),
+    "vsp_vote_witness_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
+    "vsp_vote_cast_batch": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "vsp_saver_decryptor_create": (_P, [_P, _SZ, _P, _P, C.c_uint64]),
     "vsp_saver_decryptor_free": (None, [_P, _P]),
     "vsp_saver_decryptor_msg_size": (_SZ, [_P]),

@@ -1297,6 +1297,121 @@ class Registry:
         return out.tobytes()
 
 
+class _BorrowedR1CS:
+    """the constraint system a VoteCircuit owns, as every prover, generator and checker call takes one"""
+
+    def __init__(self, ctx, handle, num_constraints, num_inputs, num_vars):
+        self.ctx, self.h = ctx, handle
+        self.num_constraints, self.num_inputs, self.num_vars = num_constraints, num_inputs, num_vars
+        self.m = ctx.lib.vsp_r1cs_domain_size(handle)
+        self.domain_kind = ("basic_radix2", "step_radix2")[ctx.lib.vsp_r1cs_domain_kind(handle)]
+
+    check = R1CS.check
+    is_satisfied = R1CS.is_satisfied
+
+    def free(self):
+        self.h = None
+
+
+class VoteCircuit:
+    """The voting circuit (vsp_vote_circuit): "I know sk and a copath such that H(sk) is a leaf of the tree with root rt,
+    sn = H(eid | sk), and m is my ballot", built from the hash `ped` (which must outlive it).  Public inputs m_1 .. m_n | eid_packed |
+    sn_packed (2) | rt_packed (2).  .cs is its constraint system for groth16 / saver calls; .blocks names the wires of a witness."""
+
+    BLOCKS = ("M", "EID_PACKED", "SN_PACKED", "RT_PACKED", "EID_BITS", "SK_BITS", "ADDRESS_BITS", "COPATH_BITS", "SN_BITS", "RT_BITS")
+
+    def __init__(self, ctx, ped, msg_size, eid_bits, depth, hash_leaves=True):
+        self.ctx = ctx
+        h = C.c_void_p(None)
+        ctx.check(ctx.lib.vsp_vote_circuit_create(ctx.h, ped.h, int(msg_size), int(eid_bits), int(depth), int(bool(hash_leaves)), C.byref(h)))
+        self.h = h
+        self.msg_size, self.eid_bits, self.depth, self.hash_leaves = int(msg_size), int(eid_bits), int(depth), bool(hash_leaves)
+        m, ni, nv = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        nnz = (C.c_size_t * 3)()
+        ctx.check(ctx.lib.vsp_vote_circuit_sizes(self.h, C.byref(m), C.byref(ni), C.byref(nv), nnz))
+        self.num_constraints, self.num_inputs, self.num_vars, self.nnz = m.value, ni.value, nv.value, [int(x) for x in nnz]
+        self.cs = _BorrowedR1CS(ctx, ctx.lib.vsp_vote_circuit_r1cs(self.h), self.num_constraints, self.num_inputs, self.num_vars)
+        self.blocks = {}
+        for i, name in enumerate(self.BLOCKS):
+            first, count = C.c_size_t(0), C.c_size_t(0)
+            ctx.check(ctx.lib.vsp_vote_circuit_wires(self.h, i, C.byref(first), C.byref(count)))
+            self.blocks[name] = (first.value, count.value)
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.vsp_vote_circuit_free(self.ctx.h, self.h)
+            self.h = None
+            self.cs.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def csr(self):
+        """the three matrices as uploaded: [(row_ptr u32 [m + 1], col u32 [nnz], coef u64 [nnz, 4])] * 3, columns ascending in every row"""
+        out = []
+        for k in range(3):
+            rp = np.zeros(self.num_constraints + 1, np.uint32); col = np.zeros(max(self.nnz[k], 1), np.uint32); coef = np.zeros((max(self.nnz[k], 1), 4), np.uint64)
+            self.ctx.check(self.ctx.lib.vsp_vote_circuit_csr(self.h, k, _ptr(rp), _ptr(col), _ptr(coef)))
+            out.append((rp, col[:self.nnz[k]], coef[:self.nnz[k]]))
+        return out
+
+    def _eid(self, eid_words):
+        return _u64(eid_words, (self.eid_bits + 63) // 64).reshape(-1)
+
+    def _members(self, sks, indices, votes):
+        sks = _u64(sks, 4)
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        votes = np.ascontiguousarray(votes, dtype=np.uint32).reshape(-1)
+        if not (sks.shape[0] == idx.shape[0] == votes.shape[0]):
+            raise ValueError("VoteCircuit: sks, indices and votes must have one entry per ballot")
+        return sks, idx, votes
+
+    def witness_host(self, eid_words, sk, index, vote, copath):
+        """one ballot's witness by the header's one-core host path from an explicit copath [depth, 4] (tests and measurements)
+        -> (witness [num_vars, 4], leaf [4])"""
+        out = np.zeros((self.num_vars, 4), np.uint64); leaf = np.zeros(4, np.uint64)
+        cp = np.ascontiguousarray(copath, dtype=np.uint64).reshape(-1)
+        rc = self.ctx.lib.vsp_vote_witness_host(self.h, _ptr(self._eid(eid_words)), _ptr(_u64(sk, 4).reshape(-1)), int(index), int(vote),
+                                                _ptr(cp if cp.size else np.zeros(4, np.uint64)), _ptr(out), _ptr(leaf))
+        if rc:
+            raise ValueError("VoteCircuit.witness_host: vote, index or sk out of range")
+        return out, leaf
+
+    def witness_batch(self, reg, eid_words, sks, indices, votes):
+        """the witnesses of count ballots on the GPU against a resident Registry (vsp_vote_witness_batch)
+        -> (witnesses [count, num_vars, 4], status u8 [count]: 0 ok, 1 not the registry's leaf, 2 vote / index / sk out of range)"""
+        sks, idx, votes = self._members(sks, indices, votes)
+        n = sks.shape[0]
+        wit = np.zeros((n, self.num_vars, 4), np.uint64); status = np.zeros(max(n, 1), np.uint8)
+        dummy = np.zeros(4, np.uint64)
+        self.ctx.check(self.ctx.lib.vsp_vote_witness_batch(self.ctx.h, self.h, reg.h, _ptr(self._eid(eid_words)), _ptr(sks if n else dummy), _ptr(idx if n else dummy),
+                                                           _ptr(votes if n else np.zeros(1, np.uint32)), n, _ptr(wit if n else dummy), _ptr(status)))
+        return wit, status[:n]
+
+    def cast_batch(self, reg, spk, pk, eid_words, sks, indices, votes, r_enc, r, s):
+        """count (1..64) ballots in one call (vsp_vote_cast_batch): the witnesses, then saver_encrypt_batch with m one-hot at the vote.
+        -> (ct, (A, B, C), [proof bytes], [ciphertext blob bytes], status); a member of non-zero status has all-zero outputs"""
+        sks, idx, votes = self._members(sks, indices, votes)
+        K, n = sks.shape[0], self.msg_size
+        rnd = [np.ascontiguousarray(x, dtype=np.uint64).reshape(K, 4) for x in (r_enc, r, s)]
+        ct = np.zeros((K, n + 2, 12), np.uint64)
+        A = np.zeros((K, 12), np.uint64); B = np.zeros((K, 24), np.uint64); Cc = np.zeros((K, 12), np.uint64)
+        proofs = np.zeros((K, 192), np.uint8); bl = np.zeros((K, self.ctx.lib.vsp_g1_vector_blob_size(n + 2)), np.uint8)
+        status = np.zeros(max(K, 1), np.uint8)
+        rc = self.ctx.lib.vsp_vote_cast_batch(self.ctx.h, self.h, reg.h, spk.h, pk.h, _ptr(self._eid(eid_words)), _ptr(sks), _ptr(idx), _ptr(votes), K, _ptr(rnd[0]),
+                                              _ptr(rnd[1]), _ptr(rnd[2]), _ptr(ct), _ptr(A), _ptr(B), _ptr(Cc), _ptr(proofs), _ptr(bl), _ptr(status))
+        results = (ct, (A, B, Cc), [proofs[k].tobytes() for k in range(K)], [bl[k].tobytes() for k in range(K)], status[:K])
+        try:
+            self.ctx.check(rc)
+        except Unsatisfied as e:
+            e.results = results
+            raise
+        return results
+
+
 class SaverDecryptor:
     """The opening side of a SAVER election resident on the GPU (vsp_saver_decryptor), made of public data only: the prepared
     Miller-loop lines of rho_sv_g2, rho_rhov_g2, H and -rho_g2, the bases e(G_i, rho_rhov_g2[i]) and their baby-step tables for

@@ -463,6 +463,18 @@ struct vsp_ballot_box {
     vsp::StageTimer timer[2];           // [0] 0-1 the screening; [1] 0-1 growth, claim and resolve, 2-3 the commit
 };
 
+// The hash's tables and a registry's tree (pedersen.hip), which the voting circuit's witnesses read in place (vote_circuit.hip)
+struct vsp_pedersen {
+    int device = 0;
+    size_t g = 0;
+    vsp::DevBuf table;              // g x 252 entries of 96 bytes
+};
+struct vsp_registry {
+    int device = 0;
+    unsigned depth = 0;
+    vsp::DevBuf nodes;              // 2^(depth + 1) - 1 digests of four words, leaves first, root last
+};
+
 namespace vsp {
 
 // option `name` of the context (vsp_set_option), or dflt when it was never set

@@ -14,17 +14,6 @@
 #include "common.h"
 #include "jubjub.h"
 
-struct vsp_pedersen {
-    int device = 0;
-    size_t g = 0;
-    vsp::DevBuf table;              // g x 252 entries of 96 bytes
-};
-struct vsp_registry {
-    int device = 0;
-    unsigned depth = 0;
-    vsp::DevBuf nodes;              // 2^(depth + 1) - 1 digests of four words, leaves first, root last
-};
-
 namespace vsp {
 
 static constexpr unsigned PED_THREADS = 256;
