@@ -339,6 +339,30 @@ int vsp_groth16_prove_batch(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, 
 int vsp_groth16_prove_batch_launch(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witnesses, size_t count,
                                    const uint64_t *r, const uint64_t *s);
 int vsp_groth16_prove_batch_finish(vsp_ctx *ctx, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out);
+/* WITNESSES IN DEVICE MEMORY.  A witness generator that runs on the GPU -- vsp_cast_witness_batch_device is one -- hands its witnesses to
+ * the batch prover, the witness check and the ballot batch where they lie.  The source is four arguments:
+ *     d_witnesses  device memory of the context's device, 16-byte aligned: `rows` rows of `stride` values of 4 canonical words each; a row's
+ *                  first num_vars values are a witness (primary || auxiliary), so stride >= num_vars
+ *     members      host memory, `count` row indices, each < rows, in any order and with repeats; NULL means rows 0 .. count - 1
+ * One kernel (csrc/prover.hip k_witness_gather, 16-byte loads and stores along a row, the map passed by value) writes z_k = (1, row
+ * members[k]) into the prover's workspace; everything behind it is the code of the host form, and proof k is byte-identical to the
+ * host form's over the same witness.  Nothing is waited for.  STREAM ORDER: the source must be complete on the context's stream when the
+ * call is made, as for every other device pointer of this header; every read of it is queued on the context's stream before the call
+ * returns, so work queued on that stream afterwards may overwrite or zero the buffer.  `members` is read before the call returns.
+ * VSP_ERR_ARG, each with its message, before anything is queued: a null pointer, a pointer that is not 16-byte aligned, stride < num_vars,
+ * members[k] >= rows (members NULL: count > rows), count outside 1..64 for the provers, a proof in flight.  Whether d_witnesses IS device
+ * memory of the context's device is not checked: no entry point of this header checks its device pointers.
+ * _launch_device / _device finish through vsp_groth16_prove_batch_finish like the host form.  vsp_r1cs_check_batch_device: any count, in
+ * pieces of 64 members; the same status bytes, first_bad_row and bad_rows as vsp_r1cs_check_batch over the same witnesses.
+ * Statistic "prove_witness_h2d_bytes": the witness bytes the prover's front half copied from the host (every host form; a device source adds none). */
+int vsp_groth16_prove_batch_launch_device(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const void *d_witnesses, size_t stride, size_t rows,
+                                          const uint32_t *members /* host count, or NULL */, size_t count /* 1..64 */, const uint64_t *r, const uint64_t *s);
+int vsp_groth16_prove_batch_device(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const void *d_witnesses, size_t stride, size_t rows,
+                                   const uint32_t *members /* host count, or NULL */, size_t count /* 1..64 */, const uint64_t *r, const uint64_t *s,
+                                   uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out);
+int vsp_r1cs_check_batch_device(vsp_ctx *ctx, const vsp_r1cs *cs, const void *d_witnesses, size_t stride, size_t rows, const uint32_t *members /* host count, or NULL */,
+                                size_t count, uint8_t *status_out /* count */, uint64_t *first_bad_row_out /* count, may be NULL */,
+                                uint64_t *bad_rows_out /* count, may be NULL */);
 /* The same proof in two halves, so that ONE host thread keeps several proofs in flight over one resident key -- one per context:
  *     vsp_groth16_prove_launch(ctxA, ...); vsp_groth16_prove_launch(ctxB, ...); vsp_groth16_prove_finish(ctxA, ...); launch(ctxA, next) ...
  * launch queues every kernel of the proof on the context's streams and returns (it copies r, s and the SAVER term; a witness in
@@ -472,6 +496,21 @@ int vsp_saver_encrypt_batch_finish(vsp_ctx *ctx, uint64_t *ct_out, uint64_t *A_o
 int vsp_saver_encrypt_batch(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *msgs, const uint64_t *witnesses,
                             size_t count /* 1..64 */, const uint64_t *r_enc, const uint64_t *r, const uint64_t *s, uint64_t *ct_out, uint64_t *A_out, uint64_t *B_out,
                             uint64_t *C_out, uint8_t *proofs_out, uint8_t *ct_blobs_out);
+/* The ballot batch over witnesses in device memory ("WITNESSES IN DEVICE MEMORY" above: the same four arguments, the same stream order,
+ * the same errors).  There is no msgs argument: the message IS the first msg_size values of each member's row.  Behind the gather those
+ * values are copied device to device into the ciphertext kernels' scalars, beside r_enc from the host; the ciphertext stream waits for an
+ * event behind the gather.  With option "saver_encrypt_gpu" = 0 the count x msg_size message scalars, and nothing else of the witnesses,
+ * are copied to the host for the host leg.  The outputs are byte-identical to vsp_saver_encrypt_batch over the same rows, under
+ * "prove_check_witness" too.  The host form's launch-time check that every message scalar is canonical has no counterpart here -- the
+ * launch never sees the values: a value >= r is found by the multi-exponentiations' census and reported by the finish (VSP_ERR_ARG) for
+ * the whole batch, as the batch prover reports it, and every ciphertext output of that batch is then zero.  r_enc, r, s: host, checked at
+ * the launch.  Both finish through vsp_saver_encrypt_batch_finish. */
+int vsp_saver_encrypt_batch_launch_device(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1cs *cs, const vsp_pk *pk, const void *d_witnesses, size_t stride,
+                                          size_t rows, const uint32_t *members /* host count, or NULL */, size_t count /* 1..64 */, const uint64_t *r_enc,
+                                          const uint64_t *r, const uint64_t *s);
+int vsp_saver_encrypt_batch_device(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1cs *cs, const vsp_pk *pk, const void *d_witnesses, size_t stride, size_t rows,
+                                   const uint32_t *members /* host count, or NULL */, size_t count /* 1..64 */, const uint64_t *r_enc, const uint64_t *r,
+                                   const uint64_t *s, uint64_t *ct_out, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out, uint8_t *ct_blobs_out);
 /* RERANDOMIZATION IN BATCHES: what the ballot box does to every ballot it receives, `count` ballots a call.
  * A vsp_saver_rerandomizer is public data of one election: the key (which must outlive it) with the device tables vsp_saver_pk_upload
  * builds -- _new makes the upload -- and one more table of the same layout in G2, 64 four-bit windows x 15 affine entries d 16^w delta_g2
@@ -930,7 +969,28 @@ int vsp_registry_to_blob(vsp_ctx *ctx, const vsp_registry *reg, uint8_t *out);
  * from an explicit copath (depth x 4 words), for tests and measurements: nothing switches to it.  leaf_out may be NULL.
  * vsp_vote_cast_batch: count (1..64) ballots = vsp_vote_witness_batch, then vsp_saver_encrypt_batch with m one-hot at the vote over the
  * members of status 0; outputs as vsp_saver_encrypt_batch (any may be NULL) plus status_out; a member of non-zero status gets all-zero
- * outputs.  The witnesses travel through host memory. */
+ * outputs.  Option "vote_cast_device" (default 1): the witnesses never leave the device -- in order: the witnesses into the circuit's
+ * buffer (vsp_cast_witness_batch_device), the status words to the host, the live members as the `members` map of
+ * vsp_saver_encrypt_batch_launch_device, the stream-ordered zeroing of the buffer right behind that launch, the finish, the scatter of
+ * the outputs to the members' slots.  With the option 0 the witnesses travel through host memory: to the host, compacted there, and back
+ * into the batch prover.  Return codes, statuses and every output byte are the same under both values, under "prove_check_witness" too.
+ * Statistics: "vote_witness_d2h_bytes" the witness bytes the vote calls copied to the host, "prove_witness_h2d_bytes" the ones the
+ * prover's front half copied back: neither moves across a call with the option 1.
+ *
+ * The device forms.  (Their names begin vsp_cast_: the vsp_vote_ names above are a closed list.)
+ * vsp_cast_witness_batch_device: count (1..64) ballots as vsp_vote_witness_batch, by the same code, but the witnesses stay in the
+ * circuit's buffer: *d_witnesses_out is device memory of `count` rows, member k in row k (all zero for a non-zero status), *stride_out =
+ * num_vars values a row -- a source for the calls under "WITNESSES IN DEVICE MEMORY", complete on the context's stream.  Only the status
+ * words come to the host; the inputs, digests and chains are zeroed before the call returns, as ever.  The rows stay until
+ * vsp_cast_witness_release zeroes them (stream-ordered on the context's stream, so it may directly follow a launch that reads them); the
+ * next vsp_cast_witness_batch_device, vsp_vote_witness_batch, vsp_vote_cast_batch or vsp_cast_batch_launch on the circuit and
+ * vsp_vote_circuit_free release them too.  One context at a time uses a circuit.
+ * vsp_cast_batch_launch / _finish: vsp_vote_cast_batch's device path in two halves, so that one thread with two contexts and two circuits
+ * builds the witnesses of one batch while the other batch proves.  The launch blocks for the status words alone (status_out is final
+ * when it returns) and queues everything else; the finish is vsp_saver_encrypt_batch_finish plus the scatter (outputs as
+ * vsp_vote_cast_batch, any may be NULL).  VSP_ERR_ARG: a finish with nothing in flight; a second launch, or any prover, batch or witness
+ * check call on that context, while one is in flight -- a batch without a live member included.  The pair takes the device path whatever
+ * "vote_cast_device" says. */
 typedef struct vsp_vote_circuit vsp_vote_circuit;
 enum { VSP_VOTE_M = 0, VSP_VOTE_EID_PACKED = 1, VSP_VOTE_SN_PACKED = 2, VSP_VOTE_RT_PACKED = 3, VSP_VOTE_EID_BITS = 4, VSP_VOTE_SK_BITS = 5,
        VSP_VOTE_ADDRESS_BITS = 6, VSP_VOTE_COPATH_BITS = 7, VSP_VOTE_SN_BITS = 8, VSP_VOTE_RT_BITS = 9 };
@@ -949,6 +1009,14 @@ int vsp_vote_cast_batch(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_registry
                         const uint64_t *sks, const uint64_t *indices, const uint32_t *votes, size_t count /* 1..64 */, const uint64_t *r_enc, const uint64_t *r,
                         const uint64_t *s, uint64_t *ct_out, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out, uint8_t *ct_blobs_out,
                         uint8_t *status_out /* count */);
+int vsp_cast_witness_batch_device(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_registry *reg, const uint64_t *eid_bits_words, const uint64_t *sks /* count x 4 */,
+                                  const uint64_t *indices /* count */, const uint32_t *votes /* count */, size_t count /* 1..64 */,
+                                  const void **d_witnesses_out /* device: count rows */, size_t *stride_out, uint8_t *status_out /* count */);
+int vsp_cast_witness_release(vsp_ctx *ctx, vsp_vote_circuit *circ);
+int vsp_cast_batch_launch(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_registry *reg, const vsp_saver_pk *spk, const vsp_pk *pk, const uint64_t *eid_bits_words,
+                          const uint64_t *sks, const uint64_t *indices, const uint32_t *votes, size_t count /* 1..64 */, const uint64_t *r_enc, const uint64_t *r,
+                          const uint64_t *s, uint8_t *status_out /* count */);
+int vsp_cast_batch_finish(vsp_ctx *ctx, uint64_t *ct_out, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out, uint8_t *ct_blobs_out);
 
 /* ---- SAVER decryption on the GPU: decrypt / verify_decryption<elgamal_verifiable> (common.hpp:1220-1223, 1282-1283) -----------------
  * The last step of the election: opening the aggregated ciphertext that vsp_tally_result returns, and checking a published result.

@@ -4,19 +4,24 @@ under its own time limit (the parent never opens the GPU and starts nothing more
 (default 5) repetitions, reported as min / median / max:
     witness   K = 1, 8, 64 ballots of registered voters: the blocking call's wall time (the witnesses land in host memory) and the
               kernels' time by HIP events ("vote_witness_ms"), as witnesses per second of the median
-    cast      K = 1, 8, 64: vsp_vote_cast_batch beside vsp_saver_encrypt_batch on witnesses made beforehand, the same key, the same
-              process: what the witness step and its round trip through host memory cost a ballot
+    cast      K = 1, 8, 64: vsp_vote_cast_batch with option vote_cast_device = 0 beside vsp_saver_encrypt_batch on witnesses made
+              beforehand, the same key, the same process: what the witness step and its round trip through host memory cost a ballot
+    device    K = 1, 8, 64, four legs alternated in one process: vsp_vote_cast_batch with vote_cast_device = 0 (the witnesses through
+              host memory: the yardstick), with vote_cast_device = 1 (the witnesses stay on the device), vsp_saver_encrypt_batch on ready
+              witnesses, and vsp_cast_batch_launch / _finish from one thread with two contexts and two circuits (two batches of K a
+              repetition, reported per batch)
     cpu       tests/cpu_build/vote_circuit_check.cpp: one ballot's witness by the header's host path, one core
 
-    python3 tools/vote_witness_time.py     prints the report and writes it to profiles/vote_witness_time.txt (OUT=path for another file)"""
+    python3 tools/vote_witness_time.py          witness, cast and cpu: prints the report and writes it to profiles/vote_witness_time.txt
+    python3 tools/vote_witness_time.py report device    the device step alone, to profiles/vote_cast_device_time.txt
+    (OUT=path for another file)"""
 import os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for d in ("", "tests"):
     sys.path.insert(0, os.path.join(ROOT, d))
 
 REPS = int(os.environ.get("R", "5"))
-OUT = os.environ.get("OUT", os.path.join(ROOT, "profiles", "vote_witness_time.txt"))
-LIMITS = {"witness": 240, "cast": 420, "cpu": 120}                  # seconds
+LIMITS = {"witness": 240, "cast": 420, "device": 400, "cpu": 120}   # seconds
 DEPTH, EID_BITS, N, KS = 20, 64, 25, (1, 8, 64)
 
 
@@ -77,13 +82,36 @@ def gpu_step(name):
         gabc = np.ascontiguousarray(parts["gamma_ABC_g1"])
         pk_w, _, _ = v.saver_generate_keypair(ctx, fr(3 * N + 2), gabc, parts["delta_g1"][0], parts["gamma_g1"][0], N)
         spk = v.SaverPublicKey(ctx, pk_w, gabc[:N + 1], N)
+        ctx2 = circ2 = None
+        if name == "device":                                        # the second context and circuit of the launch / finish leg
+            ctx2 = v.Context(0)
+            circ2 = v.VoteCircuit(ctx2, ped, N, EID_BITS, DEPTH)
+
+        def cast_with(option, K, rnd):
+            ctx.set_option("vote_cast_device", option)
+            try:
+                return circ.cast_batch(reg, spk, kp.pk, eid, sks[:K], idx[:K], votes[:K], *rnd)
+            finally:
+                ctx.set_option("vote_cast_device", 1)
+
+        def two_contexts(K, rnd):
+            args = (reg, spk, kp.pk, eid, sks[:K], idx[:K], votes[:K]) + tuple(rnd)
+            circ.cast_batch_launch(*args); circ2.cast_batch_launch(*args)
+            circ.cast_batch_finish(); circ2.cast_batch_finish()
+
         for K in KS:
             rnd = [fr(K) for _ in range(3)]
             wit, status = circ.witness_batch(reg, eid, sks[:K], idx[:K], votes[:K])
             assert not status.any()
             msgs = np.ascontiguousarray(wit[:, :N])
-            legs = {"cast_batch": lambda: circ.cast_batch(reg, spk, kp.pk, eid, sks[:K], idx[:K], votes[:K], *rnd),
+            legs = {"cast_batch": lambda: cast_with(0, K, rnd),
                     "encrypt_batch on ready witnesses": lambda: v.saver_encrypt_batch(ctx, spk, circ.cs, kp.pk, msgs, wit, *rnd)}
+            per_call = {}
+            if name == "device":
+                legs = {"cast_batch, vote_cast_device 0": legs["cast_batch"], "cast_batch, vote_cast_device 1": lambda: cast_with(1, K, rnd),
+                        "encrypt_batch on ready witnesses": legs["encrypt_batch on ready witnesses"],
+                        "launch / finish, two contexts (per batch)": lambda: two_contexts(K, rnd)}
+                per_call = {"launch / finish, two contexts (per batch)": 2}
             ms = {}
             for leg, call in legs.items():
                 call()
@@ -91,9 +119,13 @@ def gpu_step(name):
             for _ in range(REPS):                                   # the two legs alternate, so that drift meets both
                 for leg, call in legs.items():
                     ctx.synchronize()
-                    t0 = time.perf_counter(); call(); ms[leg].append((time.perf_counter() - t0) * 1e3)
+                    if ctx2:
+                        ctx2.synchronize()
+                    t0 = time.perf_counter(); call(); ms[leg].append((time.perf_counter() - t0) * 1e3 / per_call.get(leg, 1))
             for leg in legs:
-                print("K = %2d %-33s wall %s = %8.1f ballots/s" % (K, leg + ":", spread(ms[leg]), K * 1e3 / median(ms[leg])))
+                print("K = %2d %-42s wall %s = %8.1f ballots/s" % (K, leg + ":", spread(ms[leg]), K * 1e3 / median(ms[leg])))
+        if circ2:
+            circ2.free(); ctx2.close()
         spk.free(); kp.free()
     circ.free(); reg.free(); ped.free()
     ctx.close()
@@ -111,13 +143,15 @@ def cpu_step():
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1:
+    if len(sys.argv) > 1 and sys.argv[1] != "report":
         cpu_step() if sys.argv[1] == "cpu" else gpu_step(sys.argv[1])
         sys.exit(0)
+    steps = sys.argv[2:] if len(sys.argv) > 2 and sys.argv[1] == "report" else ("witness", "cast", "cpu")
+    OUT = os.environ.get("OUT", os.path.join(ROOT, "profiles", "vote_cast_device_time.txt" if tuple(steps) == ("device",) else "vote_witness_time.txt"))
     report = ["voting circuit witnesses on one GPU: depth %d, eid_bits %d, n %d, 3 generators; %d repetitions after a warm-up call; every step in its own process" %
               (DEPTH, EID_BITS, N, REPS)]
     print(report[0], flush=True)
-    for step in ("witness", "cast", "cpu"):
+    for i, step in enumerate(steps):
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), step], capture_output=True, text=True, timeout=LIMITS[step])
         except subprocess.TimeoutExpired:
@@ -125,7 +159,7 @@ if __name__ == "__main__":
             print(report[-1], flush=True)
             break
         lines = r.stdout.strip().splitlines()
-        if step == "cast" and lines:
+        if i and step != "cpu" and lines:
             lines = lines[1:]                                       # the circuit's sizes were printed by the first step
         report += lines
         print("\n".join(lines), flush=True)

@@ -419,6 +419,15 @@ class R1CS:
                                                _ptr(bad if n else np.zeros(1, np.uint64))))
         return status, first, bad
 
+    def check_device(self, ctx, d_witnesses, stride, rows, members=None, count=None):
+        """check over witnesses in device memory (vsp_r1cs_check_batch_device): d_witnesses a device pointer to `rows` rows of `stride`
+        values of 4 words, members the row of every member (None: rows 0 .. count - 1), any count.  -> as check"""
+        mem, n = _device_members(members, count)
+        status = np.zeros(max(n, 1), np.uint8); first = np.zeros(max(n, 1), np.uint64); bad = np.zeros(max(n, 1), np.uint64)
+        ctx.check(ctx.lib.vsp_r1cs_check_batch_device(ctx.h, self.h, C.c_void_p(int(d_witnesses)), int(stride), int(rows), _ptr(mem) if mem is not None else None, n,
+                                                      _ptr(status), _ptr(first), _ptr(bad)))
+        return status[:n], first[:n], bad[:n]
+
     def is_satisfied(self, ctx, witness):
         """bp.is_satisfied() (common.hpp:1109-1128) on the GPU: True exactly when every constraint holds and every value is canonical"""
         witness = _u64(witness, 4)
@@ -579,6 +588,37 @@ def groth16_prove_batch(ctx, cs, pk, witnesses, r, s):
     return _check_batch(ctx, rc, (A, B, Cc, [proofs[k].tobytes() for k in range(K)]))
 
 
+def _device_members(members, count):
+    """the `members` map of the calls over witnesses in device memory: (u32 array or None, count)"""
+    if members is None:
+        if count is None:
+            raise ValueError("witnesses in device memory: members or count is needed")
+        return None, int(count)
+    mem = np.ascontiguousarray(members, dtype=np.uint32).reshape(-1)
+    return mem, mem.shape[0]
+
+
+def groth16_prove_batch_launch_device(ctx, cs, pk, d_witnesses, stride, rows, r, s, members=None, count=None):
+    """groth16_prove_batch_launch over witnesses in device memory (vsp_groth16_prove_batch_launch_device): d_witnesses a device pointer
+    to `rows` rows of `stride` >= num_vars values of 4 canonical words, complete on the context's stream; member k is row members[k]
+    (None: rows 0 .. count - 1).  Nothing is waited for; every read of the buffer is queued on the context's stream when this
+    returns.  Finish with groth16_prove_batch_finish.  Returns K."""
+    mem, K = _device_members(members, count)
+    r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4); s = np.ascontiguousarray(s, dtype=np.uint64).reshape(-1, 4)
+    if r.shape[0] != K or s.shape[0] != K:
+        raise ValueError("prove_batch_device: r and s must be [K, 4]")
+    ctx.check(ctx.lib.vsp_groth16_prove_batch_launch_device(ctx.h, cs.h, pk.h, C.c_void_p(int(d_witnesses)), int(stride), int(rows), _ptr(mem) if mem is not None else None,
+                                                            K, _ptr(r), _ptr(s)))
+    ctx._prove_batch_count = K
+    return K
+
+
+def groth16_prove_batch_device(ctx, cs, pk, d_witnesses, stride, rows, r, s, members=None, count=None):
+    """K proofs from witnesses in device memory: launch_device + finish.  -> as groth16_prove_batch, byte for byte"""
+    groth16_prove_batch_launch_device(ctx, cs, pk, d_witnesses, stride, rows, r, s, members, count)
+    return groth16_prove_batch_finish(ctx)
+
+
 def groth16_prove_batch_launch(ctx, cs, pk, witnesses, r, s):
     """first half of groth16_prove_batch: copy the witnesses, queue every kernel of the K proofs, return K (one batch in flight per context)"""
     witnesses, r, s, K = _batch_inputs(cs, witnesses, r, s)
@@ -732,6 +772,25 @@ def saver_encrypt_batch_launch(ctx, spk, cs, pk, msgs, witnesses, r_enc, r, s):
     ctx.check(ctx.lib.vsp_saver_encrypt_batch_launch(ctx.h, spk.h, cs.h, pk.h, _ptr(msgs), _ptr(witnesses), K, _ptr(r_enc), _ptr(r), _ptr(s)))
     ctx._saver_batch = (K, spk.n)
     return K
+
+
+def saver_encrypt_batch_launch_device(ctx, spk, cs, pk, d_witnesses, stride, rows, r_enc, r, s, members=None, count=None):
+    """saver_encrypt_batch_launch over witnesses in device memory (vsp_saver_encrypt_batch_launch_device; the source as in
+    groth16_prove_batch_launch_device).  No msgs: the message is the first msg_size values of each member's row.  Returns K."""
+    mem, K = _device_members(members, count)
+    rnd = [np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4) for x in (r_enc, r, s)]
+    if any(x.shape[0] != K for x in rnd):
+        raise ValueError("encrypt_batch_device: r_enc, r and s must be [K, 4]")
+    ctx.check(ctx.lib.vsp_saver_encrypt_batch_launch_device(ctx.h, spk.h, cs.h, pk.h, C.c_void_p(int(d_witnesses)), int(stride), int(rows),
+                                                            _ptr(mem) if mem is not None else None, K, _ptr(rnd[0]), _ptr(rnd[1]), _ptr(rnd[2])))
+    ctx._saver_batch = (K, spk.n)
+    return K
+
+
+def saver_encrypt_batch_device(ctx, spk, cs, pk, d_witnesses, stride, rows, r_enc, r, s, members=None, count=None):
+    """K ballots from witnesses in device memory: launch_device + finish.  -> as saver_encrypt_batch, byte for byte"""
+    saver_encrypt_batch_launch_device(ctx, spk, cs, pk, d_witnesses, stride, rows, r_enc, r, s, members, count)
+    return saver_encrypt_batch_finish(ctx)
 
 
 def saver_encrypt_batch_finish(ctx):
@@ -1307,6 +1366,7 @@ class _BorrowedR1CS:
         self.domain_kind = ("basic_radix2", "step_radix2")[ctx.lib.vsp_r1cs_domain_kind(handle)]
 
     check = R1CS.check
+    check_device = R1CS.check_device
     is_satisfied = R1CS.is_satisfied
 
     def free(self):
@@ -1391,8 +1451,56 @@ class VoteCircuit:
                                                            _ptr(votes if n else np.zeros(1, np.uint32)), n, _ptr(wit if n else dummy), _ptr(status)))
         return wit, status[:n]
 
+    def witness_batch_device(self, reg, eid_words, sks, indices, votes):
+        """the witnesses of count (1..64) ballots left in the circuit's device buffer (vsp_cast_witness_batch_device)
+        -> (device pointer, stride in values, status u8 [count]); member k is row k.  They stay until witness_release, the next witness
+        or cast call on the circuit, or free."""
+        sks, idx, votes = self._members(sks, indices, votes)
+        n = sks.shape[0]
+        d, stride = C.c_void_p(None), C.c_size_t(0)
+        status = np.zeros(max(n, 1), np.uint8)
+        self.ctx.check(self.ctx.lib.vsp_cast_witness_batch_device(self.ctx.h, self.h, reg.h, _ptr(self._eid(eid_words)), _ptr(sks), _ptr(idx), _ptr(votes), n,
+                                                                  C.byref(d), C.byref(stride), _ptr(status)))
+        return d.value, stride.value, status[:n]
+
+    def witness_release(self):
+        """zero the witnesses a device call left in the circuit's buffer, stream-ordered (vsp_cast_witness_release)"""
+        self.ctx.check(self.ctx.lib.vsp_cast_witness_release(self.ctx.h, self.h))
+
+    def cast_batch_launch(self, reg, spk, pk, eid_words, sks, indices, votes, r_enc, r, s):
+        """first half of cast_batch on the device path (vsp_cast_batch_launch): blocks for the status words alone -> status u8 [count]"""
+        sks, idx, votes = self._members(sks, indices, votes)
+        K = sks.shape[0]
+        rnd = [np.ascontiguousarray(x, dtype=np.uint64).reshape(K, 4) for x in (r_enc, r, s)]
+        status = np.zeros(max(K, 1), np.uint8)
+        self.ctx.check(self.ctx.lib.vsp_cast_batch_launch(self.ctx.h, self.h, reg.h, spk.h, pk.h, _ptr(self._eid(eid_words)), _ptr(sks), _ptr(idx), _ptr(votes), K,
+                                                          _ptr(rnd[0]), _ptr(rnd[1]), _ptr(rnd[2]), _ptr(status)))
+        self._cast = (K, status[:K])
+        return status[:K]
+
+    def cast_batch_finish(self):
+        """second half (vsp_cast_batch_finish) -> as cast_batch"""
+        K, status = getattr(self, "_cast", None) or (0, None)
+        self._cast = None
+        if not K:
+            self.ctx.check(self.ctx.lib.vsp_cast_batch_finish(self.ctx.h, None, None, None, None, None, None))      # the library's refusal
+            raise RuntimeError("cast_batch_finish: no batch launched through this circuit")
+        n = self.msg_size
+        ct = np.zeros((K, n + 2, 12), np.uint64)
+        A = np.zeros((K, 12), np.uint64); B = np.zeros((K, 24), np.uint64); Cc = np.zeros((K, 12), np.uint64)
+        proofs = np.zeros((K, 192), np.uint8); bl = np.zeros((K, self.ctx.lib.vsp_g1_vector_blob_size(n + 2)), np.uint8)
+        rc = self.ctx.lib.vsp_cast_batch_finish(self.ctx.h, _ptr(ct), _ptr(A), _ptr(B), _ptr(Cc), _ptr(proofs), _ptr(bl))
+        results = (ct, (A, B, Cc), [proofs[k].tobytes() for k in range(K)], [bl[k].tobytes() for k in range(K)], status)
+        try:
+            self.ctx.check(rc)
+        except Unsatisfied as e:
+            e.results = results
+            raise
+        return results
+
     def cast_batch(self, reg, spk, pk, eid_words, sks, indices, votes, r_enc, r, s):
         """count (1..64) ballots in one call (vsp_vote_cast_batch): the witnesses, then saver_encrypt_batch with m one-hot at the vote.
+        With option vote_cast_device (default 1) the witnesses stay on the device; 0 sends them through host memory: the same outputs.
         -> (ct, (A, B, C), [proof bytes], [ciphertext blob bytes], status); a member of non-zero status has all-zero outputs"""
         sks, idx, votes = self._members(sks, indices, votes)
         K, n = sks.shape[0], self.msg_size

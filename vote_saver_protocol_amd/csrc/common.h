@@ -297,8 +297,13 @@ struct vsp_ctx {
         void *h_scalars = nullptr, *h_points = nullptr; size_t h_scalars_cap = 0, h_points_cap = 0;
         hipEvent_t done = nullptr;
         vsp::StageTimer timer;
-        bool active = false, gpu = false; const vsp_saver_pk *spk = nullptr; size_t count = 0;
+        bool active = false, gpu = false, device_src = false; const vsp_saver_pk *spk = nullptr; size_t count = 0;
     } saver_ct;
+    // a batch of cast ballots between vsp_cast_batch_launch and its finish (vote_circuit.hip): the members' count, the live ones' slots in
+    // member order, the key's msg_size.  Every prover launch refuses a context with a cast in flight, a cast without a live member included
+    struct {
+        bool active = false; size_t count = 0, n = 0; std::vector<uint32_t> live;
+    } cast;
     // rerandomization in batches (saver_rerand.hip): a piece's device workspace -- canonical words in and out (one buffer), scalar records,
     // Montgomery points, column sums of both groups, a status word per ballot --, the pinned staging of both directions, the timers
     // around check | columns | affine and around the G1 | G2 multiplications
@@ -555,6 +560,18 @@ HFr domain_vanishing(const vsp_domain *d, const HFr &t);
 HFr domain_element(const vsp_domain *d, size_t idx);
 // K witnesses: member k's A z, B z, C z at dA, dB, dC + k abc_stride (overwritten), its H at dH + k h_stride (domain.hip)
 int witness_map_device(vsp_ctx *ctx, const vsp_domain *d, Fr *dA, Fr *dB, Fr *dC, size_t abc_stride, unsigned K, Fr *dH, size_t h_stride);
+// the witness as the caller hands it over (prover.hip prove_front_half): plain (num_vars x 4 canonical words a witness, host memory), packed
+// (vsp_witness_pack), or rows of a device buffer -- dev: rows of `stride` values of 4 words, stride >= num_vars; member k of a piece is
+// row members[k], or row first + k where members is null (members: host memory, read before the launch returns)
+struct WitnessSrc {
+    const uint64_t *plain; const uint64_t *class_words; const uint32_t *word_offsets; const uint64_t *dense; size_t n_dense;
+    const uint64_t *dev = nullptr; size_t stride = 0, first = 0; const uint32_t *members = nullptr;
+};
+// the checks every entry point with a device source makes before anything is queued, and the source they yield (prover.hip)
+int witness_src_device(vsp_ctx *ctx, const char *who, const vsp_r1cs *cs, const void *d_witnesses, size_t stride, size_t rows, const uint32_t *members, size_t count,
+                       WitnessSrc *out);
+// vsp_groth16_prove_batch_launch over either kind of source (prover.hip); a device source leaves ctx->ev_aux recorded behind its last read
+int prove_batch_launch_src(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const WitnessSrc &w, size_t count, const uint64_t *r, const uint64_t *s);
 // vsp_groth16_prove with a hook (prover.hip): `overlap` runs on the host after every kernel is queued and before the first wait
 int prove_with_overlap(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witness, const uint64_t r[4], const uint64_t s[4],
                        const uint64_t *saver_P1, const uint64_t *saver_r_enc, uint64_t A_out[12], uint64_t B_out[24], uint64_t C_out[12],

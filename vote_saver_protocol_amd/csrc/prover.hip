@@ -219,6 +219,7 @@ static int prove_begin(vsp_ctx *ctx, bool batch, bool args_present, const vsp_r1
     if (!ctx) return VSP_ERR_ARG;
     if (!args_present) return set_error(ctx, VSP_ERR_ARG, batch ? "prove_batch: null argument or a batch outside 1..64" : "prove: null argument");
     if (ctx->prove.active) return set_error(ctx, VSP_ERR_ARG, "prove: a proof is already in flight on this context (finish it first)");
+    if (ctx->cast.active) return set_error(ctx, VSP_ERR_ARG, "prove: a batch of cast ballots is in flight on this context (finish it first)");
     for (size_t k = 0; k < K; k++)
         if (!below_mod<FrP64>(r + 4 * k) || !below_mod<FrP64>(s + 4 * k) || (saver_r_enc && !below_mod<FrP64>(saver_r_enc)))
             return set_error(ctx, VSP_ERR_ARG, batch ? "prove: r and s must be canonical (< r)" : "prove: r, s and r_enc must be canonical (< r)");
@@ -260,8 +261,6 @@ static int prove_use_streams(vsp_ctx *ctx) {
 }  // namespace vsp
 extern "C" {
 
-// the witness as the caller hands it over: plain (num_vars x 4 canonical words), or packed (vsp_witness_pack)
-struct WitnessSrc { const uint64_t *plain; const uint64_t *class_words; const uint32_t *word_offsets; const uint64_t *dense; size_t n_dense; };
 static int prove_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const WitnessSrc &w);
 static int prove_finish_impl(vsp_ctx *ctx, uint64_t A_out[12], uint64_t B_out[24], uint64_t C_out[12], uint8_t proof_out[192], const std::function<void()> *overlap);
 
@@ -375,6 +374,18 @@ __global__ __launch_bounds__(256) void k_witness_expand(const uint64_t *class_wo
     z[2 * i] = lo; z[2 * i + 1] = hi;
 }
 
+// z_k = (1, row map.row[k] of the source) for the K members of a batch whose witnesses lie in device memory (WitnessSrc::dev): grid.y the
+// member, a lane per 16 bytes of z_k -- two of them a value, so consecutive lanes load and store consecutive 16 bytes of one row.  The
+// map travels by value: 64 row indices are 256 bytes of kernel argument.  No loop; every store is a plain one.
+struct GatherMap { uint32_t row[vsp_ctx::VERDICT_MEMBERS]; };
+__global__ __launch_bounds__(256) void k_witness_gather(const uint4 *src, size_t stride, GatherMap map, size_t nv, uint4 *z) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, k = blockIdx.y;
+    if (i >= 2 * (nv + 1)) return;
+    uint4 v = make_uint4(i == 0 ? 1u : 0u, 0, 0, 0);
+    if (i >= 2) v = src[2 * (size_t)map.row[k] * stride + (i - 2)];
+    z[2 * k * (nv + 1) + i] = v;
+}
+
 // ---- the front half of every proof, and the whole device side of the stand-alone witness check (vsp_r1cs_check_batch): z_k = (1, witness_k)
 // canonical into pr_z for the K members, then A z, B z, C z of each into pr_abc (member k at pr_abc + k 3 m: A z | B z | C z, m values each,
 // zero beyond the constraint rows) and the rows "input_i * 0 = 0" of A.  There is one copy of it, so what the check approves is, word for
@@ -388,13 +399,21 @@ static int prove_front_half(vsp_ctx *ctx, const vsp_r1cs *cs, const WitnessSrc &
     Fr *dz = (Fr *)ctx->pr_z.p, *abc = (Fr *)ctx->pr_abc.p;
     std::vector<uint64_t> ones;
     const uint64_t one4[4] = {1, 0, 0, 0};
-    if (strided) {
+    if (wsrc.dev) {
+        GatherMap map{};
+        for (size_t k = 0; k < K; k++) map.row[k] = wsrc.members ? wsrc.members[k] : (uint32_t)(wsrc.first + k);
+        hipLaunchKernelGGL(k_witness_gather, dim3((unsigned)((2 * zs + 255) / 256), (unsigned)K), dim3(256), 0, st, (const uint4 *)wsrc.dev, wsrc.stride, map, nv, (uint4 *)dz);
+        VSP_LAUNCH_CHECK();
+        VSP_HIP(hipEventRecord(ctx->ev_aux, st));
+    } else if (strided) {
         // the K ones from a small host array, the witnesses by one strided copy
+        ctx->stats["prove_witness_h2d_bytes"] += (double)(K * nv * 32);
         ones.assign(K * 4, 0); for (size_t k = 0; k < K; k++) ones[4 * k] = 1;
         VSP_HIP(hipMemcpy2DAsync(dz, zs * 32, ones.data(), 32, 32, K, hipMemcpyHostToDevice, st));
         if (nv) VSP_HIP(hipMemcpy2DAsync(dz + 1, zs * 32, wsrc.plain, nv * 32, nv * 32, K, hipMemcpyHostToDevice, st));
     } else {
         VSP_HIP(hipMemcpyAsync(dz, one4, 32, hipMemcpyHostToDevice, st));
+        ctx->stats["prove_witness_h2d_bytes"] += (double)(wsrc.plain ? nv * 32 : ((nv + 31) / 32) * 12 + wsrc.n_dense * 32);
         if (wsrc.plain) VSP_HIP(hipMemcpyAsync(dz + 1, wsrc.plain, nv * 32, hipMemcpyHostToDevice, st));
         else {
             // packed witness: class map, per-word offsets and the dense values cross PCIe (a tenth of the plain witness for a 90 % boolean one); a kernel expands
@@ -418,7 +437,7 @@ static int prove_front_half(vsp_ctx *ctx, const vsp_r1cs *cs, const WitnessSrc &
     }
     if (strided) {
         VSP_HIP(hipMemcpy2DAsync(abc + nc, 3 * m * sizeof(Fr), dz, zs * sizeof(Fr), (ni + 1) * sizeof(Fr), K, hipMemcpyDeviceToDevice, st));
-        VSP_HIP(hipStreamSynchronize(st));                   // `ones` goes out of scope; the copies above are queued from pageable memory anyway
+        if (!wsrc.dev) VSP_HIP(hipStreamSynchronize(st));                   // `ones` goes out of scope; the copies above are queued from pageable memory anyway
     } else VSP_HIP(hipMemcpyAsync(abc + nc, dz, (ni + 1) * sizeof(Fr), hipMemcpyDeviceToDevice, st));
     return VSP_OK;
 }
@@ -600,16 +619,17 @@ static int prove_finish_impl(vsp_ctx *ctx, uint64_t A_out[12], uint64_t B_out[24
 // The key is plain (vsp_groth16_generate with precompute = 0, or vsp_pk_create over plain bases) or has tables of window multiples of at
 // most 16 bits (pre_c <= 16: one bucket set per witness and query -- worth it where the tables are small, i.e. at the real circuit's size);
 // other tables, or any table with option "msm_batch_tables" = 0, are refused with VSP_ERR_UNSUPPORTED.
-static int prove_batch_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witnesses, size_t K) {
+static int prove_batch_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const WitnessSrc &w, size_t K) {
     const size_t nv = cs->num_vars, ni = cs->num_inputs, m = cs->dom.m, zs = nv + 1;
     VSP_HIP(hipSetDevice(ctx->device));
     HostLap lap{ctx};                                         // vsp_get_stat "prove_batch_*_ms": where a batch's time goes on the host
-    const WitnessSrc w{witnesses, nullptr, nullptr, nullptr, 0};
     VSP_TRY(prove_front_half(ctx, cs, w, K, true));          // z_k = (1, witness_k) and A z, B z, C z of the K members
     VSP_TRY(ensure(ctx, ctx->pr_h, K * m * sizeof(Fr)));
     Fr *dz = (Fr *)ctx->pr_z.p, *abc = (Fr *)ctx->pr_abc.p, *dH = (Fr *)ctx->pr_h.p;
     VSP_TRY(prove_queue_check(ctx, cs, K));
     VSP_TRY(prove_use_streams(ctx));                         // the H chain on the context's stream (prove_launch_impl)
+    // the device form waited for nothing: the witness chains' streams start behind the gather, as prove_launch_impl's behind its copy
+    if (w.dev) for (int k = 0; k < 2; k++) VSP_HIP(hipStreamWaitEvent(ctx->prove_streams[k], ctx->ev_aux, 0));
     VSP_TRY(witness_map_device(ctx, &cs->dom, abc, abc + m, abc + 2 * m, 3 * m, (unsigned)K, dH, m));
     MsmRequest h(dH, m - 1), a(dz, nv + 1), l(dz + ni + 1, nv - ni);      // as in prove_launch_impl, K vectors each
     h.dense = true; h.batch = a.batch = l.batch = (unsigned)K; h.stride = m; a.stride = l.stride = zs;      // H coefficients are dense
@@ -695,11 +715,53 @@ static int prove_batch_finish_impl(vsp_ctx *ctx, uint64_t *A_out, uint64_t *B_ou
     }
     return VSP_OK;
 }
-int vsp_groth16_prove_batch_launch(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witnesses, size_t count, const uint64_t *r, const uint64_t *s) {
-    VSP_TRY(prove_begin(ctx, true, cs && pk && witnesses && r && s && count >= 1 && count <= 64, cs, pk, count, r, s, nullptr, nullptr));
-    int rc = prove_batch_launch_impl(ctx, cs, pk, witnesses, count);
+}  // extern "C"
+namespace vsp {
+// the batch launch over a witness source the caller has checked: K host witnesses one after the other, or rows of a device buffer
+int prove_batch_launch_src(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const WitnessSrc &w, size_t count, const uint64_t *r, const uint64_t *s) {
+    VSP_TRY(prove_begin(ctx, true, cs && pk && (w.plain || w.dev) && r && s && count >= 1 && count <= 64, cs, pk, count, r, s, nullptr, nullptr));
+    int rc = prove_batch_launch_impl(ctx, cs, pk, w, count);
     if (rc != VSP_OK) prove_cleanup(ctx, rc); else ctx->prove.active = true;
     return rc;
+}
+// the checks of a device source (include/vsp.h "witnesses in device memory"), made before anything is queued; `out` is the source
+int witness_src_device(vsp_ctx *ctx, const char *who, const vsp_r1cs *cs, const void *d_witnesses, size_t stride, size_t rows, const uint32_t *members, size_t count,
+                       WitnessSrc *out) {
+    char m[200];
+    auto refuse = [&](const char *what) { snprintf(m, sizeof m, "%s: %s", who, what); return set_error(ctx, VSP_ERR_ARG, m); };
+    if (!cs || !d_witnesses) return refuse("null argument");
+    if (stride < cs->num_vars) return refuse("the stride of the device witnesses is below num_vars");
+    if ((uintptr_t)d_witnesses & 15) return refuse("the device witnesses are not 16-byte aligned");
+    if (rows > 0xFFFFFFFFull) return refuse("more than 2^32 - 1 rows of device witnesses");
+    if (!members && count > rows) return refuse("members is NULL and count exceeds the rows of the device witnesses");
+    for (size_t k = 0; members && k < count; k++)
+        if (members[k] >= rows) {
+            snprintf(m, sizeof m, "%s: members[%zu] = %u is not a row of the device witnesses (%zu rows)", who, k, members[k], rows);
+            return set_error(ctx, VSP_ERR_ARG, m);
+        }
+    *out = WitnessSrc{};
+    out->dev = (const uint64_t *)d_witnesses; out->stride = stride; out->members = members;
+    return VSP_OK;
+}
+}  // namespace vsp
+extern "C" {
+int vsp_groth16_prove_batch_launch(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const uint64_t *witnesses, size_t count, const uint64_t *r, const uint64_t *s) {
+    const WitnessSrc w{witnesses, nullptr, nullptr, nullptr, 0};
+    return prove_batch_launch_src(ctx, cs, pk, w, count, r, s);
+}
+int vsp_groth16_prove_batch_launch_device(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const void *d_witnesses, size_t stride, size_t rows, const uint32_t *members,
+                                          size_t count, const uint64_t *r, const uint64_t *s) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!cs || !pk || !d_witnesses || !r || !s || count < 1 || count > 64) return set_error(ctx, VSP_ERR_ARG, "prove_batch_device: null argument or a batch outside 1..64");
+    WitnessSrc w;
+    VSP_TRY(witness_src_device(ctx, "prove_batch_device", cs, d_witnesses, stride, rows, members, count, &w));
+    return prove_batch_launch_src(ctx, cs, pk, w, count, r, s);
+}
+int vsp_groth16_prove_batch_device(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const void *d_witnesses, size_t stride, size_t rows, const uint32_t *members,
+                                   size_t count, const uint64_t *r, const uint64_t *s, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out) {
+    int rc = vsp_groth16_prove_batch_launch_device(ctx, cs, pk, d_witnesses, stride, rows, members, count, r, s);
+    if (rc != VSP_OK) return rc;
+    return vsp_groth16_prove_batch_finish(ctx, A_out, B_out, C_out, proofs_out);
 }
 int vsp_groth16_prove_batch_finish(vsp_ctx *ctx, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out) {
     if (!ctx) return VSP_ERR_ARG;
@@ -725,18 +787,19 @@ int vsp_groth16_prove_batch_verdicts(vsp_ctx *ctx, uint8_t *status_out, uint64_t
 
 // ---- the stand-alone witness check: bp.is_satisfied() (common.hpp:1109-1128).  The prover's front half and the verdict pass, in pieces
 // of at most 64 witnesses -- the batch prover's limit, so its workspaces pr_z / pr_abc serve and nothing new is allocated
-int vsp_r1cs_check_batch(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64_t *witnesses, size_t count, uint8_t *status_out, uint64_t *first_bad_row_out,
-                         uint64_t *bad_rows_out) {
-    if (!ctx) return VSP_ERR_ARG;
-    if (!cs || !witnesses || !status_out) return set_error(ctx, VSP_ERR_ARG, "r1cs_check: null argument");
-    if (ctx->prove.active) return set_error(ctx, VSP_ERR_ARG, "r1cs_check: a proof is in flight on this context and owns the workspace (finish it first)");
+}  // extern "C"
+// the pieces of either source: piece `first` of a host source starts at witness `first`, of a device source at member `first` of the map
+static int r1cs_check_pieces(vsp_ctx *ctx, const vsp_r1cs *cs, const WitnessSrc &all, size_t count, uint8_t *status_out, uint64_t *first_bad_row_out, uint64_t *bad_rows_out) {
+    if (ctx->prove.active || ctx->cast.active) return set_error(ctx, VSP_ERR_ARG, "r1cs_check: a proof is in flight on this context and owns the workspace (finish it first)");
     VSP_HIP(hipSetDevice(ctx->device));
     const size_t nv = cs->num_vars;
     size_t z_bytes = 0;
     int rc = VSP_OK;
     for (size_t first = 0; first < count && rc == VSP_OK; first += vsp_ctx::VERDICT_MEMBERS) {
         const size_t K = count - first < vsp_ctx::VERDICT_MEMBERS ? count - first : vsp_ctx::VERDICT_MEMBERS;
-        const WitnessSrc w{witnesses + first * nv * 4, nullptr, nullptr, nullptr, 0};
+        WitnessSrc w = all;
+        if (all.dev) { w.first = first; if (all.members) w.members = all.members + first; }
+        else w.plain = all.plain + first * nv * 4;
         rc = [&]() -> int {
             hipEvent_t t0, t1;                                                            // around the verdict kernels
             VSP_TRY(ctx->check_timer.event(ctx, 1, &t0));
@@ -762,6 +825,22 @@ int vsp_r1cs_check_batch(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64_t *witne
     if (ctx->pr_z.p && z_bytes) hipMemsetAsync(ctx->pr_z.p, 0, z_bytes < ctx->pr_z.cap ? z_bytes : ctx->pr_z.cap, ctx->stream);
     if (rc == VSP_OK) ctx->stats["r1cs_check_witnesses"] += (double)count;
     return rc;
+}
+extern "C" {
+int vsp_r1cs_check_batch(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64_t *witnesses, size_t count, uint8_t *status_out, uint64_t *first_bad_row_out,
+                         uint64_t *bad_rows_out) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!cs || !witnesses || !status_out) return set_error(ctx, VSP_ERR_ARG, "r1cs_check: null argument");
+    const WitnessSrc w{witnesses, nullptr, nullptr, nullptr, 0};
+    return r1cs_check_pieces(ctx, cs, w, count, status_out, first_bad_row_out, bad_rows_out);
+}
+int vsp_r1cs_check_batch_device(vsp_ctx *ctx, const vsp_r1cs *cs, const void *d_witnesses, size_t stride, size_t rows, const uint32_t *members, size_t count,
+                                uint8_t *status_out, uint64_t *first_bad_row_out, uint64_t *bad_rows_out) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!cs || !d_witnesses || !status_out) return set_error(ctx, VSP_ERR_ARG, "r1cs_check_device: null argument");
+    WitnessSrc w;
+    VSP_TRY(witness_src_device(ctx, "r1cs_check_device", cs, d_witnesses, stride, rows, members, count, &w));
+    return r1cs_check_pieces(ctx, cs, w, count, status_out, first_bad_row_out, bad_rows_out);
 }
 int vsp_r1cs_is_satisfied(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64_t *witness, int *satisfied_out, uint64_t *first_bad_row_out) {
     if (!ctx) return VSP_ERR_ARG;

@@ -102,22 +102,38 @@ static int ensure_pinned(vsp_ctx *ctx, void *&p, size_t &cap, size_t bytes) {
 // and the scalars and points once more in pinned memory -- 9.1 MB + 3.6 MB at msg_size 25.
 static size_t piece_ballots(const vsp_ctx *ctx) { const long c = opt(ctx, "saver_ct_chunk", 1024); return c < 1 ? 1 : (c > 1024 ? 1024 : (size_t)c); }
 
-// c ballots (msgs: c x n x 4, r_enc: c x 4) onto the ciphertext stream: scalars up, the two kernels between events 0 and 1 of the timer,
-// the points back to pinned memory, the event `done` behind them
-static int ct_queue(vsp_ctx *ctx, const vsp_saver_pk *spk, const uint64_t *msgs, const uint64_t *r_enc, size_t c) {
+// the ciphertext stream and the event behind a piece, made on first use
+static int ct_stream_ready(vsp_ctx *ctx) {
     auto &w = ctx->saver_ct;
-    const size_t n = spk->n, ns = n + 1, nc = saver_columns(n);
     VSP_HIP(hipSetDevice(ctx->device));
     if (!w.stream) VSP_HIP(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
     if (!w.done) VSP_HIP(hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
+    return VSP_OK;
+}
+// c ballots (msgs: c x n x 4, r_enc: c x 4) onto the ciphertext stream: scalars up, the two kernels between events 0 and 1 of the timer,
+// the points back to pinned memory, the event `done` behind them
+//
+// msgs null: the device form -- the batch prover's front half has gathered z_k = (1, row of member k) into pr_z, with ctx->ev_aux recorded
+// behind the gather; the message, the first msg_size values of each row, is copied from there, device to device, beside r_enc from the host
+static int ct_queue(vsp_ctx *ctx, const vsp_saver_pk *spk, const uint64_t *msgs, const uint64_t *r_enc, size_t c, size_t z_stride = 0) {
+    auto &w = ctx->saver_ct;
+    const size_t n = spk->n, ns = n + 1, nc = saver_columns(n);
+    VSP_TRY(ct_stream_ready(ctx));
     VSP_TRY(ensure_w(ctx, w.stream, w.scalars, c * ns * 32));
     VSP_TRY(ensure_w(ctx, w.stream, w.sums, c * nc * sizeof(G1XYZZ)));
     VSP_TRY(ensure_w(ctx, w.stream, w.points, c * nc * sizeof(G1Affine)));
     VSP_TRY(ensure_pinned(ctx, w.h_scalars, w.h_scalars_cap, c * ns * 32));
     VSP_TRY(ensure_pinned(ctx, w.h_points, w.h_points_cap, c * nc * sizeof(G1Affine)));
     uint64_t *hs = (uint64_t *)w.h_scalars;
-    for (size_t k = 0; k < c; k++) { memcpy(hs + k * ns * 4, r_enc + 4 * k, 32); memcpy(hs + k * ns * 4 + 4, msgs + k * n * 4, n * 32); }
-    VSP_HIP(hipMemcpyAsync(w.scalars.p, hs, c * ns * 32, hipMemcpyHostToDevice, w.stream));
+    if (msgs) {
+        for (size_t k = 0; k < c; k++) { memcpy(hs + k * ns * 4, r_enc + 4 * k, 32); memcpy(hs + k * ns * 4 + 4, msgs + k * n * 4, n * 32); }
+        VSP_HIP(hipMemcpyAsync(w.scalars.p, hs, c * ns * 32, hipMemcpyHostToDevice, w.stream));
+    } else {
+        memcpy(hs, r_enc, c * 32);
+        VSP_HIP(hipMemcpy2DAsync(w.scalars.p, ns * 32, hs, 32, 32, c, hipMemcpyHostToDevice, w.stream));
+        VSP_HIP(hipStreamWaitEvent(w.stream, ctx->ev_aux, 0));
+        VSP_HIP(hipMemcpy2DAsync((uint64_t *)w.scalars.p + 4, ns * 32, (const uint64_t *)ctx->pr_z.p + 4, z_stride * 32, n * 32, c, hipMemcpyDeviceToDevice, w.stream));
+    }
     const SaverColumn *d_cols = (const SaverColumn *)spk->d_desc;
     const SaverPair *d_pairs = (const SaverPair *)(d_cols + spk->plan.cols.size());
     const uint32_t *d_lane_col = (const uint32_t *)(d_pairs + spk->plan.pairs.size());
@@ -163,12 +179,12 @@ static void ct_host(const vsp_saver_pk *spk, const uint64_t *msgs, const uint64_
         ct_store(n, cols.data(), k, ct_out, addend_out, blobs_out);
     });
 }
-// every scalar of the batch canonical; the refusal names the member
+// every scalar of the batch canonical; the refusal names the member.  msgs null (the device form): r_enc alone is host data
 static int scalars_canonical(vsp_ctx *ctx, const char *who, size_t n, const uint64_t *msgs, const uint64_t *r_enc, size_t count) {
     char m[160];
     for (size_t k = 0; k < count; k++) {
         if (!below_mod<FrP64>(r_enc + 4 * k)) { snprintf(m, sizeof m, "%s: r_enc of member %zu is not canonical (>= r)", who, k); return set_error(ctx, VSP_ERR_ARG, m); }
-        for (size_t i = 0; i < n; i++)
+        for (size_t i = 0; msgs && i < n; i++)
             if (!below_mod<FrP64>(msgs + (k * n + i) * 4)) { snprintf(m, sizeof m, "%s: message block %zu of member %zu is not canonical (>= r)", who, i, k); return set_error(ctx, VSP_ERR_ARG, m); }
     }
     return VSP_OK;
@@ -177,6 +193,43 @@ static int scalars_canonical(vsp_ctx *ctx, const char *who, size_t n, const uint
 // a batch of ballots is in flight: launched (every prover launch clears the mark, the ballot launch sets it afterwards), and its proofs
 // not finished behind its back by vsp_groth16_prove_batch_finish
 static bool ballots_in_flight(const vsp_ctx *ctx) { return ctx->saver_ct.active && ctx->prove.active && ctx->prove.batch; }
+
+// the launch both forms share, behind their checks: the batch prover over the source, then the ciphertexts -- msgs from the host, or
+// (msgs null, a device source) the first msg_size values of each member's z in pr_z
+static int ballots_launch(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1cs *cs, const vsp_pk *pk, const WitnessSrc &src, const uint64_t *msgs, size_t count,
+                          const uint64_t *r_enc, const uint64_t *r, const uint64_t *s) {
+    const size_t n = spk->n, zs = cs->num_vars + 1;
+    VSP_TRY(prove_batch_launch_src(ctx, cs, pk, src, count, r, s));
+    auto &w = ctx->saver_ct;
+    w.gpu = opt(ctx, "saver_encrypt_gpu", 1) != 0;
+    w.device_src = msgs == nullptr;
+    int rc = VSP_OK;
+    if (w.gpu) rc = ct_queue(ctx, spk, msgs, r_enc, count, zs);
+    else {
+        // the host leg computes in the finish, inside the wait for the proofs: it keeps the scalars until then
+        rc = ensure_pinned(ctx, w.h_scalars, w.h_scalars_cap, count * (n + 1) * 32);
+        if (rc == VSP_OK) memcpy(w.h_scalars, r_enc, count * 32);
+        if (rc == VSP_OK && msgs) memcpy((uint64_t *)w.h_scalars + count * 4, msgs, count * n * 32);
+        // the device form: the count x msg_size message scalars, and nothing else, come to the host, behind the gather; the finish waits for them
+        if (rc == VSP_OK && !msgs) rc = [&]() -> int {
+            VSP_TRY(ct_stream_ready(ctx));
+            VSP_HIP(hipStreamWaitEvent(w.stream, ctx->ev_aux, 0));
+            VSP_HIP(hipMemcpy2DAsync((uint64_t *)w.h_scalars + count * 4, n * 32, (const uint64_t *)ctx->pr_z.p + 4, zs * 32, n * 32, count, hipMemcpyDeviceToHost, w.stream));
+            VSP_HIP(hipEventRecord(w.done, w.stream));
+            return VSP_OK;
+        }();
+    }
+    if (rc != VSP_OK) {
+        // the proofs are queued and cannot be recalled: finish them into nothing, keep this call's error
+        const std::string keep = ctx->err;
+        if (w.stream) hipStreamSynchronize(w.stream);      // nothing of this call still reads pr_z when the finish zeroes it
+        (void)vsp_groth16_prove_batch_finish(ctx, nullptr, nullptr, nullptr, nullptr);
+        ctx->err = keep;
+        return rc;
+    }
+    w.active = true; w.spk = spk; w.count = count;
+    return VSP_OK;
+}
 
 }  // anonymous namespace
 
@@ -245,25 +298,22 @@ int vsp_saver_encrypt_batch_launch(vsp_ctx *ctx, const vsp_saver_pk *spk, const 
             return set_error(ctx, VSP_ERR_ARG, m);
         }
     VSP_TRY(tables_ready(ctx, spk));
-    VSP_TRY(vsp_groth16_prove_batch_launch(ctx, cs, pk, witnesses, count, r, s));
-    auto &w = ctx->saver_ct;
-    w.gpu = opt(ctx, "saver_encrypt_gpu", 1) != 0;
-    int rc = VSP_OK;
-    if (w.gpu) rc = ct_queue(ctx, spk, msgs, r_enc, count);
-    else {
-        // the host leg computes in the finish, inside the wait for the proofs: it keeps the scalars until then
-        rc = ensure_pinned(ctx, w.h_scalars, w.h_scalars_cap, count * (n + 1) * 32);
-        if (rc == VSP_OK) { memcpy(w.h_scalars, r_enc, count * 32); memcpy((uint64_t *)w.h_scalars + count * 4, msgs, count * n * 32); }
-    }
-    if (rc != VSP_OK) {
-        // the proofs are queued and cannot be recalled: finish them into nothing, keep this call's error
-        const std::string keep = ctx->err;
-        (void)vsp_groth16_prove_batch_finish(ctx, nullptr, nullptr, nullptr, nullptr);
-        ctx->err = keep;
-        return rc;
-    }
-    w.active = true; w.spk = spk; w.count = count;
-    return VSP_OK;
+    const WitnessSrc src{witnesses, nullptr, nullptr, nullptr, 0};
+    return ballots_launch(ctx, spk, cs, pk, src, msgs, count, r_enc, r, s);
+}
+
+int vsp_saver_encrypt_batch_launch_device(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1cs *cs, const vsp_pk *pk, const void *d_witnesses, size_t stride, size_t rows,
+                                          const uint32_t *members, size_t count, const uint64_t *r_enc, const uint64_t *r, const uint64_t *s) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!spk || !cs || !pk || !d_witnesses || !r_enc || !r || !s || count < 1 || count > 64)
+        return set_error(ctx, VSP_ERR_ARG, "saver_encrypt_batch_device: null argument or a batch outside 1..64");
+    if (ballots_in_flight(ctx)) return set_error(ctx, VSP_ERR_ARG, "saver_encrypt_batch_device: a batch of ballots is already in flight on this context (finish it first)");
+    if (cs->num_inputs < spk->n) return set_error(ctx, VSP_ERR_ARG, "saver_encrypt_batch_device: the constraint system has fewer public inputs than message blocks");
+    WitnessSrc src;
+    VSP_TRY(witness_src_device(ctx, "saver_encrypt_batch_device", cs, d_witnesses, stride, rows, members, count, &src));
+    VSP_TRY(scalars_canonical(ctx, "saver_encrypt_batch_device", spk->n, nullptr, r_enc, count));
+    VSP_TRY(tables_ready(ctx, spk));
+    return ballots_launch(ctx, spk, cs, pk, src, nullptr, count, r_enc, r, s);
 }
 
 int vsp_saver_encrypt_batch_finish(vsp_ctx *ctx, uint64_t *ct_out, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out, uint8_t *ct_blobs_out) {
@@ -275,7 +325,10 @@ int vsp_saver_encrypt_batch_finish(vsp_ctx *ctx, uint64_t *ct_out, uint64_t *A_o
     ctx->prove.addend.assign(12 * K, 0);
     int rc;
     if (w.gpu) rc = ct_collect(ctx, n, K, 0, ct_out, ctx->prove.addend.data(), ct_blobs_out);
-    else { ct_host(w.spk, (const uint64_t *)w.h_scalars + K * 4, (const uint64_t *)w.h_scalars, K, ct_out, ctx->prove.addend.data(), ct_blobs_out); rc = VSP_OK; }
+    else {
+        rc = w.device_src ? [&]() -> int { VSP_HIP(hipEventSynchronize(w.done)); return VSP_OK; }() : VSP_OK;
+        if (rc == VSP_OK) ct_host(w.spk, (const uint64_t *)w.h_scalars + K * 4, (const uint64_t *)w.h_scalars, K, ct_out, ctx->prove.addend.data(), ct_blobs_out);
+    }
     if (rc != VSP_OK) {
         const std::string keep = ctx->err;
         (void)vsp_groth16_prove_batch_finish(ctx, nullptr, nullptr, nullptr, nullptr);
@@ -291,6 +344,11 @@ int vsp_saver_encrypt_batch_finish(vsp_ctx *ctx, uint64_t *ct_out, uint64_t *A_o
                 if (ct_out) memset(ct_out + k * ctw, 0, ctw * 8);
                 if (ct_blobs_out) memset(ct_blobs_out + k * blob, 0, blob);
             }
+    // the device form met its messages only on the device: where the proofs' census refuses the batch (a value >= r), no ciphertext leaves either
+    if (w.device_src && rc != VSP_OK && rc != VSP_ERR_UNSATISFIED) {
+        if (ct_out) memset(ct_out, 0, K * ctw * 8);
+        if (ct_blobs_out) memset(ct_blobs_out, 0, K * blob);
+    }
     return rc;
 }
 
@@ -298,6 +356,14 @@ int vsp_saver_encrypt_batch(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1c
                             const uint64_t *r_enc, const uint64_t *r, const uint64_t *s, uint64_t *ct_out, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out,
                             uint8_t *proofs_out, uint8_t *ct_blobs_out) {
     int rc = vsp_saver_encrypt_batch_launch(ctx, spk, cs, pk, msgs, witnesses, count, r_enc, r, s);
+    if (rc != VSP_OK) return rc;
+    return vsp_saver_encrypt_batch_finish(ctx, ct_out, A_out, B_out, C_out, proofs_out, ct_blobs_out);
+}
+
+int vsp_saver_encrypt_batch_device(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1cs *cs, const vsp_pk *pk, const void *d_witnesses, size_t stride, size_t rows,
+                                   const uint32_t *members, size_t count, const uint64_t *r_enc, const uint64_t *r, const uint64_t *s, uint64_t *ct_out, uint64_t *A_out,
+                                   uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out, uint8_t *ct_blobs_out) {
+    int rc = vsp_saver_encrypt_batch_launch_device(ctx, spk, cs, pk, d_witnesses, stride, rows, members, count, r_enc, r, s);
     if (rc != VSP_OK) return rc;
     return vsp_saver_encrypt_batch_finish(ctx, ct_out, A_out, B_out, C_out, proofs_out, ct_blobs_out);
 }

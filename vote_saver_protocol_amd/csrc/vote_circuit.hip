@@ -25,6 +25,7 @@ struct vsp_vote_circuit {
     // one piece of witnesses on the device: the affine table; sk | eid | the eid | sk rows | indices | votes; a status word per ballot;
     // digests; the chains' slots; the witnesses
     vsp::DevBuf d_aff, in, status, digests, slots, wit;
+    bool wit_live = false;                      // witnesses of a device call stay in `wit` until the next release (vsp_cast_witness_release)
     vsp::StageTimer timer;
 };
 
@@ -106,13 +107,21 @@ __global__ __launch_bounds__(VW_FILL_THREADS) void k_vote_fill_chunks(const JjAf
 unsigned vw_blocks(uint64_t lanes, unsigned threads) { return (unsigned)((lanes + threads - 1) / threads); }
 
 void circuit_release(vsp_ctx *ctx, vsp_vote_circuit *c) {
+    if (c->wit_live && c->wit.p) { hipMemset(c->wit.p, 0, c->wit.cap); c->wit_live = false; }
     for (DevBuf *b : {&c->d_aff, &c->in, &c->status, &c->digests, &c->slots, &c->wit}) if (b->p) hipFree(b->p);
     c->timer.destroy();
     if (c->cs) vsp_r1cs_free(ctx, c->cs);
     delete c;
 }
 
-// one piece: ballots [at, at + c) of the call
+// the stream-ordered zeroing of the witnesses a device call left in the circuit's buffer
+void witness_release(vsp_ctx *ctx, vsp_vote_circuit *circ) {
+    if (circ->wit_live && circ->wit.p) hipMemsetAsync(circ->wit.p, 0, circ->wit.cap, ctx->stream);
+    circ->wit_live = false;
+}
+
+// one piece: ballots [at, at + c) of the call.  wit_out null: the device form -- the witnesses stay in the circuit's buffer (member k at
+// row k, vc_num_vars values a row), only the status words come to the host, and the buffer is zeroed by the next release, not here
 int witness_piece(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_registry *reg, const uint64_t *eid, const uint64_t *sks, const uint64_t *indices, const uint32_t *votes,
                   size_t c, uint64_t *wit_out, uint8_t *status_out) {
     const VcParams &P = circ->P;
@@ -138,7 +147,17 @@ int witness_piece(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_registry *reg,
     }
     const size_t wit_bytes = c * nv * 4 * sizeof(uint64_t);
     auto wipe_host = [&]() { volatile uint64_t *p = h_in.data(); for (size_t i = 0; i < in_words; i++) p[i] = 0; };
-    if (!live) { memset(wit_out, 0, wit_bytes); for (size_t k = 0; k < c; k++) status_out[k] = (uint8_t)h_status[k]; wipe_host(); return VSP_OK; }
+    witness_release(ctx, circ);
+    if (!live) {
+        if (wit_out) memset(wit_out, 0, wit_bytes);
+        else {                                  // no member reaches the kernels: all-zero rows, as the host form returns them
+            VSP_TRY(ensure(ctx, circ->wit, wit_bytes));
+            VSP_HIP(hipMemsetAsync(circ->wit.p, 0, wit_bytes, st));
+        }
+        for (size_t k = 0; k < c; k++) status_out[k] = (uint8_t)h_status[k];
+        wipe_host();
+        return VSP_OK;
+    }
     const size_t slot_bytes = c * chunks * sizeof(VcSlot<Fr>), digest_bytes = c * H * 4 * sizeof(uint64_t);
     auto run = [&]() -> int {
         VSP_TRY(ensure(ctx, circ->in, in_words * sizeof(uint64_t) + c * sizeof(uint32_t)));
@@ -171,7 +190,10 @@ int witness_piece(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_registry *reg,
         VSP_LAUNCH_CHECK();
         VSP_TRY(circ->timer.mark(ctx, 1, st));
         VSP_HIP(hipMemcpyAsync(h_status.data(), circ->status.p, c * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        VSP_HIP(hipMemcpyAsync(wit_out, circ->wit.p, wit_bytes, hipMemcpyDeviceToHost, st));
+        if (wit_out) {
+            VSP_HIP(hipMemcpyAsync(wit_out, circ->wit.p, wit_bytes, hipMemcpyDeviceToHost, st));
+            ctx->stats["vote_witness_d2h_bytes"] += (double)wit_bytes;
+        }
         VSP_HIP(hipStreamSynchronize(st));
         circ->timer.add(ctx, 0, "vote_witness_ms");
         return VSP_OK;
@@ -182,10 +204,11 @@ int witness_piece(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_registry *reg,
     if (circ->in.p) hipMemsetAsync(circ->in.p, 0, circ->in.cap, st);
     if (circ->digests.p) hipMemsetAsync(circ->digests.p, 0, circ->digests.cap, st);
     if (circ->slots.p) hipMemsetAsync(circ->slots.p, 0, circ->slots.cap, st);
-    if (circ->wit.p) hipMemsetAsync(circ->wit.p, 0, circ->wit.cap, st);
+    if (circ->wit.p && (wit_out || r != VSP_OK)) hipMemsetAsync(circ->wit.p, 0, circ->wit.cap, st);
     hipStreamSynchronize(st);
     wipe_host();
-    if (r != VSP_OK) { memset(wit_out, 0, wit_bytes); return r; }
+    if (r != VSP_OK) { if (wit_out) memset(wit_out, 0, wit_bytes); return r; }
+    circ->wit_live = !wit_out;
     for (size_t k = 0; k < c; k++) status_out[k] = (uint8_t)h_status[k];
     return VSP_OK;
 }
@@ -289,7 +312,8 @@ int vsp_vote_witness_batch(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_regis
     return VSP_OK;
 }
 
-int vsp_vote_cast_batch(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_registry *reg, const vsp_saver_pk *spk, const vsp_pk *pk, const uint64_t *eid_bits_words,
+// option "vote_cast_device" = 0: the witnesses travel through host memory -- to the host, compacted there, and back into the batch prover
+static int cast_through_host(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_registry *reg, const vsp_saver_pk *spk, const vsp_pk *pk, const uint64_t *eid_bits_words,
                         const uint64_t *sks, const uint64_t *indices, const uint32_t *votes, size_t count, const uint64_t *r_enc, const uint64_t *r, const uint64_t *s,
                         uint64_t *ct_out, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out, uint8_t *ct_blobs_out, uint8_t *status_out) {
     if (!ctx) return VSP_ERR_ARG;
@@ -337,6 +361,116 @@ int vsp_vote_cast_batch(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_registry
         if (ct_blobs_out) memcpy(ct_blobs_out + k * blob_bytes, &blobs[i * blob_bytes], blob_bytes);
     }
     return rc;
+}
+
+
+// the circuit, the registry and the context belong together (the checks of vsp_vote_witness_batch, under the caller's name)
+static int cast_check_handles(vsp_ctx *ctx, const char *who, const vsp_vote_circuit *circ, const vsp_registry *reg) {
+    char m[160];
+    const char *what = circ->device != ctx->device ? "the circuit belongs to another device" : reg->device != ctx->device ? "the registry belongs to another device" :
+                       reg->depth != circ->P.depth ? "the registry's depth is not the circuit's" : nullptr;
+    if (!what) return VSP_OK;
+    snprintf(m, sizeof m, "%s: %s", who, what);
+    return set_error(ctx, VSP_ERR_ARG, m);
+}
+
+int vsp_cast_witness_batch_device(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_registry *reg, const uint64_t *eid_bits_words, const uint64_t *sks, const uint64_t *indices,
+                                  const uint32_t *votes, size_t count, const void **d_witnesses_out, size_t *stride_out, uint8_t *status_out) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!circ || !reg || !eid_bits_words || !sks || !indices || !votes || !d_witnesses_out || !stride_out || !status_out)
+        return set_error(ctx, VSP_ERR_ARG, "cast_witness_batch_device: null argument");
+    if (count == 0 || count > VW_PIECE) return set_error(ctx, VSP_ERR_ARG, "cast_witness_batch_device: 1 to 64 ballots expected");
+    VSP_TRY(cast_check_handles(ctx, "cast_witness_batch_device", circ, reg));
+    VSP_HIP(hipSetDevice(ctx->device));
+    *d_witnesses_out = nullptr; *stride_out = 0;
+    VSP_TRY(witness_piece(ctx, circ, reg, eid_bits_words, sks, indices, votes, count, nullptr, status_out));
+    *d_witnesses_out = circ->wit.p; *stride_out = vc_num_vars(circ->P);
+    return VSP_OK;
+}
+
+int vsp_cast_witness_release(vsp_ctx *ctx, vsp_vote_circuit *circ) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!circ) return set_error(ctx, VSP_ERR_ARG, "cast_witness_release: null argument");
+    if (circ->device != ctx->device) return set_error(ctx, VSP_ERR_ARG, "cast_witness_release: the circuit belongs to another device");
+    VSP_HIP(hipSetDevice(ctx->device));
+    witness_release(ctx, circ);
+    return VSP_OK;
+}
+
+int vsp_cast_batch_launch(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_registry *reg, const vsp_saver_pk *spk, const vsp_pk *pk, const uint64_t *eid_bits_words,
+                          const uint64_t *sks, const uint64_t *indices, const uint32_t *votes, size_t count, const uint64_t *r_enc, const uint64_t *r, const uint64_t *s,
+                          uint8_t *status_out) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!circ || !reg || !spk || !pk || !eid_bits_words || !sks || !indices || !votes || !r_enc || !r || !s || !status_out)
+        return set_error(ctx, VSP_ERR_ARG, "cast_batch_launch: null argument");
+    if (count == 0 || count > VW_PIECE) return set_error(ctx, VSP_ERR_ARG, "cast_batch_launch: 1 to 64 ballots expected");
+    if (ctx->cast.active || ctx->prove.active) return set_error(ctx, VSP_ERR_ARG, "cast_batch_launch: a batch is already in flight on this context (finish it first)");
+    if (spk->n != circ->P.n) return set_error(ctx, VSP_ERR_ARG, "cast_batch_launch: the SAVER key's msg_size is not the circuit's");
+    VSP_TRY(cast_check_handles(ctx, "cast_batch_launch", circ, reg));
+    VSP_HIP(hipSetDevice(ctx->device));
+    VSP_TRY(witness_piece(ctx, circ, reg, eid_bits_words, sks, indices, votes, count, nullptr, status_out));      // blocks for the status words alone
+    auto &f = ctx->cast;
+    f.live.clear();
+    for (size_t k = 0; k < count; k++) if (status_out[k] == 0) f.live.push_back((uint32_t)k);
+    const size_t L = f.live.size();
+    int rc = VSP_OK;
+    if (L) {
+        // the live members are the map; their randomness packed to the front, as the host path packs it
+        std::vector<uint64_t> rnd(3 * L * 4);
+        for (size_t i = 0; i < L; i++) {
+            const size_t k = f.live[i];
+            memcpy(&rnd[4 * i], r_enc + 4 * k, 32); memcpy(&rnd[4 * (L + i)], r + 4 * k, 32); memcpy(&rnd[4 * (2 * L + i)], s + 4 * k, 32);
+        }
+        rc = vsp_saver_encrypt_batch_launch_device(ctx, spk, circ->cs, pk, circ->wit.p, vc_num_vars(circ->P), count, f.live.data(), L, &rnd[0], &rnd[4 * L], &rnd[8 * L]);
+    }
+    witness_release(ctx, circ);                 // right behind the launch, whose gather is the only reader: stream-ordered
+    if (rc != VSP_OK) return rc;
+    f.active = true; f.count = count; f.n = circ->P.n;
+    return VSP_OK;
+}
+
+int vsp_cast_batch_finish(vsp_ctx *ctx, uint64_t *ct_out, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out, uint8_t *ct_blobs_out) {
+    if (!ctx) return VSP_ERR_ARG;
+    auto &f = ctx->cast;
+    if (!f.active) return set_error(ctx, VSP_ERR_ARG, "cast_batch_finish: no batch of cast ballots in flight on this context");
+    f.active = false;
+    const size_t count = f.count, n = f.n, L = f.live.size(), ct_words = (n + 2) * 12, blob_bytes = 8 + 48 * (n + 2);
+    std::vector<uint64_t> ct(ct_out ? L * ct_words : 0), A(A_out ? L * 12 : 0), B(B_out ? L * 24 : 0), Cc(C_out ? L * 12 : 0);
+    std::vector<uint8_t> proofs(proofs_out ? L * 192 : 0), blobs(ct_blobs_out ? L * blob_bytes : 0);
+    int rc = VSP_OK;
+    // the finish runs whatever the outputs are: nothing of the batch stays in flight
+    if (L) rc = vsp_saver_encrypt_batch_finish(ctx, ct_out ? ct.data() : nullptr, A_out ? A.data() : nullptr, B_out ? B.data() : nullptr, C_out ? Cc.data() : nullptr,
+                                               proofs_out ? proofs.data() : nullptr, ct_blobs_out ? blobs.data() : nullptr);
+    if (ct_out) memset(ct_out, 0, count * ct_words * sizeof(uint64_t));
+    if (A_out) memset(A_out, 0, count * 12 * sizeof(uint64_t));
+    if (B_out) memset(B_out, 0, count * 24 * sizeof(uint64_t));
+    if (C_out) memset(C_out, 0, count * 12 * sizeof(uint64_t));
+    if (proofs_out) memset(proofs_out, 0, count * 192);
+    if (ct_blobs_out) memset(ct_blobs_out, 0, count * blob_bytes);
+    if (rc != VSP_OK && rc != VSP_ERR_UNSATISFIED) return rc;
+    for (size_t i = 0; i < L; i++) {            // the scatter to the members' slots
+        const size_t k = f.live[i];
+        if (ct_out) memcpy(ct_out + k * ct_words, &ct[i * ct_words], ct_words * sizeof(uint64_t));
+        if (A_out) memcpy(A_out + k * 12, &A[i * 12], 12 * sizeof(uint64_t));
+        if (B_out) memcpy(B_out + k * 24, &B[i * 24], 24 * sizeof(uint64_t));
+        if (C_out) memcpy(C_out + k * 12, &Cc[i * 12], 12 * sizeof(uint64_t));
+        if (proofs_out) memcpy(proofs_out + k * 192, &proofs[i * 192], 192);
+        if (ct_blobs_out) memcpy(ct_blobs_out + k * blob_bytes, &blobs[i * blob_bytes], blob_bytes);
+    }
+    return rc;
+}
+
+int vsp_vote_cast_batch(vsp_ctx *ctx, vsp_vote_circuit *circ, const vsp_registry *reg, const vsp_saver_pk *spk, const vsp_pk *pk, const uint64_t *eid_bits_words,
+                        const uint64_t *sks, const uint64_t *indices, const uint32_t *votes, size_t count, const uint64_t *r_enc, const uint64_t *r, const uint64_t *s,
+                        uint64_t *ct_out, uint64_t *A_out, uint64_t *B_out, uint64_t *C_out, uint8_t *proofs_out, uint8_t *ct_blobs_out, uint8_t *status_out) {
+    if (!ctx) return VSP_ERR_ARG;
+    if (!opt(ctx, "vote_cast_device", 1))
+        return cast_through_host(ctx, circ, reg, spk, pk, eid_bits_words, sks, indices, votes, count, r_enc, r, s, ct_out, A_out, B_out, C_out, proofs_out, ct_blobs_out, status_out);
+    if (!circ || !reg || !spk || !pk || !eid_bits_words || !sks || !indices || !votes || !r_enc || !r || !s || !status_out)
+        return set_error(ctx, VSP_ERR_ARG, "vote_cast_batch: null argument");
+    if (count == 0 || count > VW_PIECE) return set_error(ctx, VSP_ERR_ARG, "vote_cast_batch: 1 to 64 ballots expected");
+    VSP_TRY(vsp_cast_batch_launch(ctx, circ, reg, spk, pk, eid_bits_words, sks, indices, votes, count, r_enc, r, s, status_out));
+    return vsp_cast_batch_finish(ctx, ct_out, A_out, B_out, C_out, proofs_out, ct_blobs_out);
 }
 
 }  // extern "C"
