@@ -115,7 +115,11 @@ void vsp_stats_reset(vsp_ctx *ctx);
  * context is created), but independent multi-exponentiations kept IN FLIGHT TOGETHER over the work slots overlap better with 8
  * (2^20 G1 points, four in flight: 2.86 ms per multi-exponentiation against 3.03 with the default 4; MI355X, ROCm 7.2).  A service that
  * pipelines proofs or multi-exponentiations should export GPU_MAX_HW_QUEUES=8 before the process's first HIP call;
- * vsp_get_stat("runtime_hw_queues_env") is the value this process saw (0: not set). */
+ * vsp_get_stat("runtime_hw_queues_env") is the value this process saw (0: not set).
+ *
+ * Memory.  vsp_get_stat("device_allocations_live") and ("pinned_allocations_live") are the device and the page-locked host
+ * allocations the library holds at this moment, over every context and handle of the process (vsp_dmalloc's are the caller's and not
+ * counted).  Diagnostics: a handle that is freed, or a context that is destroyed, takes the counts back to what they were before it. */
 int vsp_set_option(vsp_ctx *ctx, const char *name, long value);
 /* Diagnostic build only (libvsp_hip_diag.so, `make -C vote_saver_protocol_amd/csrc diag`: the same sources with stamps around the G1
  * accumulation loop -- in the shipped library no stamp executes and this returns VSP_ERR_UNSUPPORTED): the clock the chip held inside

@@ -112,18 +112,17 @@ int box_grow_buf(vsp_ctx *ctx, DevBuf &b, size_t bytes, size_t keep) {
     if (b.p && b.cap >= bytes) return VSP_OK;
     size_t want = b.cap * 2 > bytes ? b.cap * 2 : bytes;
     if (want < 4096) want = 4096;
-    void *p = nullptr;
-    if (hipMalloc(&p, want) != hipSuccess) return set_error(ctx, VSP_ERR_NOMEM, "ballot_box: hipMalloc failed");
+    DevBuf grown;
+    if (grown.alloc(want) != hipSuccess) return set_error(ctx, VSP_ERR_NOMEM, "ballot_box: hipMalloc failed");
     if (b.p && keep) {
-        hipError_t e = hipMemcpyAsync(p, b.p, keep, hipMemcpyDeviceToDevice, ctx->stream);
+        hipError_t e = hipMemcpyAsync(grown.p, b.p, keep, hipMemcpyDeviceToDevice, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { hipFree(p); return set_hip_error(ctx, e, "ballot_box: copy of the serial store", __FILE__, __LINE__); }
+        if (e != hipSuccess) return set_hip_error(ctx, e, "ballot_box: copy of the serial store", __FILE__, __LINE__);
     } else if (b.p) {
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { hipFree(p); return set_hip_error(ctx, e, "ballot_box: hipStreamSynchronize", __FILE__, __LINE__); }
+        const hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return set_hip_error(ctx, e, "ballot_box: hipStreamSynchronize", __FILE__, __LINE__);
     }
-    if (b.p) hipFree(b.p);
-    b.p = p; b.cap = want;
+    b = std::move(grown);                   // behind the wait: the smaller buffer goes
     return VSP_OK;
 }
 
@@ -293,11 +292,6 @@ void vsp_ballot_box_free(vsp_ctx *ctx, vsp_ballot_box *box) {
     if (!box) return;
     hipSetDevice(box->device);
     if (ctx) hipStreamSynchronize(ctx->stream);
-    for (DevBuf *b : {&box->d_role, &box->d_expected, &box->store, &box->table, &box->pend, &box->hold, &box->win, &box->pos, &box->ord, &box->flag}) {
-        if (b->p) hipFree(b->p);
-        b->p = nullptr; b->cap = 0;
-    }
-    box->timer[0].destroy(); box->timer[1].destroy();
     delete box;
 }
 

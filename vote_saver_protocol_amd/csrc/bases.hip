@@ -60,11 +60,12 @@ template <class G> static bool fp28_known_answer_check(vsp_ctx *ctx) {
     for (size_t i = n - 511; i < n; i++) for (int j = 0; j < 4; j++) sc[4 * i + j] = sc[4 * (n - 512) + j];  // one point 512 times, scalars as drawn
     const size_t esz = sizeof(typename G::Point), row = sizeof(typename G::Row28);
     const std::string sfx = "_g" + std::to_string(G::ID);        // of the stat names
-    void *d_pts = nullptr, *t28 = nullptr;
+    DevBuf pts, tab28;
     bool same = false, ran = false;
     if (ensure(ctx, ctx->msm_scalars, 2 * n * 32) == VSP_OK && ensure(ctx, ctx->val_flag, 16) == VSP_OK &&
         hipMemcpyAsync(ctx->msm_scalars.p, sc.data(), 2 * n * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
-        hipStreamSynchronize(ctx->stream) == hipSuccess && hipMalloc(&d_pts, n * esz) == hipSuccess && hipMalloc(&t28, 2 * n * row) == hipSuccess) {
+        hipStreamSynchronize(ctx->stream) == hipSuccess && pts.alloc(n * esz) == hipSuccess && tab28.alloc(2 * n * row) == hipSuccess) {
+        void *d_pts = pts.p, *t28 = tab28.p;
         const Fr *dk = (const Fr *)ctx->msm_scalars.p, *ds = dk + n;
         int rc = fixed_base_mul<G>(ctx, dk, n, d_pts);
         if (rc == VSP_OK) rc = bases_to_mont<G>(ctx, d_pts, (typename G::Point *)d_pts, n, 0, (uint32_t *)ctx->val_flag.p);
@@ -91,8 +92,6 @@ template <class G> static bool fp28_known_answer_check(vsp_ctx *ctx) {
             same = detail == 0;
         }
     }
-    if (d_pts) hipFree(d_pts);
-    if (t28) hipFree(t28);
     hipGetLastError();
     if (!ran) { ctx->stats["msm_fp28_selfcheck" + sfx] = 0.0; return false; }      // could not run (out of memory): no verdict, no 28-bit table this time
     return record_verdict(ctx, ctx->fp28_checked[gi], same, "msm_fp28_selfcheck_fault", "msm_fp28_selfcheck" + sfx, "msm_fp28",
@@ -114,7 +113,7 @@ static bool glv_wanted(vsp_ctx *ctx, int group, size_t count, unsigned pre_c) {
     return want && want_glv && pre_c == 0 && count >= 1024 && count < ((size_t)1 << 30) && (want_glv >= 2 || 2 * count * row <= glv_limit);
 }
 static void build_table28(vsp_ctx *ctx, vsp_bases *b) {
-    if (b->d28) { hipFree(b->d28); b->d28 = nullptr; }
+    b->d28.reset();
     b->glv = false;
     const long want = opt(ctx, "msm_fp28", 1), want_glv = opt(ctx, "msm_glv", 1);
     // "msm_fp28" = 2 (diagnostics: bisecting a failed check with tools/fuzz_msm.py): the 28-bit kernels WITHOUT the context-time check
@@ -122,16 +121,16 @@ static void build_table28(vsp_ctx *ctx, vsp_bases *b) {
     // window multiples for dense scalars (pre_split): the 128 / c windows of a split scalar, every row with its endomorphism image beside it
     const bool glv = (b->in_subgroup > 0 || want_glv >= 2) && (b->pre_c ? b->pre_split && want_glv : glv_wanted(ctx, b->group, b->n, 0));
     const size_t rows = table28_rows(b, glv).count;
-    void *t28 = nullptr;
-    if (hipMalloc(&t28, rows * row28_bytes(b->group)) != hipSuccess) { hipGetLastError(); return; }
-    int rc = with_group(b->group, [&](auto g) { using G = decltype(g); return msm_table28<G>(ctx, (const typename G::Point *)b->d, glv ? rows / 2 : rows, t28, glv); });
-    if (rc == VSP_OK && hipStreamSynchronize(ctx->stream) == hipSuccess) { b->d28 = t28; b->glv = glv; }
-    else { hipFree(t28); hipGetLastError(); }
+    DevBuf t28;
+    if (t28.alloc(rows * row28_bytes(b->group)) != hipSuccess) { hipGetLastError(); return; }
+    int rc = with_group(b->group, [&](auto g) { using G = decltype(g); return msm_table28<G>(ctx, b->d.as<const typename G::Point>(), glv ? rows / 2 : rows, t28.p, glv); });
+    if (rc == VSP_OK && hipStreamSynchronize(ctx->stream) == hipSuccess) { b->d28 = std::move(t28); b->glv = glv; }
+    else hipGetLastError();
 }
 // the subgroup check of plain resident bases over the context's validation word, which the caller zeroed: queued, the word read back
 // into *h_flag, and -- unless its bits 0 / 1 refuse the upload -- the verdict recorded (b->in_subgroup 1 or -1, the two stats)
 static int bases_subgroup_check(vsp_ctx *ctx, vsp_bases *b, uint32_t *h_flag) {
-    VSP_TRY(with_group(b->group, [&](auto g) { using G = decltype(g); return subgroup_check<G>(ctx, (const typename G::Point *)b->d, b->n, (uint32_t *)ctx->val_flag.p); }));
+    VSP_TRY(with_group(b->group, [&](auto g) { using G = decltype(g); return subgroup_check<G>(ctx, b->d.as<const typename G::Point>(), b->n, ctx->val_flag.as<uint32_t>()); }));
     VSP_HIP(hipMemcpyAsync(h_flag, ctx->val_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     VSP_HIP(hipStreamSynchronize(ctx->stream));
     if (*h_flag & 3u) return VSP_OK;
@@ -140,21 +139,19 @@ static int bases_subgroup_check(vsp_ctx *ctx, vsp_bases *b, uint32_t *h_flag) {
     if (b->in_subgroup < 0) ctx->stats["bases_outside_subgroup"] += 1;
     return VSP_OK;
 }
-// frees a handle that bases_create has not handed out
-struct BasesDeleter { void operator()(vsp_bases *b) const { if (b->d) hipFree(b->d); if (b->d28) hipFree(b->d28); delete b; } };
 int bases_create(vsp_ctx *ctx, int group, const void *src, bool src_on_device, size_t n, int trust, vsp_bases **out) {
     *out = nullptr;
     if (!ctx) return VSP_ERR_ARG;
     if (!src && n) return set_error(ctx, VSP_ERR_ARG, "bases: null pointer");
     hipSetDevice(ctx->device);
     const size_t esz = point_bytes(group);
-    std::unique_ptr<vsp_bases, BasesDeleter> b(new vsp_bases());
+    std::unique_ptr<vsp_bases> b(new vsp_bases());
     b->group = group; b->n = n;
-    if (hipMalloc(&b->d, n ? n * esz : 16) != hipSuccess) { b->d = nullptr; return set_error(ctx, VSP_ERR_NOMEM, "bases: hipMalloc failed"); }
+    if (b->d.alloc(n ? n * esz : 16) != hipSuccess) return set_error(ctx, VSP_ERR_NOMEM, "bases: hipMalloc failed");
     if (n) {
         if (!src_on_device) {
-            if (hipMemcpyAsync(b->d, src, n * esz, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return set_error(ctx, VSP_ERR_HIP, "bases: H2D failed");
-            src = b->d;                      // convert in place
+            if (hipMemcpyAsync(b->d.p, src, n * esz, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return set_error(ctx, VSP_ERR_HIP, "bases: H2D failed");
+            src = b->d.p;                    // convert in place
         }
         // boundary validation (include/vsp.h): coordinates below p always; the curve equation unless option "bases_check_curve" = 0
         const long check_curve = opt(ctx, "bases_check_curve", 1);
@@ -166,7 +163,7 @@ int bases_create(vsp_ctx *ctx, int group, const void *src, bool src_on_device, s
         if (hipMemsetAsync(ctx->val_flag.p, 0, 16, ctx->stream) != hipSuccess) return set_error(ctx, VSP_ERR_HIP, "bases: memset failed");
         VSP_TRY(with_group(group, [&](auto g) {
             using G = decltype(g);
-            return bases_to_mont<G>(ctx, src, (typename G::Point *)b->d, n, (int)check_curve, (uint32_t *)ctx->val_flag.p);
+            return bases_to_mont<G>(ctx, src, b->d.as<typename G::Point>(), n, (int)check_curve, (uint32_t *)ctx->val_flag.p);
         }));
         uint32_t h_flag = 0;
         if (trust == BASES_OWN) b->in_subgroup = 1;
@@ -190,12 +187,12 @@ int launch_on_bases(vsp_ctx *ctx, unsigned slot, const vsp_bases *bases, size_t 
     if (slot < VSP_MSM_SLOTS) ctx->slot_group[slot] = bases->group;
     if (bases->pre_c && rq.batch && (!opt(ctx, "msm_batch_tables", 1) || bases->pre_c > 16))      // (a batch over the table: ONE bucket set per vector)
         return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: a batch over this table of window multiples is not supported (plain bases, or windows of at most 16 bits)");
-    MsmPre pre{bases->n, first, bases->pre_c, bases->d28, bases->glv};
+    MsmPre pre{bases->n, first, bases->pre_c, bases->d28.p, bases->glv};
     rq.glv = bases->glv;
-    if (bases->pre_c) { rq.bases = bases->d; rq.pre = &pre; }
+    if (bases->pre_c) { rq.bases = bases->d.p; rq.pre = &pre; }
     else {
-        rq.bases = (const char *)bases->d + first * point_bytes(bases->group);
-        rq.table28 = bases->d28 ? (const char *)bases->d28 + table28_rows(bases, bases->glv, first).first * row28_bytes(bases->group) : nullptr;
+        rq.bases = bases->d.as<const char>() + first * point_bytes(bases->group);
+        rq.table28 = bases->d28.p ? bases->d28.as<const char>() + table28_rows(bases, bases->glv, first).first * row28_bytes(bases->group) : nullptr;
     }
     return with_group(bases->group, [&](auto g) { return msm_slot_launch<decltype(g)>(ctx, slot, rq); });
 }
@@ -223,14 +220,13 @@ static int bases_precompute(vsp_ctx *ctx, vsp_bases *b, unsigned window_bits, bo
     const unsigned W = 255 / window_bits + 1;
     const size_t esz = point_bytes(b->group);
     if ((size_t)W * b->n >= ((size_t)1 << 31)) return set_error(ctx, VSP_ERR_UNSUPPORTED, "precompute: table too large to index");
-    void *table = nullptr;
-    if (hipMalloc(&table, (size_t)W * b->n * esz) != hipSuccess) return set_error(ctx, VSP_ERR_NOMEM, "precompute: hipMalloc failed");
-    VSP_HIP(hipMemcpyAsync(table, b->d, b->n * esz, hipMemcpyDeviceToDevice, ctx->stream));
-    int rc = with_group(b->group, [&](auto g) { using G = decltype(g); return msm_precompute<G>(ctx, (typename G::Point *)table, b->n, window_bits); });
-    if (rc != VSP_OK) { hipFree(table); return rc; }
+    DevBuf table;
+    if (table.alloc((size_t)W * b->n * esz) != hipSuccess) return set_error(ctx, VSP_ERR_NOMEM, "precompute: hipMalloc failed");
+    VSP_HIP(hipMemcpyAsync(table.p, b->d.p, b->n * esz, hipMemcpyDeviceToDevice, ctx->stream));
+    VSP_TRY(with_group(b->group, [&](auto g) { using G = decltype(g); return msm_precompute<G>(ctx, table.as<typename G::Point>(), b->n, window_bits); }));
     VSP_HIP(hipStreamSynchronize(ctx->stream));
-    hipFree(b->d);
-    b->d = table; b->pre_c = window_bits;
+    b->d = std::move(table);                                 // the points go, the table stays
+    b->pre_c = window_bits;
     b->pre_split = split;                                    // only now: a refused or failed call leaves the handle as it was (bases outside the subgroup get the ordinary table: build_table28 decides)
     build_table28(ctx, b);
     return VSP_OK;
@@ -257,13 +253,11 @@ size_t vsp_bases_count(const vsp_bases *b) { return b ? b->n : 0; }
 size_t vsp_bases_device_bytes(const vsp_bases *b) {
     if (!b) return 0;
     const size_t count = b->n * (b->pre_c ? 255 / b->pre_c + 1 : 1);
-    return (count ? count * point_bytes(b->group) : 16) + (b->d28 ? table28_rows(b, b->glv).count * row28_bytes(b->group) : 0);
+    return (count ? count * point_bytes(b->group) : 16) + (b->d28.p ? table28_rows(b, b->glv).count * row28_bytes(b->group) : 0);
 }
 void vsp_bases_free(vsp_ctx *ctx, vsp_bases *b) {
     if (!b) return;
     if (ctx) { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
-    if (b->d) hipFree(b->d);
-    if (b->d28) hipFree(b->d28);
     delete b;
 }
 int vsp_bases_precompute(vsp_ctx *ctx, vsp_bases *b, unsigned window_bits) { return bases_precompute(ctx, b, window_bits, false); }

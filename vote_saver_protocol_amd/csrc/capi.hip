@@ -18,18 +18,21 @@ int set_error(vsp_ctx *ctx, int code, const char *msg) {
     if (ctx) ctx->err = msg;
     return code;
 }
-int ensure(vsp_ctx *ctx, DevBuf &b, size_t bytes) {
+int ensure(vsp_ctx *ctx, DevBuf &b, size_t bytes, hipStream_t wait) {
     if (bytes == 0) bytes = 16;
     if (b.cap >= bytes && b.p) return VSP_OK;
-    if (b.p) { VSP_HIP(hipStreamSynchronize(ctx->stream)); hipFree(b.p); b.p = nullptr; b.cap = 0; }
-    size_t want = bytes + bytes / 8;          // a little headroom so a slightly larger call does not realloc
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) { b.p = nullptr; char m[128]; snprintf(m, sizeof m, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e)); return set_error(ctx, VSP_ERR_NOMEM, m); }
-    b.cap = want;
+    if (b.p) { VSP_HIP(hipStreamSynchronize(wait)); b.reset(); }
+    const size_t want = bytes + bytes / 8;
+    const hipError_t e = b.alloc(want);
+    if (e != hipSuccess) { char m[128]; snprintf(m, sizeof m, "device allocation of %zu bytes failed: %s", want, hipGetErrorString(e)); return set_error(ctx, VSP_ERR_NOMEM, m); }
     return VSP_OK;
 }
-
-static void free_buf(DevBuf &b) { if (b.p) hipFree(b.p); b.p = nullptr; b.cap = 0; }
+int ensure_pinned(vsp_ctx *ctx, PinnedBuf &b, size_t bytes) {
+    if (bytes == 0) bytes = 16;
+    if (b.cap >= bytes && b.p) return VSP_OK;
+    VSP_HIP(b.alloc(bytes + bytes / 8));
+    return VSP_OK;
+}
 
 template <class HF> static int finish_affine(const XYZZ<HF> &acc, uint64_t *out_affine, int *out_is_inf) {
     if (out_affine) host_store_affine(out_affine, xyzz_to_affine(acc));
@@ -194,7 +197,6 @@ int vsp_selftest_tower(vsp_ctx *ctx, int level, int op, const uint64_t *a, const
         hipMemcpyAsync(out, dc.p, n * esz, hipMemcpyDeviceToHost, ctx->stream);
         if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = set_error(ctx, VSP_ERR_HIP, "selftest: kernel failed");
     }
-    free_buf(da); free_buf(db); free_buf(dc);
     return rc;
 }
 
@@ -219,7 +221,6 @@ int vsp_selftest_fp2_lanes(vsp_ctx *ctx, int form, int op, const uint64_t *a, co
         hipMemcpyAsync(rec.data(), dout.p, n * sizeof(P), hipMemcpyDeviceToHost, ctx->stream);
         if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = set_error(ctx, VSP_ERR_HIP, "selftest: kernel failed");
     }
-    free_buf(din); free_buf(dout);
     if (rc == VSP_OK)
         for (size_t i = 0; i < n; i++) {
             memcpy(out_p + i * W, &rec[(i * 4) * W], W * sizeof(uint64_t));
@@ -246,7 +247,6 @@ int vsp_selftest_field(vsp_ctx *ctx, int field, int op, const uint64_t *a, const
         hipMemcpyAsync(out, dc.p, n * esz, hipMemcpyDeviceToHost, ctx->stream);
         if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = set_error(ctx, VSP_ERR_HIP, "selftest: kernel failed");
     }
-    free_buf(da); free_buf(db); free_buf(dc);
     return rc;
 }
 
@@ -267,7 +267,6 @@ int vsp_selftest_xyzz_add(vsp_ctx *ctx, int group, int form, const uint64_t *a, 
             hipMemcpyAsync(out, dc.p, n * esz, hipMemcpyDeviceToHost, ctx->stream);
             if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = set_error(ctx, VSP_ERR_HIP, "selftest: kernel failed");
         }
-        free_buf(da); free_buf(db); free_buf(dc);
         return rc;
     });
 }
@@ -296,25 +295,13 @@ void vsp_destroy(vsp_ctx *ctx) {
     hipSetDevice(ctx->device);
     if (ctx->prove.active) msm_drain_slots(ctx);      // a proof launched and never finished: wait its kernels out before their buffers go
     hipStreamSynchronize(ctx->stream);
-    DevBuf *bufs[] = {&ctx->ntt.fwd, &ctx->ntt.inv, &ctx->ntt.pw_lo_f, &ctx->ntt.pw_hi_f, &ctx->ntt.pw_lo_i, &ctx->ntt.pw_hi_i, &ctx->ntt_scratch, &ctx->dom_scratch,
-                      &ctx->ntt.fwd29, &ctx->ntt.inv29, &ctx->ntt.pw29[0], &ctx->ntt.pw29[1], &ctx->ntt.pw29[2], &ctx->ntt.pw29[3],
-                      &ctx->msm_scalars, &ctx->val_flag, &ctx->fb_table[0], &ctx->fb_table[1], &ctx->fb_tmp, &ctx->fb_pre,
-                      &ctx->pr_z, &ctx->pr_abc, &ctx->pr_h, &ctx->pr_pack, &ctx->pr_verdict,
-                      &ctx->tally_raw, &ctx->tally_bstatus, &ctx->tally_partials,
-                      &ctx->decode[0].pts, &ctx->decode[0].pstatus, &ctx->decode[1].pts, &ctx->decode[1].pstatus,
-                      &ctx->pair_raw, &ctx->pair_g1, &ctx->pair_g2, &ctx->pair_status, &ctx->pair_ml, &ctx->pair_prod, &ctx->pair_gt, &ctx->dec_out, &ctx->screen_ws,
-                      &ctx->recv_members, &ctx->recv_mstatus, &ctx->recv_raw, &ctx->recv_rest, &ctx->recv_wire, &ctx->ped_in, &ctx->ped_out, &ctx->ped_zero};
-    for (DevBuf *b : bufs) free_buf(*b);
+    hipDeviceSynchronize();                           // a multi-exponentiation launched and never finished, a record's copy on a caller's stream
     msm_free_slots(ctx);
     saver_ct_release(ctx);
-    saver_rr_release(ctx);
-    if (ctx->h_fold) hipHostFree(ctx->h_fold);
-    if (ctx->h_verdict) hipHostFree(ctx->h_verdict);
     hipEventDestroy(ctx->ev0); hipEventDestroy(ctx->ev1); hipEventDestroy(ctx->ev_aux);
-    for (StageTimer *t : {&ctx->decode[0].timer, &ctx->decode[1].timer, &ctx->check_timer, &ctx->pair_timer, &ctx->saver_timer, &ctx->dec_timer, &ctx->screen_timer[0], &ctx->screen_timer[1], &ctx->recv_timer, &ctx->ped_timer}) t->destroy();
     for (hipStream_t ps : ctx->prove_streams) if (ps) hipStreamDestroy(ps);
     hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx;                 // every buffer and timer goes with its owner
 }
 
 const char *vsp_last_error(vsp_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -335,6 +322,8 @@ double vsp_get_stat(vsp_ctx *ctx, const char *name) {
     if (!strcmp(name, "saver_decrypt_run_steps")) return (double)DLOG_RUN_STEPS;          // constants of the giant search (csrc/gt_dlog.h)
     if (!strcmp(name, "saver_decrypt_block_lanes")) return (double)DLOG_BLOCK_LANES;
     if (!strcmp(name, "saver_decrypt_launch_lanes")) return (double)DLOG_LAUNCH_LANES;
+    if (!strcmp(name, "device_allocations_live")) return (double)DevBuf::live().load();          // process-wide (csrc/common.h OwnedBuf)
+    if (!strcmp(name, "pinned_allocations_live")) return (double)PinnedBuf::live().load();
     if (!strcmp(name, "runtime_hw_queues_env")) { const char *q = getenv("GPU_MAX_HW_QUEUES"); return q ? atof(q) : 0.0; }      // include/vsp.h "Runtime environment"
     auto it = ctx->stats.find(name);
     return it == ctx->stats.end() ? 0.0 : it->second;
@@ -552,10 +541,10 @@ int vsp_msm_finish_jacobian_device(vsp_ctx *ctx, unsigned slot, void *d_out_jaco
     if (slot >= VSP_MSM_SLOTS || !d_out_jacobian) return set_error(ctx, VSP_ERR_ARG, "msm: bad slot or null output");
     VSP_HIP(hipSetDevice(ctx->device));
     MsmWork &wk = ctx->msm_work[slot];
-    if (!wk.inited || !wk.h_rec) return set_error(ctx, VSP_ERR_ARG, "msm: finish without launch");
+    if (!wk.inited || !wk.h_rec.p) return set_error(ctx, VSP_ERR_ARG, "msm: finish without launch");
     const unsigned k = wk.rec_idx++ % MsmWork::REC_RING;
     VSP_HIP(hipEventSynchronize(wk.rec_ev[k]));                 // the copy that last read this ring entry (long done in practice; never-recorded events return at once)
-    uint64_t *rec = (uint64_t *)((char *)wk.h_rec + (size_t)k * 288);
+    uint64_t *rec = (uint64_t *)(wk.h_rec.as<char>() + (size_t)k * 288);
     size_t words = 0;
     VSP_TRY(finish_record(ctx, slot, rec, &words));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
@@ -585,18 +574,13 @@ int vsp_fold_jacobian_device(vsp_ctx *ctx, int group, const void *d_records, siz
     if (count > 4096) return set_error(ctx, VSP_ERR_ARG, "fold: more than 4096 records");
     VSP_HIP(hipSetDevice(ctx->device));
     const size_t bytes = count * 8 * with_group(group, [](auto g) { return decltype(g)::JACOBIAN_WORDS; });
-    if (bytes > ctx->h_fold_cap) {
-        if (ctx->h_fold) { hipHostFree(ctx->h_fold); ctx->h_fold = nullptr; ctx->h_fold_cap = 0; }
-        const size_t want = bytes < 8192 ? 8192 : bytes;
-        VSP_HIP(hipHostMalloc(&ctx->h_fold, want, hipHostMallocDefault));
-        ctx->h_fold_cap = want;
-    }
+    VSP_TRY(ensure_pinned(ctx, ctx->h_fold, bytes));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
     if (bytes) {
-        VSP_HIP(hipMemcpyAsync(ctx->h_fold, d_records, bytes, hipMemcpyDeviceToHost, st));
+        VSP_HIP(hipMemcpyAsync(ctx->h_fold.p, d_records, bytes, hipMemcpyDeviceToHost, st));
         VSP_HIP(hipStreamSynchronize(st));
     }
-    return vsp_fold_jacobian(ctx, group, (const uint64_t *)ctx->h_fold, count, out_affine, out_is_inf);
+    return vsp_fold_jacobian(ctx, group, ctx->h_fold.as<const uint64_t>(), count, out_affine, out_is_inf);
 }
 
 static int msm_host(vsp_ctx *ctx, int group, const uint64_t *bases, const uint64_t *scalars, size_t n, uint64_t *out_affine, int *out_is_inf) {
@@ -679,13 +663,12 @@ vsp_domain *vsp_domain_create(vsp_ctx *ctx, size_t min_size) {
     if (!ctx) return nullptr;
     hipSetDevice(ctx->device);
     vsp_domain *d = new vsp_domain();
-    if (domain_init(ctx, d, min_size) != VSP_OK) { domain_release(d); delete d; return nullptr; }
+    if (domain_init(ctx, d, min_size) != VSP_OK) { delete d; return nullptr; }
     return d;
 }
 void vsp_domain_free(vsp_ctx *ctx, vsp_domain *d) {
     if (!d) return;
     if (ctx) hipSetDevice(ctx->device);
-    domain_release(d);
     delete d;
 }
 size_t vsp_domain_size(const vsp_domain *d) { return d ? d->m : 0; }

@@ -7,6 +7,7 @@
 #include <functional>
 #include <initializer_list>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -51,17 +52,46 @@ template <class Fn> inline decltype(auto) with_group(int group, Fn &&f) {
 // bytes of one device affine point of a group
 inline size_t point_bytes(int group) { return with_group(group, [](auto g) { return sizeof(typename decltype(g)::Point); }); }
 
-struct DevBuf {
+// The owners of the library's memory: DevBuf (hipMalloc) and PinnedBuf (hipHostMalloc).  Move-only; the destructor frees, so a struct
+// that holds one frees it when the struct goes and a local frees it on every return.  Nothing waits here: whoever lets a buffer go
+// has waited for the work that uses it.  live() counts the allocations of a kind in the process ("device_allocations_live",
+// "pinned_allocations_live" of vsp_get_stat)
+template <bool PINNED> struct OwnedBuf {
     void *p = nullptr;
     size_t cap = 0;
+    OwnedBuf() = default;
+    OwnedBuf(const OwnedBuf &) = delete;
+    OwnedBuf &operator=(const OwnedBuf &) = delete;
+    OwnedBuf(OwnedBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    OwnedBuf &operator=(OwnedBuf &&o) noexcept { if (this != &o) { reset(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    ~OwnedBuf() { reset(); }
+    static std::atomic<long> &live() { static std::atomic<long> n{0}; return n; }
+    // exactly `bytes` (not zero) in place of what it held
+    hipError_t alloc(size_t bytes) {
+        reset();
+        const hipError_t e = PINNED ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        cap = bytes; live()++;
+        return hipSuccess;
+    }
+    void reset() {
+        if (p) { if (PINNED) hipHostFree(p); else hipFree(p); live()--; }
+        p = nullptr; cap = 0;
+    }
+    template <class T> T *as() const { return static_cast<T *>(p); }
 };
-// the timers around the device stages of one kind of call: up to four events, created on first use
+using DevBuf = OwnedBuf<false>;
+using PinnedBuf = OwnedBuf<true>;
+// the timers around the device stages of one kind of call: up to four events, created on first use, destroyed with the timer
 struct StageTimer {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    StageTimer() = default;
+    StageTimer(const StageTimer &) = delete;
+    StageTimer &operator=(const StageTimer &) = delete;
+    ~StageTimer() { for (hipEvent_t e : ev) if (e) hipEventDestroy(e); }
     int event(vsp_ctx *ctx, int i, hipEvent_t *out);                // event i, created on first use
     int mark(vsp_ctx *ctx, int i, hipStream_t st);                  // record event i on st
     void add(vsp_ctx *ctx, int i, const char *name) const;          // ctx->stats[name] += the time from event i to event i + 1; an error is ignored
-    void destroy() { for (hipEvent_t &e : ev) if (e) { hipEventDestroy(e); e = nullptr; } }
 };
 // the decoded points of one piece of a group (decode.hip): Montgomery affine points, a status byte per point, and the timer around
 // the decoding and the subgroup check (G1: event 3 closes the tally's sum)
@@ -132,7 +162,7 @@ struct MsmPre { size_t stride; size_t first; unsigned c; const void *table28; bo
 
 // one in-flight MSM: its stream, device workspaces (grow only) and the pinned landing buffer of its window results
 struct MsmWork {
-    static constexpr size_t PINNED_BYTES = 256 * 1024;       // window results land here (25 records of 192 / 384 bytes per window at most); a batch grows it (pinned_cap)
+    static constexpr size_t PINNED_BYTES = 256 * 1024;       // window results land here (25 records of 192 / 384 bytes per window at most); a batch grows it
     bool inited = false, own_stream = false, active = false, empty = false;
     bool dimbits = false;                  // layout of the window results of the last launch (msm_impl.inc k_dimbits / k_dimweight)
     hipStream_t stream = nullptr;          // the stream launches queue on: the slot's own one, or a borrowed one (msm_slot_use_stream)
@@ -145,13 +175,12 @@ struct MsmWork {
     DevBuf tmp_sorted, tmp_lo, off_hi, cnt_hi;      // windows wider than 16 bits: the entries ordered by the high 15 bits of the bucket index, their low bits, the segment offsets
     DevBuf glv_scalars;                  // endomorphism split: 2n half-length scalars k1_i, k2_i (interleaved)
     bool glv = false;                    // this launch runs over the split scalars and the interleaved (P, phi(P)) table
-    void *h_pinned = nullptr;
-    size_t pinned_cap = 0;
+    PinnedBuf h_pinned;
     // vsp_msm_finish_jacobian_device: the Jacobian record leaves through a small pinned ring (REC_RING entries of 288 bytes) so that the
     // copy into the caller's device buffer is an asynchronous DMA; rec_ev[k] marks the copy out of entry k as done
     static constexpr unsigned REC_RING = 4;
-    void *h_rec = nullptr; hipEvent_t rec_ev[REC_RING] = {nullptr, nullptr, nullptr, nullptr}; unsigned rec_idx = 0;
-    void *h_census = nullptr;            // pinned: count of scalars that are neither 0 nor 1
+    PinnedBuf h_rec; hipEvent_t rec_ev[REC_RING] = {nullptr, nullptr, nullptr, nullptr}; unsigned rec_idx = 0;
+    PinnedBuf h_census;                  // count of scalars that are neither 0 nor 1
     hipEvent_t census_done = nullptr;
     bool census_pending = false; size_t census_n = 0; const void *census_scalars = nullptr;
     bool check_pending = false;          // this launch's census (count + non-canonical flag) is to be read at finish
@@ -242,7 +271,7 @@ struct vsp_ctx {
     bool ntt_attr_set = false;
     int ntt29_checked = 0;              // known-answer check of k_ntt29_pass: 0 not yet (or could not run), 1 passed, -1 failed (8 x 32-bit kernel in use)
     vsp::DevBuf msm_scalars;
-    void *h_fold = nullptr; size_t h_fold_cap = 0;      // pinned landing buffer of vsp_fold_jacobian_device (the ranks' records)
+    vsp::PinnedBuf h_fold;              // landing buffer of vsp_fold_jacobian_device (the ranks' records)
     vsp::DevBuf val_flag;               // one word: validation result of the last bases upload
     int fp28_checked[2] = {0, 0};       // known-answer check of the 28-bit-limb accumulation kernels, per group: 0 not yet, 1 passed, -1 failed (kernel disabled)
     // fixed-base tables of the generators (fb_table[group - 1]), built lazily, and the scratch of the batch exponentiation
@@ -278,7 +307,7 @@ struct vsp_ctx {
     // first_bad_row [64] | bad_rows [64] | a value >= r [64] -- on the device and in the pinned buffer the asynchronous copy lands in
     static constexpr size_t VERDICT_MEMBERS = 64, VERDICT_BYTES = 3 * VERDICT_MEMBERS * sizeof(uint32_t);
     vsp::DevBuf pr_verdict;
-    void *h_verdict = nullptr;
+    vsp::PinnedBuf h_verdict;
     vsp::StageTimer check_timer;          // vsp_r1cs_check_batch: around its front half and around its verdict kernels
     // the proof or the batch of K proofs in flight between a launch and its finish (one per context): the key, r and s (K x 4 words), the
     // SAVER term (single proofs only), the bytes of z the launch wrote
@@ -294,7 +323,7 @@ struct vsp_ctx {
     struct {
         hipStream_t stream = nullptr;
         vsp::DevBuf scalars, sums, points;
-        void *h_scalars = nullptr, *h_points = nullptr; size_t h_scalars_cap = 0, h_points_cap = 0;
+        vsp::PinnedBuf h_scalars, h_points;
         hipEvent_t done = nullptr;
         vsp::StageTimer timer;
         bool active = false, gpu = false, device_src = false; const vsp_saver_pk *spk = nullptr; size_t count = 0;
@@ -309,7 +338,7 @@ struct vsp_ctx {
     // around check | columns | affine and around the G1 | G2 multiplications
     struct {
         vsp::DevBuf words, scalars, given, b_in, sums, sums2, status;
-        void *h_in = nullptr, *h_out = nullptr; size_t h_in_cap = 0, h_out_cap = 0;
+        vsp::PinnedBuf h_in, h_out;
         vsp::StageTimer timer[2];
     } saver_rr;
     // vsp_groth16_prove_batch_verdicts: status byte and first failing row of every member of the last finished batch that was checked
@@ -320,7 +349,7 @@ struct vsp_ctx {
 struct vsp_bases {
     int group = 1;          // 1 = G1, 2 = G2
     size_t n = 0;
-    void *d = nullptr;      // device array of Affine<Fp> / Affine<Fp2>, Montgomery form; with pre_c != 0 it is the table
+    vsp::DevBuf d;          // device array of Affine<Fp> / Affine<Fp2>, Montgomery form; with pre_c != 0 it is the table
                             // [W][n]: slice w holds 2^(pre_c * w) * P  (vsp_bases_precompute)
     unsigned pre_c = 0;
     int in_subgroup = 0;    // 1: every point satisfies phi(P) = lambda P (checked at upload, or the library's own multiples of a generator); -1: the check
@@ -329,7 +358,7 @@ struct vsp_bases {
                             // k = k1 + k2 lambda then needs windows over 128 bits only.  Plain bases: 2n rows, half the bucket sets to reduce.
                             // Window multiples (pre_split): 2n rows for each of the ceil(128 / pre_c) windows -- the split over ONE bucket set
     bool pre_split = false; // vsp_bases_precompute_split: the table of window multiples is meant for dense scalars and carries the endomorphism rows
-    void *d28 = nullptr;    // the same array (or table) once more on 14 x 28-bit limbs (fp28.h: 112-byte rows G1, 224-byte rows G2) for the accumulation kernel
+    vsp::DevBuf d28;        // the same array (or table) once more on 14 x 28-bit limbs (fp28.h: 112-byte rows G1, 224-byte rows G2) for the accumulation kernel
 };
 
 // math::evaluation_domain<Fr>: the basic radix-2 domain (step = 0, m = big_m = 2^log_big) or the step radix-2 domain
@@ -347,13 +376,11 @@ struct vsp_domain {
 struct vsp_r1cs {
     size_t num_constraints = 0, num_inputs = 0, num_vars = 0;
     vsp_domain dom;          // make_evaluation_domain(num_constraints + num_inputs + 1)
-    uint32_t *rp[3] = {nullptr, nullptr, nullptr};
-    uint32_t *ci[3] = {nullptr, nullptr, nullptr};
-    void *co[3] = {nullptr, nullptr, nullptr};      // Fr Montgomery
+    vsp::DevBuf rp[3], ci[3];       // row pointers, column indices (uint32_t)
+    vsp::DevBuf co[3];              // Fr Montgomery
     // column-major copy (for the generator's per-variable accumulation): col_ptr [num_vars+2], row index, coefficient
-    uint32_t *cp[3] = {nullptr, nullptr, nullptr};
-    uint32_t *ri[3] = {nullptr, nullptr, nullptr};
-    void *cot[3] = {nullptr, nullptr, nullptr};     // Fr Montgomery
+    vsp::DevBuf cp[3], ri[3];       // uint32_t
+    vsp::DevBuf cot[3];             // Fr Montgomery
 };
 
 struct vsp_keypair {
@@ -428,7 +455,7 @@ struct vsp_saver_pk {
     mutable int device = -1;
     mutable std::vector<vsp::Affine<vsp::HFp>> flat;      // (3 n + 3) x 960 points; the table of a base at infinity is all zero
     mutable vsp::SaverPlan plan;                          // which scalars meet which bases in which column, and the lanes of a ballot
-    mutable void *d_tab = nullptr, *d_desc = nullptr;     // the table and the plan (columns | pairs | lane_col) on the device
+    mutable vsp::DevBuf d_tab, d_desc;                    // the table and the plan (columns | pairs | lane_col) on the device
     mutable size_t device_bytes = 0;
 };
 
@@ -436,17 +463,17 @@ struct vsp_saver_pk {
 struct vsp_vk {
     size_t n_abc = 0;
     uint8_t alpha_beta[576];            // e(alpha, beta), canonical tower order
-    void *d_expect = nullptr;           // the same value, Fp12 in Montgomery form
-    void *d_neg = nullptr;              // two G2Affine, Montgomery: -gamma_g2, -delta_g2
-    void *d_tab = nullptr;              // n_abc rows of 16 G1Affine, Montgomery: d * gamma_ABC[i], d = 0..15 (d = 0: infinity)
+    vsp::DevBuf d_expect;               // the same value, Fp12 in Montgomery form
+    vsp::DevBuf d_neg;                  // two G2Affine, Montgomery: -gamma_g2, -delta_g2
+    vsp::DevBuf d_tab;                  // n_abc rows of 16 G1Affine, Montgomery: d * gamma_ABC[i], d = 0..15 (d = 0: infinity)
 };
 // A SAVER verifier: the Groth16 key as above, and the prepared lines (pairing.h) of the election key's G2 members in the order of the
 // pairs of a ballot: t_g2[0..n] | -H | -gamma_g2 | -delta_g2, then beta_g2 and alpha_g1 for the screened check's e(alpha, beta)^Z (screen.hip)
 struct vsp_saver_verifier {
     int device = 0;
     size_t n = 0;                       // msg_size
-    vsp_vk *vk = nullptr;
-    void *d_lines = nullptr;            // (n + 5) x MILLER_LINES LineCoeffs, Montgomery
+    std::unique_ptr<vsp_vk> vk;
+    vsp::DevBuf d_lines;                // (n + 5) x MILLER_LINES LineCoeffs, Montgomery
     vsp::Affine<vsp::HFp> alpha_g1;     // host, Montgomery
 };
 
@@ -513,7 +540,11 @@ template <class Fn> inline void host_parallel_for(size_t n, Fn f, unsigned max_t
     for (auto &x : th) x.join();
 }
 int set_error(vsp_ctx *ctx, int code, const char *msg);
-int ensure(vsp_ctx *ctx, DevBuf &b, size_t bytes);
+// b holds at least `bytes`: grow only, with an eighth of headroom so that a slightly larger call does not allocate again; nothing of
+// the old contents is kept.  The device form waits for `wait` (the stream whose work may still use b) before it frees
+int ensure(vsp_ctx *ctx, DevBuf &b, size_t bytes, hipStream_t wait);
+inline int ensure(vsp_ctx *ctx, DevBuf &b, size_t bytes) { return ensure(ctx, b, bytes, ctx->stream); }
+int ensure_pinned(vsp_ctx *ctx, PinnedBuf &b, size_t bytes);
 
 #define VSP_HIP(call)                                                                        \
     do {                                                                                     \
@@ -550,7 +581,6 @@ int ntt_ensure_twiddles(vsp_ctx *ctx, unsigned log_m);
 int ntt_ensure_coset_tables(vsp_ctx *ctx, unsigned log_m, const uint64_t *g4);
 // evaluation domains (domain.hip)
 int domain_init(vsp_ctx *ctx, vsp_domain *d, size_t min_size);      // make_evaluation_domain's choice + the coset divisors
-void domain_release(vsp_domain *d);
 void domain_basic(vsp_domain *d, unsigned log_m);                   // the basic radix-2 domain of size 2^log_m (log_m = 0 allowed)
 int fr_from_mont_device(vsp_ctx *ctx, Fr *d_a, size_t n);
 int domain_fft_device(vsp_ctx *ctx, const vsp_domain *d, Fr *d_a, int inverse, const uint64_t *coset_g, const HFr *extra_scale);
@@ -577,17 +607,17 @@ int prove_with_overlap(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_pk *pk, const
                        const uint64_t *saver_P1, const uint64_t *saver_r_enc, uint64_t A_out[12], uint64_t B_out[24], uint64_t C_out[12],
                        uint8_t proof_out[192], const std::function<void()> *overlap);
 
-// ballots in batches (saver_batch.hip): what vsp_destroy and vsp_saver_pk_free release
+// ballots in batches (saver_batch.hip): the stream and the event vsp_destroy lets go, the device half of a key vsp_saver_pk_free does
 void saver_ct_release(vsp_ctx *ctx);
 void saver_pk_release_device(vsp_saver_pk *spk);
-void saver_rr_release(vsp_ctx *ctx);                            // saver_rerand.hip
+// a plan's columns | pairs | lane_col in one device buffer
+int upload_plan(vsp_ctx *ctx, const SaverPlan &p, DevBuf &out);
 
 // MSM on device-resident Montgomery bases; result as host XYZZ (Montgomery, 64-bit limbs).  The templates over the group: msm_impl.inc,
 // instantiated by msm_g1.hip / msm_g2.hip.  Everything without a template parameter is group-independent and defined once, in
 // msm_sort.hip (but msm_diag_clock: msm_g1.hip, beside the kernel whose stamps it reads).
 inline MsmWork &slot(vsp_ctx *ctx, unsigned i) { return ctx->msm_work[i]; }
 // the stages of one launch that msm_sort.hip owns; msm_launch<F> (msm_impl.inc) calls them between its own
-int ensure_w(vsp_ctx *ctx, hipStream_t st, DevBuf &b, size_t bytes);      // b holds at least `bytes` (grow only; waits for st before it frees)
 int work_init(vsp_ctx *ctx, MsmWork &wk, hipStream_t stream_or_null);
 int msm_census(vsp_ctx *ctx, MsmWork &wk, const Fr *d_scalars, size_t n, hipStream_t on_stream = nullptr, unsigned batch = 1, size_t batch_stride = 0);
 int msm_split_scalars(vsp_ctx *ctx, MsmWork &wk, MsmLaunch &L, const MsmGeom &g);

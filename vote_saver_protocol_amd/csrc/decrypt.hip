@@ -34,9 +34,9 @@ struct vsp_saver_decryptor {
     uint64_t max_value = 0, giants = 0; // giant steps: ceil((max_value + 1) / B)
     unsigned b = 0, fp_bits = 64;
     std::vector<uint8_t> base;          // n x 576: base_i, canonical tower order
-    void *d_lines = nullptr;            // (2 n + 2) x MILLER_LINES LineCoeffs
-    void *d_base = nullptr, *d_g = nullptr;     // n Fp12 each
-    void *d_keys = nullptr, *d_js = nullptr;    // n x B fingerprints (8 bytes) and exponents (4 bytes)
+    vsp::DevBuf d_lines;                // (2 n + 2) x MILLER_LINES LineCoeffs
+    vsp::DevBuf d_base, d_g;            // n Fp12 each
+    vsp::DevBuf d_keys, d_js;           // n x B fingerprints (8 bytes) and exponents (4 bytes)
 };
 
 namespace vsp {
@@ -194,7 +194,6 @@ int decrypt_selftest_gt_pow(vsp_ctx *ctx, const void *d_a, const void *d_b, void
 void saver_decryptor_free(vsp_ctx *ctx, vsp_saver_decryptor *dec) {
     if (!dec) return;
     if (ctx) { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
-    for (void *p : {dec->d_lines, dec->d_base, dec->d_g, dec->d_keys, dec->d_js}) if (p) hipFree(p);
     delete dec;
 }
 size_t saver_decryptor_msg_size(const vsp_saver_decryptor *dec) { return dec->n; }
@@ -216,8 +215,8 @@ static int decryptor_build(vsp_ctx *ctx, vsp_saver_decryptor *dec, const uint64_
     std::vector<LineCoeffs<HFp>> lines(q.size() * MILLER_LINES);                                        // LineCoeffs<HFp> and <Fp>: the same bytes
     host_parallel_for(q.size(), [&](size_t j) { prepare_g2(q[j], lines.data() + j * MILLER_LINES); });
     const size_t line_bytes = lines.size() * sizeof(LineCoeffs<HFp>);
-    VSP_HIP(hipMalloc(&dec->d_lines, line_bytes));
-    VSP_HIP(hipMemcpyAsync(dec->d_lines, lines.data(), line_bytes, hipMemcpyHostToDevice, st));
+    VSP_HIP(dec->d_lines.alloc(line_bytes));
+    VSP_HIP(hipMemcpyAsync(dec->d_lines.p, lines.data(), line_bytes, hipMemcpyHostToDevice, st));
     VSP_HIP(hipStreamSynchronize(st));
     // base_i = e(G_i, W_i) by the pairing kernels; one means a degenerate key
     dec->base.resize(576 * n);
@@ -230,30 +229,30 @@ static int decryptor_build(vsp_ctx *ctx, vsp_saver_decryptor *dec, const uint64_
         bg[i] = to_mont(e);
     }
     host_parallel_for(n, [&](size_t i) { bg[n + i] = dlog_giant_stride(bg[i], dec->b); });
-    VSP_HIP(hipMalloc(&dec->d_base, n * sizeof(HFp12)));
-    VSP_HIP(hipMalloc(&dec->d_g, n * sizeof(HFp12)));
-    VSP_HIP(hipMemcpyAsync(dec->d_base, bg.data(), n * sizeof(HFp12), hipMemcpyHostToDevice, st));
-    VSP_HIP(hipMemcpyAsync(dec->d_g, bg.data() + n, n * sizeof(HFp12), hipMemcpyHostToDevice, st));
+    VSP_HIP(dec->d_base.alloc(n * sizeof(HFp12)));
+    VSP_HIP(dec->d_g.alloc(n * sizeof(HFp12)));
+    VSP_HIP(hipMemcpyAsync(dec->d_base.p, bg.data(), n * sizeof(HFp12), hipMemcpyHostToDevice, st));
+    VSP_HIP(hipMemcpyAsync(dec->d_g.p, bg.data() + n, n * sizeof(HFp12), hipMemcpyHostToDevice, st));
     VSP_HIP(hipStreamSynchronize(st));
     // the baby tables: fingerprints on the GPU, the sort by fingerprint on the host, once
-    VSP_HIP(hipMalloc(&dec->d_keys, n * B * sizeof(uint64_t)));
-    VSP_HIP(hipMalloc(&dec->d_js, n * B * sizeof(uint32_t)));
+    VSP_HIP(dec->d_keys.alloc(n * B * sizeof(uint64_t)));
+    VSP_HIP(dec->d_js.alloc(n * B * sizeof(uint32_t)));
     const size_t runs = (B + DLOG_RUN_STEPS - 1) / DLOG_RUN_STEPS;
     VSP_TRY(ctx->dec_timer.mark(ctx, 0, st));
-    hipLaunchKernelGGL(k_dlog_table, dim3((unsigned)((runs + DLOG_BLOCK_LANES - 1) / DLOG_BLOCK_LANES), (unsigned)n), dim3(DLOG_BLOCK_LANES), 0, st, (const Fp12 *)dec->d_base,
-                       dec->b, dec->fp_bits, (uint64_t *)dec->d_keys);
+    hipLaunchKernelGGL(k_dlog_table, dim3((unsigned)((runs + DLOG_BLOCK_LANES - 1) / DLOG_BLOCK_LANES), (unsigned)n), dim3(DLOG_BLOCK_LANES), 0, st, dec->d_base.as<const Fp12>(),
+                       dec->b, dec->fp_bits, dec->d_keys.as<uint64_t>());
     VSP_LAUNCH_CHECK();
     VSP_TRY(ctx->dec_timer.mark(ctx, 1, st));
     std::vector<uint64_t> keys(n * B);
     std::vector<uint32_t> js(n * B);
-    VSP_HIP(hipMemcpyAsync(keys.data(), dec->d_keys, keys.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    VSP_HIP(hipMemcpyAsync(keys.data(), dec->d_keys.p, keys.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     VSP_HIP(hipStreamSynchronize(st));
     ctx->dec_timer.add(ctx, 0, "saver_decrypt_table_ms");
     const auto t0 = std::chrono::steady_clock::now();
     host_parallel_for(n, [&](size_t i) { dlog_sort_table(keys.data() + i * B, js.data() + i * B, B); });
     ctx->stats["saver_decrypt_sort_ms"] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    VSP_HIP(hipMemcpyAsync(dec->d_keys, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    VSP_HIP(hipMemcpyAsync(dec->d_js, js.data(), js.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    VSP_HIP(hipMemcpyAsync(dec->d_keys.p, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    VSP_HIP(hipMemcpyAsync(dec->d_js.p, js.data(), js.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     VSP_HIP(hipStreamSynchronize(st));
     return VSP_OK;
 }
@@ -299,7 +298,7 @@ static int decrypt_workspace(vsp_ctx *ctx, size_t c, size_t n, size_t slots, siz
 // pair_status + c
 static int decrypt_values(vsp_ctx *ctx, const vsp_saver_decryptor *dec, size_t c, size_t slots) {
     hipLaunchKernelGGL(k_dec_values, dim3((unsigned)((c + DLOG_BLOCK_LANES - 1) / DLOG_BLOCK_LANES), (unsigned)slots), dim3(DLOG_BLOCK_LANES), 0, ctx->stream,
-                       (const G1Affine *)ctx->pair_g1.p, (const LineCoeffs<Fp> *)dec->d_lines, c, dec->n, (Fp12 *)ctx->pair_ml.p);
+                       (const G1Affine *)ctx->pair_g1.p, dec->d_lines.as<const LineCoeffs<Fp>>(), c, dec->n, (Fp12 *)ctx->pair_ml.p);
     VSP_LAUNCH_CHECK();
     return pairing_final_exp(ctx, ctx->pair_ml.p, slots * c, ctx->pair_gt.p, (uint8_t *)ctx->pair_status.p + c);
 }
@@ -338,7 +337,7 @@ int saver_decrypt_batch(vsp_ctx *ctx, const vsp_saver_decryptor *dec, const uint
         for (uint64_t lane0 = 0; lane0 < runs; lane0 += lanes) {
             ctx->stats["saver_decrypt_dlog_launches"] += 1;
             hipLaunchKernelGGL(k_dlog_search, dim3((unsigned)((lanes + DLOG_BLOCK_LANES - 1) / DLOG_BLOCK_LANES), (unsigned)items), dim3(DLOG_BLOCK_LANES), 0, st,
-                               (const Fp12 *)ctx->pair_gt.p, (const Fp12 *)dec->d_base, (const Fp12 *)dec->d_g, (const uint64_t *)dec->d_keys, (const uint32_t *)dec->d_js, c,
+                               (const Fp12 *)ctx->pair_gt.p, dec->d_base.as<const Fp12>(), dec->d_g.as<const Fp12>(), dec->d_keys.as<const uint64_t>(), dec->d_js.as<const uint32_t>(), c,
                                dec->b, dec->fp_bits, dec->max_value, dec->giants, lane0, lanes, result);
             VSP_LAUNCH_CHECK();
             if (lane0 + lanes >= runs) break;                                                            // the last launch: nothing left to decide
@@ -391,7 +390,7 @@ int saver_verify_decryption_batch(vsp_ctx *ctx, const vsp_saver_decryptor *dec, 
         VSP_TRY(ctx->dec_timer.mark(ctx, 1, st));
         VSP_TRY(decrypt_values(ctx, dec, c, n + 1));
         VSP_TRY(ctx->dec_timer.mark(ctx, 2, st));
-        hipLaunchKernelGGL(k_dec_power, dim3(blocks, (unsigned)n), dim3(DLOG_BLOCK_LANES), 0, st, (const Fp12 *)ctx->pair_gt.p, (const Fp12 *)dec->d_base,
+        hipLaunchKernelGGL(k_dec_power, dim3(blocks, (unsigned)n), dim3(DLOG_BLOCK_LANES), 0, st, (const Fp12 *)ctx->pair_gt.p, dec->d_base.as<const Fp12>(),
                            (const uint64_t *)d_msgs, c, n, (const uint8_t *)status, power_ok);
         VSP_LAUNCH_CHECK();
         VSP_TRY(ctx->dec_timer.mark(ctx, 3, st));

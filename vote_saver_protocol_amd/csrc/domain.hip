@@ -214,7 +214,6 @@ int fr_from_mont_device(vsp_ctx *ctx, Fr *a, size_t n) {
     VSP_LAUNCH_CHECK();
     return VSP_OK;
 }
-void domain_release(vsp_domain *d) { if (d->zinv.p) hipFree(d->zinv.p); d->zinv.p = nullptr; d->zinv.cap = 0; }
 
 HFr domain_vanishing(const vsp_domain *d, const HFr &t) {
     HFr a = sub(h_pow(t, d->big_m), HFr::one());
@@ -275,9 +274,9 @@ int domain_divide_by_z_device(vsp_ctx *ctx, const vsp_domain *d, Fr *p) {
 // u[j] = L_j(t), Montgomery form, device
 int domain_lagrange_device(vsp_ctx *ctx, const vsp_domain *d, const HFr &t, Fr *u) {
     hipStream_t st = ctx->stream;
-    DevBuf lo, hi, pre, kbuf;
-    auto done = [&](int rc) { hipStreamSynchronize(st); DevBuf *all[] = {&lo, &hi, &pre, &kbuf}; for (DevBuf *b : all) if (b->p) hipFree(b->p); return rc; };
-    if (ensure(ctx, pre, d->m * sizeof(Fr)) != VSP_OK || ensure(ctx, kbuf, 2 * sizeof(LagConsts)) != VSP_OK) return done(VSP_ERR_NOMEM);
+    DevBuf lo, hi, pre, kbuf;                 // every return below is behind the wait for the kernels that read them
+    VSP_TRY(ensure(ctx, pre, d->m * sizeof(Fr)));
+    VSP_TRY(ensure(ctx, kbuf, 2 * sizeof(LagConsts)));
     const bool in_domain = is_zero(domain_vanishing(d, t));
     // the radix-2 subgroups to evaluate: (size, generator, point x, coefficient, offset, stride/shift of the extra denominators)
     struct Part { size_t n; HFr w, x, coef, shift, mult; size_t stride, off; } parts[2];
@@ -297,12 +296,11 @@ int domain_lagrange_device(vsp_ctx *ctx, const vsp_domain *d, const HFr &t, Fr *
     for (int k = 0; k < np; k++) {
         const Part &p = parts[k];
         const size_t hi_count = p.n > ((size_t)1 << PW_LOG) ? (p.n >> PW_LOG) : 1;
-        int rc = upload_power_tables(ctx, p.w, hi_count, lo, hi);
-        if (rc != VSP_OK) return done(rc);
+        VSP_TRY(upload_power_tables(ctx, p.w, hi_count, lo, hi));
         LagConsts kc; kc.x = to_dev(in_domain ? t : p.x); kc.coef = to_dev(in_domain ? p.mult : p.coef); kc.shift = to_dev(p.shift);
         LagConsts *kd = (LagConsts *)kbuf.p + k;
         if (hipMemcpyAsync(kd, &kc, sizeof kc, hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return done(set_error(ctx, VSP_ERR_HIP, "lagrange: constants upload failed"));
+            return set_error(ctx, VSP_ERR_HIP, "lagrange: constants upload failed");
         if (in_domain) {
             hipLaunchKernelGGL(k_lagrange_onehot, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, st, (const Fr *)lo.p, (const Fr *)hi.p, kd, p.n, u + p.off);
         } else {
@@ -310,10 +308,10 @@ int domain_lagrange_device(vsp_ctx *ctx, const vsp_domain *d, const HFr &t, Fr *
             hipLaunchKernelGGL(k_lagrange, dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, st, (const Fr *)lo.p, (const Fr *)hi.p, kd, p.n, p.stride,
                                (Fr *)pre.p + p.off, u + p.off);
         }
-        if (hipGetLastError() != hipSuccess) return done(set_error(ctx, VSP_ERR_HIP, "lagrange: kernel launch failed"));
-        if (hipStreamSynchronize(st) != hipSuccess) return done(set_error(ctx, VSP_ERR_HIP, "lagrange: kernel failed"));   // lo/hi are reused
+        if (hipGetLastError() != hipSuccess) return set_error(ctx, VSP_ERR_HIP, "lagrange: kernel launch failed");
+        if (hipStreamSynchronize(st) != hipSuccess) return set_error(ctx, VSP_ERR_HIP, "lagrange: kernel failed");   // lo/hi are reused
     }
-    return done(VSP_OK);
+    return VSP_OK;
 }
 
 // r1cs_to_qap::witness_map of one witness as a sequence: 6 transforms, the pointwise kernel, the last transform

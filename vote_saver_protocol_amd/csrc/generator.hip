@@ -57,8 +57,9 @@ __global__ __launch_bounds__(256) void k_affine_from_mont_g2(const G2Affine *in,
     G2Affine p = in[i]; p.x = from_mont(p.x); p.y = from_mont(p.y); out[i] = p;
 }
 
-// the generator's scratch holds functions of the toxic waste (powers of t, exponent vectors): zeroed before it goes back to the allocator
-static void free_dev(DevBuf &b) { if (b.p) { hipMemset(b.p, 0, b.cap); hipFree(b.p); } b.p = nullptr; b.cap = 0; }
+// the generator's scratch holds functions of the toxic waste (powers of t, exponent vectors): zeroed before it goes back to the allocator.
+// Explicitly, on every way out of the generator: a DevBuf's destructor frees and does not zero
+static void wipe(DevBuf &b) { if (b.p) hipMemset(b.p, 0, b.cap); b.reset(); }
 }  // anonymous namespace
 }  // namespace vsp
 
@@ -90,10 +91,10 @@ vsp_keypair *vsp_groth16_generate(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64
 
     DevBuf t_lo, t_hi, u, At, Bt, Ct, A_sc, B_sc, H_sc, L_sc, ABC_sc, pts, kbuf;
     vsp_keypair *kp = new vsp_keypair();
+    auto wipe_scratch = [&]() { for (DevBuf *b : {&t_lo, &t_hi, &u, &At, &Bt, &Ct, &A_sc, &B_sc, &H_sc, &L_sc, &ABC_sc, &pts, &kbuf}) wipe(*b); };
     auto fail = [&](const char *msg) -> vsp_keypair * {
         if (msg) set_error(ctx, VSP_ERR_HIP, msg);
-        DevBuf *all[] = {&t_lo, &t_hi, &u, &At, &Bt, &Ct, &A_sc, &B_sc, &H_sc, &L_sc, &ABC_sc, &pts, &kbuf};
-        for (DevBuf *b : all) free_dev(*b);
+        wipe_scratch();
         vsp_keypair_free(ctx, kp);
         return nullptr;
     };
@@ -110,7 +111,7 @@ vsp_keypair *vsp_groth16_generate(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64
     const unsigned cblk = (unsigned)((ncols + 255) / 256);
     Fr *Xt[3] = {(Fr *)At.p, (Fr *)Bt.p, (Fr *)Ct.p};
     for (int mm = 0; mm < 3; mm++)
-        hipLaunchKernelGGL(k_qap_columns, dim3(cblk), dim3(256), 0, st, (const uint32_t *)cs->cp[mm], (const uint32_t *)cs->ri[mm], (const Fr *)cs->cot[mm],
+        hipLaunchKernelGGL(k_qap_columns, dim3(cblk), dim3(256), 0, st, cs->cp[mm].as<const uint32_t>(), cs->ri[mm].as<const uint32_t>(), cs->cot[mm].as<const Fr>(),
                            (const Fr *)u.p, ncols, nc, ni, mm == 0 ? 1 : 0, Xt[mm]);
     hipLaunchKernelGGL(k_key_exponents, dim3(cblk), dim3(256), 0, st, (const Fr *)At.p, (const Fr *)Bt.p, (const Fr *)Ct.p, kd, ncols, ni,
                        (Fr *)A_sc.p, (Fr *)B_sc.p, (Fr *)L_sc.p, (Fr *)ABC_sc.p);
@@ -141,8 +142,7 @@ vsp_keypair *vsp_groth16_generate(vsp_ctx *ctx, const vsp_r1cs *cs, const uint64
     mul2(toxic + 8, kp->beta_g2); mul2(toxic + 16, kp->delta_g2); mul2(toxic + 12, kp->gamma_g2); mul1(toxic + 12, kp->gamma_g1);
     kp->pk = vsp_pk_create(ctx, kp->alpha_g1, kp->beta_g1, kp->beta_g2, kp->delta_g1, kp->delta_g2, kp->q[0], kp->q[1], kp->q[2], kp->q[3], kp->q[4]);
     if (!kp->pk || hipStreamSynchronize(st) != hipSuccess) return fail("generate: failed");
-    DevBuf *all[] = {&t_lo, &t_hi, &u, &At, &Bt, &Ct, &A_sc, &B_sc, &H_sc, &L_sc, &ABC_sc, &pts, &kbuf};
-    for (DevBuf *b : all) free_dev(*b);
+    wipe_scratch();
     return kp;
 }
 
@@ -174,11 +174,10 @@ int vsp_keypair_export(vsp_ctx *ctx, const vsp_keypair *kp, int which, uint64_t 
     DevBuf tmp;
     VSP_TRY(ensure(ctx, tmp, b->n * esz));
     unsigned blk = (unsigned)((b->n + 255) / 256);
-    if (b->group == 1) hipLaunchKernelGGL(k_affine_from_mont_g1, dim3(blk), dim3(256), 0, ctx->stream, (const G1Affine *)b->d, (G1Affine *)tmp.p, b->n);
-    else hipLaunchKernelGGL(k_affine_from_mont_g2, dim3(blk), dim3(256), 0, ctx->stream, (const G2Affine *)b->d, (G2Affine *)tmp.p, b->n);
+    if (b->group == 1) hipLaunchKernelGGL(k_affine_from_mont_g1, dim3(blk), dim3(256), 0, ctx->stream, b->d.as<const G1Affine>(), tmp.as<G1Affine>(), b->n);
+    else hipLaunchKernelGGL(k_affine_from_mont_g2, dim3(blk), dim3(256), 0, ctx->stream, b->d.as<const G2Affine>(), tmp.as<G2Affine>(), b->n);
     hipError_t e = hipMemcpyAsync(out, tmp.p, b->n * esz, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    hipFree(tmp.p);
     if (e != hipSuccess) return set_error(ctx, VSP_ERR_HIP, "keypair_export: copy failed");
     return VSP_OK;
 }

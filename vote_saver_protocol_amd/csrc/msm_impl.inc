@@ -987,7 +987,7 @@ template <class F> static int msm_geometry(vsp_ctx *ctx, MsmWork &wk, MsmLaunch 
         if ((g.single != 0) != (pre != nullptr) || (pre && (g.idx_stride != pre->stride * imul || g.idx_first != pre->first * imul || g.c != pre->c)))
             return set_error(ctx, VSP_ERR_ARG, "msm: shared plan needs bases precomputed alike");
     } else {
-        VSP_TRY(ensure_w(ctx, L.st, wk.counters, 64));
+        VSP_TRY(ensure(ctx, wk.counters, 64, L.st));
         // effective problem size: scalars other than 0 and 1 (one small kernel + a read-back); the census may have been queued
         // earlier by msm_census (the prover queues all of them before any heavy kernel).  The same kernel flags scalars >= r.
         // The count only steers the window size / part length, never the result, so a slot that has seen a vector of this
@@ -1000,7 +1000,7 @@ template <class F> static int msm_geometry(vsp_ctx *ctx, MsmWork &wk, MsmLaunch 
                 if (wk.neff_cache_n == n && !opt(ctx, "msm_census_sync", 0)) n_eff = wk.neff_cache;
                 else {
                     VSP_HIP(hipEventSynchronize(wk.census_done));
-                    uint32_t h_cnt = *(volatile uint32_t *)wk.h_census / batch;      // (a batch is counted together: the mean per vector)
+                    uint32_t h_cnt = *wk.h_census.template as<volatile uint32_t>() / batch;      // (a batch is counted together: the mean per vector)
                     n_eff = h_cnt < 256 ? 256 : h_cnt;
                 }
             }
@@ -1065,26 +1065,24 @@ template <class F> static int msm_buffers(vsp_ctx *ctx, MsmWork &wk, MsmLaunch &
     L.Smax = g.G + L.M / g.T + 1;
     L.per_w = dims_per_w(g);
     { const size_t need = (size_t)g.Wr * DIMBITS_STRIDE * sizeof(XYZZ<F>);      // room for either layout of the window results
-      if (need > wk.pinned_cap) {                                                // (a batch: K times the windows; the slot is idle here, nothing writes the old buffer)
+      if (need > wk.h_pinned.cap) {                                              // (a batch: K times the windows; the slot is idle here, nothing writes the old buffer)
           if (need > ((size_t)64 << 20)) return set_error(ctx, VSP_ERR_UNSUPPORTED, "msm: too many windows (a batch: fewer vectors per call)");
           VSP_HIP(hipStreamSynchronize(st));
-          void *nb = nullptr;
-          if (hipHostMalloc(&nb, need, hipHostMallocDefault) != hipSuccess) return set_error(ctx, VSP_ERR_NOMEM, "msm: pinned buffer for the window results");
-          hipHostFree(wk.h_pinned); wk.h_pinned = nb; wk.pinned_cap = need;
+          VSP_TRY(ensure_pinned(ctx, wk.h_pinned, need));
       } }
-    VSP_TRY(ensure_w(ctx, st, wk.buckets, g.G * sizeof(XYZZ<F>)));
-    VSP_TRY(ensure_w(ctx, st, wk.partials, L.Smax * sizeof(XYZZ<F>)));
-    VSP_TRY(ensure_w(ctx, st, wk.dims, (size_t)g.Wr * L.per_w * sizeof(XYZZ<F>)));
-    VSP_TRY(ensure_w(ctx, st, wk.winres, (size_t)g.Wr * DIMBITS_STRIDE * sizeof(XYZZ<F>)));      // room for either layout (4 or 25 records per window)
+    VSP_TRY(ensure(ctx, wk.buckets, g.G * sizeof(XYZZ<F>), st));
+    VSP_TRY(ensure(ctx, wk.partials, L.Smax * sizeof(XYZZ<F>), st));
+    VSP_TRY(ensure(ctx, wk.dims, (size_t)g.Wr * L.per_w * sizeof(XYZZ<F>), st));
+    VSP_TRY(ensure(ctx, wk.winres, (size_t)g.Wr * DIMBITS_STRIDE * sizeof(XYZZ<F>), st));      // room for either layout (4 or 25 records per window)
     L.nblk = (unsigned)((L.n + MSM_THREADS - 1) / MSM_THREADS);
     L.gblk = (unsigned)((g.G + MSM_THREADS - 1) / MSM_THREADS);
     L.ablk = (unsigned)((L.Smax + MSM_THREADS - 1) / MSM_THREADS);
     if (L.plan_from) return VSP_OK;
-    for (DevBuf *b : {&wk.cnt, &wk.off, &wk.cursor, &wk.nsub, &wk.suboff, &wk.heavy, &wk.medium}) VSP_TRY(ensure_w(ctx, st, *b, (g.G + 1) * 4));
-    VSP_TRY(ensure_w(ctx, st, wk.sorted, L.M * 4));
-    VSP_TRY(ensure_w(ctx, st, wk.partbucket, L.Smax * 4));
-    VSP_TRY(ensure_w(ctx, st, wk.perm, L.Smax * 4));
-    VSP_TRY(ensure_w(ctx, st, wk.sizehist, 2 * SZ_BINS * 4));
+    for (DevBuf *b : {&wk.cnt, &wk.off, &wk.cursor, &wk.nsub, &wk.suboff, &wk.heavy, &wk.medium}) VSP_TRY(ensure(ctx, *b, (g.G + 1) * 4, st));
+    VSP_TRY(ensure(ctx, wk.sorted, L.M * 4, st));
+    VSP_TRY(ensure(ctx, wk.partbucket, L.Smax * 4, st));
+    VSP_TRY(ensure(ctx, wk.perm, L.Smax * 4, st));
+    VSP_TRY(ensure(ctx, wk.sizehist, 2 * SZ_BINS * 4, st));
     return VSP_OK;
 }
 
@@ -1106,14 +1104,14 @@ template <class F> static int msm_accumulate(vsp_ctx *ctx, MsmWork &wk, const Ms
 #endif
     if constexpr (have28) if (L.table28) {
         // 14 x 28-bit accumulation; bucket parts that meet an equal-x pair are listed and redone by the generic kernel
-        VSP_TRY(ensure_w(ctx, st, wk.redo, (L.Smax + 1) * sizeof(uint32_t)));
+        VSP_TRY(ensure(ctx, wk.redo, (L.Smax + 1) * sizeof(uint32_t), st));
         uint32_t *redo = (uint32_t *)wk.redo.p;               // [0] = count, list from [1]
         if (L.plan_from) VSP_HIP(hipMemsetAsync(redo, 0, sizeof(uint32_t), st));      // (k_plan cleared it when it ran in this launch)
         // the bucket sums stay in the 28-bit form from here to the results per window; the parts the generic kernel redoes (equal-x
         // pairs) are written to the 12 x 32-bit arrays of the same indexing and, converted, to the 28-bit ones
-        VSP_TRY(ensure_w(ctx, st, wk.buckets28, g.G * sizeof(XYZZ<F28>)));
-        VSP_TRY(ensure_w(ctx, st, wk.partials28, L.Smax * sizeof(XYZZ<F28>)));
-        VSP_TRY(ensure_w(ctx, st, wk.dims, (size_t)g.Wr * L.per_w * sizeof(XYZZ<F28>)));
+        VSP_TRY(ensure(ctx, wk.buckets28, g.G * sizeof(XYZZ<F28>), st));
+        VSP_TRY(ensure(ctx, wk.partials28, L.Smax * sizeof(XYZZ<F28>), st));
+        VSP_TRY(ensure(ctx, wk.dims, (size_t)g.Wr * L.per_w * sizeof(XYZZ<F28>), st));
         XYZZ<F28> *buckets28 = (XYZZ<F28> *)wk.buckets28.p, *partials28 = (XYZZ<F28> *)wk.partials28.p;
         VSP_HIP(hipEventRecord(wk.ev0, st));                  // ev0 .. ev1 bracket the accumulation kernel alone
 #if VSP_MSM_GROUP == 1
@@ -1135,7 +1133,7 @@ template <class F> static int msm_accumulate(vsp_ctx *ctx, MsmWork &wk, const Ms
                            (const uint32_t *)pl->off.p, (const uint32_t *)pl->suboff.p, (const uint32_t *)pl->partbucket.p, buckets, partials,
                            (const uint32_t *)(redo + 1), (const uint32_t *)redo, L.rq.glv, buckets28, partials28);
         VSP_LAUNCH_CHECK();
-        return launch_tail<F28>(ctx, st, pl, g, L.dimbits, buckets28, partials28, (XYZZ<F28> *)wk.dims.p, winres, (XYZZ<F> *)wk.h_pinned);
+        return launch_tail<F28>(ctx, st, pl, g, L.dimbits, buckets28, partials28, (XYZZ<F28> *)wk.dims.p, winres, wk.h_pinned.template as<XYZZ<F>>());
     }
     VSP_HIP(hipEventRecord(wk.ev0, st));
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_accum<F>), dim3(L.ablk * LaneView<F>::LANES), dim3(MSM_THREADS), 0, st, bases, (const uint32_t *)pl->sorted.p,
@@ -1143,7 +1141,7 @@ template <class F> static int msm_accumulate(vsp_ctx *ctx, MsmWork &wk, const Ms
                        g.G, g.T, buckets, partials);
     VSP_HIP(hipEventRecord(wk.ev1, st));
     VSP_LAUNCH_CHECK();
-    return launch_tail<F>(ctx, st, pl, g, L.dimbits, buckets, partials, (XYZZ<F> *)wk.dims.p, winres, (XYZZ<F> *)wk.h_pinned);
+    return launch_tail<F>(ctx, st, pl, g, L.dimbits, buckets, partials, (XYZZ<F> *)wk.dims.p, winres, wk.h_pinned.template as<XYZZ<F>>());
 }
 
 // one multi-exponentiation (common.h MsmRequest); plan_from: the work slot rq.plan_from names, or null
@@ -1212,7 +1210,7 @@ static int msm_finish_wait(vsp_ctx *ctx, MsmWork &wk, unsigned out_count, bool *
     // experiment builds only (tools/dimsum_prefetch_probe.py): the bucket sums and the digit sums of the multi-exponentiation just finished,
     // generic 12 x 32-bit form ("msm_fp28" = 0), for an off-line comparison against big-integer sums
     if (const char *dir = getenv("VSP_DEBUG_DUMP_DIR")) {
-        if (FILE *f = fopen((std::string(dir) + "/winres.bin").c_str(), "wb")) { fwrite(wk.h_pinned, 1, (size_t)g.Wr * (wk.dimbits ? DIMBITS_STRIDE : 4) * sizeof(XYZZ<HF>), f); fclose(f); }
+        if (FILE *f = fopen((std::string(dir) + "/winres.bin").c_str(), "wb")) { fwrite(wk.h_pinned.p, 1, (size_t)g.Wr * (wk.dimbits ? DIMBITS_STRIDE : 4) * sizeof(XYZZ<HF>), f); fclose(f); }
         const unsigned per_w = dims_per_w(g);
         std::vector<char> hb(g.G * sizeof(XYZZ<F>)), hd((size_t)g.Wr * per_w * sizeof(XYZZ<F>));
         if (wk.buckets.p && wk.dims.p && hipMemcpy(hb.data(), wk.buckets.p, hb.size(), hipMemcpyDeviceToHost) == hipSuccess &&
@@ -1229,7 +1227,7 @@ static int msm_finish_wait(vsp_ctx *ctx, MsmWork &wk, unsigned out_count, bool *
         // length, refuse the result when a scalar was not canonical
         wk.check_pending = false;
         VSP_HIP(hipEventSynchronize(wk.census_done));
-        const volatile uint32_t *hc = (const volatile uint32_t *)wk.h_census;
+        const volatile uint32_t *hc = wk.h_census.template as<const volatile uint32_t>();
         if (wk.n >= 4096) { const uint32_t c0 = hc[0] / (wk.g.K ? wk.g.K : 1u); wk.neff_cache_n = wk.n; wk.neff_cache = c0 < 256 ? 256 : c0; }
         if (hc[2]) return set_error(ctx, VSP_ERR_ARG, "msm: a scalar is not canonical (>= r)");
     }
@@ -1257,7 +1255,7 @@ static int msm_finish_wait(vsp_ctx *ctx, MsmWork &wk, unsigned out_count, bool *
 }
 template <class F, class HF> static void msm_fold(const MsmWork &wk, XYZZ<HF> *out) {
     const MsmGeom &g = wk.g;
-    const XYZZ<HF> *wr = (const XYZZ<HF> *)wk.h_pinned;
+    const XYZZ<HF> *wr = wk.h_pinned.template as<const XYZZ<HF>>();
     // Horner over bit positions: window w contributes D2 at c*w + q1 + q0, D1 at c*w + q0, D0 + Tot at c*w.  A batch: one chain per vector over
     // its own windows [k Wk, (k + 1) Wk) (one bucket set per window), or over its one bucket set in the shared-set mode
     const unsigned per = g.single ? 1u : (g.K > 1 ? g.Wk : g.Wr);      // window results per vector (shared-set mode: its one bucket set)
@@ -1307,21 +1305,17 @@ template <class G> int msm_precompute(vsp_ctx *ctx, typename G::Point *table, si
     const unsigned W = 255 / c + 1;
     hipStream_t st = ctx->stream;
     DevBuf tmp, pre;
-    VSP_TRY(ensure_w(ctx, st, tmp, n * sizeof(XYZZ<F>)));
-    int rc = ensure_w(ctx, st, pre, n * sizeof(F));
-    if (rc == VSP_OK) {
-        const unsigned blk = (unsigned)((n + MSM_THREADS - 1) / MSM_THREADS);
-        const size_t chunks = (n + PRE_CHUNK - 1) / PRE_CHUNK;
-        for (unsigned w = 1; w < W; w++) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_shift_window<F>), dim3(blk * LaneView<F>::LANES), dim3(MSM_THREADS), 0, st, (const Affine<F> *)(table + (size_t)(w - 1) * n), n, c, (XYZZ<F> *)tmp.p);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_batch_affine_mont<F>), dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, st, (const XYZZ<F> *)tmp.p, n, (F *)pre.p,
-                               table + (size_t)w * n);
-        }
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = set_error(ctx, VSP_ERR_HIP, "precompute: kernel failed");
+    VSP_TRY(ensure(ctx, tmp, n * sizeof(XYZZ<F>), st));
+    VSP_TRY(ensure(ctx, pre, n * sizeof(F), st));
+    const unsigned blk = (unsigned)((n + MSM_THREADS - 1) / MSM_THREADS);
+    const size_t chunks = (n + PRE_CHUNK - 1) / PRE_CHUNK;
+    for (unsigned w = 1; w < W; w++) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_shift_window<F>), dim3(blk * LaneView<F>::LANES), dim3(MSM_THREADS), 0, st, (const Affine<F> *)(table + (size_t)(w - 1) * n), n, c, (XYZZ<F> *)tmp.p);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_batch_affine_mont<F>), dim3((unsigned)((chunks + 63) / 64)), dim3(64), 0, st, (const XYZZ<F> *)tmp.p, n, (F *)pre.p,
+                           table + (size_t)w * n);
     }
-    if (tmp.p) hipFree(tmp.p);
-    if (pre.p) hipFree(pre.p);
-    return rc;
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return set_error(ctx, VSP_ERR_HIP, "precompute: kernel failed");
+    return VSP_OK;                                          // behind the wait: tmp and pre go here
 }
 
 template <class G> int msm_table28(vsp_ctx *ctx, const typename G::Point *table, size_t count, void *d_out, bool glv) {

@@ -928,20 +928,9 @@ __global__ __launch_bounds__(256) void k_partsort(const uint32_t *cnt, const uin
 
 // ------------------------------------------------------------------------------------------------
 // Host side: the stages of msm_launch (msm_impl.inc) that launch the kernels above, declared in common.h, and the work slots.
-int ensure_w(vsp_ctx *ctx, hipStream_t st, DevBuf &b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.cap >= bytes && b.p) return VSP_OK;
-    if (b.p) { VSP_HIP(hipStreamSynchronize(st)); hipFree(b.p); b.p = nullptr; b.cap = 0; }
-    size_t want = bytes + bytes / 8;
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) { b.p = nullptr; return set_error(ctx, VSP_ERR_NOMEM, "msm: hipMalloc failed"); }
-    b.cap = want;
-    return VSP_OK;
-}
-
 static int exclusive_scan_w(vsp_ctx *ctx, MsmWork &wk, const uint32_t *in, size_t n, uint32_t *out, uint32_t *out2) {
     size_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-    VSP_TRY(ensure_w(ctx, wk.stream, wk.blocksum, (nb + 1) * sizeof(uint32_t)));
+    VSP_TRY(ensure(ctx, wk.blocksum, (nb + 1) * sizeof(uint32_t), wk.stream));
     uint32_t *bs = (uint32_t *)wk.blocksum.p;
     hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(MSM_THREADS), 0, wk.stream, in, n, bs);
     hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(MSM_THREADS), 0, wk.stream, bs, nb);
@@ -955,9 +944,7 @@ int work_init(vsp_ctx *ctx, MsmWork &wk, hipStream_t stream_or_null) {
         VSP_HIP(hipEventCreate(&wk.ev0)); VSP_HIP(hipEventCreate(&wk.ev1));
         VSP_HIP(hipEventCreateWithFlags(&wk.done, hipEventDisableTiming));
         VSP_HIP(hipEventCreateWithFlags(&wk.plan_ready, hipEventDisableTiming));
-        VSP_HIP(hipHostMalloc(&wk.h_pinned, MsmWork::PINNED_BYTES, hipHostMallocDefault)); wk.pinned_cap = MsmWork::PINNED_BYTES;
-        VSP_HIP(hipHostMalloc(&wk.h_census, 64, hipHostMallocDefault));
-        VSP_HIP(hipHostMalloc(&wk.h_rec, MsmWork::REC_RING * 288, hipHostMallocDefault));
+        VSP_HIP(wk.h_pinned.alloc(MsmWork::PINNED_BYTES)); VSP_HIP(wk.h_census.alloc(64)); VSP_HIP(wk.h_rec.alloc(MsmWork::REC_RING * 288));
         for (unsigned k = 0; k < MsmWork::REC_RING; k++) VSP_HIP(hipEventCreateWithFlags(&wk.rec_ev[k], hipEventDisableTiming));
         VSP_HIP(hipEventCreateWithFlags(&wk.census_done, hipEventDisableTiming));
         wk.inited = true;
@@ -973,11 +960,11 @@ int work_init(vsp_ctx *ctx, MsmWork &wk, hipStream_t stream_or_null) {
 // queue the 0/1 census of a scalar vector on the slot's stream (result read by the next msm_launch of the same vector)
 int msm_census(vsp_ctx *ctx, MsmWork &wk, const Fr *d_scalars, size_t n, hipStream_t on_stream, unsigned batch, size_t batch_stride) {
     hipStream_t st = on_stream ? on_stream : wk.stream;
-    VSP_TRY(ensure_w(ctx, st, wk.counters, 64));
+    VSP_TRY(ensure(ctx, wk.counters, 64, st));
     VSP_HIP(hipMemsetAsync(wk.counters.p, 0, 64, st));
     { unsigned cb = (unsigned)((n + 255) / 256); if (cb > 1024) cb = 1024;
       hipLaunchKernelGGL(k_classify, dim3(cb, batch), dim3(256), 0, st, d_scalars, n, (uint32_t *)wk.counters.p, batch_stride); }
-    VSP_HIP(hipMemcpyAsync(wk.h_census, (uint32_t *)wk.counters.p + 1, 12, hipMemcpyDeviceToHost, st));      // [0] count, [2] non-canonical flag
+    VSP_HIP(hipMemcpyAsync(wk.h_census.p, (uint32_t *)wk.counters.p + 1, 12, hipMemcpyDeviceToHost, st));      // [0] count, [2] non-canonical flag
     VSP_HIP(hipEventRecord(wk.census_done, st));
     wk.census_pending = true; wk.census_n = n; wk.census_scalars = (const void *)d_scalars;
     return VSP_OK;
@@ -989,7 +976,7 @@ int msm_split_scalars(vsp_ctx *ctx, MsmWork &wk, MsmLaunch &L, const MsmGeom &g)
     L.fused_split = L.rq.glv && !L.plan_from && g.c <= 16 && ((opt(ctx, "msm_fused_split", 1) && 2 * n >= ((size_t)1 << 15) && L.sort_mode != 2) || g.K > 1);
     if (!L.rq.glv) return VSP_OK;
     if (!L.plan_from && !L.fused_split) {
-        VSP_TRY(ensure_w(ctx, L.st, wk.glv_scalars, 2 * n * sizeof(Fr)));
+        VSP_TRY(ensure(ctx, wk.glv_scalars, 2 * n * sizeof(Fr), L.st));
         hipLaunchKernelGGL(k_glv_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, L.st, L.rq.scalars, n, (Fr *)wk.glv_scalars.p);
         VSP_LAUNCH_CHECK();
         L.scalars = (const Fr *)wk.glv_scalars.p;
@@ -1030,12 +1017,12 @@ static int msm_sort_staged(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const 
     const unsigned chunks = (unsigned)((npp + MS_CHUNK - 1) / MS_CHUNK);
     const size_t H1 = (size_t)parents * 257 * chunks, S1 = (size_t)parents * 256, H2 = S1 * nb2;
     const size_t P2 = (M + MS_CHUNK - 1) / MS_CHUNK + S1;      // pieces of the second pass: at most one partial piece per segment
-    VSP_TRY(ensure_w(ctx, st, wk.pairs_a, M * sizeof(uint2)));
-    VSP_TRY(ensure_w(ctx, st, wk.pairs_b, M * sizeof(uint2)));
-    VSP_TRY(ensure_w(ctx, st, wk.ms_h1, (H1 + 1) * 4)); VSP_TRY(ensure_w(ctx, st, wk.ms_h1s, (H1 + 1) * 4));
+    VSP_TRY(ensure(ctx, wk.pairs_a, M * sizeof(uint2), st));
+    VSP_TRY(ensure(ctx, wk.pairs_b, M * sizeof(uint2), st));
+    VSP_TRY(ensure(ctx, wk.ms_h1, (H1 + 1) * 4, st)); VSP_TRY(ensure(ctx, wk.ms_h1s, (H1 + 1) * 4, st));
     const size_t P3 = (M + MS_CHUNK - 1) / MS_CHUNK + M / MS_SEG_LONG + 1;      // pieces of the third: only segments longer than MS_SEG_LONG have any
     // ms_h2: the second pass's piece histograms | the third's | piece counts | pbase2 | pbase3
-    VSP_TRY(ensure_w(ctx, st, wk.ms_h2, (P2 * 256 + P3 * 64 + (H2 + 1) + (S1 + 1) + (H2 + 1)) * 4)); VSP_TRY(ensure_w(ctx, st, wk.ms_h2s, (H2 + 1) * 4));
+    VSP_TRY(ensure(ctx, wk.ms_h2, (P2 * 256 + P3 * 64 + (H2 + 1) + (S1 + 1) + (H2 + 1)) * 4, st)); VSP_TRY(ensure(ctx, wk.ms_h2s, (H2 + 1) * 4, st));
     uint2 *pa = (uint2 *)wk.pairs_a.p, *pb = (uint2 *)wk.pairs_b.p;
     uint32_t *h1 = (uint32_t *)wk.ms_h1.p, *h1s = (uint32_t *)wk.ms_h1s.p, *h2 = (uint32_t *)wk.ms_h2.p, *h2s = (uint32_t *)wk.ms_h2s.p;
     uint32_t *h3 = h2 + P2 * 256, *pcount = h3 + P3 * 64, *pbase2 = pcount + (H2 + 1), *pbase3 = pbase2 + (S1 + 1);
@@ -1072,12 +1059,12 @@ static int msm_sort_wide(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const Ms
     MsmGeom gh = g; gh.c = 16; gh.B = 1u << 15; gh.lb = 0; gh.G = (size_t)g.Wr << 15;
     const unsigned nchunks = lds_chunks(g, n);
     const size_t chunk_len = (n + nchunks - 1) / nchunks;
-    VSP_TRY(ensure_w(ctx, st, wk.digits, (size_t)g.W * n * 3));
-    VSP_TRY(ensure_w(ctx, st, wk.blockhist, (size_t)nchunks * g.W * gh.B * sizeof(uint32_t)));
-    VSP_TRY(ensure_w(ctx, st, wk.cnt_hi, (gh.G + 1) * 4));
-    VSP_TRY(ensure_w(ctx, st, wk.off_hi, (gh.G + 1) * 4));
-    VSP_TRY(ensure_w(ctx, st, wk.tmp_sorted, L.M * 4));
-    VSP_TRY(ensure_w(ctx, st, wk.tmp_lo, L.M));
+    VSP_TRY(ensure(ctx, wk.digits, (size_t)g.W * n * 3, st));
+    VSP_TRY(ensure(ctx, wk.blockhist, (size_t)nchunks * g.W * gh.B * sizeof(uint32_t), st));
+    VSP_TRY(ensure(ctx, wk.cnt_hi, (gh.G + 1) * 4, st));
+    VSP_TRY(ensure(ctx, wk.off_hi, (gh.G + 1) * 4, st));
+    VSP_TRY(ensure(ctx, wk.tmp_sorted, L.M * 4, st));
+    VSP_TRY(ensure(ctx, wk.tmp_lo, L.M, st));
     uint16_t *hi = (uint16_t *)wk.digits.p; uint8_t *lo = (uint8_t *)(hi + (size_t)g.W * n);
     uint32_t *blockhist = (uint32_t *)wk.blockhist.p, *cnt_hi = (uint32_t *)wk.cnt_hi.p, *off_hi = (uint32_t *)wk.off_hi.p;
     const size_t lds_bytes = (size_t)gh.B * sizeof(uint32_t);
@@ -1103,8 +1090,8 @@ static int msm_sort_lds(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const Msm
     const bool batch_single = g.single && g.K > 1;          // K bucket sets, each fed by its vector's Wk windows: their histograms must lie together
     const unsigned nchunks = batch_single ? 1u : lds_chunks(g, n);
     const size_t chunk_len = (n + nchunks - 1) / nchunks;
-    VSP_TRY(ensure_w(ctx, st, wk.digits, (size_t)g.W * n * sizeof(uint16_t) + (size_t)g.K * n));      // + one sign byte per scalar (endomorphism split), per vector of a batch
-    VSP_TRY(ensure_w(ctx, st, wk.blockhist, (size_t)nchunks * g.W * g.B * sizeof(uint32_t)));
+    VSP_TRY(ensure(ctx, wk.digits, (size_t)g.W * n * sizeof(uint16_t) + (size_t)g.K * n, st));      // + one sign byte per scalar (endomorphism split), per vector of a batch
+    VSP_TRY(ensure(ctx, wk.blockhist, (size_t)nchunks * g.W * g.B * sizeof(uint32_t), st));
     uint16_t *digits = (uint16_t *)wk.digits.p; uint32_t *blockhist = (uint32_t *)wk.blockhist.p;
     uint8_t *flips = (uint8_t *)(digits + (size_t)g.W * n);
     const size_t lds_bytes = (size_t)g.B * sizeof(uint32_t);
@@ -1112,7 +1099,7 @@ static int msm_sort_lds(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const Msm
     if (L.fused_split) hipLaunchKernelGGL(k_glv_digits, dim3((unsigned)((L.rq.n + MSM_THREADS - 1) / MSM_THREADS), g.K), dim3(MSM_THREADS), 0, st, L.rq.scalars, L.rq.n, g, digits, flips);
     else hipLaunchKernelGGL(k_digits, dim3(L.nblk, g.K), dim3(MSM_THREADS), 0, st, L.scalars, g, digits, flips);
     hipLaunchKernelGGL(k_count_lds, dim3(nchunks * g.W), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)digits, g, nchunks, chunk_len, blockhist);
-    VSP_TRY(ensure_w(ctx, st, wk.blocksum, ((size_t)L.gblk + 2) * sizeof(uint32_t)));      // (the three-kernel scan shares this buffer and may have regrown it)
+    VSP_TRY(ensure(ctx, wk.blocksum, ((size_t)L.gblk + 2) * sizeof(uint32_t), st));      // (the three-kernel scan shares this buffer and may have regrown it)
     uint32_t *tilesum = (uint32_t *)wk.blocksum.p;
     hipLaunchKernelGGL(k_chunk_prefix, dim3(L.gblk), dim3(MSM_THREADS), 0, st, blockhist, batch_single ? g.Wk : (g.single ? nchunks * g.W : nchunks), g.G, cnt,
                        L.fused_scans ? tilesum : (uint32_t *)nullptr, batch_single ? (size_t)g.B : g.G);
@@ -1152,11 +1139,11 @@ int msm_bucket_plan(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const MsmGeom
     const hipStream_t st = L.st;
     const uint32_t *cnt = (const uint32_t *)wk.cnt.p;
     uint32_t *nsub = (uint32_t *)wk.nsub.p, *suboff = (uint32_t *)wk.suboff.p;
-    VSP_TRY(ensure_w(ctx, st, wk.blocksum, ((size_t)L.gblk + 2) * sizeof(uint32_t)));
+    VSP_TRY(ensure(ctx, wk.blocksum, ((size_t)L.gblk + 2) * sizeof(uint32_t), st));
     uint32_t *tilesum = (uint32_t *)wk.blocksum.p;
     uint32_t *size_hist = (uint32_t *)wk.sizehist.p, *bin_cursor = size_hist + SZ_BINS;
     uint32_t *redo0 = nullptr;                              // the accumulation's hand-back counter, cleared by k_plan when this launch goes on to accumulate over its own plan
-    if (!L.rq.plan_only && L.table28) { VSP_TRY(ensure_w(ctx, st, wk.redo, (L.Smax + 1) * sizeof(uint32_t))); redo0 = (uint32_t *)wk.redo.p; }
+    if (!L.rq.plan_only && L.table28) { VSP_TRY(ensure(ctx, wk.redo, (L.Smax + 1) * sizeof(uint32_t), st)); redo0 = (uint32_t *)wk.redo.p; }
     hipLaunchKernelGGL(k_plan, dim3(L.gblk), dim3(MSM_THREADS), 0, st, cnt, g.G, g.T, nsub, (uint32_t *)wk.heavy.p, (uint32_t *)wk.medium.p, (uint32_t *)wk.counters.p,
                        L.fused_scans ? tilesum : (uint32_t *)nullptr, size_hist, 2u * SZ_BINS, redo0);
     VSP_LAUNCH_CHECK();
@@ -1213,20 +1200,16 @@ void msm_drain_slots(vsp_ctx *ctx) {
     hipStreamSynchronize(ctx->stream);
     hipGetLastError();
 }
+// the events and the own stream of every slot (its memory goes with the context)
 void msm_free_slots(vsp_ctx *ctx) {
     for (unsigned i = 0; i < VSP_MSM_SLOTS; i++) {
         MsmWork &w = ctx->msm_work[i];
-        DevBuf *bufs[] = {&w.cnt, &w.off, &w.cursor, &w.nsub, &w.suboff, &w.blocksum, &w.sorted, &w.heavy, &w.counters, &w.digits, &w.blockhist,
-                          &w.partbucket, &w.perm, &w.sizehist, &w.buckets, &w.partials, &w.dims, &w.winres, &w.medium, &w.redo, &w.glv_scalars, &w.buckets28, &w.partials28, &w.tmp_sorted, &w.tmp_lo, &w.off_hi, &w.cnt_hi, &w.pairs_a, &w.pairs_b, &w.ms_h1, &w.ms_h1s, &w.ms_h2, &w.ms_h2s};
-        for (DevBuf *b : bufs) { if (b->p) hipFree(b->p); b->p = nullptr; b->cap = 0; }
-        if (w.inited) {
-            hipEventDestroy(w.ev0); hipEventDestroy(w.ev1); hipEventDestroy(w.done); hipEventDestroy(w.plan_ready);
-            hipHostFree(w.h_pinned); hipHostFree(w.h_census); hipEventDestroy(w.census_done);
-            hipHostFree(w.h_rec); for (unsigned k = 0; k < MsmWork::REC_RING; k++) hipEventDestroy(w.rec_ev[k]);
-            if (w.own_stream && w.own) hipStreamDestroy(w.own);
-            w.own = nullptr; w.stream = nullptr; w.own_stream = false;
-            w.inited = false;
-        }
+        if (!w.inited) continue;
+        hipEventDestroy(w.ev0); hipEventDestroy(w.ev1); hipEventDestroy(w.done); hipEventDestroy(w.plan_ready); hipEventDestroy(w.census_done);
+        for (unsigned k = 0; k < MsmWork::REC_RING; k++) hipEventDestroy(w.rec_ev[k]);
+        if (w.own_stream && w.own) hipStreamDestroy(w.own);
+        w.own = nullptr; w.stream = nullptr; w.own_stream = false;
+        w.inited = false;
     }
 }
 

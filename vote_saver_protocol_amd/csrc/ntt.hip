@@ -391,7 +391,7 @@ int ntt_ensure_twiddles(vsp_ctx *ctx, unsigned log_m) {
     unsigned lg = log_m < 1 ? 1 : log_m;
     size_t count = (size_t)1 << (lg - 1);
     size_t hi_count = count > ((size_t)1 << PW_LOG) ? (count >> PW_LOG) : 1;
-    DevBuf lo, hi;
+    DevBuf lo, hi;                // gone at every return
     for (int dir = 0; dir < 2; dir++) {
         HFr w = host_omega(lg);
         if (dir) w = inv(w);
@@ -403,7 +403,6 @@ int ntt_ensure_twiddles(vsp_ctx *ctx, unsigned log_m) {
         VSP_LAUNCH_CHECK();
     }
     VSP_HIP(hipStreamSynchronize(ctx->stream));
-    hipFree(lo.p); hipFree(hi.p);
     t.log = lg;
     t.log29 = 0;                 // the 29-bit copies follow on demand (ntt29_ensure_tables)
     return VSP_OK;
@@ -481,9 +480,10 @@ static void ntt29_known_answer_check(vsp_ctx *ctx) {
     h[0] = h[1] = h[2] = h[3] = 0;                            // a zero and r - 1 among them
     h[4] = 0xffffffff00000000ULL; h[5] = 0x53bda402fffe5bfeULL; h[6] = 0x3339d80809a1d805ULL; h[7] = 0x73eda753299d7d48ULL;
     const uint64_t g7[4] = {7, 0, 0, 0};
-    void *d = nullptr;
+    DevBuf buf;
     bool ran = false, same = true;
-    if (hipMalloc(&d, bytes) == hipSuccess) {
+    if (buf.alloc(bytes) == hipSuccess) {
+        void *d = buf.p;
         ran = true;
         for (int inverse = 0; inverse < 2 && ran; inverse++) {
             for (int path = 0; path < 2 && ran; path++) {
@@ -497,7 +497,6 @@ static void ntt29_known_answer_check(vsp_ctx *ctx) {
             }
             if (ran && memcmp(o29.data(), o32.data(), bytes) != 0) same = false;
         }
-        hipFree(d);
     }
     hipGetLastError();
     if (!ran) { ctx->stats["ntt_fr29_selfcheck"] = 0.0; return; }

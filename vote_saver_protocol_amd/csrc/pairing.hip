@@ -373,9 +373,6 @@ int pairing_multi_batch(vsp_ctx *ctx, const uint64_t *g1, const uint64_t *g2, si
 void pairing_vk_free(vsp_ctx *ctx, vsp_vk *vk) {
     if (!vk) return;
     if (ctx) { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
-    if (vk->d_expect) hipFree(vk->d_expect);
-    if (vk->d_neg) hipFree(vk->d_neg);
-    if (vk->d_tab) hipFree(vk->d_tab);
     delete vk;
 }
 
@@ -386,10 +383,10 @@ vsp_vk *pairing_vk_create(vsp_ctx *ctx, const uint64_t *alpha_g1, const uint64_t
     }
     for (size_t i = 0; i < n_abc; i++)
         if (!affine_valid<G1>(gamma_abc_g1 + 12 * i)) { set_error(ctx, VSP_ERR_ARG, "vk_create: a gamma_ABC point is not canonical or not on the curve"); return nullptr; }
-    vsp_vk *vk = new vsp_vk();
+    std::unique_ptr<vsp_vk> vk(new vsp_vk());               // every failure below is behind a wait for the stream, or before anything is queued over vk
     vk->n_abc = n_abc;
-    auto fail = [&](const char *msg) { if (msg) set_error(ctx, VSP_ERR_HIP, msg); pairing_vk_free(ctx, vk); return (vsp_vk *)nullptr; };
-    if (pairing_multi_batch(ctx, alpha_g1, beta_g2, 1, 1, vk->alpha_beta, nullptr) != VSP_OK) return fail(nullptr);
+    auto fail = [&](const char *msg) { set_error(ctx, VSP_ERR_HIP, msg); return (vsp_vk *)nullptr; };
+    if (pairing_multi_batch(ctx, alpha_g1, beta_g2, 1, 1, vk->alpha_beta, nullptr) != VSP_OK) return nullptr;
     HFp12 e; memcpy(&e, vk->alpha_beta, sizeof e); e = to_mont(e);                       // HFp12 and Fp12: the same bytes
     Affine<HFp2> ng[2] = {host_load_affine<HFp2>(gamma_g2), host_load_affine<HFp2>(delta_g2)};
     for (auto &q : ng) q.y = neg(q.y);                                                   // infinity stays x = y = 0
@@ -401,13 +398,13 @@ vsp_vk *pairing_vk_create(vsp_ctx *ctx, const uint64_t *alpha_g1, const uint64_t
         tab[i * 16].x = HFp::zero(); tab[i * 16].y = HFp::zero();
         for (int d = 1; d < 16; d++) { xyzz_madd(acc, g); tab[i * 16 + d] = xyzz_to_affine(acc); }
     });
-    if (hipMalloc(&vk->d_expect, sizeof e) != hipSuccess || hipMalloc(&vk->d_neg, sizeof ng) != hipSuccess ||
-        hipMalloc(&vk->d_tab, tab.size() * sizeof(Affine<HFp>)) != hipSuccess) return fail("vk_create: hipMalloc failed");
-    if (hipMemcpyAsync(vk->d_expect, &e, sizeof e, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(vk->d_neg, ng, sizeof ng, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(vk->d_tab, tab.data(), tab.size() * sizeof(Affine<HFp>), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+    if (vk->d_expect.alloc(sizeof e) != hipSuccess || vk->d_neg.alloc(sizeof ng) != hipSuccess ||
+        vk->d_tab.alloc(tab.size() * sizeof(Affine<HFp>)) != hipSuccess) return fail("vk_create: hipMalloc failed");
+    if (hipMemcpyAsync(vk->d_expect.p, &e, sizeof e, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(vk->d_neg.p, ng, sizeof ng, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(vk->d_tab.p, tab.data(), tab.size() * sizeof(Affine<HFp>), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess) return fail("vk_create: upload failed");
-    return vk;
+    return vk.release();
 }
 const uint8_t *pairing_vk_alpha_beta(const vsp_vk *vk) { return vk->alpha_beta; }
 size_t pairing_vk_n_abc(const vsp_vk *vk) { return vk->n_abc; }
@@ -423,10 +420,10 @@ int pairing_verify_batch(vsp_ctx *ctx, const vsp_vk *vk, const uint64_t *inputs,
         ProofArgs d;
         VSP_TRY(upload_proofs(ctx, (uint64_t *)ctx->pair_raw.p, A, B, C, inputs, at, c, L, d));
         hipLaunchKernelGGL(k_verify_prepare, dim3((unsigned)((c + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, d.A, d.B, d.C, d.scalars, c,
-                           vk->n_abc, (const G1Affine *)vk->d_tab, (const G2Affine *)vk->d_neg, (G1Affine *)ctx->pair_g1.p, (G2Affine *)ctx->pair_g2.p,
+                           vk->n_abc, vk->d_tab.as<const G1Affine>(), vk->d_neg.as<const G2Affine>(), (G1Affine *)ctx->pair_g1.p, (G2Affine *)ctx->pair_g2.p,
                            (uint8_t *)ctx->pair_status.p);
         VSP_LAUNCH_CHECK();
-        VSP_TRY(pairing_stages(ctx, 3, c, (const Fp12 *)vk->d_expect, false));
+        VSP_TRY(pairing_stages(ctx, 3, c, vk->d_expect.as<const Fp12>(), false));
         VSP_HIP(hipMemcpyAsync(verdict_out + at, (const uint8_t *)ctx->pair_status.p + 3 * c + c, c, hipMemcpyDeviceToHost, st));
         VSP_HIP(hipStreamSynchronize(st));
         pairing_add_times(ctx);
@@ -437,8 +434,7 @@ int pairing_verify_batch(vsp_ctx *ctx, const vsp_vk *vk, const uint64_t *inputs,
 // ---- SAVER ballot verdicts
 void saver_verifier_free(vsp_ctx *ctx, vsp_saver_verifier *ver) {
     if (!ver) return;
-    pairing_vk_free(ctx, ver->vk);                                   // waits for the stream
-    if (ver->d_lines) hipFree(ver->d_lines);
+    if (ctx) { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
     delete ver;
 }
 size_t saver_verifier_msg_size(const vsp_saver_verifier *ver) { return ver->n; }
@@ -451,8 +447,8 @@ vsp_saver_verifier *saver_verifier_create(vsp_ctx *ctx, size_t n, const uint64_t
         if (!affine_valid<G2>(t_g2 + 24 * j)) { set_error(ctx, VSP_ERR_ARG, "saver_verifier_create: a t_g2 point is not canonical or not on its curve"); return nullptr; }
     vsp_vk *vk = pairing_vk_create(ctx, alpha_g1, beta_g2, gamma_g2, delta_g2, gamma_abc_g1, n_abc);      // validates the Groth16 key
     if (!vk) return nullptr;
-    vsp_saver_verifier *ver = new vsp_saver_verifier();
-    ver->device = ctx->device; ver->n = n; ver->vk = vk;
+    std::unique_ptr<vsp_saver_verifier> ver(new vsp_saver_verifier());
+    ver->device = ctx->device; ver->n = n; ver->vk.reset(vk);
     ver->alpha_g1 = host_load_affine<HFp>(alpha_g1);
     std::vector<Affine<HFp2>> q(n + 5);
     for (size_t j = 0; j <= n; j++) q[j] = host_load_affine<HFp2>(t_g2 + 24 * j);
@@ -464,13 +460,13 @@ vsp_saver_verifier *saver_verifier_create(vsp_ctx *ctx, size_t n, const uint64_t
     std::vector<LineCoeffs<HFp>> lines(q.size() * MILLER_LINES);                                        // LineCoeffs<HFp> and <Fp>: the same bytes
     host_parallel_for(q.size(), [&](size_t j) { prepare_g2(q[j], lines.data() + j * MILLER_LINES); });
     const size_t bytes = lines.size() * sizeof(LineCoeffs<HFp>);
-    if (hipMalloc(&ver->d_lines, bytes) != hipSuccess || hipMemcpyAsync(ver->d_lines, lines.data(), bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+    if (ver->d_lines.alloc(bytes) != hipSuccess || hipMemcpyAsync(ver->d_lines.p, lines.data(), bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess) {
         set_error(ctx, VSP_ERR_HIP, "saver_verifier_create: the prepared lines could not be uploaded");
-        saver_verifier_free(ctx, ver);
+        hipStreamSynchronize(ctx->stream);                               // `lines` and the handle go
         return nullptr;
     }
-    return ver;
+    return ver.release();
 }
 
 int saver_piece_prepare(vsp_ctx *ctx, const vsp_saver_verifier *ver, const BallotSource &src, size_t at, size_t c, StageTimer &timer) {
@@ -495,7 +491,7 @@ int saver_piece_prepare(vsp_ctx *ctx, const vsp_saver_verifier *ver, const Ballo
     VSP_TRY(upload_proofs(ctx, d_ct + ct_words, src.A, src.B, src.C, src.rest, at, c, L, d));
     VSP_TRY(timer.mark(ctx, 0, st));
     hipLaunchKernelGGL(k_ballot_prepare, dim3((unsigned)((c + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, d_ct, d.scalars, d.A, d.B, d.C, c, n,
-                       ver->vk->n_abc, (const G1Affine *)ver->vk->d_tab, pts, a_pts, (G2Affine *)ctx->pair_g2.p, (uint8_t *)ctx->pair_status.p);
+                       ver->vk->n_abc, ver->vk->d_tab.as<const G1Affine>(), pts, a_pts, (G2Affine *)ctx->pair_g2.p, (uint8_t *)ctx->pair_status.p);
     VSP_LAUNCH_CHECK();
     VSP_TRY(timer.mark(ctx, 1, st));
     return VSP_OK;
@@ -513,7 +509,7 @@ static int saver_piece_judge(vsp_ctx *ctx, const vsp_saver_verifier *ver, size_t
     uint8_t *status = (uint8_t *)ctx->pair_status.p;
     const unsigned blocks = (unsigned)((c + PAIRING_THREADS - 1) / PAIRING_THREADS);
     hipLaunchKernelGGL(k_miller_ballot, dim3(blocks, (unsigned)(ng + 1)), dim3(PAIRING_THREADS), 0, st, (const G1Affine *)pts, (const G1Affine *)a_pts,
-                       (const G2Affine *)ctx->pair_g2.p, (const LineCoeffs<Fp> *)ver->d_lines, c, n, G, ng, (Fp12 *)ctx->pair_ml.p);
+                       (const G2Affine *)ctx->pair_g2.p, ver->d_lines.as<const LineCoeffs<Fp>>(), c, n, G, ng, (Fp12 *)ctx->pair_ml.p);
     VSP_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_ballot_product, dim3(blocks), dim3(PAIRING_THREADS), 0, st, (const Fp12 *)ctx->pair_ml.p, c, ng, (Fp12 *)ctx->pair_prod.p);
     VSP_LAUNCH_CHECK();
@@ -521,7 +517,7 @@ static int saver_piece_judge(vsp_ctx *ctx, const vsp_saver_verifier *ver, size_t
     // both final exponentiations of a piece in one launch: flag[i] for i < c says "equation 1 of ballot i holds" (the value is one),
     // for i >= c "equation 2 of ballot i - c holds" (the value is the key's e(alpha, beta))
     hipLaunchKernelGGL(k_final_exp, dim3((unsigned)((2 * c + PAIRING_THREADS - 1) / PAIRING_THREADS)), dim3(PAIRING_THREADS), 0, st, (const Fp12 *)ctx->pair_prod.p,
-                       (const uint8_t *)nullptr, 2 * c, c, (const Fp12 *)ver->vk->d_expect, (Fp12 *)nullptr, status + c);
+                       (const uint8_t *)nullptr, 2 * c, c, ver->vk->d_expect.as<const Fp12>(), (Fp12 *)nullptr, status + c);
     VSP_LAUNCH_CHECK();
     VSP_TRY(ctx->saver_timer.mark(ctx, 3, st));
     flags.resize(3 * c);

@@ -220,11 +220,6 @@ int reg_build_levels(vsp_ctx *ctx, const vsp_pedersen *ped, uint64_t *nodes, uns
     return VSP_OK;
 }
 
-void reg_release(vsp_registry *reg) {
-    if (reg->nodes.p) hipFree(reg->nodes.p);
-    delete reg;
-}
-
 int ped_check_handle(vsp_ctx *ctx, const vsp_pedersen *ped, const char *who) {
     if (ped->device != ctx->device) { std::string m = std::string(who) + ": the hash's tables belong to another device"; return set_error(ctx, VSP_ERR_ARG, m.c_str()); }
     return VSP_OK;
@@ -276,7 +271,6 @@ void vsp_pedersen_free(vsp_ctx *ctx, vsp_pedersen *ped) {
     if (!ped) return;
     hipSetDevice(ped->device);
     if (ctx) hipStreamSynchronize(ctx->stream);
-    if (ped->table.p) hipFree(ped->table.p);
     delete ped;
 }
 
@@ -345,7 +339,7 @@ int vsp_registry_build(vsp_ctx *ctx, const vsp_pedersen *ped, const uint64_t *pk
         return VSP_OK;
     };
     const int r = build();
-    if (r != VSP_OK) { hipStreamSynchronize(st); reg_release(reg); return r; }
+    if (r != VSP_OK) { hipStreamSynchronize(st); delete reg; return r; }
     *out = reg;
     return VSP_OK;
 }
@@ -397,7 +391,7 @@ int vsp_registry_from_blob(vsp_ctx *ctx, const vsp_pedersen *ped, const uint8_t 
         return VSP_OK;
     };
     const int r = load();
-    if (r != VSP_OK) { hipStreamSynchronize(st); reg_release(reg); return r; }
+    if (r != VSP_OK) { hipStreamSynchronize(st); delete reg; return r; }
     if (first_bad_node_out) *first_bad_node_out = bad;
     *out = reg;
     return VSP_OK;
@@ -407,7 +401,7 @@ void vsp_registry_free(vsp_ctx *ctx, vsp_registry *reg) {
     if (!reg) return;
     hipSetDevice(reg->device);
     if (ctx) hipStreamSynchronize(ctx->stream);
-    reg_release(reg);
+    delete reg;
 }
 
 unsigned vsp_registry_depth(const vsp_registry *reg) { return reg ? reg->depth : 0; }

@@ -78,9 +78,9 @@ vsp_r1cs *vsp_r1cs_upload(vsp_ctx *ctx, size_t num_constraints, size_t num_input
     if (!ctx) return nullptr;
     if (!row_ptr_a || !row_ptr_b || !row_ptr_c || num_inputs > num_vars) { set_error(ctx, VSP_ERR_ARG, "r1cs_upload: bad argument"); return nullptr; }
     hipSetDevice(ctx->device);
-    vsp_r1cs *cs = new vsp_r1cs();
+    std::unique_ptr<vsp_r1cs> cs(new vsp_r1cs());            // a failure below lets it go with what it holds
     cs->num_constraints = num_constraints; cs->num_inputs = num_inputs; cs->num_vars = num_vars;
-    if (domain_init(ctx, &cs->dom, num_constraints + num_inputs + 1) != VSP_OK) { delete cs; return nullptr; }
+    if (domain_init(ctx, &cs->dom, num_constraints + num_inputs + 1) != VSP_OK) return nullptr;
     const uint32_t *rp[3] = {row_ptr_a, row_ptr_b, row_ptr_c}, *ci[3] = {col_a, col_b, col_c};
     const uint64_t *co[3] = {coef_a, coef_b, coef_c};
     for (int m = 0; m < 3; m++) {                             // every matrix before anything is allocated: row pointers monotone from 0, arrays present
@@ -89,23 +89,22 @@ vsp_r1cs *vsp_r1cs_upload(vsp_ctx *ctx, size_t num_constraints, size_t num_input
         for (size_t r = 0; r < num_constraints && mono; r++) mono = rp[m][r] <= rp[m][r + 1];
         if (!mono || (nnz && (!ci[m] || !co[m]))) {
             set_error(ctx, VSP_ERR_ARG, !mono ? "r1cs_upload: row pointers must start at 0 and not decrease" : "r1cs_upload: null column / coefficient array with nnz > 0");
-            vsp_r1cs_free(ctx, cs); return nullptr;
+            return nullptr;
         }
     }
     for (int m = 0; m < 3; m++) {
         size_t nnz = rp[m][num_constraints];
-        for (size_t e = 0; e < nnz; e++) if (ci[m][e] > num_vars) { set_error(ctx, VSP_ERR_ARG, "r1cs_upload: column out of range"); vsp_r1cs_free(ctx, cs); return nullptr; }
-        for (size_t e = 0; e < nnz; e++) if (!below_mod<FrP64>(co[m] + 4 * e)) { set_error(ctx, VSP_ERR_ARG, "r1cs_upload: a coefficient is not canonical (>= r)"); vsp_r1cs_free(ctx, cs); return nullptr; }
-        bool ok = hipMalloc((void **)&cs->rp[m], (num_constraints + 1) * 4) == hipSuccess &&
-                  hipMalloc((void **)&cs->ci[m], (nnz ? nnz : 1) * 4) == hipSuccess &&
-                  hipMalloc(&cs->co[m], (nnz ? nnz : 1) * sizeof(Fr)) == hipSuccess;
-        if (!ok) { set_error(ctx, VSP_ERR_NOMEM, "r1cs_upload: hipMalloc"); vsp_r1cs_free(ctx, cs); return nullptr; }
-        if (hipMemcpyAsync(cs->rp[m], rp[m], (num_constraints + 1) * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(cs->ci[m], ci[m], nnz * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(cs->co[m], co[m], nnz * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-            set_error(ctx, VSP_ERR_HIP, "r1cs_upload: host-to-device copy failed"); vsp_r1cs_free(ctx, cs); return nullptr;
+        for (size_t e = 0; e < nnz; e++) if (ci[m][e] > num_vars) { set_error(ctx, VSP_ERR_ARG, "r1cs_upload: column out of range"); return nullptr; }
+        for (size_t e = 0; e < nnz; e++) if (!below_mod<FrP64>(co[m] + 4 * e)) { set_error(ctx, VSP_ERR_ARG, "r1cs_upload: a coefficient is not canonical (>= r)"); return nullptr; }
+        bool ok = cs->rp[m].alloc((num_constraints + 1) * 4) == hipSuccess && cs->ci[m].alloc((nnz ? nnz : 1) * 4) == hipSuccess &&
+                  cs->co[m].alloc((nnz ? nnz : 1) * sizeof(Fr)) == hipSuccess;
+        if (!ok) { set_error(ctx, VSP_ERR_NOMEM, "r1cs_upload: hipMalloc"); return nullptr; }
+        if (hipMemcpyAsync(cs->rp[m].p, rp[m], (num_constraints + 1) * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(cs->ci[m].p, ci[m], nnz * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            hipMemcpyAsync(cs->co[m].p, co[m], nnz * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+            set_error(ctx, VSP_ERR_HIP, "r1cs_upload: host-to-device copy failed"); return nullptr;
         }
-        if (nnz) hipLaunchKernelGGL(k_fr_to_mont, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, ctx->stream, (Fr *)cs->co[m], nnz);
+        if (nnz) hipLaunchKernelGGL(k_fr_to_mont, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, ctx->stream, cs->co[m].as<Fr>(), nnz);
         // column-major copy by a counting sort over the column index
         std::vector<uint32_t> colptr(num_vars + 2, 0), rows(nnz ? nnz : 1);
         std::vector<uint64_t> cot((nnz ? nnz : 1) * 4);
@@ -117,28 +116,23 @@ vsp_r1cs *vsp_r1cs_upload(vsp_ctx *ctx, size_t num_constraints, size_t num_input
                 uint32_t pos = cur[ci[m][e]]++;
                 rows[pos] = (uint32_t)r; memcpy(&cot[4 * (size_t)pos], co[m] + 4 * (size_t)e, 32);
             }
-        ok = hipMalloc((void **)&cs->cp[m], (num_vars + 2) * 4) == hipSuccess && hipMalloc((void **)&cs->ri[m], (nnz ? nnz : 1) * 4) == hipSuccess &&
-             hipMalloc(&cs->cot[m], (nnz ? nnz : 1) * sizeof(Fr)) == hipSuccess;
-        if (!ok) { set_error(ctx, VSP_ERR_NOMEM, "r1cs_upload: hipMalloc"); vsp_r1cs_free(ctx, cs); return nullptr; }
-        if (hipMemcpy(cs->cp[m], colptr.data(), (num_vars + 2) * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(cs->ri[m], rows.data(), nnz * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(cs->cot[m], cot.data(), nnz * sizeof(Fr), hipMemcpyHostToDevice) != hipSuccess) {
-            set_error(ctx, VSP_ERR_HIP, "r1cs_upload: host-to-device copy failed"); vsp_r1cs_free(ctx, cs); return nullptr;
+        ok = cs->cp[m].alloc((num_vars + 2) * 4) == hipSuccess && cs->ri[m].alloc((nnz ? nnz : 1) * 4) == hipSuccess &&
+             cs->cot[m].alloc((nnz ? nnz : 1) * sizeof(Fr)) == hipSuccess;
+        if (!ok) { set_error(ctx, VSP_ERR_NOMEM, "r1cs_upload: hipMalloc"); return nullptr; }
+        if (hipMemcpy(cs->cp[m].p, colptr.data(), (num_vars + 2) * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(cs->ri[m].p, rows.data(), nnz * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(cs->cot[m].p, cot.data(), nnz * sizeof(Fr), hipMemcpyHostToDevice) != hipSuccess) {
+            set_error(ctx, VSP_ERR_HIP, "r1cs_upload: host-to-device copy failed"); return nullptr;
         }
-        if (nnz) hipLaunchKernelGGL(k_fr_to_mont, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, ctx->stream, (Fr *)cs->cot[m], nnz);
+        if (nnz) hipLaunchKernelGGL(k_fr_to_mont, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, ctx->stream, cs->cot[m].as<Fr>(), nnz);
     }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) { set_error(ctx, VSP_ERR_HIP, "r1cs_upload: sync"); vsp_r1cs_free(ctx, cs); return nullptr; }
-    return cs;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) { set_error(ctx, VSP_ERR_HIP, "r1cs_upload: sync"); return nullptr; }
+    return cs.release();
 }
 
 void vsp_r1cs_free(vsp_ctx *ctx, vsp_r1cs *cs) {
     if (!cs) return;
     if (ctx) hipSetDevice(ctx->device);
-    domain_release(&cs->dom);
-    for (int m = 0; m < 3; m++) {
-        if (cs->rp[m]) hipFree(cs->rp[m]); if (cs->ci[m]) hipFree(cs->ci[m]); if (cs->co[m]) hipFree(cs->co[m]);
-        if (cs->cp[m]) hipFree(cs->cp[m]); if (cs->ri[m]) hipFree(cs->ri[m]); if (cs->cot[m]) hipFree(cs->cot[m]);
-    }
     delete cs;
 }
 
@@ -431,8 +425,8 @@ static int prove_front_half(vsp_ctx *ctx, const vsp_r1cs *cs, const WitnessSrc &
     // evaluation vectors (witness_map part 1): A z, B z, C z, plus the rows "input_i * 0 = 0" in A
     VSP_HIP(hipMemsetAsync(abc, 0, K * 3 * m * sizeof(Fr), st));
     if (nc) for (int j = 0; j < 3; j++) {
-        hipLaunchKernelGGL(k_csr_matvec, dim3((unsigned)((nc + 255) / 256), (unsigned)K), dim3(256), 0, st, (const uint32_t *)cs->rp[j], (const uint32_t *)cs->ci[j],
-                           (const Fr *)cs->co[j], (const Fr *)dz, nc, abc + (size_t)j * m, zs, 3 * m);
+        hipLaunchKernelGGL(k_csr_matvec, dim3((unsigned)((nc + 255) / 256), (unsigned)K), dim3(256), 0, st, cs->rp[j].as<const uint32_t>(), cs->ci[j].as<const uint32_t>(),
+                           cs->co[j].as<const Fr>(), (const Fr *)dz, nc, abc + (size_t)j * m, zs, 3 * m);
         VSP_LAUNCH_CHECK();
     }
     if (strided) {
@@ -452,7 +446,7 @@ static int verdict_queue(vsp_ctx *ctx, const vsp_r1cs *cs, size_t K, bool with_c
     hipStream_t st = ctx->stream;
     if (K > M) return set_error(ctx, VSP_ERR_ARG, "r1cs_check: more members than the verdict records hold");
     VSP_TRY(ensure(ctx, ctx->pr_verdict, vsp_ctx::VERDICT_BYTES));
-    if (!ctx->h_verdict) VSP_HIP(hipHostMalloc(&ctx->h_verdict, vsp_ctx::VERDICT_BYTES, hipHostMallocDefault));
+    if (!ctx->h_verdict.p) VSP_HIP(ctx->h_verdict.alloc(vsp_ctx::VERDICT_BYTES));
     uint32_t *first_bad = (uint32_t *)ctx->pr_verdict.p, *bad_rows = first_bad + M, *flag = first_bad + 2 * M;
     if (t0) VSP_HIP(hipEventRecord(t0, st));
     VSP_HIP(hipMemsetD32Async((hipDeviceptr_t)first_bad, (int)(uint32_t)nc, M, st));
@@ -466,7 +460,7 @@ static int verdict_queue(vsp_ctx *ctx, const vsp_r1cs *cs, size_t K, bool with_c
         VSP_LAUNCH_CHECK();
     }
     if (t1) VSP_HIP(hipEventRecord(t1, st));
-    VSP_HIP(hipMemcpyAsync(ctx->h_verdict, first_bad, vsp_ctx::VERDICT_BYTES, hipMemcpyDeviceToHost, st));
+    VSP_HIP(hipMemcpyAsync(ctx->h_verdict.p, first_bad, vsp_ctx::VERDICT_BYTES, hipMemcpyDeviceToHost, st));
     return VSP_OK;
 }
 // option "prove_check_witness" (default 0): every prover entry point queues the verdict pass between its front half and witness_map_device;
@@ -478,7 +472,7 @@ static int prove_queue_check(vsp_ctx *ctx, const vsp_r1cs *cs, size_t K) {
 // member k's record in the pinned buffer
 struct Verdict { uint32_t first_bad_row, bad_rows, not_canonical; };
 static Verdict verdict_of(const vsp_ctx *ctx, size_t k) {
-    const volatile uint32_t *h = (const volatile uint32_t *)ctx->h_verdict;
+    const volatile uint32_t *h = ctx->h_verdict.as<const volatile uint32_t>();
     return Verdict{h[k], h[vsp_ctx::VERDICT_MEMBERS + k], h[2 * vsp_ctx::VERDICT_MEMBERS + k]};
 }
 
@@ -637,7 +631,7 @@ static int prove_batch_launch_impl(vsp_ctx *ctx, const vsp_r1cs *cs, const vsp_p
     VSP_TRY(launch_on_bases(ctx, 1, pk->A, 0, a));
     // A, B1 and B2 multiply by the same K witness vectors: one digit sort and bucket plan (A's) serves the three (option "prove_batch_share_plan")
     const long share = opt(ctx, "prove_batch_share_plan", 1);
-    const bool same_shape = pk->A->glv == pk->B1->glv && pk->A->glv == pk->B2->glv && (pk->A->d28 != nullptr) == (pk->B1->d28 != nullptr) && (pk->A->d28 != nullptr) == (pk->B2->d28 != nullptr) &&
+    const bool same_shape = pk->A->glv == pk->B1->glv && pk->A->glv == pk->B2->glv && (pk->A->d28.p != nullptr) == (pk->B1->d28.p != nullptr) && (pk->A->d28.p != nullptr) == (pk->B2->d28.p != nullptr) &&
                             pk->A->pre_c == pk->B1->pre_c && pk->A->pre_c == pk->B2->pre_c && pk->A->n == pk->B1->n && pk->A->n == pk->B2->n;
     MsmRequest b = a; b.plan_from = share && same_shape && nv + 1 > 0 ? 1 : -1;
     VSP_TRY(launch_on_bases(ctx, 3, pk->B2, 0, b));

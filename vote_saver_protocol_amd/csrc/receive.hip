@@ -82,7 +82,7 @@ int receive_piece_prepare(vsp_ctx *ctx, const vsp_saver_verifier *ver, const Rec
     if (lo > rp.count || c > rp.count - lo) return set_error(ctx, VSP_ERR_ARG, "saver_receive_blobs: a range outside the decoded piece");
     hipLaunchKernelGGL(k_receive_prepare, dim3((unsigned)((c + RECEIVE_THREADS - 1) / RECEIVE_THREADS)), dim3(RECEIVE_THREADS), 0, ctx->stream, (const G1Affine *)rp.members,
                        (const G1Affine *)rp.ac, (const G2Affine *)rp.b, rp.rest, rp.wire, rp.wire_stride, rp.count, lo, c, ver->n, ver->vk->n_abc,
-                       (const G1Affine *)ver->vk->d_tab, (G1Affine *)d_pts, (G1Affine *)d_a, (G2Affine *)d_b, d_status, rp.box_row);
+                       ver->vk->d_tab.as<const G1Affine>(), (G1Affine *)d_pts, (G1Affine *)d_a, (G2Affine *)d_b, d_status, rp.box_row);
     VSP_LAUNCH_CHECK();
     return VSP_OK;
 }

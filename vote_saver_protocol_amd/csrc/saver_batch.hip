@@ -70,30 +70,16 @@ static int tables_ready(vsp_ctx *ctx, const vsp_saver_pk *spk) {
     // host Montgomery points and device ones are the same bytes (fixedbase_impl.inc build_fixed_table)
     static_assert(sizeof(Affine<HFp>) == sizeof(G1Affine), "one table for the host and the device");
     const size_t tab_bytes = spk->flat.size() * sizeof(G1Affine);
-    const size_t cb = pl.cols.size() * sizeof(SaverColumn), pb = pl.pairs.size() * sizeof(SaverPair), lb = pl.lane_col.size() * sizeof(uint32_t);
-    void *d_tab = nullptr, *d_desc = nullptr;
-    if (hipMalloc(&d_tab, tab_bytes) != hipSuccess || hipMalloc(&d_desc, cb + pb + lb) != hipSuccess) {
-        if (d_tab) hipFree(d_tab);
-        spk->flat.clear();
-        return set_error(ctx, VSP_ERR_NOMEM, "saver_pk_upload: hipMalloc of the key's tables failed");
-    }
-    hipError_t e = hipMemcpy(d_tab, spk->flat.data(), tab_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_desc, pl.cols.data(), cb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy((char *)d_desc + cb, pl.pairs.data(), pb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy((char *)d_desc + cb + pb, pl.lane_col.data(), lb, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(d_tab); hipFree(d_desc); spk->flat.clear(); return set_hip_error(ctx, e, "hipMemcpy of the key's tables", __FILE__, __LINE__); }
-    spk->d_tab = d_tab; spk->d_desc = d_desc; spk->device = ctx->device; spk->device_bytes = tab_bytes + cb + pb + lb;
+    DevBuf d_tab, d_desc;
+    int rc = VSP_OK;
+    if (d_tab.alloc(tab_bytes) != hipSuccess) rc = set_error(ctx, VSP_ERR_NOMEM, "saver_pk_upload: hipMalloc of the key's tables failed");
+    else if (const hipError_t e = hipMemcpy(d_tab.p, spk->flat.data(), tab_bytes, hipMemcpyHostToDevice); e != hipSuccess) rc = set_hip_error(ctx, e, "hipMemcpy of the key's tables", __FILE__, __LINE__);
+    else rc = upload_plan(ctx, pl, d_desc);
+    if (rc != VSP_OK) { spk->flat.clear(); return rc; }
+    spk->device = ctx->device; spk->device_bytes = d_tab.cap + d_desc.cap;
+    spk->d_tab = std::move(d_tab); spk->d_desc = std::move(d_desc);
     ctx->stats["saver_ct_table_ms"] += now_ms() - t0;
     spk->uploaded.store(true, std::memory_order_release);
-    return VSP_OK;
-}
-
-// pinned host memory of at least `bytes` (grow only)
-static int ensure_pinned(vsp_ctx *ctx, void *&p, size_t &cap, size_t bytes) {
-    if (cap >= bytes && p) return VSP_OK;
-    if (p) { hipHostFree(p); p = nullptr; cap = 0; }
-    VSP_HIP(hipHostMalloc(&p, bytes + bytes / 8, hipHostMallocDefault));
-    cap = bytes + bytes / 8;
     return VSP_OK;
 }
 
@@ -119,12 +105,12 @@ static int ct_queue(vsp_ctx *ctx, const vsp_saver_pk *spk, const uint64_t *msgs,
     auto &w = ctx->saver_ct;
     const size_t n = spk->n, ns = n + 1, nc = saver_columns(n);
     VSP_TRY(ct_stream_ready(ctx));
-    VSP_TRY(ensure_w(ctx, w.stream, w.scalars, c * ns * 32));
-    VSP_TRY(ensure_w(ctx, w.stream, w.sums, c * nc * sizeof(G1XYZZ)));
-    VSP_TRY(ensure_w(ctx, w.stream, w.points, c * nc * sizeof(G1Affine)));
-    VSP_TRY(ensure_pinned(ctx, w.h_scalars, w.h_scalars_cap, c * ns * 32));
-    VSP_TRY(ensure_pinned(ctx, w.h_points, w.h_points_cap, c * nc * sizeof(G1Affine)));
-    uint64_t *hs = (uint64_t *)w.h_scalars;
+    VSP_TRY(ensure(ctx, w.scalars, c * ns * 32, w.stream));
+    VSP_TRY(ensure(ctx, w.sums, c * nc * sizeof(G1XYZZ), w.stream));
+    VSP_TRY(ensure(ctx, w.points, c * nc * sizeof(G1Affine), w.stream));
+    VSP_TRY(ensure_pinned(ctx, w.h_scalars, c * ns * 32));
+    VSP_TRY(ensure_pinned(ctx, w.h_points, c * nc * sizeof(G1Affine)));
+    uint64_t *hs = w.h_scalars.as<uint64_t>();
     if (msgs) {
         for (size_t k = 0; k < c; k++) { memcpy(hs + k * ns * 4, r_enc + 4 * k, 32); memcpy(hs + k * ns * 4 + 4, msgs + k * n * 4, n * 32); }
         VSP_HIP(hipMemcpyAsync(w.scalars.p, hs, c * ns * 32, hipMemcpyHostToDevice, w.stream));
@@ -134,18 +120,18 @@ static int ct_queue(vsp_ctx *ctx, const vsp_saver_pk *spk, const uint64_t *msgs,
         VSP_HIP(hipStreamWaitEvent(w.stream, ctx->ev_aux, 0));
         VSP_HIP(hipMemcpy2DAsync((uint64_t *)w.scalars.p + 4, ns * 32, (const uint64_t *)ctx->pr_z.p + 4, z_stride * 32, n * 32, c, hipMemcpyDeviceToDevice, w.stream));
     }
-    const SaverColumn *d_cols = (const SaverColumn *)spk->d_desc;
+    const SaverColumn *d_cols = spk->d_desc.as<const SaverColumn>();
     const SaverPair *d_pairs = (const SaverPair *)(d_cols + spk->plan.cols.size());
     const uint32_t *d_lane_col = (const uint32_t *)(d_pairs + spk->plan.pairs.size());
     const unsigned ballot_lanes = (unsigned)spk->plan.lane_col.size();
     VSP_TRY(w.timer.mark(ctx, 0, w.stream));
-    hipLaunchKernelGGL(k_saver_ct, dim3((unsigned)((c * ballot_lanes + CT_BLOCK - 1) / CT_BLOCK)), dim3(CT_BLOCK), 0, w.stream, (const G1Affine *)spk->d_tab, d_cols, d_pairs,
+    hipLaunchKernelGGL(k_saver_ct, dim3((unsigned)((c * ballot_lanes + CT_BLOCK - 1) / CT_BLOCK)), dim3(CT_BLOCK), 0, w.stream, spk->d_tab.as<const G1Affine>(), d_cols, d_pairs,
                        d_lane_col, ballot_lanes, (unsigned)nc, (unsigned)ns, (const uint64_t *)w.scalars.p, c, (G1XYZZ *)w.sums.p);
     VSP_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_saver_ct_affine, dim3((unsigned)((c * nc + 63) / 64)), dim3(64), 0, w.stream, (const G1XYZZ *)w.sums.p, c * nc, (G1Affine *)w.points.p);
     VSP_LAUNCH_CHECK();
     VSP_TRY(w.timer.mark(ctx, 1, w.stream));
-    VSP_HIP(hipMemcpyAsync(w.h_points, w.points.p, c * nc * sizeof(G1Affine), hipMemcpyDeviceToHost, w.stream));
+    VSP_HIP(hipMemcpyAsync(w.h_points.p, w.points.p, c * nc * sizeof(G1Affine), hipMemcpyDeviceToHost, w.stream));
     VSP_HIP(hipEventRecord(w.done, w.stream));
     return VSP_OK;
 }
@@ -161,7 +147,7 @@ static int ct_collect(vsp_ctx *ctx, size_t n, size_t c, size_t at, uint64_t *ct_
     auto &w = ctx->saver_ct;
     VSP_HIP(hipEventSynchronize(w.done));
     w.timer.add(ctx, 0, "saver_ct_ms");
-    for (size_t k = 0; k < c; k++) ct_store(n, (const uint64_t *)w.h_points + k * saver_columns(n) * 12, at + k, ct_out, addend_out, blobs_out);
+    for (size_t k = 0; k < c; k++) ct_store(n, w.h_points.as<const uint64_t>() + k * saver_columns(n) * 12, at + k, ct_out, addend_out, blobs_out);
     return VSP_OK;
 }
 // the host leg (option "saver_encrypt_gpu" = 0): the same columns over the same tables, one lane per column, a ballot per task
@@ -207,14 +193,14 @@ static int ballots_launch(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1cs 
     if (w.gpu) rc = ct_queue(ctx, spk, msgs, r_enc, count, zs);
     else {
         // the host leg computes in the finish, inside the wait for the proofs: it keeps the scalars until then
-        rc = ensure_pinned(ctx, w.h_scalars, w.h_scalars_cap, count * (n + 1) * 32);
-        if (rc == VSP_OK) memcpy(w.h_scalars, r_enc, count * 32);
-        if (rc == VSP_OK && msgs) memcpy((uint64_t *)w.h_scalars + count * 4, msgs, count * n * 32);
+        rc = ensure_pinned(ctx, w.h_scalars, count * (n + 1) * 32);
+        if (rc == VSP_OK) memcpy(w.h_scalars.p, r_enc, count * 32);
+        if (rc == VSP_OK && msgs) memcpy(w.h_scalars.as<uint64_t>() + count * 4, msgs, count * n * 32);
         // the device form: the count x msg_size message scalars, and nothing else, come to the host, behind the gather; the finish waits for them
         if (rc == VSP_OK && !msgs) rc = [&]() -> int {
             VSP_TRY(ct_stream_ready(ctx));
             VSP_HIP(hipStreamWaitEvent(w.stream, ctx->ev_aux, 0));
-            VSP_HIP(hipMemcpy2DAsync((uint64_t *)w.h_scalars + count * 4, n * 32, (const uint64_t *)ctx->pr_z.p + 4, zs * 32, n * 32, count, hipMemcpyDeviceToHost, w.stream));
+            VSP_HIP(hipMemcpy2DAsync(w.h_scalars.as<uint64_t>() + count * 4, n * 32, (const uint64_t *)ctx->pr_z.p + 4, zs * 32, n * 32, count, hipMemcpyDeviceToHost, w.stream));
             VSP_HIP(hipEventRecord(w.done, w.stream));
             return VSP_OK;
         }();
@@ -233,16 +219,22 @@ static int ballots_launch(vsp_ctx *ctx, const vsp_saver_pk *spk, const vsp_r1cs 
 
 }  // anonymous namespace
 
+int upload_plan(vsp_ctx *ctx, const SaverPlan &pl, DevBuf &out) {
+    const size_t cb = pl.cols.size() * sizeof(SaverColumn), pb = pl.pairs.size() * sizeof(SaverPair), lb = pl.lane_col.size() * sizeof(uint32_t);
+    DevBuf d;
+    if (d.alloc(cb + pb + lb) != hipSuccess) return set_error(ctx, VSP_ERR_NOMEM, "hipMalloc of a plan failed");
+    hipError_t e = hipMemcpy(d.p, pl.cols.data(), cb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d.as<char>() + cb, pl.pairs.data(), pb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d.as<char>() + cb + pb, pl.lane_col.data(), lb, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return set_hip_error(ctx, e, "hipMemcpy of a plan", __FILE__, __LINE__);
+    out = std::move(d);
+    return VSP_OK;
+}
 void saver_ct_release(vsp_ctx *ctx) {
     auto &w = ctx->saver_ct;
     if (w.stream) hipStreamSynchronize(w.stream);
-    for (DevBuf *b : {&w.scalars, &w.sums, &w.points}) { if (b->p) hipFree(b->p); b->p = nullptr; b->cap = 0; }
-    if (w.h_scalars) hipHostFree(w.h_scalars);
-    if (w.h_points) hipHostFree(w.h_points);
-    w.h_scalars = w.h_points = nullptr; w.h_scalars_cap = w.h_points_cap = 0;
     if (w.done) hipEventDestroy(w.done);
     w.done = nullptr;
-    w.timer.destroy();
     if (w.stream) hipStreamDestroy(w.stream);
     w.stream = nullptr;
 }
@@ -250,8 +242,8 @@ void saver_pk_release_device(vsp_saver_pk *spk) {
     if (!spk->uploaded.load()) return;
     hipSetDevice(spk->device);
     hipDeviceSynchronize();                  // a context may still be reading the tables
-    hipFree(spk->d_tab); hipFree(spk->d_desc);
-    spk->d_tab = spk->d_desc = nullptr; spk->device_bytes = 0;
+    spk->d_tab.reset(); spk->d_desc.reset();
+    spk->device_bytes = 0;
     spk->uploaded.store(false);
 }
 
@@ -327,7 +319,7 @@ int vsp_saver_encrypt_batch_finish(vsp_ctx *ctx, uint64_t *ct_out, uint64_t *A_o
     if (w.gpu) rc = ct_collect(ctx, n, K, 0, ct_out, ctx->prove.addend.data(), ct_blobs_out);
     else {
         rc = w.device_src ? [&]() -> int { VSP_HIP(hipEventSynchronize(w.done)); return VSP_OK; }() : VSP_OK;
-        if (rc == VSP_OK) ct_host(w.spk, (const uint64_t *)w.h_scalars + K * 4, (const uint64_t *)w.h_scalars, K, ct_out, ctx->prove.addend.data(), ct_blobs_out);
+        if (rc == VSP_OK) ct_host(w.spk, w.h_scalars.as<const uint64_t>() + K * 4, w.h_scalars.as<const uint64_t>(), K, ct_out, ctx->prove.addend.data(), ct_blobs_out);
     }
     if (rc != VSP_OK) {
         const std::string keep = ctx->err;

@@ -20,7 +20,7 @@ struct vsp_saver_rerandomizer {
     int device = 0;
     size_t n = 0;
     vsp::SaverPlan plan, plan2;             // the G1 columns over the key's tables, the G2 column over d_tab2
-    void *d_desc = nullptr, *d_desc2 = nullptr, *d_tab2 = nullptr;      // a plan on the device: columns | pairs | lane_col
+    vsp::DevBuf d_desc, d_desc2, d_tab2;    // a plan on the device: columns | pairs | lane_col
     size_t device_bytes = 0;
 };
 
@@ -173,24 +173,6 @@ template <class F> __global__ __launch_bounds__(RR_THREADS) void k_rr_mul(const 
     rr_store_affine(&acc, &out[ballot * out_per + out_at - j]);
 }
 
-static int ensure_pinned(vsp_ctx *ctx, void *&p, size_t &cap, size_t bytes) {
-    if (cap >= bytes && p) return VSP_OK;
-    if (p) { hipHostFree(p); p = nullptr; cap = 0; }
-    VSP_HIP(hipHostMalloc(&p, bytes + bytes / 8, hipHostMallocDefault));
-    cap = bytes + bytes / 8;
-    return VSP_OK;
-}
-static int upload_plan(vsp_ctx *ctx, const SaverPlan &pl, void **d_out, size_t *bytes) {
-    const size_t cb = pl.cols.size() * sizeof(SaverColumn), pb = pl.pairs.size() * sizeof(SaverPair), lb = pl.lane_col.size() * sizeof(uint32_t);
-    void *d = nullptr;
-    if (hipMalloc(&d, cb + pb + lb) != hipSuccess) return set_error(ctx, VSP_ERR_NOMEM, "saver_rerandomizer_new: hipMalloc of a plan failed");
-    hipError_t e = hipMemcpy(d, pl.cols.data(), cb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy((char *)d + cb, pl.pairs.data(), pb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy((char *)d + cb + pb, pl.lane_col.data(), lb, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(d); return set_hip_error(ctx, e, "hipMemcpy of a plan", __FILE__, __LINE__); }
-    *d_out = d; *bytes += cb + pb + lb;
-    return VSP_OK;
-}
 template <class F> static void launch_columns(hipStream_t st, const void *d_tab, const void *d_desc, const SaverPlan &pl, const uint64_t *d_scalars, const void *d_given, unsigned given_per,
                                               size_t c, void *d_sums) {
     constexpr unsigned BLOCK = sizeof(XYZZ<F>) > 192 ? 128 : 256;           // 48 KB of LDS either way
@@ -223,10 +205,10 @@ static int rr_piece(vsp_ctx *ctx, const vsp_saver_rerandomizer *rr, const uint64
     VSP_TRY(ensure(ctx, w.sums, c * nc * sizeof(G1XYZZ)));
     VSP_TRY(ensure(ctx, w.sums2, c * sizeof(G2XYZZ)));
     VSP_TRY(ensure(ctx, w.status, c * sizeof(uint32_t)));
-    VSP_TRY(ensure_pinned(ctx, w.h_in, w.h_in_cap, g1_bytes + g2_bytes + sc_bytes));
-    VSP_TRY(ensure_pinned(ctx, w.h_out, w.h_out_cap, g1_bytes + g2_bytes + c * sizeof(uint32_t)));
+    VSP_TRY(ensure_pinned(ctx, w.h_in, g1_bytes + g2_bytes + sc_bytes));
+    VSP_TRY(ensure_pinned(ctx, w.h_out, g1_bytes + g2_bytes + c * sizeof(uint32_t)));
     // the given points of a ballot in the order of its G1 outputs: ct | C | A; then every B; then the scalar records
-    uint64_t *h1 = (uint64_t *)w.h_in, *h2 = h1 + c * ng * 12, *hs = h2 + c * 24;
+    uint64_t *h1 = w.h_in.as<uint64_t>(), *h2 = h1 + c * ng * 12, *hs = h2 + c * 24;
     host_parallel_for(c, [&](size_t k) {
         uint64_t *row = h1 + k * ng * 12;
         memcpy(row, ct + (at + k) * ctw, ctw * 8);
@@ -251,9 +233,9 @@ static int rr_piece(vsp_ctx *ctx, const vsp_saver_rerandomizer *rr, const uint64
     hipLaunchKernelGGL(k_rr_check<Fp2>, blocks(c), dim3(RR_THREADS), 0, st, (const uint64_t *)d_words2, (size_t)1, c, b_in, (uint32_t *)w.status.p);
     VSP_LAUNCH_CHECK();
     VSP_TRY(w.timer[0].mark(ctx, 1, st));
-    launch_columns<Fp>(st, spk->d_tab, rr->d_desc, rr->plan, d_scal, given, (unsigned)ng, c, w.sums.p);
+    launch_columns<Fp>(st, spk->d_tab.p, rr->d_desc.p, rr->plan, d_scal, given, (unsigned)ng, c, w.sums.p);
     VSP_LAUNCH_CHECK();
-    launch_columns<Fp2>(st, rr->d_tab2, rr->d_desc2, rr->plan2, d_scal, nullptr, 0, c, w.sums2.p);
+    launch_columns<Fp2>(st, rr->d_tab2.p, rr->d_desc2.p, rr->plan2, d_scal, nullptr, 0, c, w.sums2.p);
     VSP_LAUNCH_CHECK();
     VSP_TRY(w.timer[0].mark(ctx, 2, st));
     // from here on the canonical inputs are dead: the outputs take their place
@@ -268,8 +250,8 @@ static int rr_piece(vsp_ctx *ctx, const vsp_saver_rerandomizer *rr, const uint64
     hipLaunchKernelGGL(k_rr_mul<Fp2>, blocks(c), dim3(RR_THREADS), 0, st, (const G2Affine *)b_in, 1u, 0u, d_scal, RR_ZINV, 1u, (const G2XYZZ *)w.sums2.p, 1u, 0u, c, w4, out2, 1u, 0u);
     VSP_LAUNCH_CHECK();
     VSP_TRY(w.timer[1].mark(ctx, 2, st));
-    VSP_HIP(hipMemcpyAsync(w.h_out, d_words, g1_bytes + g2_bytes, hipMemcpyDeviceToHost, st));
-    VSP_HIP(hipMemcpyAsync((char *)w.h_out + g1_bytes + g2_bytes, w.status.p, c * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    VSP_HIP(hipMemcpyAsync(w.h_out.p, d_words, g1_bytes + g2_bytes, hipMemcpyDeviceToHost, st));
+    VSP_HIP(hipMemcpyAsync(w.h_out.as<char>() + g1_bytes + g2_bytes, w.status.p, c * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     VSP_HIP(hipStreamSynchronize(st));
     w.timer[0].add(ctx, 0, "saver_rerandomize_check_ms"); w.timer[0].add(ctx, 1, "saver_rerandomize_columns_ms"); w.timer[0].add(ctx, 2, "saver_rerandomize_affine_ms");
     w.timer[1].add(ctx, 0, "saver_rerandomize_g1_ms"); w.timer[1].add(ctx, 1, "saver_rerandomize_g2_ms");
@@ -279,15 +261,6 @@ static int rr_piece(vsp_ctx *ctx, const vsp_saver_rerandomizer *rr, const uint64
 }
 
 }  // anonymous namespace
-
-void saver_rr_release(vsp_ctx *ctx) {
-    auto &w = ctx->saver_rr;
-    for (DevBuf *b : {&w.words, &w.scalars, &w.given, &w.b_in, &w.sums, &w.sums2, &w.status}) { if (b->p) hipFree(b->p); b->p = nullptr; b->cap = 0; }
-    if (w.h_in) hipHostFree(w.h_in);
-    if (w.h_out) hipHostFree(w.h_out);
-    w.h_in = w.h_out = nullptr; w.h_in_cap = w.h_out_cap = 0;
-    w.timer[0].destroy(); w.timer[1].destroy();
-}
 
 }  // namespace vsp
 
@@ -299,7 +272,7 @@ vsp_saver_rerandomizer *vsp_saver_rerandomizer_new(vsp_ctx *ctx, vsp_saver_pk *s
     if (!spk || !delta_g2) { set_error(ctx, VSP_ERR_ARG, "saver_rerandomizer_new: null argument"); return nullptr; }
     if (!affine_valid<G2>(delta_g2)) { set_error(ctx, VSP_ERR_ARG, "saver_rerandomizer_new: delta_g2 is not a curve point"); return nullptr; }
     if (vsp_saver_pk_upload(ctx, spk) != VSP_OK) return nullptr;
-    vsp_saver_rerandomizer *rr = new vsp_saver_rerandomizer();
+    std::unique_ptr<vsp_saver_rerandomizer> rr(new vsp_saver_rerandomizer());      // nothing has used its memory when a failure below lets it go
     rr->spk = spk; rr->device = ctx->device; rr->n = spk->n;
     const size_t n = spk->n;
     std::vector<uint8_t> base_inf(saver_rerand_columns(n), 0);
@@ -312,22 +285,17 @@ vsp_saver_rerandomizer *vsp_saver_rerandomizer_new(vsp_ctx *ctx, vsp_saver_pk *s
     // host Montgomery points and device ones are the same bytes
     static_assert(sizeof(Affine<HFp2>) == sizeof(G2Affine), "one table for the host and the device");
     const size_t tab_bytes = tab.size() * sizeof(G2Affine);
-    int rc = hipSetDevice(ctx->device) == hipSuccess ? VSP_OK : set_error(ctx, VSP_ERR_HIP, "saver_rerandomizer_new: hipSetDevice failed");
-    if (rc == VSP_OK && hipMalloc(&rr->d_tab2, tab_bytes) != hipSuccess) { rr->d_tab2 = nullptr; rc = set_error(ctx, VSP_ERR_NOMEM, "saver_rerandomizer_new: hipMalloc of the delta_g2 table failed"); }
-    if (rc == VSP_OK) { const hipError_t e = hipMemcpy(rr->d_tab2, tab.data(), tab_bytes, hipMemcpyHostToDevice); if (e != hipSuccess) rc = set_hip_error(ctx, e, "hipMemcpy of the delta_g2 table", __FILE__, __LINE__); }
-    rr->device_bytes = tab_bytes;
-    if (rc == VSP_OK) rc = upload_plan(ctx, rr->plan, &rr->d_desc, &rr->device_bytes);
-    if (rc == VSP_OK) rc = upload_plan(ctx, rr->plan2, &rr->d_desc2, &rr->device_bytes);
-    if (rc != VSP_OK) { vsp_saver_rerandomizer_free(ctx, rr); return nullptr; }
-    return rr;
+    if (hipSetDevice(ctx->device) != hipSuccess) { set_error(ctx, VSP_ERR_HIP, "saver_rerandomizer_new: hipSetDevice failed"); return nullptr; }
+    if (rr->d_tab2.alloc(tab_bytes) != hipSuccess) { set_error(ctx, VSP_ERR_NOMEM, "saver_rerandomizer_new: hipMalloc of the delta_g2 table failed"); return nullptr; }
+    if (const hipError_t e = hipMemcpy(rr->d_tab2.p, tab.data(), tab_bytes, hipMemcpyHostToDevice); e != hipSuccess) { set_hip_error(ctx, e, "hipMemcpy of the delta_g2 table", __FILE__, __LINE__); return nullptr; }
+    if (upload_plan(ctx, rr->plan, rr->d_desc) != VSP_OK || upload_plan(ctx, rr->plan2, rr->d_desc2) != VSP_OK) return nullptr;
+    rr->device_bytes = rr->d_tab2.cap + rr->d_desc.cap + rr->d_desc2.cap;
+    return rr.release();
 }
 void vsp_saver_rerandomizer_free(vsp_ctx *, vsp_saver_rerandomizer *rr) {
     if (!rr) return;
     hipSetDevice(rr->device);
     hipDeviceSynchronize();                  // a context may still be reading the table
-    if (rr->d_tab2) hipFree(rr->d_tab2);
-    if (rr->d_desc) hipFree(rr->d_desc);
-    if (rr->d_desc2) hipFree(rr->d_desc2);
     delete rr;
 }
 size_t vsp_saver_rerandomizer_msg_size(const vsp_saver_rerandomizer *rr) { return rr ? rr->n : 0; }
@@ -353,7 +321,7 @@ int vsp_saver_rerandomize_batch(vsp_ctx *ctx, const vsp_saver_rerandomizer *rr, 
     for (size_t at = 0; at < count; at += piece) {
         const size_t c = count - at < piece ? count - at : piece;
         VSP_TRY(rr_piece(ctx, rr, rnd, ct, A, B, C, at, c, pre));
-        const uint64_t *h1 = (const uint64_t *)ctx->saver_rr.h_out, *h2 = h1 + c * ng * 12;
+        const uint64_t *h1 = ctx->saver_rr.h_out.as<const uint64_t>(), *h2 = h1 + c * ng * 12;
         const uint32_t *hst = (const uint32_t *)(h2 + c * 24);
         host_parallel_for(c, [&](size_t j) {
             const size_t k = at + j;

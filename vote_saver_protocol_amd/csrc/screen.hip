@@ -183,7 +183,7 @@ int screen_level(ScreenPiece &p, size_t len, bool first, std::vector<uint8_t> &h
     VSP_TRY(t1.mark(ctx, 1, st));
     // 6. the fixed-argument Miller loops and the two values of every range
     hipLaunchKernelGGL(k_screen_miller, dim3((unsigned)((R * na + SCREEN_THREADS - 1) / SCREEN_THREADS)), dim3(SCREEN_THREADS), 0, st, (const G1Affine *)p.w.args,
-                       (const LineCoeffs<Fp> *)p.ver->d_lines, na, R * na, p.w.ml);
+                       p.ver->d_lines.as<const LineCoeffs<Fp>>(), na, R * na, p.w.ml);
     VSP_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_screen_combine, dim3((unsigned)((2 * R + SCREEN_THREADS - 1) / SCREEN_THREADS)), dim3(SCREEN_THREADS), 0, st, (const Fp12 *)p.w.ml, prod, na, R,
                        p.w.eq);

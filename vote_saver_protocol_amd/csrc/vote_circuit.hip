@@ -108,8 +108,6 @@ unsigned vw_blocks(uint64_t lanes, unsigned threads) { return (unsigned)((lanes 
 
 void circuit_release(vsp_ctx *ctx, vsp_vote_circuit *c) {
     if (c->wit_live && c->wit.p) { hipMemset(c->wit.p, 0, c->wit.cap); c->wit_live = false; }
-    for (DevBuf *b : {&c->d_aff, &c->in, &c->status, &c->digests, &c->slots, &c->wit}) if (b->p) hipFree(b->p);
-    c->timer.destroy();
     if (c->cs) vsp_r1cs_free(ctx, c->cs);
     delete c;
 }

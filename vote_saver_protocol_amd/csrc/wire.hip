@@ -305,11 +305,12 @@ vsp_keypair *vsp_pk_from_blob(vsp_ctx *ctx, const uint8_t *blob, size_t len, int
     if (off != len) return fail("pk_from_blob: trailing bytes");
     if (hipSetDevice(ctx->device) != hipSuccess) return fail("pk_from_blob: device");
     hipStream_t st = ctx->stream;
-    void *d_raw = nullptr, *d_pts = nullptr;
+    DevBuf raw, pts;
     size_t maxn = 1; for (int s = 0; s < 4; s++) if (cnt[s] > maxn) maxn = cnt[s];
-    if (hipMalloc(&d_raw, len) != hipSuccess || hipMalloc(&d_pts, maxn * sizeof(G2Affine)) != hipSuccess || ensure(ctx, ctx->val_flag, 16) != VSP_OK) {
-        if (d_raw) hipFree(d_raw); if (d_pts) hipFree(d_pts); set_error(ctx, VSP_ERR_NOMEM, "pk_from_blob: hipMalloc failed"); return nullptr;
+    if (raw.alloc(len) != hipSuccess || pts.alloc(maxn * sizeof(G2Affine)) != hipSuccess || ensure(ctx, ctx->val_flag, 16) != VSP_OK) {
+        set_error(ctx, VSP_ERR_NOMEM, "pk_from_blob: hipMalloc failed"); return nullptr;
     }
+    void *d_raw = raw.p, *d_pts = pts.p;
     vsp_keypair *kp = new vsp_keypair();
     memset(kp->gamma_g2, 0, sizeof kp->gamma_g2); memset(kp->gamma_g1, 0, sizeof kp->gamma_g1);
     bool ok = hipMemcpyAsync(d_raw, blob, len, hipMemcpyHostToDevice, st) == hipSuccess && hipMemsetAsync(ctx->val_flag.p, 0, 16, st) == hipSuccess;
@@ -335,7 +336,7 @@ vsp_keypair *vsp_pk_from_blob(vsp_ctx *ctx, const uint8_t *blob, size_t len, int
         }
     }
     hipStreamSynchronize(st);
-    hipFree(d_raw); hipFree(d_pts);         // before the window multiples are built: the raw blob (0.6 GB at 2^20 constraints) is no longer needed
+    raw.reset(); pts.reset();               // before the window multiples are built: the raw blob (0.6 GB at 2^20 constraints) is no longer needed
     // precompute: the bit mask of vsp_groth16_generate -- bit 0 = the recommended set A, B(G1), B(G2), L (H stays plain); bits 1..5 = A, B(G1), B(G2), H, L
     for (int i = 0; i < 5 && ok; i++) {
         const bool pre_this = ((precompute & 1) && i != 3) || ((precompute >> (i + 1)) & 1);
