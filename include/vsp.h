@@ -107,6 +107,9 @@ void vsp_stats_reset(vsp_ctx *ctx);
  * 2: the staged sort for every window of 12 bits and more), "msm_wide_windows" (0: never more than 16 bits per window), "msm_fold" (0: 255-bit
  * scalars are not folded to min(k, r - k) where the window width divides 255), "msm_fused_split" (0: the endomorphism split and the digit
  * extraction run as two kernels over the scalars instead of one), "msm_fused_scans" (0: the bucket scans take three kernels each),
+ * "msm_scatter_rounds" (the LDS counting sort places its entries one range of buckets at a time, so that the lines it writes are
+ * completed in L2: 0 = as many rounds as the size asks for, n = n rounds, rounded down to a power of two, 32 at most; 1 = a single pass;
+ * vsp_get_stat "msm_scatter_rounds": the rounds of the last sort),
  * "prove_check_witness" (default 0; 1: every prover entry point checks its witnesses against the constraint system and refuses the ones
  * that fail -- "witness check" below).
  *

@@ -19,6 +19,7 @@
 #include "point_decode.h"
 #include "saver_ct.h"
 #include "saver_rerand.h"
+#include "lds_sort_map.h"
 
 struct vsp_ctx;
 namespace vsp {

@@ -312,10 +312,12 @@ __global__ __launch_bounds__(256) void k_digits_wide(const Fr *scalars, MsmGeom 
     }
 }
 
-// blockhist[chunk][w][b] = number of digits of value b in (chunk, w)
-__global__ __launch_bounds__(CS_THREADS) VSP_CS_ATTR void k_count_lds(const uint16_t *digits, MsmGeom g, unsigned nchunks, size_t chunk_len, uint32_t *blockhist) {
+// blockhist[chunk][w][b] = number of digits of value b in (chunk, w); the block's (w, chunk) and the grid: lds_sort_map.h
+__global__ __launch_bounds__(CS_THREADS) VSP_CS_ATTR void k_count_lds(const uint16_t *digits, MsmGeom g, unsigned nchunks, size_t chunk_len, uint32_t *blockhist, bool labelled) {
     extern __shared__ uint32_t lds_hist[];
-    const unsigned w = blockIdx.x % g.W, chunk = blockIdx.x / g.W;
+    const LdsSortBlock blk = lds_sort_block(blockIdx.x, g.W, nchunks, labelled);
+    if (!blk.valid) return;                                   // (the whole block: the labelled grid, rounded up for a W that is no multiple of 8)
+    const unsigned w = blk.w, chunk = blk.chunk;
     VSP_CS_UNROLL
     for (unsigned b = threadIdx.x; b < g.B; b += CS_THREADS) lds_hist[b] = 0;
     __syncthreads();
@@ -375,11 +377,28 @@ __global__ __launch_bounds__(256) void k_chunk_prefix(uint32_t *blockhist, unsig
     if (tilesum) block_sum_to(run, &tilesum[blockIdx.x]);         // the scan that follows (k_scan_tiles256) starts from these
 }
 
+// Places every entry of the block's (window, chunk) at its bucket's cursor, in `rounds` passes over the chunk: pass r handles exactly the
+// entries whose bucket index lies in range r of `rounds` equal ranges (index >> range_shift == r, range_shift = log2(B / rounds)) and
+// skips the rest.  The cursors are set up once; every entry is placed once, through the same cursor, so cnt, off and the set of
+// entries of every bucket are those of a single pass -- only the order inside a bucket may differ, as it does from run to run anyway.
+// Why: the kernel is bound by its scattered 4-byte stores.  In one pass the workgroups of a window spray their window's slice of
+// `sorted` (8 MB at 2^21 entries) for the whole life of the kernel, twice the 4 MiB of the L2 they share (lds_sort_map.h), and a dirty
+// line is evicted holding one or two valid dwords: WRITE_SIZE 627 MB per launch for 67 MB of entries.  A range whose slice stays
+// resident is completed in L2 and leaves once: with the rounds put around the single-pass loop below, 16 of them brought WRITE_SIZE
+// to 67 MB; the round loop as it stands, which keeps the workgroups less in step, to 303 MB (486 MB at 4 rounds).  But a round is a
+// whole pass of ballots and shuffles over the chunk, about 25 us per 16.7 M digits -- it is bound by instruction issue, not by the
+// non-temporal re-read of the digits and sign bytes -- so the host asks for few rounds or none (lds_sort_rounds): 4 at 2^20 points,
+// where the kernel takes 196 us instead of 215 and the step with four in flight 2.74 ms instead of 2.84.  One round is the single
+// pass as it always was, loop and loads.  No barrier between rounds: workgroups that start together stay roughly in step, which is
+// all the locality needs.  Figures: profiles/scatter_rounds_*.txt, DESIGN.md 3.1.
 __global__ __launch_bounds__(CS_THREADS) VSP_CS_ATTR void k_scatter_lds(const uint16_t *digits, const uint8_t *flips, MsmGeom g, unsigned nchunks, size_t chunk_len,
                                                             const uint32_t *blockhist, const uint32_t *off, uint32_t *sorted,
-                                                            const uint8_t *lo_in, uint8_t *lo_out) {      // wide windows: the low-bits byte travels with the entry
+                                                            const uint8_t *lo_in, uint8_t *lo_out,      // wide windows: the low-bits byte travels with the entry
+                                                            unsigned rounds, unsigned range_shift, bool labelled) {
     extern __shared__ uint32_t lds_cur[];
-    const unsigned w = blockIdx.x % g.W, chunk = blockIdx.x / g.W;
+    const LdsSortBlock blk = lds_sort_block(blockIdx.x, g.W, nchunks, labelled);      // the histogram this block reads is the one the same block of k_count_lds wrote
+    if (!blk.valid) return;
+    const unsigned w = blk.w, chunk = blk.chunk;
     const size_t gbase = g.single ? (size_t)(w / g.Wk) * g.B : (size_t)w * g.B;
     const uint32_t *pre = blockhist + ((size_t)chunk * g.W + w) * g.B;
     VSP_CS_UNROLL
@@ -387,40 +406,108 @@ __global__ __launch_bounds__(CS_THREADS) VSP_CS_ATTR void k_scatter_lds(const ui
     __syncthreads();
     const size_t i0 = (size_t)chunk * chunk_len, i1 = i0 + chunk_len < g.n ? i0 + chunk_len : g.n;
     const uint16_t *dw = digits + (size_t)w * g.n;
+    const uint8_t *fw = flips ? flips + (size_t)(w / g.Wk) * g.n : nullptr;     // (one sign byte per scalar of every vector of a batch)
     const bool use_flips = !lo_in && (g.sbits == 128u || g.fold);
-    // CS_MLP digits (and their sign bytes) are requested before the first of them is used.  (Measured: k_count_lds 40 -> 30 us; this
-    // kernel stays at 0.21 ms for 16.7 M entries -- it is bound by its 16.7 M scattered 4-byte writes, not by the digit loads.)
-    for (size_t base = i0; base < i1; base += (size_t)CS_MLP * CS_THREADS) {
-        uint16_t dd[CS_MLP]; uint8_t ff[CS_MLP];
+    const unsigned lane = threadIdx.x & 63u;
+    const size_t step = (size_t)CS_MLP * CS_THREADS;
+    if (rounds == 1) {
+        // the single pass: CS_MLP digits (and their sign bytes) are requested before the first of them is used.  (Measured: k_count_lds
+        // 40 -> 30 us; this kernel stays at 0.21 ms for 16.7 M entries -- it is bound by its 16.7 M scattered 4-byte writes.)
+        for (size_t base = i0; base < i1; base += step) {
+            uint16_t dd[CS_MLP]; uint8_t ff[CS_MLP];
 #pragma unroll
-        for (unsigned j = 0; j < CS_MLP; j++) {
-            const size_t i = base + (size_t)j * CS_THREADS + threadIdx.x;
-            dd[j] = i < i1 ? dw[i] : DIGIT_NONE;
-            ff[j] = (use_flips && i < i1) ? flips[(size_t)(w / g.Wk) * g.n + i] : (uint8_t)0;      // (one sign byte per scalar of every vector of a batch)
+            for (unsigned j = 0; j < CS_MLP; j++) {
+                const size_t i = base + (size_t)j * CS_THREADS + threadIdx.x;
+                dd[j] = i < i1 ? dw[i] : DIGIT_NONE;
+                ff[j] = (use_flips && i < i1) ? fw[i] : (uint8_t)0;
+            }
+#pragma unroll
+            for (unsigned j = 0; j < CS_MLP; j++) {
+                const size_t i = base + (size_t)j * CS_THREADS + threadIdx.x;
+                const uint16_t d = dd[j];
+                const bool valid = d != DIGIT_NONE;
+                const uint32_t key = d & 0x7FFFu;
+                const unsigned long long act = __ballot(valid);
+                if (act) {
+                    // as k_count_lds: the lanes sharing the first valid lane's bucket take their positions from one atomic
+                    const int lead = __ffsll((long long)act) - 1;
+                    const uint32_t lkey = (uint32_t)__shfl((int)key, lead, 64);
+                    const bool same = valid && key == lkey;
+                    const unsigned long long grp = __ballot(same);
+                    uint32_t pos = 0;
+                    if (same && (int)lane == lead) pos = atomicAdd(&lds_cur[lkey], (uint32_t)__popcll(grp));
+                    pos = (uint32_t)__shfl((int)pos, lead, 64) + (uint32_t)__popcll(grp & ((1ull << lane) - 1ull));
+                    if (valid && !same) pos = atomicAdd(&lds_cur[key], 1u);
+                    if (valid) {
+                        uint32_t sign;
+                        if (lo_in) { const uint8_t l = lo_in[(size_t)w * g.n + i]; sign = l >> 7; lo_out[pos] = l & 0x7Fu; }
+                        else sign = (uint32_t)(d >> 15) ^ (uint32_t)ff[j];
+                        sorted[pos] = entry_of(g, w, i) | (sign << 31);
+                    }
+                }
+            }
         }
+        return;
+    }
+    // rounds: the streams are read again and again, non-temporally, so that they do not push the dirty lines of `sorted` out of L2
+    // CS_MLP digits (and their sign bytes) per thread and batch
+    auto load_batch = [&](size_t base, uint16_t (&dd)[CS_MLP], uint8_t (&ff)[CS_MLP]) {
 #pragma unroll
         for (unsigned j = 0; j < CS_MLP; j++) {
             const size_t i = base + (size_t)j * CS_THREADS + threadIdx.x;
-            const uint16_t d = dd[j];
-            const bool valid = d != DIGIT_NONE;
-            const uint32_t key = d & 0x7FFFu;
-            const unsigned long long act = __ballot(valid);
-            if (act) {
-                // as k_count_lds: the lanes sharing the first valid lane's bucket take their positions from one atomic
-                const int lead = __ffsll((long long)act) - 1;
-                const uint32_t lkey = (uint32_t)__shfl((int)key, lead, 64);
-                const bool same = valid && key == lkey;
-                const unsigned long long grp = __ballot(same);
-                const unsigned lane = threadIdx.x & 63u;
-                uint32_t pos = 0;
-                if (same && (int)lane == lead) pos = atomicAdd(&lds_cur[lkey], (uint32_t)__popcll(grp));
-                pos = (uint32_t)__shfl((int)pos, lead, 64) + (uint32_t)__popcll(grp & ((1ull << lane) - 1ull));
-                if (valid && !same) pos = atomicAdd(&lds_cur[key], 1u);
-                if (valid) {
-                    uint32_t sign;
-                    if (lo_in) { const uint8_t l = lo_in[(size_t)w * g.n + i]; sign = l >> 7; lo_out[pos] = l & 0x7Fu; }
-                    else sign = (uint32_t)(d >> 15) ^ (uint32_t)ff[j];
-                    sorted[pos] = entry_of(g, w, i) | (sign << 31);
+            dd[j] = i < i1 ? __builtin_nontemporal_load(&dw[i]) : DIGIT_NONE;
+            ff[j] = (use_flips && i < i1) ? __builtin_nontemporal_load(&fw[i]) : (uint8_t)0;
+        }
+    };
+#pragma unroll 1
+    for (unsigned round = 0; round < rounds; round++) {
+        // The next batch is requested before this one is worked on, and the LDS atomics of the whole batch are issued before the first
+        // of their results is used (the build runs without the machine scheduler: the order below is the order of issue).  Measured
+        // against rounds around the single-pass loop, 8 MiB of `sorted` per label: 4 rounds 188 -> 173 us; a pass by itself got no
+        // cheaper (26 us), so it is issue that bounds it, not these latencies (profiles/scatter_rounds_sweep.txt, A against B)
+        uint16_t dn[CS_MLP]; uint8_t fn[CS_MLP];
+        load_batch(i0, dn, fn);
+        for (size_t base = i0; base < i1; base += step) {
+            uint16_t dd[CS_MLP]; uint8_t ff[CS_MLP];
+#pragma unroll
+            for (unsigned j = 0; j < CS_MLP; j++) { dd[j] = dn[j]; ff[j] = fn[j]; }
+            if (base + step < i1) load_batch(base + step, dn, fn);
+            // first half: the atomics.  grp: the lanes that share the first valid lane's bucket lkey (as in k_count_lds, they take their
+            // positions from ONE atomic, their leader's); got: what the lane's own atomic returned (the leader's, or a lane's outside grp)
+            unsigned long long grp[CS_MLP]; uint32_t lkey[CS_MLP], got[CS_MLP];
+#pragma unroll
+            for (unsigned j = 0; j < CS_MLP; j++) {
+                const uint16_t d = dd[j];
+                const uint32_t key = d & 0x7FFFu;             // (the sign bit is no part of the bucket index; DIGIT_NONE is tested on the whole digit)
+                const bool valid = d != DIGIT_NONE && (key >> range_shift) == round;
+                const unsigned long long act = __ballot(valid);
+                grp[j] = 0; lkey[j] = 0; got[j] = 0;
+                if (act) {
+                    const int lead = __ffsll((long long)act) - 1;
+                    lkey[j] = (uint32_t)__shfl((int)key, lead, 64);
+                    const bool same = valid && key == lkey[j];
+                    grp[j] = __ballot(same);
+                    if (same && (int)lane == lead) got[j] = atomicAdd(&lds_cur[key], (uint32_t)__popcll(grp[j]));
+                    if (valid && !same) got[j] = atomicAdd(&lds_cur[key], 1u);
+                }
+            }
+            // second half: the positions and the stores
+#pragma unroll
+            for (unsigned j = 0; j < CS_MLP; j++) {
+                if (grp[j]) {                                 // (a wave with a valid lane has a leader's group, and the leader is its first lane)
+                    const size_t i = base + (size_t)j * CS_THREADS + threadIdx.x;
+                    const uint16_t d = dd[j];
+                    const uint32_t key = d & 0x7FFFu;
+                    const bool valid = d != DIGIT_NONE && (key >> range_shift) == round;
+                    const bool same = valid && key == lkey[j];
+                    const uint32_t from_lead = (uint32_t)__shfl((int)got[j], __ffsll((long long)grp[j]) - 1, 64);      // (every lane takes part)
+                    const uint32_t pos = same ? from_lead + (uint32_t)__popcll(grp[j] & ((1ull << lane) - 1ull)) : got[j];
+                    if (valid) {
+                        uint32_t sign;
+                        if (lo_in) { const uint8_t l = __builtin_nontemporal_load(&lo_in[(size_t)w * g.n + i]); sign = l >> 7; lo_out[pos] = l & 0x7Fu; }
+                        else sign = (uint32_t)(d >> 15) ^ (uint32_t)ff[j];
+                        sorted[pos] = entry_of(g, w, i) | (sign << 31);
+                    }
                 }
             }
         }
@@ -999,6 +1086,18 @@ static unsigned lds_chunks(const MsmGeom &g, size_t n) {
     while (nchunks > 1 && n / nchunks < 8192) nchunks >>= 1;
     return nchunks;
 }
+// rounds of k_scatter_lds over bucket ranges (lds_sort_map.h; option "msm_scatter_rounds": 0 = by the size of the slices, n = n rounds,
+// 1 = a single pass) and the shift that takes a bucket index to its range; g: the geometry the kernel is launched with
+// `automatic`: whether the rule may take rounds by itself (the sort of windows up to 16 bits, which the sweep covered; the two-pass sort of
+// wider windows runs in rounds only where the option asks for them).  labelled: which block mapping both kernels use (lds_sort_map.h):
+// the labelled one only where rounds run -- for the rule's own choices, multiples of 8, it is the even mapping anyway
+static void lds_scatter_rounds(vsp_ctx *ctx, const MsmGeom &g, size_t n, bool automatic, unsigned &rounds, unsigned &range_shift, bool &labelled) {
+    const long forced = opt(ctx, "msm_scatter_rounds", 0);
+    rounds = forced > 0 || automatic ? lds_sort_rounds(g.W, g.Wk, g.K, g.single != 0, g.B, n, forced) : 1u;
+    labelled = rounds > 1;
+    range_shift = (unsigned)(__builtin_ctz(g.B) - __builtin_ctz(rounds));
+    ctx->stats["msm_scatter_rounds"] = rounds;
+}
 
 // staged sort: 8 + 8 bits through LDS tiles, the rest inside LDS (k_ms_*): every global write is a run of whole lines
 static int msm_sort_staged(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const MsmGeom &g) {
@@ -1070,12 +1169,15 @@ static int msm_sort_wide(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const Ms
     const size_t lds_bytes = (size_t)gh.B * sizeof(uint32_t);
     VSP_TRY(lds_sort_attrs(ctx));
     hipLaunchKernelGGL(k_digits_wide, dim3(L.nblk), dim3(MSM_THREADS), 0, st, L.scalars, g, hi, lo);
-    hipLaunchKernelGGL(k_count_lds, dim3(nchunks * g.W), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)hi, gh, nchunks, chunk_len, blockhist);
+    unsigned rounds, range_shift; bool labelled;
+    lds_scatter_rounds(ctx, gh, n, false, rounds, range_shift, labelled);
+    const unsigned grid = lds_sort_grid(g.W, nchunks, labelled);
+    hipLaunchKernelGGL(k_count_lds, dim3(grid), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)hi, gh, nchunks, chunk_len, blockhist, labelled);
     hipLaunchKernelGGL(k_chunk_prefix, dim3((unsigned)((gh.G + MSM_THREADS - 1) / MSM_THREADS)), dim3(MSM_THREADS), 0, st, blockhist, g.single ? nchunks * g.W : nchunks, gh.G, cnt_hi, (uint32_t *)nullptr, gh.G);
     VSP_LAUNCH_CHECK();
     VSP_TRY(exclusive_scan_w(ctx, wk, cnt_hi, gh.G, off_hi, nullptr));
-    hipLaunchKernelGGL(k_scatter_lds, dim3(nchunks * g.W), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)hi, (const uint8_t *)nullptr, gh, nchunks, chunk_len,
-                       (const uint32_t *)blockhist, (const uint32_t *)off_hi, (uint32_t *)wk.tmp_sorted.p, (const uint8_t *)lo, (uint8_t *)wk.tmp_lo.p);
+    hipLaunchKernelGGL(k_scatter_lds, dim3(grid), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)hi, (const uint8_t *)nullptr, gh, nchunks, chunk_len,
+                       (const uint32_t *)blockhist, (const uint32_t *)off_hi, (uint32_t *)wk.tmp_sorted.p, (const uint8_t *)lo, (uint8_t *)wk.tmp_lo.p, rounds, range_shift, labelled);
     { size_t wg = (gh.G + 3) / 4; if (wg > 65536) wg = 65536;
       hipLaunchKernelGGL(k_segment_sort, dim3((unsigned)wg), dim3(256), 0, st, (const uint32_t *)wk.tmp_sorted.p, (const uint8_t *)wk.tmp_lo.p, (const uint32_t *)off_hi,
                          gh.G, g.lb, (uint32_t *)wk.cnt.p, (uint32_t *)wk.off.p, (uint32_t *)wk.sorted.p); }
@@ -1098,7 +1200,10 @@ static int msm_sort_lds(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const Msm
     VSP_TRY(lds_sort_attrs(ctx));
     if (L.fused_split) hipLaunchKernelGGL(k_glv_digits, dim3((unsigned)((L.rq.n + MSM_THREADS - 1) / MSM_THREADS), g.K), dim3(MSM_THREADS), 0, st, L.rq.scalars, L.rq.n, g, digits, flips);
     else hipLaunchKernelGGL(k_digits, dim3(L.nblk, g.K), dim3(MSM_THREADS), 0, st, L.scalars, g, digits, flips);
-    hipLaunchKernelGGL(k_count_lds, dim3(nchunks * g.W), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)digits, g, nchunks, chunk_len, blockhist);
+    unsigned rounds, range_shift; bool labelled;
+    lds_scatter_rounds(ctx, g, n, true, rounds, range_shift, labelled);
+    const unsigned grid = lds_sort_grid(g.W, nchunks, labelled);
+    hipLaunchKernelGGL(k_count_lds, dim3(grid), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)digits, g, nchunks, chunk_len, blockhist, labelled);
     VSP_TRY(ensure(ctx, wk.blocksum, ((size_t)L.gblk + 2) * sizeof(uint32_t), st));      // (the three-kernel scan shares this buffer and may have regrown it)
     uint32_t *tilesum = (uint32_t *)wk.blocksum.p;
     hipLaunchKernelGGL(k_chunk_prefix, dim3(L.gblk), dim3(MSM_THREADS), 0, st, blockhist, batch_single ? g.Wk : (g.single ? nchunks * g.W : nchunks), g.G, cnt,
@@ -1106,8 +1211,8 @@ static int msm_sort_lds(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const Msm
     VSP_LAUNCH_CHECK();
     if (L.fused_scans) hipLaunchKernelGGL(k_scan_tiles256, dim3(L.gblk), dim3(MSM_THREADS), 0, st, (const uint32_t *)cnt, g.G, (const uint32_t *)tilesum, off, (uint32_t *)nullptr);
     else VSP_TRY(exclusive_scan_w(ctx, wk, cnt, g.G, off, nullptr));
-    hipLaunchKernelGGL(k_scatter_lds, dim3(nchunks * g.W), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)digits, (const uint8_t *)flips, g, nchunks, chunk_len,
-                       (const uint32_t *)blockhist, (const uint32_t *)off, (uint32_t *)wk.sorted.p, (const uint8_t *)nullptr, (uint8_t *)nullptr);
+    hipLaunchKernelGGL(k_scatter_lds, dim3(grid), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)digits, (const uint8_t *)flips, g, nchunks, chunk_len,
+                       (const uint32_t *)blockhist, (const uint32_t *)off, (uint32_t *)wk.sorted.p, (const uint8_t *)nullptr, (uint8_t *)nullptr, rounds, range_shift, labelled);
     VSP_LAUNCH_CHECK();
     return VSP_OK;
 }
