@@ -106,12 +106,24 @@ void vsp_stats_reset(vsp_ctx *ctx);
  * multi-exponentiation -- a blocking read-back); "msm_sort" (0: by size; 1: never the staged sort of large wide-window problems;
  * 2: the staged sort for every window of 12 bits and more), "msm_wide_windows" (0: never more than 16 bits per window), "msm_fold" (0: 255-bit
  * scalars are not folded to min(k, r - k) where the window width divides 255), "msm_fused_split" (0: the endomorphism split and the digit
- * extraction run as two kernels over the scalars instead of one), "msm_fused_scans" (0: the bucket scans take three kernels each),
+ * extraction run as two kernels over the scalars instead of one; vsp_get_stat "msm_glv_split_launches" counts the launches of the split as
+ * a kernel of its own -- small problems and windows wider than 16 bits take it under either value), "msm_fused_scans" (0: the bucket
+ * scans take three kernels each, as they do above 2^20 buckets; vsp_get_stat "msm_scan3_launches" counts the bucket scans queued that way),
+ * "msm_accum28_asm" (default 1: the G1 accumulation over the 28-bit table runs the generated gfx950 loop; 0: its C++ twin k_accum28_cxx,
+ * the same additions in the same order -- the only 28-bit accumulation of the portable diagnostic build; vsp_get_stat
+ * "msm_accum28_cxx_launches" counts the twin's launches),
+ * "prove_witness_streams" (default 1: the prover's four witness multi-exponentiations run as two chains on the two streams the context
+ * created first, ahead of every work slot's, so that each chain has a hardware queue to itself; 0: each on its work slot's own stream),
  * "msm_scatter_rounds" (the LDS counting sort places its entries one range of buckets at a time, so that the lines it writes are
  * completed in L2: 0 = as many rounds as the size asks for, n = n rounds, rounded down to a power of two, 32 at most; 1 = a single pass;
  * vsp_get_stat "msm_scatter_rounds": the rounds of the last sort),
  * "prove_check_witness" (default 0; 1: every prover entry point checks its witnesses against the constraint system and refuses the ones
  * that fail -- "witness check" below).
+ * Test hooks, never for a caller: "msm_fp28_selfcheck_fault" and "ntt_fr29_selfcheck_fault" (1: the self-check above reports a mismatch
+ * it did not find, so that the suite can watch the context fall back to the generic kernels).
+ * The names above and the ones the later sections of this header introduce are all there are: vsp_set_option returns VSP_ERR_ARG for any
+ * other name, vsp_last_error quotes it, nothing is stored and the context stays usable.  (A name that nothing reads would otherwise be
+ * accepted in silence and leave its caller on the default path.)
  *
  * Runtime environment.  Results never depend on it.  GPU_MAX_HW_QUEUES (HIP runtime, read once when the runtime starts; default 4
  * hardware queues per stream priority): one proof's latency does not depend on it (the prover's two chains take their queues when the

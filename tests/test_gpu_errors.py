@@ -62,6 +62,35 @@ def test_status_codes_and_messages(ctx, cref):
     assert np.array_equal(v.multiexp(ctx, b, s, 1), cref.msm_g1(b, s))
 
 
+def test_unknown_option_names_are_refused(cref):
+    """vsp_set_option knows the names the library reads and refuses every other with VSP_ERR_ARG and the name in the error text -- a
+    misspelt option would leave a variant test on the default path without a word.  Nothing is stored, a known name is still taken, and the
+    next multi-exponentiation on the context gives the oracle's point."""
+    c = v.Context(0)
+    try:
+        for name in ("prove_early_assembly", "msm_windowbits", "MSM_GLV", "msm_glv ", ""):
+            assert c.lib.vsp_set_option(c.h, name.encode(), 1) == -1, name
+            assert '"%s"' % name in c.last_error() and "unknown option" in c.last_error()
+        with pytest.raises(v.VspError, match="prove_early_assembly"):
+            c.set_option("prove_early_assembly", 0)
+        assert "prove_early_assembly" not in c.options
+        assert c.lib.vsp_set_option(c.h, NULL, 1) == -1
+        n = 3000                                                               # a 28-bit table and the endomorphism split: the default path, untouched
+        b = cref.g1_batch_mul_gen(rand_fr_array(n, 12)); s = rand_fr_array(n, 13)
+        B = c.upload_bases(b, 1); d_s = c.to_device(s)
+        try:
+            got, inf = B.msm(d_s)
+            assert not inf and np.array_equal(got, cref.msm_g1(b, s))
+            assert c.stat("msm_endomorphism_split") == 1 and c.stat("msm_accum28_cxx_launches") == 0
+            c.set_option("msm_accum28_asm", 0)                                 # a known name is taken, and acts
+            got, _ = B.msm(d_s)
+            assert np.array_equal(got, cref.msm_g1(b, s)) and c.stat("msm_accum28_cxx_launches") == 1
+        finally:
+            c.dfree(d_s); B.free()
+    finally:
+        c.close()
+
+
 def test_boundary_validation_of_scalars_and_bases(ctx, cref):
     """include/vsp.h: VSP_ERR_ARG for a scalar >= r, a base coordinate >= p, a base off the curve (the reference's field types
     cannot hold such values; a raw-limb boundary must refuse them instead of returning another point)."""

@@ -623,14 +623,20 @@ def test_msm_g2_2p21_config5_shard_plain_bases(ctx, cref):
 @pytest.mark.gpu
 @pytest.mark.parametrize("option,value", [("msm_dimbits", 0), ("msm_dimbits", 1), ("msm_dimsum_lanes", 8), ("msm_dimsum_lanes", 16),
                                           ("msm_dimsum_lanes", 32), ("msm_dimsum_lanes", 64), ("msm_glv", 0), ("msm_glv", 2), ("msm_fp28", 0),
-                                          ("msm_dimsum_prefetch", 1)])
+                                          ("msm_dimsum_prefetch", 1), ("msm_accum28_asm", 0), ("msm_fused_split", 0), ("msm_fused_scans", 0),
+                                          ("msm_dimsum_maxw", 256), ("msm_dimsum_maxw", 4096), ("msm_debug_counts", 1)])
 def test_msm_same_result_under_every_kernel_variant_option(cref, option, value):
     """the tuning options of include/vsp.h pick kernel variants (lanes per bucket-digit sum, bit-decomposed or weighted last step of the
-    bucket reduction, endomorphism split, 28-bit or 12 x 32-bit accumulation): every variant gives the oracle's point, on plain and on
-    precomputed bases, dense and boolean-heavy scalars, both groups"""
+    bucket reduction, endomorphism split, 28-bit or 12 x 32-bit accumulation, the generated accumulation loop or its C++ twin, split and
+    scans fused or not, the lane plan's wave bound): every variant gives the oracle's point, on plain and on precomputed bases, dense and
+    boolean-heavy scalars, both groups -- and, at G1 3000 and G2 2500, on the hard set of test_gpu_msm_variants.py (infinity bases, equal-x
+    runs, a cancelling sum, the edge scalars of the endomorphism split and of the signed digits, whole range and sub-range)"""
+    from test_gpu_msm_variants import run_matrix
     c = v.Context(0)
     try:
         c.set_option(option, value)
+        for group, n in ((1, 3000), (2, 2500)):
+            run_matrix(c, cref, group, n)
         for group, n in ((1, 3000), (1, 40000), (2, 2500), (2, 33000)):
             if (group, n) not in _VARIANT_CASES:               # inputs and the oracle's answers once for all options
                 ks = rand_fr_array(n, seed=600 + n)

@@ -44,21 +44,46 @@ def test_prove_bit_exact_vs_oracle(ctx, cref, nc, ni):
     pk.free(); dcs.free(); [x.free() for x in q]; kp.free(); cs.free()
 
 
-@pytest.mark.parametrize("option,value", [("prove_witness_streams", 0), ("msm_dimbits", 0), ("msm_dimbits", 1), ("prove_early_assembly", 0),
-                                          ("prove_plan_first", 1), ("prove_h_first", 0), ("msm_slot_normal_priority", 1), ("msm_glv", 0)])
+@pytest.mark.parametrize("option,value", [("prove_witness_streams", 0), ("msm_dimbits", 0), ("msm_dimbits", 1), ("prove_host_threads", 0),
+                                          ("prove_plan_first", 1), ("prove_h_first", 0), ("msm_slot_normal_priority", 1), ("msm_glv", 0),
+                                          ("prove_fixed_base", 0), ("msm_accum28_asm", 0), ("msm_fused_split", 0), ("msm_fused_scans", 0)])
 def test_prove_is_the_same_proof_under_every_scheduling_option(cref, option, value):
-    """the documented tuning options (include/vsp.h) change how the work is queued or which kernel variant folds the buckets, never the
-    result: the same proof bytes as the oracle's, on a context of its own so that stream-creation options take effect"""
+    """the documented tuning options (include/vsp.h) change how the work is queued, where the host assembles the proof or which kernel
+    variant runs, never the result: the same proof bytes as the oracle's, on a context of its own so that stream-creation options take
+    effect.  (vsp_set_option refuses a name the library does not read, so no case here can be testing the default path by a misspelling.)"""
     c = v.Context(0)
     try:
         c.set_option(option, value)
         for precompute in (None, "all"):
             cs, wit, kp, dcs, pk, q, r, s = build(c, cref, 1500, 7, seed=31, precompute=precompute)
+            eA, eB, eC = kp.prove(wit, r, s)
+            exp_bytes = o.g1_compress(o.g1_from_limbs(eA)) + o.g2_compress(o.g2_from_limbs(eB)) + o.g1_compress(o.g1_from_limbs(eC))
             for _ in range(2):                                  # twice: the second call reuses warm workspaces and cached censuses
                 A, B, Cc, proof = v.groth16_prove(c, dcs, pk, wit, r, s)
-                eA, eB, eC = kp.prove(wit, r, s)
                 assert np.array_equal(A, eA) and np.array_equal(B, eB) and np.array_equal(Cc, eC), (option, value, precompute)
+                assert proof == exp_bytes, (option, value, precompute)
             pk.free(); dcs.free(); [x.free() for x in q]; kp.free(); cs.free()
+    finally:
+        c.close()
+
+
+def test_prove_with_the_saver_term_on_the_serial_host_path(cref):
+    """"prove_host_threads" = 0 and "prove_fixed_base" = 0 together: the four multiples of delta by double-and-add, the folds and the assembly
+    on the calling thread, one after the other -- and with a SAVER P1 / r_enc the fifth host job, r_enc * P1 on C.  The oracle's points with
+    and without the SAVER term, twice (the second call over warm workspaces)"""
+    c = v.Context(0)
+    try:
+        c.set_option("prove_host_threads", 0); c.set_option("prove_fixed_base", 0)
+        cs, wit, kp, dcs, pk, q, r, s = build(c, cref, 300, 5, seed=300)
+        P1 = kp.part("A_query")[3]; renc = L(987654321, 4)
+        want = {False: kp.prove(wit, r, s), True: kp.prove(wit, r, s, P1=P1, r_enc=renc)}
+        assert not np.array_equal(want[False][2], want[True][2])
+        for saver in (True, False, True):
+            A, B, Cc, proof = v.groth16_prove(c, dcs, pk, wit, r, s, **(dict(saver_P1=P1, saver_r_enc=renc) if saver else {}))
+            eA, eB, eC = want[saver]
+            assert np.array_equal(A, eA) and np.array_equal(B, eB) and np.array_equal(Cc, eC), saver
+            assert proof == o.g1_compress(o.g1_from_limbs(eA)) + o.g2_compress(o.g2_from_limbs(eB)) + o.g1_compress(o.g1_from_limbs(eC))
+        pk.free(); dcs.free(); [x.free() for x in q]; kp.free(); cs.free()
     finally:
         c.close()
 

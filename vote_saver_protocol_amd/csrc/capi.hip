@@ -339,8 +339,27 @@ int vsp_diag_clock_ntt(vsp_ctx *ctx, int reset, double *ghz_out, double *waves_o
     VSP_HIP(hipSetDevice(ctx->device));
     return ntt_diag_clock(ctx, reset, ghz_out, waves_out);
 }
+// Every option the library reads (opt / record_verdict, common.h), documented in include/vsp.h.  vsp_set_option refuses any other name: a
+// misspelt option would otherwise be stored, read by nothing, and leave its caller -- a test, most likely -- on the default path without a
+// word.  tests/test_option_coverage_cpu.py holds this table against the reads in csrc, the header and the names the suite sets.
+static const char *const KNOWN_OPTIONS[] = {
+    "ballot_box_table_bits", "bases_check_curve", "bases_check_subgroup", "generate_precompute_window",
+    "msm_accum28_asm", "msm_batch_tables", "msm_census_sync", "msm_debug_counts", "msm_dimbits", "msm_dimsum_dense", "msm_dimsum_lanes",
+    "msm_dimsum_maxw", "msm_dimsum_prefetch", "msm_fold", "msm_fp28", "msm_fused_scans", "msm_fused_split", "msm_glv", "msm_scatter_rounds",
+    "msm_slot_normal_priority", "msm_sort", "msm_split", "msm_wide_windows", "msm_window_bits",
+    "ntt_fr29", "pairing_chunk", "pedersen_lanes",
+    "prove_batch_share_plan", "prove_check_witness", "prove_fixed_base", "prove_h_first", "prove_host_threads", "prove_plan_first", "prove_witness_streams",
+    "registry_fused_levels", "saver_ct_chunk", "saver_decrypt_baby_bits", "saver_decrypt_fp_bits", "saver_encrypt_gpu", "saver_rerandomize_chunk",
+    "saver_rerandomize_w4", "saver_screen_chunk", "saver_screen_split", "saver_verify_group", "tally_chunk_points", "vote_cast_device",
+    "witness_map_batched",
+    // test hooks: the context's self-check of its hand-laid-out routines reports a mismatch it did not find
+    "msm_fp28_selfcheck_fault", "ntt_fr29_selfcheck_fault",
+};
 int vsp_set_option(vsp_ctx *ctx, const char *name, long value) {
     if (!ctx || !name) return VSP_ERR_ARG;
+    bool known = false;
+    for (const char *k : KNOWN_OPTIONS) known = known || !strcmp(k, name);
+    if (!known) return set_error(ctx, VSP_ERR_ARG, (std::string("set_option: unknown option \"") + name + "\"").c_str());
     ctx->opts[name] = value;
     return VSP_OK;
 }

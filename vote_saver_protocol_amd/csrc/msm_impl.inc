@@ -1119,11 +1119,12 @@ template <class F> static int msm_accumulate(vsp_ctx *ctx, MsmWork &wk, const Ms
 #if defined(VSP_PORTABLE_MUL)
         use_asm = 0;                                        // the diagnostic build without hand-laid-out routines: the C++ twin of the generated loop
 #endif
-        if (!use_asm)
+        if (!use_asm) {
             hipLaunchKernelGGL(k_accum28_cxx, dim3(L.ablk), dim3(MSM_THREADS), 0, st, (const Row28 *)L.table28, (const uint32_t *)pl->sorted.p,
                                (const uint32_t *)pl->off.p, (const uint32_t *)pl->suboff.p, (const uint32_t *)pl->perm.p, (const uint32_t *)pl->partbucket.p,
                                g.G, g.T, buckets28, partials28, redo + 1, redo);
-        else
+            ctx->stats["msm_accum28_cxx_launches"] += 1;
+        } else
 #endif
         hipLaunchKernelGGL(k_accum28, dim3(L.ablk * LaneView<F>::LANES), dim3(MSM_THREADS), 0, st, (const Row28 *)L.table28, (const uint32_t *)pl->sorted.p,
                            (const uint32_t *)pl->off.p, (const uint32_t *)pl->suboff.p, (const uint32_t *)pl->perm.p, (const uint32_t *)pl->partbucket.p,

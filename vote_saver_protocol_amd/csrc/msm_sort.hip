@@ -1066,6 +1066,7 @@ int msm_split_scalars(vsp_ctx *ctx, MsmWork &wk, MsmLaunch &L, const MsmGeom &g)
         VSP_TRY(ensure(ctx, wk.glv_scalars, 2 * n * sizeof(Fr), L.st));
         hipLaunchKernelGGL(k_glv_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, L.st, L.rq.scalars, n, (Fr *)wk.glv_scalars.p);
         VSP_LAUNCH_CHECK();
+        ctx->stats["msm_glv_split_launches"] += 1;
         L.scalars = (const Fr *)wk.glv_scalars.p;
     }
     L.n = 2 * n;                                            // from here on: 2n points (P_i, phi(P_i)), 2n scalars (k1_i, k2_i)
@@ -1210,7 +1211,7 @@ static int msm_sort_lds(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const Msm
                        L.fused_scans ? tilesum : (uint32_t *)nullptr, batch_single ? (size_t)g.B : g.G);
     VSP_LAUNCH_CHECK();
     if (L.fused_scans) hipLaunchKernelGGL(k_scan_tiles256, dim3(L.gblk), dim3(MSM_THREADS), 0, st, (const uint32_t *)cnt, g.G, (const uint32_t *)tilesum, off, (uint32_t *)nullptr);
-    else VSP_TRY(exclusive_scan_w(ctx, wk, cnt, g.G, off, nullptr));
+    else { VSP_TRY(exclusive_scan_w(ctx, wk, cnt, g.G, off, nullptr)); ctx->stats["msm_scan3_launches"] += 1; }
     hipLaunchKernelGGL(k_scatter_lds, dim3(grid), dim3(CS_THREADS), lds_bytes, st, (const uint16_t *)digits, (const uint8_t *)flips, g, nchunks, chunk_len,
                        (const uint32_t *)blockhist, (const uint32_t *)off, (uint32_t *)wk.sorted.p, (const uint8_t *)nullptr, (uint8_t *)nullptr, rounds, range_shift, labelled);
     VSP_LAUNCH_CHECK();
@@ -1253,7 +1254,7 @@ int msm_bucket_plan(vsp_ctx *ctx, MsmWork &wk, const MsmLaunch &L, const MsmGeom
                        L.fused_scans ? tilesum : (uint32_t *)nullptr, size_hist, 2u * SZ_BINS, redo0);
     VSP_LAUNCH_CHECK();
     if (L.fused_scans) hipLaunchKernelGGL(k_scan_tiles256, dim3(L.gblk), dim3(MSM_THREADS), 0, st, (const uint32_t *)nsub, g.G, (const uint32_t *)tilesum, suboff, (uint32_t *)nullptr);
-    else VSP_TRY(exclusive_scan_w(ctx, wk, nsub, g.G, suboff, nullptr));
+    else { VSP_TRY(exclusive_scan_w(ctx, wk, nsub, g.G, suboff, nullptr)); ctx->stats["msm_scan3_launches"] += 1; }
     uint32_t *part_bucket = (uint32_t *)wk.partbucket.p, *perm = (uint32_t *)wk.perm.p;
     hipLaunchKernelGGL(k_partinfo, dim3(L.ablk), dim3(256), 0, st, cnt, (const uint32_t *)suboff, g.G, g.T, part_bucket, size_hist);
     hipLaunchKernelGGL(k_binscan, dim3(1), dim3(SZ_BINS), 0, st, (const uint32_t *)size_hist, bin_cursor);
